@@ -10,7 +10,15 @@ workload: BASELINE.json configs[1] — MIPLIB ex10 LP relaxation, fp64, 1 GPU.  
           settings: max_iter=300, FixedRegularization(1e-8, -1e-8), AdaptiveStep(0.99), tol 1e-8.
 step    : one MPC iteration (factorize + predictor/corrector solves + step), inputs resident in HBM.
           W warmup iterations (untimed solve), then EXACTLY K iterations of a fresh solve after
-          initialize! (the MPC loop only, as cnt.total_time in src/solver.jl:181,407).
+          initialize! (the MPC loop only, as cnt.total_time in src/solver.jl:181,407).  A solve that
+          reaches optimality before K iterations (ex10: 22) is followed by further solves, each from
+          an untimed initialize!, until K iterations are timed.
+plain   : without --full the run sets up, warms up, times the K steps and prints the line (value,
+          ms_per_step, the timed leg's own figures); --dump-outputs DIR writes the point the last
+          timed step left (x, y, z_L, z_U, constraint values, summary) as DIR/<name>.npy.
+--full  : adds everything else, as below: the solve to optimality with its parity object, the legs
+          of the other configs, the CPU baseline and HiGHS (--no-opt, --legs, --no-cpu, --no-highs
+          trim it).
 legs    : every other BASELINE config gets a leg of the same schema under its own key of the line
           ("supportcase10" configs[3], "dense_qp" configs[2], "neos" configs[4]): iters/s over a timed
           run, the dominant kernel's roofline (HIP events on the launch stream; PMC traffic from the
@@ -335,41 +343,82 @@ def timed_leg(solver, steps, warmup, dist, sharded, barrier, config="ex10"):
     """The timed part of a leg: `warmup` untimed iterations with every LDL^T kernel kind event-timed
     (the dominant kind), then EXACTLY `steps` iterations after initialize!, bracketed by barriers
     (barrier() also synchronises the device), HIP events around the dominant kind only (its roofline);
-    whole-job numbers by `aggregate` (max time over ranks).  Returns (leg, warm stats, stats)."""
+    whole-job numbers by `aggregate` (max time over ranks).  A solve that ends before its share of the
+    iterations (optimality) is followed by another from initialize! (outside the clock) for the rest.
+    Returns (leg, warm stats, stats of the last timed solve)."""
     import torch
     solver.set_kernel_timing()
     solver.set_max_iter(max(warmup, 1))
-    solver.solve()
+    done = solver.solve().iter
+    while 0 < done < warmup:
+        solver.set_max_iter(warmup - done)
+        k = solver.solve().iter
+        if k <= 0:
+            break
+        done += k
     warm = solver.kernel_stats()
     dominant = max(warm, key=lambda k: k["time_ms"])["name"]
     breakdown = {k["name"]: round(k["time_ms"], 3) for k in sorted(warm, key=lambda k: -k["time_ms"]) if k["launches"]}
     solver.set_kernel_timing(1 << [k["name"] for k in warm].index(dominant))
-    solver.set_max_iter(steps)
-    solver.initialize()
-    barrier()
-    t0 = time.perf_counter()
-    # the MPC loop only: update_solution!'s host copies of the solution vectors come after the
-    # reference's cnt.total_time (src/solver.jl:406-413) and are not part of an iteration
-    st = solver.solve(fetch_solution=False)
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-    barrier()
-    dt = time.perf_counter() - t0
-    iters = st.iter
+    dt, iters, sts = 0.0, 0, []
+    while iters < steps:
+        solver.set_max_iter(steps - iters)
+        solver.initialize()
+        barrier()
+        t0 = time.perf_counter()
+        # the MPC loop only: update_solution!'s host copies of the solution vectors come after the
+        # reference's cnt.total_time (src/solver.jl:406-413) and are not part of an iteration
+        st = solver.solve(fetch_solution=False)
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        barrier()
+        dt += time.perf_counter() - t0
+        sts.append(st)
+        if st.iter <= 0:  # a solve that makes no iteration would never fill the count
+            break
+        iters += st.iter
     roof = roofline(solver.kernel_stats(), dominant, config)
     solver.set_kernel_timing(0)
     dt, total_iters, per_rank = aggregate(dt, iters, dist, sharded)
+    # the library's own clock around the timed iterations (every timed solve's cnt.total_time)
+    lib_s = sum(s.counters.total_time for s in sts) if all(hasattr(s, "counters") for s in sts) else None
     return ({"iters_per_s": total_iters / dt, "ms_per_iter": 1e3 * dt / max(iters, 1), "steps": steps,
-             "warmup": warmup, "iters_timed": iters, "roofline": roof, "kernel_ms_warmup": breakdown,
-             "per_rank_s": per_rank}, warm, st)
+             "warmup": warmup, "iters_timed": iters, "timed_solves": len(sts), "roofline": roof,
+             "kernel_ms_warmup": breakdown, "per_rank_s": per_rank, "loop_total_time_s": lib_s}, warm, st)
+
+
+def dump_outputs(solver, st, out_dir, cap_bytes=64 << 20):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as
+    <out_dir>/<name>.npy (float64): the unscaled point update_solution! returns (solution, multipliers,
+    multipliers_L, multipliers_U, constraints) read back from the device as the timed solve left it,
+    and `summary` = [status, iterations of the last timed solve, objective, dual objective, inf_pr,
+    inf_du, inf_compl].  An array that would take the files past `cap_bytes` in all is cut to a fixed
+    seeded sample of its entries (in index order)."""
+    import ctypes as C
+    import numpy as np
+    from madipm_amd import _lib as L
+    nx, m = solver.qp.nvar, solver.qp.ncon
+    x, zl, zu, y, cons = np.empty(nx), np.empty(nx), np.empty(nx), np.empty(m), np.empty(m)
+    L.check(L.lib.madipm_solver_get_solution(solver.h, L.ptr(x, C.c_double), L.ptr(y, C.c_double),
+                                             L.ptr(zl, C.c_double), L.ptr(zu, C.c_double), L.ptr(cons, C.c_double)),
+            "get_solution")
+    arrays = {"solution": x, "multipliers": y, "multipliers_L": zl, "multipliers_U": zu, "constraints": cons,
+              "summary": np.array([st.status, st.iter, st.objective, st.dual_objective, st.primal_feas,
+                                   st.dual_feas, st.inf_compl], np.float64)}
+    cap = cap_bytes // 8 // len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def run_leg(config, steps, warmup, comm=None, dist=None, sharded=False, barrier=None, world=1, opt=True,
-            ordering=None):
+            ordering=None, dump=None):
     """One BASELINE config end to end: build (the reference pipeline), analysis + upload (timed), W
     warmup iterations with every LDL^T kernel kind event-timed (the dominant kind), EXACTLY `steps`
     iterations after initialize! with HIP events around the dominant kind only, whole-job numbers
-    (max time over ranks), then (opt) a solve to optimality: status, iterations, loop time, end to end
+    (max time over ranks), then (dump) the timed solve's outputs to that folder and (opt) a solve to optimality: status, iterations, loop time, end to end
     = analysis + initialisation + loop, and golden_parity.  Returns (leg dict, solver, qp)."""
     import torch
     from madipm_amd import MPCSolver
@@ -397,8 +446,9 @@ def run_leg(config, steps, warmup, comm=None, dist=None, sharded=False, barrier=
                 "fronts": info["nsuper"], "levels": info["nlevels"], "leaf_batch_members": info["lb_members"],
                 "parallelism": f"subtree-shard{world}" if sharded else f"replicas{world}",
                 "analysis_s": t_analysis, "iteration_roofline": iteration_roofline(info, ms),
-                "loop_total_time_s": st.counters.total_time,  # the library's own clock around the K iterations
                 "collectives": collective_volume(info, warm, world)})
+    if dump and (dist is None or dist.get_rank() == 0):
+        dump_outputs(solver, st, dump)
     if opt:
         solver.set_max_iter(300)
         t1 = time.perf_counter()
@@ -423,6 +473,13 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="ex10")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the solve to optimality with its parity, the legs of the other "
+                         "BASELINE configs, the CPU baseline and HiGHS (trimmed by --no-opt, --legs, --no-cpu, "
+                         "--no-highs); without it the run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left (solution, multipliers, multipliers_L, "
+                         "multipliers_U, constraints, summary) as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--highs", action=argparse.BooleanOptionalAction, default=True,
                     help="time HiGHS-IPM (scipy) on the same LP as a third-party CPU datapoint")
@@ -462,12 +519,15 @@ def main():
         torch.cuda.synchronize()
 
     main_leg, solver, qp = run_leg(args.config, args.steps, args.warmup, comm, dist, sharded, barrier, world,
-                                   opt=not args.no_opt, ordering=args.ordering)
+                                   opt=args.full and not args.no_opt, ordering=args.ordering,
+                                   dump=args.dump_outputs)
     kperm = solver.kkt_perm() if rank == 0 else None
     del solver
 
     base = args.config.partition("@")[0]
-    if args.legs is None:
+    if not args.full:
+        legs = []
+    elif args.legs is None:
         legs = ["supportcase10", "dense_qp", "neos"] if world == 1 else ["neos"]
     else:
         legs = [] if args.legs == "none" else [c for c in args.legs.split(",") if c]
@@ -501,7 +561,8 @@ def main():
             "value": it["iters_per_s"],
             "unit": "iters/s",
             "n_gpus": world,
-            "steps": args.steps,
+            "steps": it["iters_timed"],  # the iterations under the clock: --steps
+            "timed_solves": it["timed_solves"],
             "warmup": args.warmup,
             "ms_per_step": it["ms_per_iter"],
             "higher_is_better": True,
@@ -521,7 +582,7 @@ def main():
             "cpu_baseline": None,
             "parity": it.get("parity"),
         }
-        if not args.no_cpu and world == 1 and not base.startswith(("dense_qp", "neos")):
+        if args.full and not args.no_cpu and world == 1 and not base.startswith(("dense_qp", "neos")):
             try:
                 (r_status, r_obj, r_iter), out["cpu_baseline"] = cpu_baseline(args.config, kperm,
                                                                                baseline_threads())

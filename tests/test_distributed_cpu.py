@@ -88,6 +88,42 @@ class _FakeSolver:
         return types.SimpleNamespace(iter=self.k)
 
 
+class _ConvergingSolver(_FakeSolver):
+    """A solve ends at optimality after 22 iterations (ex10) or at max_iter, whichever comes first."""
+
+    def __init__(self):
+        super().__init__(0)
+        self.inits, self.calls = 0, []
+
+    def initialize(self):
+        self.inits += 1
+
+    def solve(self, fetch_solution=True):
+        st = super().solve(fetch_solution)
+        st.iter = min(self.k, 22)
+        self.calls.append((fetch_solution, st.iter))
+        return st
+
+
+def test_timed_leg_times_exactly_steps_past_optimality():
+    """--steps sets the number of timed iterations even past the 22 a solve needs: further solves, each
+    from an initialize! of its own, make up the rest (50 = 22 + 22 + 6; warm-up 30 = 22 + 8)."""
+    import bench
+    s = _ConvergingSolver()
+    leg, _, st = bench.timed_leg(s, 50, 30, None, False, lambda: None)
+    assert [k for f, k in s.calls if f] == [22, 8]          # warm-up (solve() initialises itself)
+    assert [k for f, k in s.calls if not f] == [22, 22, 6]  # timed
+    assert s.inits == 3 and st.iter == 6
+    assert leg["steps"] == 50 and leg["iters_timed"] == 50 and leg["timed_solves"] == 3
+    dt = leg["per_rank_s"][0]
+    assert dt >= 0.15  # the three timed solves' 0.05 s each; initialize! is outside the clock
+    assert leg["ms_per_iter"] == pytest.approx(1e3 * dt / 50) and leg["iters_per_s"] == pytest.approx(50 / dt)
+    # within one solve nothing changes: one initialize!, one timed solve
+    s = _ConvergingSolver()
+    leg, _, st = bench.timed_leg(s, 20, 5, None, False, lambda: None)
+    assert s.calls == [(True, 5), (False, 20)] and s.inits == 1 and leg["timed_solves"] == 1
+
+
 def _leg_worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)

@@ -5,7 +5,7 @@
 set -o pipefail
 TAG=${1:?tag}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-MADIPM_SYMBOLIC_TIMING=1 timeout -k 10 600 python bench.py --config dense_qp --steps 2 --warmup 1 --no-cpu > $OUT/dense_qp_bench.log 2>&1 \
+MADIPM_SYMBOLIC_TIMING=1 timeout -k 10 600 python bench.py --full --config dense_qp --steps 2 --warmup 1 --no-cpu > $OUT/dense_qp_bench.log 2>&1 \
   || { echo "dense_qp bench FAILED"; tail -20 $OUT/dense_qp_bench.log; exit 1; }
 tail -1 $OUT/dense_qp_bench.log | cut -c1-400
 grep -E "^(setup_host|LDLSolver|symbolic)" $OUT/dense_qp_bench.log | head -40
