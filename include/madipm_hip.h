@@ -381,6 +381,10 @@ int madipm_solver_trace(madipm_solver_t s, madipm_iter_trace* out, int32_t cap);
 int madipm_solver_ldl_info(madipm_solver_t s, madipm_ldl_info* info);
 /* fill-reducing pivot order of the K2 factorization (length nvar_std + ncon, K2 unknowns [x; y]) */
 int madipm_solver_ldl_perm(madipm_solver_t s, int32_t* perm);
+/* lanes per row of the MPC loop's SpMV kernels (4, 8, 16, 32 or 64): chosen at construction from the
+ * mean row length of [H A^T; A], or forced by the environment variable MADIPM_SPMV_G (one of those five
+ * values; anything else is ignored).  Returns the width, < 0 on error.  [ABI 0.2.3, additive] */
+int madipm_solver_spmv_group(madipm_solver_t s);
 /* the solver's LDL^T: timing as madipm_ldl_set_timing / madipm_ldl_kernel_stats */
 int madipm_solver_set_timing(madipm_solver_t s, uint32_t mask);
 int madipm_solver_kernel_stats(madipm_solver_t s, madipm_kstat* out);

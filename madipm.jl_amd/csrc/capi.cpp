@@ -620,6 +620,13 @@ int madipm_solver_ldl_perm(madipm_solver_t s, int32_t* perm) {
   MADIPM_API_END
 }
 
+int madipm_solver_spmv_group(madipm_solver_t s) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  return s->s->spmv_group();
+  MADIPM_API_END
+}
+
 int madipm_solver_set_timing(madipm_solver_t s, uint32_t mask) {
   MADIPM_API_BEGIN
   MADIPM_REQUIRE(s, "null argument");

@@ -1853,6 +1853,10 @@ void MPCSolver::setup_host(const madipm_qp& q) {
     const double avg = (double)(Hci.size() + 2 * Jci.size()) / std::max(1, n + m);
     spmv_g_ = 4;
     while (spmv_g_ < 64 && spmv_g_ * 2 < avg) spmv_g_ *= 2;
+    if (const char* e = std::getenv("MADIPM_SPMV_G")) {  // tests / A-B: force the width (4..64, power of two)
+      const int g = std::atoi(e);
+      if (g == 4 || g == 8 || g == 16 || g == 32 || g == 64) spmv_g_ = g;
+    }
   }
   std::vector<int64_t> diag_pos(Kcp.begin(), Kcp.end() - 1);  // the diagonal leads every column
 

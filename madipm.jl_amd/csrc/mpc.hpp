@@ -54,6 +54,7 @@ class MPCSolver {
   const std::vector<madipm_iter_trace>& trace() const { return trace_; }
   LinSolver& ldl() { return *ldl_; }
   hipStream_t stream() const { return stream_; }
+  int spmv_group() const { return spmv_g_; }  // lanes per row of the SpMV kernels (heuristic or MADIPM_SPMV_G)
 
  private:
   void setup_host(const madipm_qp& qp);

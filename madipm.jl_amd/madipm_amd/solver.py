@@ -145,6 +145,7 @@ L._sig("madipm_solver_get_solution", C.c_int, [L.vp, L.f64p, L.f64p, L.f64p, L.f
 L._sig("madipm_solver_trace", C.c_int, [L.vp, C.POINTER(IterTrace), C.c_int32])
 L._sig("madipm_solver_ldl_info", C.c_int, [L.vp, C.POINTER(L.LDLInfo)])
 L._sig("madipm_solver_ldl_perm", C.c_int, [L.vp, L.i32p])
+L._sig("madipm_solver_spmv_group", C.c_int, [L.vp])
 L._sig("madipm_solver_set_timing", C.c_int, [L.vp, C.c_uint32])
 L._sig("madipm_solver_kernel_stats", C.c_int, [L.vp, C.POINTER(L.KStat)])
 L._sig("madipm_solver_destroy", None, [L.vp])
@@ -356,6 +357,11 @@ class MPCSolver:
         p = np.empty(n, np.int32)
         L.check(L.lib.madipm_solver_ldl_perm(self.h, L.ptr(p, C.c_int32)), "kkt_perm")
         return p
+
+    def spmv_group(self) -> int:
+        """Lanes per row of the MPC loop's SpMV kernels (4..64): the mean-row heuristic's choice, or the
+        value forced by MADIPM_SPMV_G at construction."""
+        return L.check(L.lib.madipm_solver_spmv_group(self.h), "spmv_group")
 
     def set_kernel_timing(self, mask: int = (1 << L.NKERNELS) - 1):
         """Record HIP events around every launch of the LDL^T kernel kinds in `mask` (bit k = kind k,

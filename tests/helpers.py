@@ -123,3 +123,206 @@ def many_leaf_k2(n, seed=0):
     Lw = sp.tril(K).tocsc()
     Lw.sort_indices()
     return K, Lw
+
+
+# ---------------------------------------------------------------- general-form problems for the
+# returned-point tests (test_mpc_point_gpu.py; pinned on the oracle in test_point_helpers_cpu.py)
+def scaled_general(kind, minimize=True):
+    """A general-form LP / QP on which set_scaling! does scale (obj_scale < 1, con_scale < 1 on some
+    rows), with fixed variables, an objective constant, a non-zero x0 and, for minimize=False, the
+    maximisation of the negated objective (the same point; objective c0 - (min - c0)).
+
+    Base: random_lp(60, 120, 0.05, 0, ineq_frac=0.3, free_frac=0.05) / random_qp(40, 90, 0.08, 3).
+    Rows are multiplied by 10**U(0, 4) (30 % of them kept at 1), c and H by 1e3, c0 = 7.5, variables 3
+    and 17 are fixed (at 0.5 when their upper bound was finite, else at 1)."""
+    from madipm_amd.instances import random_lp, random_qp
+    from madipm_amd.qp import QuadraticModel
+    base = {"lp": lambda: random_lp(60, 120, 0.05, 0, ineq_frac=0.3, free_frac=0.05),
+            "qp": lambda: random_qp(40, 90, 0.08, 3)}[kind]()
+    rng = np.random.default_rng(11)
+    m, n = base.ncon, base.nvar
+    fac = 10.0 ** rng.uniform(0.0, 4.0, m)
+    fac[rng.random(m) < 0.3] = 1.0
+    lvar, uvar = base.lvar.copy(), base.uvar.copy()
+    for j in (3, 17):
+        lvar[j] = uvar[j] = 0.5 if np.isfinite(base.uvar[j]) else 1.0
+    sg = 1.0 if minimize else -1.0
+    return QuadraticModel(c=sg * 1e3 * base.c, Hrows=base.Hrows, Hcols=base.Hcols, Hvals=sg * 1e3 * base.Hvals,
+                          Arows=base.Arows, Acols=base.Acols, Avals=base.Avals * fac[base.Arows],
+                          lcon=base.lcon * fac, ucon=base.ucon * fac, lvar=lvar, uvar=uvar,
+                          c0=7.5, x0=rng.uniform(0.1, 1.0, n), minimize=minimize,
+                          name=f"scaled_{kind}_{'min' if minimize else 'max'}")
+
+
+ROWLEN_LENGTHS = (1, 3, 4, 5, 8, 9, 19, 32, 33, 64, 65, 129, 131)
+
+
+def rowlen_qp(seed=0, hess=True):
+    """n = 200, m = 39: A's row lengths are ROWLEN_LENGTHS x 3 — around every lane-group width G of the
+    SpMV kernels (1, G - 1, G, G + 1, 2G, 2G + 1, > 4G for G = 4 .. 64).  Column 0 is in every row (a
+    J^T row of 39 entries), the other columns of a row are drawn without replacement.  Bounds, free
+    variables, inequality / ranged rows and the feasible, bounded construction are random_lp's
+    (b = A x0, c = A^T y0 + z0 - H x0).  hess=True: H = diag(U[1e-2, 1]) + sparse B B^T + v v^T with v on
+    70 variables (H rows of ~70 entries; the mean row of [H A^T; A] then selects G = 32, without H 8)."""
+    from madipm_amd.qp import QuadraticModel
+    rng = np.random.default_rng(seed)
+    n, lens = 200, np.tile(ROWLEN_LENGTHS, 3)
+    m = len(lens)
+    rows, cols = [], []
+    for i, ln in enumerate(lens):
+        rows += [i] * int(ln)
+        cols += [0] + list(1 + rng.choice(n - 1, int(ln) - 1, replace=False))
+    vals = rng.standard_normal(len(rows))
+    vals[np.abs(vals) < 0.1] = 0.5
+    A = sp.coo_matrix((vals, (rows, cols)), shape=(m, n)).tocsr()
+    lvar = np.zeros(n)
+    uvar = np.where(rng.random(n) < 0.5, rng.uniform(1.0, 5.0, n), np.inf)
+    free = rng.random(n) < 0.05
+    lvar[free], uvar[free] = -np.inf, np.inf
+    x0 = np.where(np.isfinite(uvar), uvar * rng.uniform(0.2, 0.8, n), rng.uniform(0.5, 2.0, n))
+    x0[free] = rng.standard_normal(free.sum())
+    b = A @ x0
+    y0 = rng.standard_normal(m)
+    z0 = rng.uniform(0.0, 1.0, n)
+    z0[free] = 0.0
+    c = A.T @ y0 + z0
+    lcon, ucon = b.copy(), b.copy()
+    ineq = rng.random(m) < 0.3
+    lcon[ineq] = b[ineq] - rng.uniform(0.1, 1.0, ineq.sum())
+    ucon[ineq] = np.where(rng.random(ineq.sum()) < 0.5, np.inf, b[ineq] + rng.uniform(0.1, 1.0, ineq.sum()))
+    Hr = Hc = Hv = []
+    if hess:
+        B = sp.random(n, n // 4, density=3.0 / n, random_state=rng)
+        v = np.zeros(n)
+        v[rng.choice(n, 70, replace=False)] = rng.uniform(0.1, 0.5, 70)
+        H = sp.diags(rng.uniform(1e-2, 1.0, n)) + B @ B.T + sp.csr_matrix(np.outer(v, v))
+        c = c - H @ x0
+        Hl = sp.tril(H).tocoo()
+        Hr, Hc, Hv = Hl.row, Hl.col, Hl.data
+    Ac = A.tocoo()
+    return QuadraticModel(c=c, Hrows=Hr, Hcols=Hc, Hvals=Hv, Arows=Ac.row, Acols=Ac.col, Avals=Ac.data,
+                          lcon=lcon, ucon=ucon, lvar=lvar, uvar=uvar, x0=rng.uniform(0.1, 1.0, n),
+                          name=f"rowlen_{'qp' if hess else 'lp'}_s{seed}")
+
+
+def spmv_mean_row(qp):
+    """Mean row length of [H A^T; A] (H symmetric in full, A with its slack columns): the figure
+    MPCSolver picks the SpMV lane-group width from, and that width (4 doubled while 2 G < mean, <= 64).
+    For problems without fixed variables (their rows and columns would leave H and A)."""
+    assert not np.any(qp.lvar == qp.uvar)
+    H = sp.coo_matrix((np.ones(qp.nnzh), (qp.Hrows, qp.Hcols)), shape=(qp.nvar, qp.nvar)).tocsr()
+    nnzh = (H + H.T).nnz
+    A = sp.coo_matrix((np.ones(qp.nnzj), (qp.Arows, qp.Acols)), shape=(qp.ncon, qp.nvar)).tocsr()
+    ns = int(np.sum(qp.lcon != qp.ucon))
+    mean = (nnzh + 2.0 * (A.nnz + ns)) / max(1, qp.nvar + ns + qp.ncon)
+    g = 4
+    while g < 64 and 2 * g < mean:
+        g *= 2
+    return mean, g
+
+
+def _dense_pd(n, rng):
+    P = rng.standard_normal((n, n))
+    H = P @ P.T / n + np.eye(n)
+    r, c = np.tril_indices(n)
+    return H, r, c, H[r, c]
+
+
+def free_eq_qp():
+    """n = 30 free variables, m = 10 equality rows, dense positive definite H = P P^T / n + I: no bounded
+    coordinate at all (nlb = nub = 0).  Returns (qp, x, y, objective) with the exact solution of
+    [H A^T; A 0] [x; y] = [-c; b] (the solver's sign of y: c + H x + A^T y = 0)."""
+    from madipm_amd.qp import QuadraticModel
+    rng = np.random.default_rng(5)
+    n, m = 30, 10
+    H, r, c_, hv = _dense_pd(n, rng)
+    c = rng.standard_normal(n)
+    A = rng.standard_normal((m, n))
+    b = rng.standard_normal(m)
+    K = np.block([[H, A.T], [A, np.zeros((m, m))]])
+    sol = np.linalg.solve(K, np.concatenate([-c, b]))
+    x, y = sol[:n], sol[n:]
+    ar, ac = np.nonzero(A)
+    qp = QuadraticModel(c=c, Hrows=r, Hcols=c_, Hvals=hv, Arows=ar, Acols=ac, Avals=A[ar, ac], lcon=b, ucon=b.copy(),
+                        lvar=np.full(n, -np.inf), uvar=np.full(n, np.inf), name="free_eq_qp")
+    return qp, x, y, float(c @ x + 0.5 * x @ H @ x)
+
+
+def box_qp():
+    """free_eq_qp's H and c with no constraint at all (m = 0) and 0 <= x <= 1."""
+    from madipm_amd.qp import QuadraticModel
+    rng = np.random.default_rng(5)
+    n = 30
+    H, r, c_, hv = _dense_pd(n, rng)
+    c = rng.standard_normal(n)
+    return QuadraticModel(c=c, Hrows=r, Hcols=c_, Hvals=hv, Arows=[], Acols=[], Avals=[], lcon=[], ucon=[],
+                          lvar=np.zeros(n), uvar=np.ones(n), name="box_qp")
+
+
+def kkt_properties_general(qp, st):
+    """Optimality certificate of a returned point (x, y, zl, zu, constraints) on the unscaled
+    general-form problem min/max c0 + c'x + x'Hx/2, lcon <= Ax <= ucon, lvar <= x <= uvar, in the solver's
+    sign convention (kkt_properties: the multipliers are those of min sigma f, sigma = -1 for
+    maximisation).  An inequality row i has the slack s_i = (Ax)_i in [lcon_i, ucon_i], whose
+    stationarity gives y_i = z_upper - z_lower: y_i >= 0 without a lower side, <= 0 without an upper.
+
+      du      |sigma (c + Hx) + A'y - zl + zu| over the non-fixed variables / (1 + |c|_inf)
+      cons    |constraints - Ax|_i / (|A||x|)_i, the worst row
+      pr      the worst row violation of lcon <= Ax <= ucon / max(1, (|A||x|)_i)
+      bounds  the worst violation of lvar <= x <= uvar (negative inside)
+      zmin    the smallest of zl, zu on their bounded coordinates
+      ysign   the wrong-signed part of y on the one-sided rows / (1 + |c|_inf)  (the slack's part of du)
+      zoff    the largest |zl|, |zu| where they must vanish: fixed variables and absent bounds
+      compl   the largest product multiplier x distance, over variable bounds and row sides
+      pobj    the objective at x;  dobj: the dual bound (fixed variables enter with their reduced cost)
+    """
+    n, m = qp.nvar, qp.ncon
+    sg = 1.0 if getattr(qp, "minimize", True) else -1.0
+    A = sp.csr_matrix((qp.Avals, (qp.Arows, qp.Acols)), shape=(m, n))
+    x, y, zl, zu = st.solution, st.multipliers, st.multipliers_L, st.multipliers_U
+    assert len(x) == len(zl) == len(zu) == n and len(y) == len(st.constraints) == m
+    hx = np.zeros(n)
+    np.add.at(hx, qp.Hrows, qp.Hvals * x[qp.Hcols])
+    off = qp.Hrows != qp.Hcols
+    np.add.at(hx, qp.Hcols[off], qp.Hvals[off] * x[qp.Hrows[off]])
+    fixed = qp.lvar == qp.uvar
+    lo = np.isfinite(qp.lvar) & ~fixed
+    hi = np.isfinite(qp.uvar) & ~fixed
+    r = sg * (qp.c + hx) + A.T @ y - zl + zu
+    du = np.max(np.abs(r[~fixed]), initial=0.0) / (1.0 + np.max(np.abs(qp.c), initial=0.0))
+    ax = A @ x
+    absax = abs(A) @ np.abs(x)
+    cons = np.max(np.abs(st.constraints - ax) / np.where(absax > 0, absax, 1.0), initial=0.0)
+    with np.errstate(invalid="ignore"):
+        viol = np.maximum(np.maximum(qp.lcon - ax, ax - qp.ucon), 0.0)
+    pr = np.max(viol / np.maximum(1.0, absax), initial=0.0)
+    bounds = max(np.max((qp.lvar - x)[lo | fixed], initial=-1.0), np.max((x - qp.uvar)[hi | fixed], initial=-1.0))
+    ineq = qp.lcon != qp.ucon
+    rlo, rhi = ineq & np.isfinite(qp.lcon), ineq & np.isfinite(qp.ucon)
+    zrl, zru = np.maximum(-y, 0.0), np.maximum(y, 0.0)            # the slack's z_lower / z_upper
+    zmin = min(np.min(zl[lo], initial=0.0), np.min(zu[hi], initial=0.0))
+    # y is stepped on its own, so its sign on a one-sided row holds to the slack's dual residual: as du
+    ysign = max(np.max(-y[ineq & ~rlo], initial=0.0), np.max(y[ineq & ~rhi], initial=0.0)) \
+        / (1.0 + np.max(np.abs(qp.c), initial=0.0))
+    zoff = max(np.max(np.abs(zl[~lo]), initial=0.0), np.max(np.abs(zu[~hi]), initial=0.0))
+    compl = max(np.max(np.abs((x - qp.lvar)[lo] * zl[lo]), initial=0.0),
+                np.max(np.abs((qp.uvar - x)[hi] * zu[hi]), initial=0.0),
+                np.max(np.abs(zrl[rlo] * (ax - qp.lcon)[rlo]), initial=0.0),
+                np.max(np.abs(zru[rhi] * (qp.ucon - ax)[rhi]), initial=0.0))
+    pobj = qp.c0 + qp.c @ x + 0.5 * x @ hx
+    dmin = (sg * qp.c0 - y[~ineq] @ qp.lcon[~ineq] + zrl[rlo] @ qp.lcon[rlo] - zru[rhi] @ qp.ucon[rhi]
+            + zl[lo] @ qp.lvar[lo] - zu[hi] @ qp.uvar[hi] + r[fixed] @ x[fixed] - sg * 0.5 * x @ hx)
+    return dict(pr=pr, du=du, cons=cons, bounds=bounds, zmin=zmin, ysign=ysign, zoff=zoff, compl=compl, pobj=pobj, dobj=sg * dmin)
+
+
+def assert_certificate(qp, st, objective):
+    """The thresholds of test_fullsize_vs_oracle on the general-form certificate.  cons: a row of <= 131
+    entries summed in any order, scaled and un-scaled by con_scale, is within (131 + 3) eps ~ 3e-14 of
+    |A||x|; ysign is the slack's share of the dual residual (as du); zoff is exact."""
+    p = kkt_properties_general(qp, st)
+    assert p["pr"] <= 1e-6 and p["du"] <= 1e-6 and p["ysign"] <= 1e-6, p
+    assert p["cons"] <= 1e-13, p
+    assert p["bounds"] <= 1e-8 and p["zmin"] >= -1e-10 and p["zoff"] == 0.0, p
+    assert abs(p["pobj"] - p["dobj"]) <= 1e-6 * max(1.0, abs(p["pobj"])), p
+    assert abs(p["pobj"] - objective) <= 1e-9 * max(1.0, abs(p["pobj"])), (p["pobj"], objective)
+    return p

@@ -38,7 +38,7 @@ def _oracle_opts(kw):
         o["step_rule"] = ("conservative", rule.tau)
     elif isinstance(rule, S.MehrotraAdaptiveStep):
         o["step_rule"] = ("mehrotra", rule.gamma_f)
-    for k in ("max_iter", "tol", "max_ncorr"):
+    for k in ("max_iter", "tol", "max_ncorr", "scaling"):
         if k in kw:
             o[k] = kw[k]
     kkt = kw.get("kkt_system")
