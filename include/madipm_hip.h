@@ -390,6 +390,43 @@ int madipm_solver_set_timing(madipm_solver_t s, uint32_t mask);
 int madipm_solver_kernel_stats(madipm_solver_t s, madipm_kstat* out);
 void madipm_solver_destroy(madipm_solver_t s);
 
+/* ------------------------------------------------------------------ re-solve with new data  [ABI 0.2.4, additive]
+ * A sequence of problems with one sparsity pattern: the ordering, the symbolic factorisation, the device
+ * plan and every allocation of an existing solver are kept and only the numbers are replaced.
+ * (madipm_version() still returns 203: these three symbols are the whole addition, no struct changed.)
+ *
+ * New numbers for the problem an existing solver was created with.  Any pointer may be NULL (= keep the
+ * current data); lengths are the creation-time nvar / ncon / nnzj / nnzh; HOST pointers, read during the
+ * call only.  The pattern and the classification of every bound are fixed at creation. */
+typedef struct madipm_qp_update {
+  const double *c; const double *c0;            /* c0: pointer so that NULL means "keep" */
+  const double *Hvals, *Avals;                  /* in the creation-time COO order */
+  const double *lcon, *ucon, *lvar, *uvar;
+  const double *x0, *y0;
+} madipm_qp_update;
+
+/* Builds, once, the host and device index plans of the refresh from the madipm_qp the solver was created
+ * with.  Its dimensions must be the creation-time ones; its index arrays are copied, and so is Avals (the
+ * solver keeps no host copy of A otherwise, and a later update with Avals == NULL has to keep them); the
+ * other fields are not read.  A second call is a no-op.  A solver that never calls it gets no extra work
+ * and no extra host or device memory.  Cost: 16 B of device plan + 8 B of device staging + 16 B of host
+ * memory per entry of A, 12 B + 8 B per stored entry of H. */
+int madipm_solver_prepare_update(madipm_solver_t s, const madipm_qp* qp);
+/* Installs the new data; the next madipm_solver_initialize / madipm_solver_solve runs on the new problem
+ * from its x0 / y0.  Starts no solve, allocates no device memory, runs no analysis, and returns with the
+ * solver's stream idle.  The matrix values are refreshed by device kernels with the bits a fresh
+ * madipm_solver_create of the updated problem would have uploaded.
+ * Rejected (negative code, madipm_last_error() names the first offending index and what changed, solver
+ * untouched): a change, with the merged data, of an equality row (lcon == ucon) into a ranged one or back,
+ * of a fixed variable (lvar == uvar) into a free one or back, of an infinite bound into a finite one or
+ * back; and a call before madipm_solver_prepare_update.
+ * madipm_solver_create_dist: every rank calls it with the same data. */
+int madipm_solver_update(madipm_solver_t s, const madipm_qp_update* u);
+/* n_analyses: linear-solver analyses run for this solver (1 after creation, and it stays 1); n_updates:
+ * successful updates; last_update_s: host wall time of the last one, its stream synchronisation included.
+ * Any pointer may be NULL. */
+int madipm_solver_counters(madipm_solver_t s, int64_t* n_analyses, int64_t* n_updates, double* last_update_s);
+
 #ifdef __cplusplus
 }
 #endif

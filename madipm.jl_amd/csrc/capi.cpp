@@ -645,6 +645,32 @@ int madipm_solver_kernel_stats(madipm_solver_t s, madipm_kstat* out) {
 
 void madipm_solver_destroy(madipm_solver_t s) { delete s; }
 
+int madipm_solver_prepare_update(madipm_solver_t s, const madipm_qp* qp) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s && qp, "null argument");
+  s->s->prepare_update(*qp);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_update(madipm_solver_t s, const madipm_qp_update* u) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s && u, "null argument");
+  s->s->update(*u);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_counters(madipm_solver_t s, int64_t* n_analyses, int64_t* n_updates, double* last_update_s) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  if (n_analyses) *n_analyses = s->s->n_analyses();
+  if (n_updates) *n_updates = s->s->n_updates();
+  if (last_update_s) *last_update_s = s->s->last_update_s();
+  return 0;
+  MADIPM_API_END
+}
+
 int madipm_update_step(int32_t rule, double tau, double mu, int32_t nlb, int32_t nub, const double* d_x_lr,
                        const double* d_xl_r, const double* d_zl_r, const double* d_dx_lr, const double* d_dzl,
                        const double* d_x_ur, const double* d_xu_r, const double* d_zu_r, const double* d_dx_ur,

@@ -48,6 +48,26 @@ struct QPHost {
   std::vector<double> con_scale;
   double obj_scale = 1;
   std::vector<double> x, xl, xu, rhs, y;
+  bool anyfix = false;  // a fixed structural variable: J is built from a filtered COO, cfix is non-zero
+};
+
+// What numeric_host hands to the device besides QPHost's own vectors
+struct HostNumeric {
+  std::vector<double> gfix, cfix, cs;
+};
+
+// The refresh plan (prepare_update).  Every destination entry of a value array owns a list of COO
+// sources, [sp[q], sp[q + 1]) into src, in ascending input index: csr_from_coo's merge order.  J's lists
+// are kept once, in J^T's entry order (whose column-index array already names each entry's constraint
+// row, i.e. its con_scale); J's own values are gathered from J^T's through j2jt.  32-bit throughout.
+struct UpdatePlan {
+  std::vector<int32_t> Ar, Ac;  // host copy of A's COO for the host passes (slack start, row maxima, cfix)
+  std::vector<double> Av;
+  DBuf<double> Araw, Hraw, cscale;      // device staging: raw Avals / Hvals, con_scale
+  DBuf<int32_t> tsp, tsrc, jtk, j2jt;   // J^T entry -> sources, -> its Kx_ slot; J entry -> J^T entry
+  DBuf<int32_t> hsp, hsrc, hk, hdpos;   // H entry -> sources, -> its Kx_ slot (-1: upper triangle);
+                                        // hdpos[i] = H's entry (i, i) or -1
+  int64_t nJ = 0, nH = 0;               // destination entries of J (= J^T) and H
 };
 
 namespace {
@@ -1557,6 +1577,7 @@ MPCSolver::MPCSolver(const madipm_qp& qp, const madipm_options& opt, Comm* comm)
 // shards on this device (ldl.nshards > 1, ShardGroup)
 std::unique_ptr<LinSolver> MPCSolver::make_linsolver(int n, const int64_t* cp, const int32_t* ri,
                                                      const SymbolicOptions& so) {
+  ++n_analyses_;
   if (comm_ && comm_->size > 1) {
     SymbolicOptions o = so;
     o.nshards = comm_->size;
@@ -1568,58 +1589,11 @@ std::unique_ptr<LinSolver> MPCSolver::make_linsolver(int n, const int64_t* cp, c
   return std::make_unique<LDLSolver>(n, cp, ri, so, opt_.ldl.pivot_tol);
 }
 
-// Host-side construction: MPCSolver(...) (structure.jl:79-178), MadNLP.initialize!/set_scaling!
-// [EXT] and the K2 pattern of SparseKKTSystem [EXT] (SURVEY Appendix B).
-void MPCSolver::setup_host(const madipm_qp& q) {
-  PhaseClock clk("setup_host");
-  H_ = std::make_unique<QPHost>();
-  QPHost& P = *H_;
-  MADIPM_REQUIRE(q.nvar >= 0 && q.ncon >= 0, "negative dimensions");
-  P.nx = q.nvar;
-  P.m = q.ncon;
-  const int nx = P.nx, m = P.m;
-  auto cp = [](const double* a, int64_t n, double dflt = 0.0) {
-    std::vector<double> v(n, dflt);
-    if (a) std::copy(a, a + n, v.begin());
-    return v;
-  };
-  P.c = cp(q.c, nx);
-  P.lvar = cp(q.lvar, nx, -INF);
-  P.uvar = cp(q.uvar, nx, INF);
-  P.lcon = cp(q.lcon, m, -INF);
-  P.ucon = cp(q.ucon, m, INF);
-  P.x0 = cp(q.x0, nx);
-  P.y0 = cp(q.y0, m);
-  P.c0 = q.c0;
-  P.minimize = q.minimize != 0;
-  P.sgn = P.minimize ? 1.0 : -1.0;
-  P.Hr.assign(q.Hrows, q.Hrows + q.nnzh);
-  P.Hc.assign(q.Hcols, q.Hcols + q.nnzh);
-  P.Hv.assign(q.Hvals, q.Hvals + q.nnzh);
-  P.Ar = q.Arows;
-  P.Ac = q.Acols;
-  P.Av = q.Avals;
-  P.nnzA = q.nnzj;
-  for (int64_t k = 0; k < q.nnzh; ++k)
-    MADIPM_REQUIRE(P.Hr[k] >= P.Hc[k] && P.Hr[k] < nx && P.Hc[k] >= 0, "H must be lower-triangular COO in range");
-  {
-    std::atomic<bool> bad{false};
-    par_range(q.nnzj, [&](int, int64_t a, int64_t b) {
-      bool ok = true;
-      for (int64_t k = a; k < b; ++k) ok &= P.Ar[k] >= 0 && P.Ar[k] < m && P.Ac[k] >= 0 && P.Ac[k] < nx;
-      if (!ok) bad = true;
-    });
-    MADIPM_REQUIRE(!bad, "A index out of range");
-  }
-  clk("copy + validate");
-  // ---- index sets: MadNLP.get_index_constraints (EnforceEquality, MakeParameter) [EXT]
-  for (int i = 0; i < m; ++i)
-    if (P.lcon[i] != P.ucon[i]) P.ind_ineq.push_back(i);
-  P.ns = (int)P.ind_ineq.size();
-  const int n = nx + P.ns;
-  P.n = n;
-  P.xl.resize(n);
-  P.xu.resize(n);
+// xl / xu of [x; s] as given: the variables' bounds, then the ranged rows' (before relaxation and scaling)
+static void raw_bounds(QPHost& P) {
+  const int nx = P.nx;
+  P.xl.resize(P.n);
+  P.xu.resize(P.n);
   for (int i = 0; i < nx; ++i) {
     P.xl[i] = P.lvar[i];
     P.xu[i] = P.uvar[i];
@@ -1628,18 +1602,17 @@ void MPCSolver::setup_host(const madipm_qp& q) {
     P.xl[nx + k] = P.lcon[P.ind_ineq[k]];
     P.xu[nx + k] = P.ucon[P.ind_ineq[k]];
   }
-  P.fixed.assign(n, 0);
-  for (int i = 0; i < n; ++i) {
-    if (P.xl[i] == P.xu[i]) {
-      P.ind_fixed.push_back(i);
-      P.fixed[i] = 1;
-    } else {
-      if (P.xl[i] != -INF) P.ind_lb.push_back(i);
-      if (P.xu[i] != INF) P.ind_ub.push_back(i);
-    }
-  }
-  // structure.jl:172-173 field swap => update_barrier! tests nlb + nub > 0 (SURVEY A.5)
-  P.has_ineq = (P.ind_lb.size() + P.ind_ub.size()) > 0;
+}
+
+// The numeric part of the construction: everything of size O(n + m) that depends on the problem's numbers
+// (and the O(nnz) host sums behind it), from QPHost's data, its index sets and A's COO.  The constructor
+// and update() both run it, so a refreshed solver holds the bits a fresh one would.
+void MPCSolver::numeric_host(HostNumeric& o, std::vector<int32_t>* jr, std::vector<int32_t>* jc,
+                             std::vector<double>* jv) {
+  PhaseClock clk("numeric_host");
+  QPHost& P = *H_;
+  const int nx = P.nx, m = P.m, n = P.n;
+  raw_bounds(P);
   // ---- MadNLP.initialize!(cb, ...) [EXT]
   P.x.assign(n, 0.0);
   for (int i = 0; i < nx; ++i) P.x[i] = P.x0[i];
@@ -1658,6 +1631,7 @@ void MPCSolver::setup_host(const madipm_qp& q) {
     for (int64_t k = 0; k < P.nnzA; ++k) ax[P.Ar[k]] += P.Av[k] * P.x[P.Ac[k]];
     for (int k = 0; k < P.ns; ++k) P.x[nx + k] = ax[P.ind_ineq[k]];
   }
+  clk("bounds + slack start A x");
   // initialize_variables! (Ipopt bound push) [EXT]
   const double bp = opt_.bound_push, bf = opt_.bound_fac;
   for (int i = 0; i < n; ++i) {
@@ -1714,6 +1688,120 @@ void MPCSolver::setup_host(const madipm_qp& q) {
     for (int i = 0; i < m; ++i) P.rhs[i] *= P.con_scale[i];
   }
   obj_scale_ = P.obj_scale;
+  clk("bound push + scaling");
+  // fixed variables (MakeParameter): their Hessian terms -> objective constant / gradient shift ...
+  o.gfix.assign(n, 0.0);
+  o.cfix.assign(m, 0.0);
+  double const_fixed = 0.0;
+  for (size_t k = 0; k < P.Hv.size(); ++k) {
+    const int r = P.Hr[k], c = P.Hc[k];
+    const bool fr = P.fixed[r], fc = P.fixed[c];
+    if (!fr && !fc) continue;
+    const double v = P.obj_scale * P.sgn * P.Hv[k];
+    if (fr && fc) {
+      const_fixed += (r == c ? 0.5 : 1.0) * v * P.x[r] * P.x[c];
+      continue;
+    }
+    // cross term with a fixed variable -> constant gradient shift
+    if (!fr) o.gfix[r] += v * P.x[c];
+    if (!fc) o.gfix[c] += v * P.x[r];
+  }
+  // ... and their Jacobian columns -> cfix, summed in input order: the sequential pass (which, at
+  // construction, also collects the COO of the columns that stay)
+  if (P.anyfix) {
+    const int64_t nz = P.nnzA;
+    for (int64_t k = 0; k < nz; ++k) {
+      const int r = P.Ar[k], c = P.Ac[k];
+      const double v = P.con_scale[r] * P.Av[k];
+      if (P.fixed[c]) {
+        o.cfix[r] += v * P.x[c];
+        continue;
+      }
+      if (jr) {
+        jr->push_back(r);
+        jc->push_back(c);
+        jv->push_back(v);
+      }
+    }
+  }
+  o.cs.assign(n, 0.0);
+  for (int i = 0; i < nx; ++i) o.cs[i] = P.obj_scale * P.sgn * P.c[i];
+  c0s_ = P.obj_scale * (P.sgn * P.c0) + const_fixed;
+  // norm_b (solver.jl:173) on host
+  norm_b_ = 0;
+  for (double v : P.rhs) norm_b_ = std::max(norm_b_, std::fabs(v));
+  clk("fixed terms, cs, norms");
+}
+
+// Host-side construction: MPCSolver(...) (structure.jl:79-178), MadNLP.initialize!/set_scaling!
+// [EXT] and the K2 pattern of SparseKKTSystem [EXT] (SURVEY Appendix B).
+void MPCSolver::setup_host(const madipm_qp& q) {
+  PhaseClock clk("setup_host");
+  H_ = std::make_unique<QPHost>();
+  QPHost& P = *H_;
+  MADIPM_REQUIRE(q.nvar >= 0 && q.ncon >= 0, "negative dimensions");
+  P.nx = q.nvar;
+  P.m = q.ncon;
+  const int nx = P.nx, m = P.m;
+  auto cp = [](const double* a, int64_t n, double dflt = 0.0) {
+    std::vector<double> v(n, dflt);
+    if (a) std::copy(a, a + n, v.begin());
+    return v;
+  };
+  P.c = cp(q.c, nx);
+  P.lvar = cp(q.lvar, nx, -INF);
+  P.uvar = cp(q.uvar, nx, INF);
+  P.lcon = cp(q.lcon, m, -INF);
+  P.ucon = cp(q.ucon, m, INF);
+  P.x0 = cp(q.x0, nx);
+  P.y0 = cp(q.y0, m);
+  P.c0 = q.c0;
+  P.minimize = q.minimize != 0;
+  P.sgn = P.minimize ? 1.0 : -1.0;
+  P.Hr.assign(q.Hrows, q.Hrows + q.nnzh);
+  P.Hc.assign(q.Hcols, q.Hcols + q.nnzh);
+  P.Hv.assign(q.Hvals, q.Hvals + q.nnzh);
+  P.Ar = q.Arows;
+  P.Ac = q.Acols;
+  P.Av = q.Avals;
+  P.nnzA = q.nnzj;
+  for (int64_t k = 0; k < q.nnzh; ++k)
+    MADIPM_REQUIRE(P.Hr[k] >= P.Hc[k] && P.Hr[k] < nx && P.Hc[k] >= 0, "H must be lower-triangular COO in range");
+  {
+    std::atomic<bool> bad{false};
+    par_range(q.nnzj, [&](int, int64_t a, int64_t b) {
+      bool ok = true;
+      for (int64_t k = a; k < b; ++k) ok &= P.Ar[k] >= 0 && P.Ar[k] < m && P.Ac[k] >= 0 && P.Ac[k] < nx;
+      if (!ok) bad = true;
+    });
+    MADIPM_REQUIRE(!bad, "A index out of range");
+  }
+  clk("copy + validate");
+  // ---- index sets: MadNLP.get_index_constraints (EnforceEquality, MakeParameter) [EXT]
+  for (int i = 0; i < m; ++i)
+    if (P.lcon[i] != P.ucon[i]) P.ind_ineq.push_back(i);
+  P.ns = (int)P.ind_ineq.size();
+  const int n = nx + P.ns;
+  P.n = n;
+  raw_bounds(P);
+  P.fixed.assign(n, 0);
+  for (int i = 0; i < n; ++i) {
+    if (P.xl[i] == P.xu[i]) {
+      P.ind_fixed.push_back(i);
+      P.fixed[i] = 1;
+    } else {
+      if (P.xl[i] != -INF) P.ind_lb.push_back(i);
+      if (P.xu[i] != INF) P.ind_ub.push_back(i);
+    }
+  }
+  // structure.jl:172-173 field swap => update_barrier! tests nlb + nub > 0 (SURVEY A.5)
+  P.has_ineq = (P.ind_lb.size() + P.ind_ub.size()) > 0;
+  for (int i = 0; i < nx && !P.anyfix; ++i) P.anyfix = P.fixed[i];
+  // ---- everything that depends on the numbers and is O(n + m) long: shared with update()
+  HostNumeric num;
+  std::vector<int32_t> jr, jc;
+  std::vector<double> jv;
+  numeric_host(num, &jr, &jc, &jv);
   clk("initialize + scaling");
 
   // ---- device problem data
@@ -1727,21 +1815,10 @@ void MPCSolver::setup_host(const madipm_qp& q) {
   // scaled Hessian (full symmetric CSR over n; MakeParameter zeroes fixed rows/cols), diagonal apart
   std::vector<int32_t> hr, hc;
   std::vector<double> hv, Hdiag(n, 0.0);
-  std::vector<double> gfix(n, 0.0), cfix(m, 0.0);
-  double const_fixed = 0.0;
   for (size_t k = 0; k < P.Hv.size(); ++k) {
     const int r = P.Hr[k], c = P.Hc[k];
     const double v = P.obj_scale * P.sgn * P.Hv[k];
-    const bool fr = P.fixed[r], fc = P.fixed[c];
-    if (fr && fc) {
-      const_fixed += (r == c ? 0.5 : 1.0) * v * P.x[r] * P.x[c];
-      continue;
-    }
-    if (fr || fc) {  // cross term with a fixed variable -> constant gradient shift
-      if (!fr) gfix[r] += v * P.x[c];
-      if (!fc) gfix[c] += v * P.x[r];
-      continue;
-    }
+    if (P.fixed[r] || P.fixed[c]) continue;  // numeric_host: const_fixed / gfix
     if (r == c) {
       Hdiag[r] += v;
       hr.push_back(r);
@@ -1761,32 +1838,15 @@ void MPCSolver::setup_host(const madipm_qp& q) {
   hvec<double> Hcv;
   csr_from_coo(n, hr, hc, hv, Hrp, Hci, Hcv);
   // scaled Jacobian with slack columns (m x n); fixed columns zeroed (their term -> cfix).  Without a
-  // fixed column every entry is kept in input order and read straight from the caller's A
-  std::vector<int32_t> jr, jc;
-  std::vector<double> jv;
-  bool anyfix = false;
-  for (int i = 0; i < nx && !anyfix; ++i) anyfix = P.fixed[i];
-  {
-    const int64_t nz = P.nnzA;
-    if (anyfix) {  // cfix sums in input order: the sequential pass
-      for (int64_t k = 0; k < nz; ++k) {
-        const int r = P.Ar[k], c = P.Ac[k];
-        const double v = P.con_scale[r] * P.Av[k];
-        if (P.fixed[c]) {
-          cfix[r] += v * P.x[c];
-          continue;
-        }
-        jr.push_back(r);
-        jc.push_back(c);
-        jv.push_back(v);
-      }
-      for (int k = 0; k < P.ns; ++k) {
-        jr.push_back(P.ind_ineq[k]);
-        jc.push_back(nx + k);
-        jv.push_back(-1.0);
-      }
+  // fixed column every entry is kept in input order and read straight from the caller's A; with one,
+  // numeric_host's cfix pass has filled the COO
+  const bool anyfix = P.anyfix;
+  if (anyfix)
+    for (int k = 0; k < P.ns; ++k) {
+      jr.push_back(P.ind_ineq[k]);
+      jc.push_back(nx + k);
+      jv.push_back(-1.0);
     }
-  }
   clk("H CSR + J COO");
   std::vector<int64_t> Jrp, JTrp;
   hvec<int32_t> Jci, JTci;
@@ -1808,9 +1868,6 @@ void MPCSolver::setup_host(const madipm_qp& q) {
     csr_from_coo(n, nj, col, row, val, JTrp, JTci, JTcv);
   }
   clk("J, J^T CSR");
-  std::vector<double> cs(n, 0.0);
-  for (int i = 0; i < nx; ++i) cs[i] = P.obj_scale * P.sgn * P.c[i];
-  c0s_ = P.obj_scale * (P.sgn * P.c0) + const_fixed;
   // K2 lower CSC: diag(n+m) + H strictly-lower + J at rows n+r  (SparseKKTSystem [EXT]), built by
   // columns: column j < n = [j; H's rows i > j (row j of the symmetric CSR H, ascending); n + the rows r
   // of column j of J (row j of J^T's CSR, ascending)], column j >= n = [j]
@@ -1944,9 +2001,9 @@ void MPCSolver::setup_host(const madipm_qp& q) {
   up(y_, P.y);
   up(rhs_, P.rhs);
   up(Hdiag_, Hdiag);
-  up(cs_, cs);
-  up(gfix_, gfix);
-  up(cfix_, cfix);
+  up(cs_, num.cs);
+  up(gfix_, num.gfix);
+  up(cfix_, num.cfix);
   up(diag_pos_, diag_pos);
   up(Kx_, Kv);
   up(ind_lb_, P.ind_lb);
@@ -2011,13 +2068,321 @@ void MPCSolver::setup_host(const madipm_qp& q) {
   st_.zero(s);
   MADIPM_HIP(hipStreamSynchronize(s));
   clk("uploads");
-  // norm_b (solver.jl:173) on host
-  norm_b_ = 0;
-  for (double v : P.rhs) norm_b_ = std::max(norm_b_, std::fabs(v));
   // the host copies of J, J^T and K2 (dense QP: ~18 GB) are released on a thread of their own: their
   // page-table teardown took 2.1 s of the construction on the box (r6) with nothing waiting for it
   free_async(std::move(Jci), std::move(JTci), std::move(Jcv), std::move(JTcv), std::move(Kri), std::move(Kv),
              std::move(Hci), std::move(Hcv));
+}
+
+// ======================================================================= re-solve with new numbers
+// madipm_solver_prepare_update / madipm_solver_update: the pattern, the ordering, the symbolic
+// factorisation, the device plan and every allocation stay; the vectors are recomputed by numeric_host
+// and the matrix values (Jv_, JTv_, Hv_, Hdiag_, the H and J entries of Kx_, K0_) by the kernels below.
+namespace {
+
+// The kernels round as the host construction does: each product con_scale[r] * Av[k] or
+// (obj_scale * sgn) * Hv[k] is rounded before it is added (no FMA: contraction is off inside them), a
+// destination's first source is taken as it is and the others are added in ascending input index.
+// One thread per destination entry: the writes are coalesced, the sources are gathered; no atomics.
+__global__ void k_refresh_jt(int64_t nd, const int32_t* __restrict__ sp, const int32_t* __restrict__ src,
+                             const int32_t* __restrict__ row, const double* __restrict__ cs,
+                             const double* __restrict__ raw, const int32_t* __restrict__ kpos,
+                             double* __restrict__ JTv, double* __restrict__ Kx, double* __restrict__ K0) {
+#pragma clang fp contract(off)
+  GRID_LOOP(q, nd) {
+    const int a = sp[q], b = sp[q + 1];
+    if (a == b) continue;  // a slack column's -1.0 never changes
+    const double s = cs[row[q]];
+    double acc = s * raw[src[a]];
+    for (int t = a + 1; t < b; ++t) {
+      const double p = s * raw[src[t]];
+      acc = acc + p;
+    }
+    JTv[q] = acc;
+    const int kp = kpos[q];  // ascending in q: K2's column j holds row j of J^T contiguously
+    Kx[kp] = acc;
+    if (K0) K0[kp] = acc;
+  }
+}
+__global__ void k_refresh_h(int64_t nd, const int32_t* __restrict__ sp, const int32_t* __restrict__ src, double os,
+                            const double* __restrict__ raw, const int32_t* __restrict__ kpos,
+                            double* __restrict__ Hv, double* __restrict__ Kx, double* __restrict__ K0) {
+#pragma clang fp contract(off)
+  GRID_LOOP(q, nd) {
+    const int a = sp[q], b = sp[q + 1];
+    if (a == b) continue;
+    double acc = os * raw[src[a]];
+    for (int t = a + 1; t < b; ++t) {
+      const double p = os * raw[src[t]];
+      acc = acc + p;
+    }
+    Hv[q] = acc;
+    const int kp = kpos[q];  // -1: diagonal or upper triangle (K2 keeps H's strict lower part)
+    if (kp >= 0) {
+      Kx[kp] = acc;
+      if (K0) K0[kp] = acc;
+    }
+  }
+}
+// Hdiag[i] is the host's 0.0 + v1 + v2 + ...; H's entry (i, i) is v1 + v2 + ...: they differ only where
+// every source is -0.0, which adding 0.0 to the entry restores
+__global__ void k_refresh_hdiag(int n, const int32_t* __restrict__ pos, const double* __restrict__ Hv,
+                                double* __restrict__ Hdiag) {
+#pragma clang fp contract(off)
+  GRID_LOOP(i, n) {
+    const int p = pos[i];
+    Hdiag[i] = p >= 0 ? 0.0 + Hv[p] : 0.0;
+  }
+}
+__global__ void k_refresh_gather(int64_t nd, const int32_t* __restrict__ map, const double* __restrict__ from,
+                                 double* __restrict__ to) {
+  GRID_LOOP(q, nd) to[q] = from[map[q]];
+}
+
+// csr_from_coo's structure for the COO (r, c) without its values: destination entries sorted by
+// (row, column), each with the ids of its COO entries in input order (id < 0: a constant entry, no source)
+struct CooPlan {
+  std::vector<int32_t> sp, src, drow, dcol;
+};
+CooPlan coo_plan(int nrow, const std::vector<int32_t>& r, const std::vector<int32_t>& c,
+                 const std::vector<int32_t>& id) {
+  const int64_t N = (int64_t)r.size();
+  std::vector<int64_t> start(nrow + 1, 0);
+  for (int64_t k = 0; k < N; ++k) start[r[k] + 1]++;
+  for (int i = 0; i < nrow; ++i) start[i + 1] += start[i];
+  std::vector<int32_t> ord(N);
+  {
+    std::vector<int64_t> fill(start.begin(), start.end() - 1);
+    for (int64_t k = 0; k < N; ++k) ord[fill[r[k]]++] = (int32_t)k;
+  }
+  CooPlan P;
+  P.sp.reserve(N + 1);
+  P.src.reserve(N);
+  P.drow.reserve(N);
+  P.dcol.reserve(N);
+  for (int i = 0; i < nrow; ++i) {
+    const auto b = ord.begin() + start[i], e = ord.begin() + start[i + 1];
+    if (!std::is_sorted(b, e, [&](int32_t x, int32_t y) { return c[x] < c[y]; }))
+      std::stable_sort(b, e, [&](int32_t x, int32_t y) { return c[x] < c[y]; });
+    for (auto it = b; it != e; ++it) {
+      if (it == b || c[*it] != c[*(it - 1)]) {
+        P.sp.push_back((int32_t)P.src.size());
+        P.drow.push_back(i);
+        P.dcol.push_back(c[*it]);
+      }
+      if (id[*it] >= 0) P.src.push_back(id[*it]);
+    }
+  }
+  P.sp.push_back((int32_t)P.src.size());
+  return P;
+}
+
+// what setup_host derives from one coordinate's bounds: fixed, or finite lower (2) | finite upper (4)
+int bound_class(double l, double u) { return l == u ? 1 : (l != -INF ? 2 : 0) | (u != INF ? 4 : 0); }
+void require_same_class(const char* what, int idx, double l0, double u0, double l1, double u1) {
+  const int a = bound_class(l0, u0), b = bound_class(l1, u1);
+  if (a == b) return;
+  std::string how;
+  if ((a == 1) != (b == 1))
+    how = a == 1 ? "was fixed (lower == upper bound) and would become free"
+                 : "was free (lower != upper bound) and would become fixed";
+  else if ((a & 2) != (b & 2))
+    how = (a & 2) ? "had a finite lower bound that would become infinite"
+                  : "had an infinite lower bound that would become finite";
+  else
+    how = (a & 4) ? "had a finite upper bound that would become infinite"
+                  : "had an infinite upper bound that would become finite";
+  throw Error(std::string("madipm_solver_update: ") + what + " " + std::to_string(idx) + " " + how +
+                  " (the classification of every bound is fixed at creation; nothing was changed)",
+              -3);
+}
+
+}  // namespace
+
+void MPCSolver::prepare_update(const madipm_qp& q) {
+  if (plan_) return;
+  QPHost& P = *H_;
+  const int nx = P.nx, m = P.m, n = P.n;
+  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
+  MADIPM_REQUIRE(q.nvar == nx && q.ncon == m && q.nnzj == na && q.nnzh == nh,
+                 "madipm_solver_prepare_update: nvar / ncon / nnzj / nnzh differ from the problem the solver was "
+                 "created with");
+  MADIPM_REQUIRE(na == 0 || (q.Arows && q.Acols && q.Avals), "madipm_solver_prepare_update: null A arrays");
+  MADIPM_REQUIRE(na + P.ns < INT32_MAX && 2 * nh < INT32_MAX && nnzK_ < INT32_MAX,
+                 "madipm_solver_prepare_update: the refresh plan has 32-bit indices (nnz < 2^31)");
+  auto pl = std::make_unique<UpdatePlan>();
+  pl->Ar.assign(q.Arows, q.Arows + na);
+  pl->Ac.assign(q.Acols, q.Acols + na);
+  pl->Av.assign(q.Avals, q.Avals + na);
+  for (int64_t k = 0; k < na; ++k)
+    MADIPM_REQUIRE(pl->Ar[k] >= 0 && pl->Ar[k] < m && pl->Ac[k] >= 0 && pl->Ac[k] < nx,
+                   "madipm_solver_prepare_update: A index out of range");
+  // ---- J^T (n x m): the COO setup_host builds (fixed columns dropped, one -1 per slack column), transposed
+  std::vector<int32_t> er, ec, id;
+  er.reserve(na + P.ns);
+  ec.reserve(na + P.ns);
+  id.reserve(na + P.ns);
+  for (int64_t k = 0; k < na; ++k) {
+    if (P.fixed[pl->Ac[k]]) continue;
+    er.push_back(pl->Ar[k]);
+    ec.push_back(pl->Ac[k]);
+    id.push_back((int32_t)k);
+  }
+  for (int k = 0; k < P.ns; ++k) {
+    er.push_back(P.ind_ineq[k]);
+    ec.push_back(nx + k);
+    id.push_back(-1);
+  }
+  const CooPlan T = coo_plan(n, ec, er, id);
+  const int64_t nJ = (int64_t)T.drow.size();
+  std::vector<int32_t>().swap(er);
+  std::vector<int32_t>().swap(ec);
+  std::vector<int32_t>().swap(id);
+  // J's entries sorted by (row, column) = J^T's, bucketed by their column index in ascending order
+  std::vector<int32_t> j2jt(nJ);
+  {
+    std::vector<int64_t> rs(m + 1, 0);
+    for (int64_t t = 0; t < nJ; ++t) rs[T.dcol[t] + 1]++;
+    for (int i = 0; i < m; ++i) rs[i + 1] += rs[i];
+    for (int64_t t = 0; t < nJ; ++t) j2jt[rs[T.dcol[t]]++] = (int32_t)t;
+  }
+  // ---- H (n x n, symmetric): an off-diagonal source feeds (r, c) and (c, r); fixed rows / columns feed none
+  std::vector<int32_t> hr, hc, hid;
+  for (int64_t k = 0; k < nh; ++k) {
+    const int r = P.Hr[k], c = P.Hc[k];
+    if (P.fixed[r] || P.fixed[c]) continue;
+    hr.push_back(r);
+    hc.push_back(c);
+    hid.push_back((int32_t)k);
+    if (r != c) {
+      hr.push_back(c);
+      hc.push_back(r);
+      hid.push_back((int32_t)k);
+    }
+  }
+  const CooPlan Hp = coo_plan(n, hr, hc, hid);
+  const int64_t nH = (int64_t)Hp.drow.size();
+  // the plan must address exactly the arrays the constructor uploaded
+  MADIPM_REQUIRE((int64_t)Jv_.n == std::max<int64_t>(nJ, 1) && (int64_t)JTv_.n == std::max<int64_t>(nJ, 1) &&
+                     (int64_t)Hv_.n == std::max<int64_t>(nH, 1),
+                 "madipm_solver_prepare_update: the index arrays are not the ones the solver was created with");
+  // ---- K2's columns: [j; H's rows i > j; n + J^T's row j]
+  std::vector<int64_t> hup(n, 0), jtc(n, 0), Kcp(n + m + 1, 0);
+  for (int64_t t = 0; t < nH; ++t) hup[Hp.drow[t]] += Hp.dcol[t] > Hp.drow[t];
+  for (int64_t t = 0; t < nJ; ++t) jtc[T.drow[t]]++;
+  for (int j = 0; j < n + m; ++j) Kcp[j + 1] = Kcp[j] + 1 + (j < n ? hup[j] + jtc[j] : 0);
+  MADIPM_REQUIRE(Kcp[n + m] == nnzK_,
+                 "madipm_solver_prepare_update: the index arrays are not the ones the solver was created with");
+  std::vector<int32_t> hk(nH, -1), hdpos(n, -1), jtk(nJ);
+  {
+    std::vector<int64_t> nxt(n);
+    for (int j = 0; j < n; ++j) nxt[j] = Kcp[j] + 1;
+    for (int64_t t = 0; t < nH; ++t) {
+      const int i = Hp.drow[t], j = Hp.dcol[t];
+      if (j > i) hk[t] = (int32_t)nxt[i]++;
+      if (j == i) hdpos[i] = (int32_t)t;
+    }
+    for (int64_t t = 0; t < nJ; ++t) jtk[t] = (int32_t)nxt[T.drow[t]]++;
+  }
+  // ---- device side: plans + staging (the only allocations of the refresh path)
+  hipStream_t s = stream_;
+  auto up = [&](auto& buf, const auto& vec) {
+    buf.alloc(std::max<size_t>(vec.size(), 1));
+    buf.upload(vec.data(), vec.size(), s);
+  };
+  up(pl->tsp, T.sp);
+  up(pl->tsrc, T.src);
+  up(pl->jtk, jtk);
+  up(pl->j2jt, j2jt);
+  up(pl->hsp, Hp.sp);
+  up(pl->hsrc, Hp.src);
+  up(pl->hk, hk);
+  up(pl->hdpos, hdpos);
+  up(pl->Araw, pl->Av);
+  up(pl->Hraw, P.Hv);
+  pl->cscale.alloc(std::max(m, 1));
+  pl->nJ = nJ;
+  pl->nH = nH;
+  MADIPM_HIP(hipStreamSynchronize(s));
+  // the host passes of numeric_host read A from the plan's copy from now on
+  P.Ar = pl->Ar.data();
+  P.Ac = pl->Ac.data();
+  P.Av = pl->Av.data();
+  plan_ = std::move(pl);
+}
+
+void MPCSolver::update(const madipm_qp_update& u) {
+  const double t0 = now();
+  PhaseClock clk("update");
+  MADIPM_REQUIRE(plan_, "madipm_solver_update: call madipm_solver_prepare_update on this solver first (it builds "
+                        "the refresh plan)");
+  QPHost& P = *H_;
+  UpdatePlan& pl = *plan_;
+  const int nx = P.nx, m = P.m, n = P.n;
+  // ---- the classification setup_host derived must hold for the merged data; checked before anything changes
+  const double* lv = u.lvar ? u.lvar : P.lvar.data();
+  const double* uv = u.uvar ? u.uvar : P.uvar.data();
+  const double* lc = u.lcon ? u.lcon : P.lcon.data();
+  const double* uc = u.ucon ? u.ucon : P.ucon.data();
+  for (int i = 0; i < m; ++i) {
+    const bool was = P.lcon[i] == P.ucon[i], is = lc[i] == uc[i];
+    if (was != is)
+      throw Error("madipm_solver_update: constraint " + std::to_string(i) +
+                      (was ? " was an equality (lcon == ucon) and would become ranged"
+                           : " was ranged (lcon != ucon) and would become an equality") +
+                      " (the classification of every bound is fixed at creation; nothing was changed)",
+                  -3);
+  }
+  for (int i = 0; i < nx; ++i) require_same_class("variable", i, P.lvar[i], P.uvar[i], lv[i], uv[i]);
+  for (int k = 0; k < P.ns; ++k) {
+    const int r = P.ind_ineq[k];
+    require_same_class("constraint", r, P.lcon[r], P.ucon[r], lc[r], uc[r]);
+  }
+  clk("classification check");
+  // ---- install
+  auto put = [](std::vector<double>& dst, const double* src) {
+    if (src && src != dst.data()) std::copy(src, src + dst.size(), dst.begin());
+  };
+  put(P.c, u.c);
+  if (u.c0) P.c0 = *u.c0;
+  put(P.Hv, u.Hvals);
+  put(pl.Av, u.Avals);
+  put(P.lvar, u.lvar);
+  put(P.uvar, u.uvar);
+  put(P.lcon, u.lcon);
+  put(P.ucon, u.ucon);
+  put(P.x0, u.x0);
+  put(P.y0, u.y0);
+  clk("copy");
+  HostNumeric num;
+  numeric_host(num);
+  clk("numeric_host");
+  hipStream_t s = stream_;
+  auto send = [&](double* dst, const std::vector<double>& v) {
+    if (!v.empty()) MADIPM_HIP(hipMemcpyAsync(dst, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  };
+  send(rhs_.p, P.rhs);
+  send(cs_.p, num.cs);
+  send(gfix_.p, num.gfix);
+  send(cfix_.p, num.cfix);
+  send(pl.cscale.p, P.con_scale);
+  if (u.Avals) send(pl.Araw.p, pl.Av);
+  if (u.Hvals) send(pl.Hraw.p, P.Hv);
+  // ---- matrix values on the device
+  double* K0 = kkt_ == KKT_K25 ? K0_.p : nullptr;
+  if (pl.nJ) {
+    k_refresh_jt<<<blocks(pl.nJ), NT, 0, s>>>(pl.nJ, pl.tsp, pl.tsrc, JTci_, pl.cscale, pl.Araw, pl.jtk, JTv_, Kx_, K0);
+    k_refresh_gather<<<blocks(pl.nJ), NT, 0, s>>>(pl.nJ, pl.j2jt, JTv_, Jv_);
+  }
+  if (pl.nH)
+    k_refresh_h<<<blocks(pl.nH), NT, 0, s>>>(pl.nH, pl.hsp, pl.hsrc, P.obj_scale * P.sgn, pl.Hraw, pl.hk, Hv_, Kx_, K0);
+  if (n) k_refresh_hdiag<<<blocks(n), NT, 0, s>>>(n, pl.hdpos, Hv_, Hdiag_);
+  MADIPM_HIP(hipGetLastError());
+  MADIPM_HIP(hipStreamSynchronize(s));
+  clk("uploads + kernels");
+  initialized_ = false;  // the next solve() initialises from the new x0 / y0
+  ++n_updates_;
+  last_update_s_ = now() - t0;
 }
 
 // Launch helpers (the DV view is rebuilt from member buffers; cheap, host-only)

@@ -40,7 +40,9 @@ struct DevState {
   LDLStatus ldl_status;  // the linear solver's status (external_status): one read-back per iteration
 };
 
-struct QPHost;  // host copy of the problem (mpc.hip)
+struct QPHost;       // host copy of the problem (mpc.hip)
+struct HostNumeric;  // value-dependent host quantities of size O(n + m) (mpc.hip)
+struct UpdatePlan;   // index plans of the value refresh, built by prepare_update (mpc.hip)
 
 class MPCSolver {
  public:
@@ -55,9 +57,21 @@ class MPCSolver {
   LinSolver& ldl() { return *ldl_; }
   hipStream_t stream() const { return stream_; }
   int spmv_group() const { return spmv_g_; }  // lanes per row of the SpMV kernels (heuristic or MADIPM_SPMV_G)
+  // New numbers for the same pattern (madipm_solver_prepare_update / _update / _counters): prepare_update
+  // builds the refresh plan once (a solver that never calls it pays nothing); update installs the data
+  // without touching the linear solver and leaves the stream idle.
+  void prepare_update(const madipm_qp& qp);
+  void update(const madipm_qp_update& u);
+  int64_t n_analyses() const { return n_analyses_; }
+  int64_t n_updates() const { return n_updates_; }
+  double last_update_s() const { return last_update_s_; }
 
  private:
   void setup_host(const madipm_qp& qp);
+  // the value-dependent host part of the construction, shared with update(); jr/jc/jv (creation with a
+  // fixed variable only) receive the Jacobian's COO in the same pass that sums cfix
+  void numeric_host(HostNumeric& o, std::vector<int32_t>* jr = nullptr, std::vector<int32_t>* jc = nullptr,
+                    std::vector<double>* jv = nullptr);
   std::unique_ptr<LinSolver> make_linsolver(int n, const int64_t* cp, const int32_t* ri, const SymbolicOptions& so);
   void initialize();
   void init_starting_point();
@@ -136,6 +150,9 @@ class MPCSolver {
   std::vector<madipm_iter_trace> trace_;
   double fs0_ = 0;  // device factorisation seconds at initialize! (cnt.linear_solver_time origin)
   DevState last_{};                // the state of the last termination test
+  std::unique_ptr<UpdatePlan> plan_;  // null until prepare_update
+  int64_t n_analyses_ = 0, n_updates_ = 0;
+  double last_update_s_ = 0;
 };
 
 // update_step! on caller-given vectors (madipm_update_step); v = the 10 device pointers in header order

@@ -168,3 +168,53 @@ MadIPM.sparse_csc_format(::Type{<:ROCArray}) = ROCSparseMatrixCSC
 MadIPM._colptr(A::ROCSparseMatrixCSC) = A.colPtr
 MadIPM._rowval(A::ROCSparseMatrixCSC) = A.rowVal
 MadIPM._nzval(A::ROCSparseMatrixCSC) = A.nzVal
+
+# ------------------------------------------------------------ re-solve with new numbers  (madipm_hip.h, ABI 0.2.4)
+# madipm_qp_update: host pointers read during the call only; C_NULL keeps the solver's current data.
+# Lengths are the creation-time nvar / ncon / nnzj / nnzh, Hvals / Avals in the creation-time COO order.
+struct MadipmQPUpdate
+    c::Ptr{Float64}
+    c0::Ptr{Float64}          # a pointer, so that C_NULL means "keep"
+    Hvals::Ptr{Float64}
+    Avals::Ptr{Float64}
+    lcon::Ptr{Float64}
+    ucon::Ptr{Float64}
+    lvar::Ptr{Float64}
+    uvar::Ptr{Float64}
+    x0::Ptr{Float64}
+    y0::Ptr{Float64}
+end
+
+_ptr_or_null(a::Nothing) = Ptr{Float64}(C_NULL)
+_ptr_or_null(a::Vector{Float64}) = pointer(a)
+
+# Builds the refresh plan once, from the Ref{MadipmQP} the solver was created with (a second call is a no-op).
+function solver_prepare_update(h::Ptr{Cvoid}, q::Base.RefValue)
+    GC.@preserve q check(ccall((:madipm_solver_prepare_update, libmadipm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}),
+                               h, Base.unsafe_convert(Ptr{Cvoid}, q)), "madipm_solver_prepare_update")
+    return
+end
+
+# Installs new numbers; the next madipm_solver_solve runs on the updated problem from its x0 / y0.  An error
+# (a change of the classification of a bound; no prepare_update) leaves the solver as it was.
+function solver_update(h::Ptr{Cvoid}; c=nothing, c0=nothing, Hvals=nothing, Avals=nothing, lcon=nothing,
+                       ucon=nothing, lvar=nothing, uvar=nothing, x0=nothing, y0=nothing)
+    c0v = c0 === nothing ? nothing : Float64[c0]
+    GC.@preserve c c0v Hvals Avals lcon ucon lvar uvar x0 y0 begin
+        u = Ref(MadipmQPUpdate(_ptr_or_null(c), _ptr_or_null(c0v), _ptr_or_null(Hvals), _ptr_or_null(Avals),
+                               _ptr_or_null(lcon), _ptr_or_null(ucon), _ptr_or_null(lvar), _ptr_or_null(uvar),
+                               _ptr_or_null(x0), _ptr_or_null(y0)))
+        check(ccall((:madipm_solver_update, libmadipm), Cint, (Ptr{Cvoid}, Ref{MadipmQPUpdate}), h, u),
+              "madipm_solver_update")
+    end
+    return
+end
+
+# (n_analyses, n_updates, last_update_s): analyses run for this solver (stays 1), successful updates, host
+# wall time of the last one
+function solver_counters(h::Ptr{Cvoid})
+    na, nu, t = Ref{Int64}(0), Ref{Int64}(0), Ref{Float64}(0.0)
+    check(ccall((:madipm_solver_counters, libmadipm), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Float64}),
+                h, na, nu, t), "madipm_solver_counters")
+    return (n_analyses = na[], n_updates = nu[], last_update_s = t[])
+end

@@ -18,7 +18,8 @@ def __getattr__(name):
                 "SparseKKTSystem", "ScaledSparseKKTSystem", "NormalKKTSystem", "ExecutionStats",
                 "SOLVE_SUCCEEDED", "INFEASIBLE_PROBLEM_DETECTED", "MAXIMUM_ITERATIONS_EXCEEDED",
                 "MAXIMUM_WALLTIME_EXCEEDED", "DIVERGING_ITERATES", "ERROR_IN_STEP_COMPUTATION", "INTERNAL_ERROR",
-                "STATUS_NAMES", "RCCLComm", "HostComm", "SolveException", "UnfactorizedSolveException"):
+                "STATUS_NAMES", "RCCLComm", "HostComm", "SolveException", "UnfactorizedSolveException",
+                "MadIPMError"):  # MadIPMError: what MPCSolver.update raises on a change of classification
         from . import solver
         return getattr(solver, name)
     if name == "HIPLDLSolver":

@@ -13,6 +13,7 @@ Every computation of the solve runs in libmadipm_hip on the GPU; there is no CPU
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -106,6 +107,12 @@ class QPStruct(C.Structure):
                 ("lvar", L.f64p), ("uvar", L.f64p), ("x0", L.f64p), ("y0", L.f64p), ("minimize", C.c_int32)]
 
 
+class QPUpdate(C.Structure):
+    """madipm_qp_update: new numbers for an existing solver's problem; a NULL pointer keeps the current data."""
+    _fields_ = [("c", L.f64p), ("c0", L.f64p), ("Hvals", L.f64p), ("Avals", L.f64p), ("lcon", L.f64p),
+                ("ucon", L.f64p), ("lvar", L.f64p), ("uvar", L.f64p), ("x0", L.f64p), ("y0", L.f64p)]
+
+
 class Stats(C.Structure):
     _fields_ = [("status", C.c_int32), ("iter", C.c_int32), ("objective", C.c_double),
                 ("dual_objective", C.c_double), ("inf_pr", C.c_double), ("inf_du", C.c_double),
@@ -124,6 +131,7 @@ class UnfactorizedSolveException(Exception):
     (src/linear_solver.jl:6-17) failed (LDLFactorizations' ldiv! on an unfactorized object [EXT])."""
 
 
+MadIPMError = L.MadIPMError  # a refused library call (MPCSolver.update on a change of classification)
 EXC_NONE, EXC_SOLVE, EXC_UNFACTORIZED = 0, 1, 2
 _EXCEPTIONS = {EXC_SOLVE: SolveException, EXC_UNFACTORIZED: UnfactorizedSolveException}
 
@@ -149,6 +157,9 @@ L._sig("madipm_solver_spmv_group", C.c_int, [L.vp])
 L._sig("madipm_solver_set_timing", C.c_int, [L.vp, C.c_uint32])
 L._sig("madipm_solver_kernel_stats", C.c_int, [L.vp, C.POINTER(L.KStat)])
 L._sig("madipm_solver_destroy", None, [L.vp])
+L._sig("madipm_solver_prepare_update", C.c_int, [L.vp, C.POINTER(QPStruct)])
+L._sig("madipm_solver_update", C.c_int, [L.vp, C.POINTER(QPUpdate)])
+L._sig("madipm_solver_counters", C.c_int, [L.vp, L.i64p, L.i64p, L.f64p])
 
 
 class RCCLComm:
@@ -314,6 +325,7 @@ class MPCSolver:
         self.options = load_options(**kwargs)
         self.rethrow_error = bool(kwargs.get("rethrow_error", False))
         self._keep = []
+        self._update_ready = False  # madipm_solver_prepare_update has run (update() calls it on first use)
         q = QPStruct()
         q.nvar, q.ncon = qp.nvar, qp.ncon
         q.nnzh, q.nnzj = qp.nnzh, qp.nnzj
@@ -422,6 +434,48 @@ class MPCSolver:
                               counters=Counters(k=st.iter, total_time=st.total_time,
                                                 linear_solver_time=st.linear_solver_time, init_time=st.init_time),
                               trace=self.trace())
+
+    def update(self, *, c=None, c0=None, Hvals=None, Avals=None, lcon=None, ucon=None, lvar=None, uvar=None,
+               x0=None, y0=None):
+        """New numbers for the same sparsity pattern: the next solve() runs on the updated problem from its
+        x0 / y0, with the ordering, the symbolic factorisation, the device plan and every buffer of this
+        solver kept (no re-analysis).  An argument left None keeps the current data; Hvals / Avals are in the
+        creation-time COO order.  The classification of every bound is fixed at creation: turning an
+        equality row into a ranged one, a fixed variable into a free one, or a finite bound into an infinite
+        one (or back) raises MadIPMError and leaves the solver as it was.  self.qp becomes an updated copy;
+        the caller's arrays are never modified and are kept alive for the call only."""
+        qp = self.qp
+        want = {"c": qp.nvar, "Hvals": qp.nnzh, "Avals": qp.nnzj, "lcon": qp.ncon, "ucon": qp.ncon,
+                "lvar": qp.nvar, "uvar": qp.nvar, "x0": qp.nvar, "y0": qp.ncon}
+        given = {"c": c, "Hvals": Hvals, "Avals": Avals, "lcon": lcon, "ucon": ucon, "lvar": lvar, "uvar": uvar,
+                 "x0": x0, "y0": y0}
+        u, new = QPUpdate(), {}
+        for k, a in given.items():
+            if a is None:
+                continue
+            a = np.array(a, dtype=np.float64, order="C", ndmin=1)  # a copy: self.qp never aliases the caller's
+            if a.shape != (want[k],):
+                raise ValueError(f"update: {k} has shape {a.shape}, expected ({want[k]},)")
+            new[k] = a
+            setattr(u, k, L.ptr(a, C.c_double))
+        c0v = None
+        if c0 is not None:
+            c0v = C.c_double(float(c0))
+            u.c0 = C.pointer(c0v)
+            new["c0"] = float(c0)
+        if not self._update_ready:
+            # the refresh plan, once: the creation-time arrays of self._q are alive in self._keep
+            L.check(L.lib.madipm_solver_prepare_update(self.h, C.byref(self._q)), "prepare_update")
+            self._update_ready = True
+        L.check(L.lib.madipm_solver_update(self.h, C.byref(u)), "update")
+        self.qp = dataclasses.replace(qp, **new)
+
+    def counters(self) -> dict:
+        """n_analyses: linear-solver analyses run for this solver (stays 1); n_updates: successful update()
+        calls; last_update_s: host wall time of the last one (its stream synchronisation included)."""
+        na, nu, t = C.c_int64(), C.c_int64(), C.c_double()
+        L.check(L.lib.madipm_solver_counters(self.h, C.byref(na), C.byref(nu), C.byref(t)), "counters")
+        return {"n_analyses": int(na.value), "n_updates": int(nu.value), "last_update_s": float(t.value)}
 
     def trace(self) -> list:
         n = L.check(L.lib.madipm_solver_trace(self.h, None, 0), "trace")

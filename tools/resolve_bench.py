@@ -1,0 +1,102 @@
+"""Re-solve with new numbers against re-construction, on the ex10 and supportcase10 stand-ins
+(python tools/resolve_bench.py [ex10 supportcase10 ...]; MADIPM_SYMBOLIC_TIMING=1 adds update()'s phases
+on stderr).
+
+Per instance: construct_s (MPCSolver(qp), bench.py's analysis_s), prepare_update_s (the refresh plan, once),
+update_s (counters()["last_update_s"]: host wall time of one update, its stream synchronisation included;
+median of 10 after 2 warm-ups) and solve_s (initialize! + the MPC loop on the updated problem, same
+median).  Every update installs c, the finite bounds and the values of A (and H) times 1 + 1e-3 U(-1, 1),
+seeded — lower and upper bound of a coordinate by the same factor, so the classification of every bound is
+the creation-time one.  The last updated solve is compared with a fresh solver on the same data
+(matches_fresh: same status, iterations, objective bits).  Ends with one JSON line."""
+import dataclasses
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "madipm.jl_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+from madipm_amd import MPCSolver  # noqa: E402
+from madipm_amd import _lib  # noqa: E402
+
+WARMUP, REPS, REL = 2, 10, 1e-3
+
+
+def perturb(qp, rng):
+    """The value fields of qp under relative noise REL that keeps every classification."""
+    def f(k):
+        return 1.0 + REL * rng.uniform(-1.0, 1.0, k)
+    fv, fc = f(qp.nvar), f(qp.ncon)
+    return dict(c=qp.c * f(qp.nvar), Avals=qp.Avals * f(qp.nnzj), Hvals=qp.Hvals * f(qp.nnzh),
+                lvar=qp.lvar * fv, uvar=qp.uvar * fv, lcon=qp.lcon * fc, ucon=qp.ucon * fc)
+
+
+def run(name):
+    qp, desc = bench.build_problem(name)
+    opts = bench.solver_opts()
+    MPCSolver(qp, **opts)                      # the first construction of a process pays one-off set-up
+    t = time.perf_counter()
+    s = MPCSolver(qp, **opts)
+    construct_s = time.perf_counter() - t
+    t = time.perf_counter()
+    st0 = s.solve(fetch_solution=False)
+    solve0_s = time.perf_counter() - t
+    rng = np.random.default_rng(0)
+    new = perturb(qp, rng)
+    t = time.perf_counter()
+    s.update(**new)                            # the first update builds the plan
+    first_update_s = time.perf_counter() - t
+    prepare_update_s = first_update_s - s.counters()["last_update_s"]
+    upd, call, sol, its = [], [], [], []
+    for rep in range(WARMUP + REPS):
+        new = perturb(qp, rng)
+        t = time.perf_counter()
+        s.update(**new)
+        t_call = time.perf_counter() - t
+        t = time.perf_counter()
+        st = s.solve(fetch_solution=False)
+        t_solve = time.perf_counter() - t
+        if rep >= WARMUP:
+            upd.append(s.counters()["last_update_s"])
+            call.append(t_call)
+            sol.append(t_solve)
+            its.append(st.iter)
+    fresh = MPCSolver(dataclasses.replace(qp, **new), **opts).solve(fetch_solution=False)
+    c = s.counters()
+    update_s, solve_s = statistics.median(upd), statistics.median(sol)
+    return {"instance": name, "description": desc, "nvar": qp.nvar, "ncon": qp.ncon, "nnzj": qp.nnzj, "nnzh": qp.nnzh,
+            "construct_s": construct_s, "prepare_update_s": prepare_update_s, "update_s": update_s,
+            "update_call_s": statistics.median(call),   # MPCSolver.update: + the Python copies of the arrays
+            "solve_s": solve_s, "first_solve_s": solve0_s, "status": st.status, "first_status": st0.status,
+            "iters": its, "first_iters": st0.iter,
+            "update_plus_solve_s": update_s + solve_s, "construct_plus_solve_s": construct_s + solve_s,
+            "speedup": (construct_s + solve_s) / (update_s + solve_s),
+            "matches_fresh": bool(fresh.status == st.status and fresh.iter == st.iter
+                                  and np.float64(fresh.objective).tobytes() == np.float64(st.objective).tobytes()),
+            "n_analyses": c["n_analyses"], "n_updates": c["n_updates"]}
+
+
+def main():
+    torch.cuda.set_device(0)
+    _lib.check(_lib.madipm_set_device(0), "madipm_set_device")
+    torch.zeros(1, device="cuda")
+    out = []
+    for name in sys.argv[1:] or ["ex10", "supportcase10"]:
+        r = run(name)
+        print(f"{name}: construct_s {r['construct_s']:.4f}  prepare_update_s {r['prepare_update_s']:.4f}  "
+              f"update_s {r['update_s']:.5f}  solve_s {r['solve_s']:.4f}  ->  update + solve "
+              f"{r['update_plus_solve_s']:.4f} s against construct + solve {r['construct_plus_solve_s']:.4f} s "
+              f"(x{r['speedup']:.1f}), matches_fresh {r['matches_fresh']}", flush=True)
+        out.append(r)
+    print(json.dumps({"resolve_bench": out, "warmup": WARMUP, "reps": REPS, "rel_noise": REL}))
+
+
+if __name__ == "__main__":
+    main()
