@@ -326,3 +326,181 @@ def assert_certificate(qp, st, objective):
     assert abs(p["pobj"] - p["dobj"]) <= 1e-6 * max(1.0, abs(p["pobj"])), p
     assert abs(p["pobj"] - objective) <= 1e-9 * max(1.0, abs(p["pobj"])), (p["pobj"], objective)
     return p
+
+
+# ---------------------------------------------------------------- prescribed front trees for the
+# LDL^T shape sweep (test_ldl_shapes_gpu.py; pinned on the host in test_front_tree_cpu.py)
+FRONT_TREE_OPTS = dict(ordering=0, relax=0)   # with MADIPM_BIG_MERGE=0: the supernodes are the nodes
+
+
+def front_tree_nodes(root):
+    """The nodes of a front tree (w, b, children) in postorder, the numbering of front_tree_k2: dicts
+    with first (the node's first column), w, r = w + b, parent (postorder index, -1 at the root),
+    depth, children (indices) and rows (the b global indices of its rows below the diagonal block)."""
+    nodes = []
+
+    def visit(node, depth):
+        w, b, children = node
+        kids = [visit(c, depth + 1) for c in children]
+        me = len(nodes)
+        first = nodes[-1]["first"] + nodes[-1]["w"] if nodes else 0
+        nodes.append(dict(first=first, w=int(w), b=int(b), r=int(w + b), parent=-1, depth=depth, children=kids))
+        for k in kids:
+            nodes[k]["parent"] = me
+        return me
+
+    visit(root, 0)
+    assert nodes[-1]["b"] == 0, "the root has no rows below it"
+    for nd in nodes:
+        if nd["parent"] < 0:
+            nd["rows"] = np.zeros(0, np.int64)
+            continue
+        p, b = nodes[nd["parent"]], nd["b"]
+        assert 1 <= b <= p["w"], (nd, p)
+        assert len(p["children"]) >= 2, "a non-leaf needs two children on its column 0 to stay a supernode"
+        # the parent's column 0 and an even spread of its other columns: distinct because b - 1 <= w_p - 1
+        local = np.r_[0, 1 + (np.arange(b - 1) * (p["w"] - 1)) // max(1, b - 1)].astype(np.int64)
+        assert len(np.unique(local)) == b and local.max() < p["w"]
+        nd["rows"] = p["first"] + local
+    return nodes
+
+
+def front_tree_k2(root, seed):
+    """A quasi-definite matrix whose multifrontal fronts are prescribed.  A node is (w, b, children): a
+    dense w x w diagonal block +-(B B^T / w + I) 10^U(-0.5, 0.5), the sign alternating by depth (+ at
+    the root), and, for a non-root node, a dense b x w coupling block N(0, 1) / sqrt(w + b) in b of its
+    parent's w columns (column 0 and an even spread of the others: relative indices with gaps).
+    Postorder numbering.  Every non-leaf has >= 2 children, all reaching its column 0, so with
+    FRONT_TREE_OPTS and MADIPM_BIG_MERGE=0 the supernodes are the nodes: (w, r) = (w, w + b).
+    Returns (K, lower CSC with sorted indices, nodes of front_tree_nodes)."""
+    nodes = front_tree_nodes(root)
+    rng = np.random.default_rng(seed)
+    N = nodes[-1]["first"] + nodes[-1]["w"]
+    Kd = np.zeros((N, N))
+    for nd in nodes:
+        f, w, b = nd["first"], nd["w"], nd["b"]
+        B = rng.standard_normal((w, w))
+        sign = 1.0 if nd["depth"] % 2 == 0 else -1.0
+        Kd[f:f + w, f:f + w] = sign * (B @ B.T / w + np.eye(w)) * 10.0 ** rng.uniform(-0.5, 0.5)
+        if b:
+            Cb = rng.standard_normal((b, w)) / np.sqrt(w + b)
+            Kd[nd["rows"], f:f + w] = Cb
+            Kd[f:f + w, nd["rows"]] = Cb.T
+    K = sp.csc_matrix(Kd)
+    K.sort_indices()
+    Lw = sp.tril(K).tocsc()
+    Lw.sort_indices()
+    return K, Lw, nodes
+
+
+def fronts_in_pivot_order(nodes, perm, first, parent, nrows):
+    """Matches the analysis' supernodes (first, parent, nrows in pivot order; perm[k] = the column
+    eliminated k-th) to the prescribed nodes and asserts that they ARE the nodes: each supernode holds
+    exactly one node's columns in order, with its r and its parent.  Returns (node_of[s], front_of[k]):
+    the node of supernode s and the supernode of pivot k."""
+    by_first = {nd["first"]: i for i, nd in enumerate(nodes)}
+    ns = len(nrows)
+    assert ns == len(nodes), (ns, len(nodes))
+    node_of = []
+    for s in range(ns):
+        cols = np.asarray(perm[first[s]:first[s + 1]])
+        i = by_first.get(int(cols[0]), -1)
+        assert i >= 0, f"supernode {s} starts at column {cols[0]}, inside a node"
+        nd = nodes[i]
+        assert np.array_equal(cols, nd["first"] + np.arange(nd["w"])) and nrows[s] == nd["r"], \
+            f"supernode {s}: w={len(cols)} r={nrows[s]}, node {i} has w={nd['w']} r={nd['r']}"
+        node_of.append(i)
+    for s in range(ns):
+        want = nodes[node_of[s]]["parent"]
+        assert (parent[s] < 0 and want < 0) or (parent[s] >= 0 and node_of[parent[s]] == want), (s, parent[s], want)
+    return node_of, np.repeat(np.arange(ns), np.diff(first))
+
+
+def front_tree_classes(nodes, small_front_max=128, tree_fact=True):
+    """info()'s nbig, tree_fronts, tree_medium and max_front for prescribed fronts, restating the
+    unsharded planner without batched leaf columns (csrc/symbolic.hpp thresholds, symbolic.cpp's storage
+    and factorisation-tree passes): a front is big when r > small_front_max; a tree front has r <= 256, is
+    no childless front of r <= 32 (a pre-leaf), has only pre-leaves and tree fronts as children and at
+    most 8 tree children; medium tree fronts have r > 192.  fold_fronts / fold_leaves: the tree fronts of
+    r <= 192 whose pre-leaf children are all micro leaves (w <= 2, r <= 32), which they fold, and those
+    leaves (few enough here to fit the LDS carve).  Also returns the per-node tree flags."""
+    ftree = [False] * len(nodes)
+    for s, nd in enumerate(nodes):       # postorder: children first
+        if not tree_fact or nd["r"] > 256 or (not nd["children"] and nd["r"] <= 32):
+            continue
+        ok = all(ftree[c] or (not nodes[c]["children"] and nodes[c]["r"] <= 32) for c in nd["children"])
+        ftree[s] = ok and sum(ftree[c] for c in nd["children"]) <= 8
+    fold_fronts = fold_leaves = 0
+    for s, nd in enumerate(nodes):
+        pre = [nodes[c] for c in nd["children"] if not ftree[c]]
+        if ftree[s] and nd["r"] <= 192 and pre and all(c["w"] <= 2 and c["r"] <= 32 for c in pre):
+            fold_fronts += 1
+            fold_leaves += len(pre)
+    return dict(nbig=sum(nd["r"] > small_front_max for nd in nodes), tree_fronts=sum(ftree),
+                tree_medium=sum(f and nd["r"] > 192 for f, nd in zip(ftree, nodes)),
+                max_front=max(nd["r"] for nd in nodes), fold_fronts=fold_fronts, fold_leaves=fold_leaves), ftree
+
+
+LEAF_SHAPE_R = (2, 3, 17, 32, 33, 48, 64, 65, 96, 128, 129, 160, 191, 192, 193, 224, 256, 257, 300)
+
+
+def leaf_shape_widths(r):
+    """The pivot-column counts swept at r front rows: around the micro path (w <= 2), the 16-column
+    in-LDS pivot blocks, the 64-column panels and tiles, 128, and update blocks of 1, 16 and 17 rows."""
+    return sorted({w for w in (1, 2, 3, 15, 16, 17, 33, 63, 64, 65, 127, 128, 129, r - 17, r - 16, r - 1)
+                   if 1 <= w <= r - 1})
+
+
+def leaf_shape_tree(r, w):
+    """Three leaves under one dense root: two of (w, r), one with half the columns and the same update
+    rows; the root has max b + 3 columns (r = w)."""
+    b = r - w
+    return (b + 3, 0, [(w, b, []), (w, b, []), (max(1, w // 2), b, [])])
+
+
+# (w_m, b_m) of the mids, k leaves each of (w, b): three mids per tree under a root of max b_m + 3 columns
+ASSEMBLY_TREES = {
+    # every child a micro leaf (w <= 2, r <= 32): the fold; k = 9 pre-leaves are no fan-in
+    "micro_fold": [((16, 8), 2, (1, 1)), ((40, 33), 8, (2, 7)), ((64, 64), 9, (1, 1))],
+    # pre-leaves that are no micro leaves (w = 3) next to r = 33 tree children, fan-in 8 and 9
+    "preleaf_vs_tree": [((16, 8), 9, (3, 16)), ((40, 33), 8, (17, 16)), ((40, 33), 9, (17, 16))],
+    "fanin_lds": [((64, 64), 8, (33, 40)), ((64, 64), 9, (33, 40)), ((100, 30), 2, (64, 64))],
+    "fanin_packed": [((100, 30), 8, (17, 16)), ((100, 30), 9, (65, 100)), ((130, 129), 2, (65, 100))],
+    # 128 / 129 update rows: gathered versus block-wise children, at the leaves and at the mids
+    "gather_128_129": [((130, 129), 2, (129, 129)), ((130, 129), 8, (64, 64)), ((200, 57), 2, (129, 129))],
+    "medium_mids": [((200, 57), 8, (33, 40)), ((200, 57), 9, (17, 16)), ((130, 129), 9, (3, 16))],
+    "big_mids": [((257, 100), 2, (65, 100)), ((257, 100), 8, (2, 7)), ((257, 100), 9, (33, 40))],
+    "big_mixed": [((257, 100), 2, (129, 129)), ((200, 57), 2, (64, 64)), ((16, 8), 8, (1, 1))],
+}
+
+
+def assembly_tree(name):
+    mids = ASSEMBLY_TREES[name]
+    for (wm, bm), k, (w, b) in mids:
+        assert b <= wm and k in (2, 8, 9)
+    return (max(bm for (_, bm), _, _ in mids) + 3, 0, [(wm, bm, [(w, b, [])] * k) for (wm, bm), k, (w, b) in mids])
+
+
+def perturbed_values(Lw, seed):
+    """vals * (1 + 0.3 U(0, 1)) per stored lower entry (the refactorisation's new matrix) and the
+    symmetric K of those values."""
+    vals2 = Lw.data * (1.0 + 0.3 * np.random.default_rng(seed).uniform(0.0, 1.0, Lw.nnz))
+    L2 = sp.csc_matrix((vals2, Lw.indices, Lw.indptr), shape=Lw.shape)
+    K2 = (L2 + sp.tril(L2, -1).T).tocsc()
+    K2.sort_indices()
+    return vals2, K2
+
+
+def dense_ldlt_longdouble(K):
+    """Pivots of the no-pivot LDL^T of a symmetric matrix in np.longdouble, right-looking on dense
+    storage (a column's structural zeros are skipped: their updates are exact zeros)."""
+    A = np.asarray(K.todense() if sp.issparse(K) else K).astype(np.longdouble)
+    n = A.shape[0]
+    d = np.empty(n, np.longdouble)
+    for k in range(n):
+        d[k] = A[k, k]
+        idx = k + 1 + np.flatnonzero(A[k + 1:, k])
+        if idx.size:
+            a = A[idx, k]
+            A[np.ix_(idx, idx)] -= np.outer(a / d[k], a)
+    return d
