@@ -441,6 +441,40 @@ def front_tree_classes(nodes, small_front_max=128, tree_fact=True):
                 max_front=max(nd["r"] for nd in nodes), fold_fronts=fold_fronts, fold_leaves=fold_leaves), ftree
 
 
+class FrontTreeCase:
+    """A prescribed-front matrix (front_tree_k2), the right-hand sides of the GPU sweeps — a random b,
+    e_j of the first leaf's first pivot, e_{N-1}, as one contiguous (3, N) block — and the prescribed
+    count of positive pivots (the columns of the blocks at even depth)."""
+
+    def __init__(self, root, seed):
+        self.root = root
+        self.K, self.Lw, self.nodes = front_tree_k2(root, seed)
+        self.N = self.K.shape[0]
+        rng = np.random.default_rng(seed + 2)
+        self.B = np.zeros((3, self.N))
+        self.B[0] = rng.standard_normal(self.N)
+        self.B[1, self.nodes[0]["first"]] = 1.0
+        self.B[2, self.N - 1] = 1.0
+        self.pos = sum(nd["w"] for nd in self.nodes if nd["depth"] % 2 == 0)
+        self.firsts = np.array([nd["first"] for nd in self.nodes])
+
+    def node_of_pivot(self, perm, k):
+        return int(np.searchsorted(self.firsts, perm[k], side="right") - 1)
+
+    def front_of_pivot(self, perm, k):
+        i = self.node_of_pivot(perm, k)
+        return f"front {i} (w={self.nodes[i]['w']}, r={self.nodes[i]['r']})"
+
+
+def assert_front_tree_plan(info, nodes, sfm, tree_fact, tag):
+    """A solver's info() has the classes that the prescribed fronts stand for (front_tree_classes), one
+    supernode per node and no batched leaf columns: a case that no longer reaches its path fails."""
+    want, _ = front_tree_classes(nodes, sfm, tree_fact)
+    got = {k: info[k] for k in want}
+    assert got == want and info["nsuper"] == len(nodes) and info["lb_groups"] == 0, \
+        f"{tag}: the plan misses its classes: {got} (nsuper {info['nsuper']}), prescribed {want}"
+
+
 LEAF_SHAPE_R = (2, 3, 17, 32, 33, 48, 64, 65, 96, 128, 129, 160, 191, 192, 193, 224, 256, 257, 300)
 
 
@@ -504,3 +538,209 @@ def dense_ldlt_longdouble(K):
             a = A[idx, k]
             A[np.ix_(idx, idx)] -= np.outer(a / d[k], a)
     return d
+
+
+# ---------------------------------------------------------------- planted pivot failures
+# (test_ldl_pivot_failure_gpu.py; pinned on the oracle in test_pivot_plants_cpu.py)
+PLANT_TOL = 1e-8          # the solvers' pivot_tol for tiny plants: six decades above the planted |d_k|
+                          # (<= 1e-12, pinned), seven below the smallest good pivot (>= 0.1, pinned)
+PLANT_COLUMNS = (0, 16, 17, 64, 65)   # and w - 1: pivot-block and panel boundaries of a front
+EXACT_VALUES = (0.0, -0.0, float("nan"), float("inf"))
+
+# the trees of the failed-pivot tests: (name, root, seed), the shape sweep's matrices (same seeds)
+PLANT_LEAF_SHAPES = ((32, 2), (32, 16), (64, 17), (128, 65), (192, 64), (224, 65), (300, 129))
+PLANT_ASSEMBLY = ("micro_fold", "big_mixed", "medium_mids")
+EXACT_LEAF_SHAPES = ((32, 2), (32, 16), (128, 65), (300, 129))
+# root plants only: nine tree children exceed the tree launch's fan-in of 8, so the root (43 rows) is
+# factorised after it by one in-LDS launch of roots — the plan that puts the root tail on a side stream
+ROOT_TAIL_TREE = (43, 0, [(33, 40, [])] * 9)
+
+
+def plant_tree(name):
+    """(root, seed) of a failed-pivot tree: 'leaf_R_W', 'root_tail' or an ASSEMBLY_TREES name."""
+    if name.startswith("leaf_"):
+        r, w = (int(t) for t in name.split("_")[1:])
+        return leaf_shape_tree(r, w), 1000 * r + w
+    if name == "root_tail":
+        return ROOT_TAIL_TREE, 77
+    return assembly_tree(name), sorted(ASSEMBLY_TREES).index(name)
+
+
+def plant_tree_names():
+    return [f"leaf_{r}_{w}" for r, w in PLANT_LEAF_SHAPES] + list(PLANT_ASSEMBLY)
+
+
+def root_plant_tree_names():
+    return plant_tree_names() + ["root_tail"]
+
+
+def plant_sfms(name):
+    """small_front_max values of a tree's configurations: 128, plus 192 for leaf_192_64."""
+    return (128, 192) if name == "leaf_192_64" else (128,)
+
+
+def plant_pivot(Lw, vals, perm, k, kind, d_ref=None, value=None):
+    """New lower-CSC values (same pattern as Lw, sorted indices) in which only the diagonal entry of
+    column j = perm[k] differs from vals:
+      'tiny'   K[j,j] -= d_ref[k]         pivot k becomes rounding noise (fails pivot_tol = PLANT_TOL)
+      'flip'   K[j,j] -= 1.5 d_ref[k]     pivot k becomes about -d_ref[k] / 2 (no failure, other inertia)
+      'exact'  K[j,j]  = value            (k the first column of a childless front: d_k = K[j,j] exactly)
+    d_ref: the oracle's pivots of the good matrix in the order perm."""
+    j = int(perm[k])
+    p = int(Lw.indptr[j])
+    assert Lw.indices[p] == j, "the diagonal entry leads its lower-CSC column"
+    out = np.array(vals, dtype=np.float64, copy=True)
+    if kind == "tiny":
+        out[p] -= d_ref[k]
+    elif kind == "flip":
+        out[p] -= 1.5 * d_ref[k]
+    elif kind == "exact":
+        out[p] = value
+    else:
+        raise ValueError(kind)
+    return out
+
+
+def symmetric_from_lower(Lw, vals):
+    """The symmetric CSC matrix of lower-CSC values on Lw's pattern (as perturbed_values builds it: the
+    diagonal is taken once, so a planted NaN or inf stays what it is)."""
+    L2 = sp.csc_matrix((np.asarray(vals, np.float64), Lw.indices, Lw.indptr), shape=Lw.shape)
+    K2 = (L2 + sp.tril(L2, -1).T).tocsc()
+    K2.sort_indices()
+    return K2
+
+
+def first_bad_pivot(d, nvalid, tol):
+    """The solver's failure rule on a pivot vector of which d[:nvalid + 1] is computed (the oracle stops
+    at an exact zero pivot, which it stores): the smallest k with !(|d_k| > tol) or |d_k| = inf; -1 if none."""
+    d = np.asarray(d)[:min(len(d), nvalid + 1)]
+    with np.errstate(invalid="ignore"):
+        bad = ~(np.abs(d) > tol) | np.isinf(d)
+    return int(np.argmax(bad)) if bad.any() else -1
+
+
+def oracle_plant(Lw, vals, perm, tol):
+    """(first bad pivot index or -1, the oracle's pivots, how many of them are computed) for lower-CSC
+    values in the pivot order perm."""
+    from oracle.ldl import OracleLDL
+    o = OracleLDL(symmetric_from_lower(Lw, vals), perm)
+    n = int(o.factorize())
+    d = o.diag()
+    nv = min(n + 1, Lw.shape[0])
+    return first_bad_pivot(d, n, tol), d, nv
+
+
+def front_plant_columns(w):
+    return sorted({c for c in PLANT_COLUMNS + (w - 1,) if 0 <= c < w})
+
+
+def tree_plant_pivots(nodes, perm, first, parent, nrows):
+    """[(pivot index k, node index, local column)] of the plants of a tree: front_plant_columns of every
+    front, in the analysis' pivot order (through fronts_in_pivot_order)."""
+    node_of, _ = fronts_in_pivot_order(nodes, perm, first, parent, nrows)
+    out = []
+    for s, i in enumerate(node_of):
+        out += [(int(first[s]) + c, i, c) for c in front_plant_columns(nodes[i]["w"])]
+    return out
+
+
+def plant_required_classes(nodes, sfm, tree_fact, big_dag):
+    """The front classes (names of the issue's list) that a configuration's plants reach, from the
+    planner model front_tree_classes, which every GPU configuration asserts against info()."""
+    want, ftree = front_tree_classes(nodes, sfm, tree_fact)
+    seen = {"root"}
+    for s, nd in enumerate(nodes):
+        leaf, w, r = not nd["children"], nd["w"], nd["r"]
+        if leaf and w <= 2 and r <= 32:
+            p = nd["parent"]       # folded: the parent is a fold front of front_tree_classes
+            pre = [nodes[q] for q in nodes[p]["children"] if not ftree[q]]
+            folded = ftree[p] and nodes[p]["r"] <= 192 and all(c["w"] <= 2 and c["r"] <= 32 for c in pre)
+            assert not folded or want["fold_leaves"] > 0
+            seen.add("micro_folded" if folded else "micro_unfolded")
+        elif leaf and r <= 32:
+            seen.add("tiny")
+        elif ftree[s] and r > 192:
+            seen.add("tree_medium")
+        elif ftree[s]:
+            seen.add("lds_tree")
+        elif r <= sfm:
+            seen.add("lds_level")
+        else:
+            seen.add("big_dag" if big_dag else "big_step")
+    return seen
+
+
+PLANT_CLASSES = ("micro_unfolded", "micro_folded", "tiny", "lds_level", "lds_tree", "tree_medium", "big_dag",
+                 "big_step", "root")
+
+
+def plant_configs(name, nodes, tree_fact):
+    """[(small_front_max, MADIPM_BIG_DAG, MADIPM_BIG_KPAN)] of a tree under one MADIPM_TREE_FACT: the
+    DAG / per-step and panel-depth sweep only where a front can be big (r >= 129)."""
+    big = max(nd["r"] for nd in nodes) >= 129
+    dk = [("1", "1"), ("1", "4"), ("0", "1"), ("0", "4")] if big else [(None, None)]
+    return [(sfm, dag, kpan) for sfm in plant_sfms(name) for dag, kpan in dk]
+
+
+def _pivot_of(nodes, perm, first, parent, nrows):
+    node_of, _ = fronts_in_pivot_order(nodes, perm, first, parent, nrows)
+    sup_of = {i: s for s, i in enumerate(node_of)}
+    return lambda i, c: int(first[sup_of[i]]) + c
+
+
+def pair_plant_pivots(name, nodes, perm, first, parent, nrows):
+    """[(k1, k2, nodes (i1, i2))], k1 < k2 in different subtrees, for the two-plants-at-once cases.
+    big_mixed: a micro leaf with a column of the 257-column mid (the analysis orders that mid's subtree
+    last, so the micro leaf holds the smaller index) and with a column of the 200-column mid (r = 257,
+    ordered before the micro leaves: the big front holds the smaller index).  leaf_128_65: the first
+    leaf with the third, and the third with the second (eliminated in the order first, third, second)."""
+    k = _pivot_of(nodes, perm, first, parent, nrows)
+    if name == "big_mixed":
+        micro = [i for i, nd in enumerate(nodes) if nd["w"] == 1 and nd["r"] == 2]
+        m257 = next(i for i, nd in enumerate(nodes) if nd["w"] == 257)
+        m200 = next(i for i, nd in enumerate(nodes) if nd["w"] == 200)
+        raw = [(micro[0], 0, m257, c) for c in (0, 64, 256)] + [(micro[-1], 0, m200, c) for c in (0, 65, 199)]
+    elif name == "leaf_128_65":
+        raw = [(0, 0, 2, 0), (0, 64, 2, 31), (0, 17, 2, 16), (2, 0, 1, 0), (2, 31, 1, 64), (2, 16, 1, 65)]
+    else:
+        raise ValueError(name)
+    out = []
+    for ia, ca, ib, cb in raw:
+        (k1, i1), (k2, i2) = sorted([(k(ia, ca), ia), (k(ib, cb), ib)])
+        out.append((k1, k2, (i1, i2)))
+    return out
+
+
+FLIP_TREES = ("big_mixed", "medium_mids")   # also the Cholesky-semantics trees (quasi-definite)
+
+
+def flip_plant_pivots(name, nodes, perm, first, parent, nrows):
+    """[(k, node)] of the flip plants: a column of a small leaf and a column of a big mid."""
+    k = _pivot_of(nodes, perm, first, parent, nrows)
+    leaf_w, leaf_c, mid_w, mid_c = {"big_mixed": (64, 17, 257, 65), "medium_mids": (33, 16, 200, 64)}[name]
+    leaf = next(i for i, nd in enumerate(nodes) if nd["w"] == leaf_w and not nd["children"])
+    mid = next(i for i, nd in enumerate(nodes) if nd["w"] == mid_w and nd["children"])
+    return [(k(leaf, leaf_c), leaf), (k(mid, mid_c), mid)]
+
+
+def exact_plant_pivots(nodes, perm, first, parent, nrows):
+    """[(k, node)]: the first column of every childless front (d_k = K[j,j] exactly there)."""
+    k = _pivot_of(nodes, perm, first, parent, nrows)
+    return [(k(i, 0), i) for i, nd in enumerate(nodes) if not nd["children"]]
+
+
+def batched_leaf_problem():
+    """dense_k2(128, 200, 3), natural order (N = 328): one batched-leaf group whose 200 members are the
+    single-column leaves x_j.  Returns (K, Lw, member pivots planted: first, a middle one, last)."""
+    K, Lw = dense_k2(128, 200, 3)
+    return K, Lw, (0, 101, 199)
+
+
+def signed_diagonal(n=20001, seed=7):
+    """A diagonal matrix with random signs and magnitudes in [0.5, 2]: more columns than one grid pass
+    of the inertia kernel (64 blocks) covers.  Returns (lower CSC, the diagonal)."""
+    rng = np.random.default_rng(seed)
+    d = rng.uniform(0.5, 2.0, n) * rng.choice([-1.0, 1.0], n)
+    Lw = sp.diags(d).tocsc()
+    Lw.sort_indices()
+    return Lw, d

@@ -26,8 +26,8 @@ import numpy as np
 import pytest
 import scipy.sparse.linalg as spla
 
-from helpers import (ASSEMBLY_TREES, FRONT_TREE_OPTS, LEAF_SHAPE_R, assembly_tree, front_tree_classes,
-                     front_tree_k2, leaf_shape_tree, leaf_shape_widths, perturbed_values)
+from helpers import (ASSEMBLY_TREES, FRONT_TREE_OPTS, LEAF_SHAPE_R, FrontTreeCase, assembly_tree,
+                     assert_front_tree_plan, leaf_shape_tree, leaf_shape_widths, perturbed_values)
 from oracle.ldl import OracleLDL
 
 pytestmark = pytest.mark.gpu
@@ -41,22 +41,13 @@ def _berr(K, x, b):
     return np.max(np.abs(K @ x - b)) / (spla.norm(K, np.inf) * np.max(np.abs(x)) + np.max(np.abs(b)))
 
 
-class _Case:
+class _Case(FrontTreeCase):
     """A tree's matrices, right-hand sides and oracle results: computed once, shared by its configurations."""
 
     def __init__(self, root, seed):
-        self.root = root
-        self.K, self.Lw, self.nodes = front_tree_k2(root, seed)
-        self.N = self.K.shape[0]
+        super().__init__(root, seed)
         vals2, K2 = perturbed_values(self.Lw, seed + 1)
         self.mats = [(self.K, self.Lw.data.copy()), (K2, vals2)]
-        rng = np.random.default_rng(seed + 2)
-        self.B = np.zeros((3, self.N))
-        self.B[0] = rng.standard_normal(self.N)
-        self.B[1, self.nodes[0]["first"]] = 1.0
-        self.B[2, self.N - 1] = 1.0
-        self.pos = sum(nd["w"] for nd in self.nodes if nd["depth"] % 2 == 0)
-        self.firsts = np.array([nd["first"] for nd in self.nodes])
         self._ref = {}
 
     def ref(self, perm):
@@ -71,10 +62,6 @@ class _Case:
                 out.append((o.diag(), X, np.array([_berr(M, x, b) for x, b in zip(X, self.B)])))
             self._ref[key] = out
         return self._ref[key]
-
-    def front_of_pivot(self, perm, k):
-        i = int(np.searchsorted(self.firsts, perm[k], side="right") - 1)
-        return f"front {i} (w={self.nodes[i]['w']}, r={self.nodes[i]['r']})"
 
 
 _CASES = {}
@@ -98,11 +85,7 @@ def _run(case, sfm, tree_fact, stats, tag):
     from madipm_amd.linear_solver import HIPLDLSolver
     N, Lw = case.N, case.Lw
     ls = HIPLDLSolver(N, Lw.indptr, Lw.indices, small_front_max=sfm, **FRONT_TREE_OPTS)
-    want, _ = front_tree_classes(case.nodes, sfm, tree_fact)
-    info = ls.info()
-    got = {k: info[k] for k in want}
-    assert got == want and info["nsuper"] == len(case.nodes) and info["lb_groups"] == 0, \
-        f"{tag}: the plan misses its classes: {got} (nsuper {info['nsuper']}), prescribed {want}"
+    assert_front_tree_plan(ls.info(), case.nodes, sfm, tree_fact, tag)
     perm = ls.perm()
     dev = torch.device("cuda:0")
     fails = []

@@ -40,11 +40,14 @@ def _free_column_lp():
                lvar=[0.0, 0.0, -INF], uvar=[INF, INF, INF], name="free_column")
 
 
-def _run_pair(qp, reg, pivot_tol=0.0, max_ncorr=0, **extra):
-    """GPU solve (AMD order) and the oracle with the oracle LDL^T in the GPU's pivot order."""
+def _run_pair(qp, reg, pivot_tol=0.0, max_ncorr=0, ldl_info=None, **extra):
+    """GPU solve (AMD order) and the oracle with the oracle LDL^T in the GPU's pivot order.
+    ldl_info: a dict that receives the GPU solver's LDL^T plan."""
     from madipm_amd import MPCSolver, FixedRegularization
     s = MPCSolver(qp, regularization=FixedRegularization(*reg), ordering=1, pivot_tol=pivot_tol,
                   max_ncorr=max_ncorr, max_iter=100, **extra)
+    if ldl_info is not None:
+        ldl_info.update(s.ldl_info())
     gpu = s.solve()
     o = OracleMPC(qp, OracleOptions(regularization=("fixed",) + tuple(reg), max_ncorr=max_ncorr, max_iter=100,
                                     **{k: v for k, v in extra.items() if k in ("check_residual", "tol_linear_solve")}))
@@ -70,6 +73,33 @@ def test_regularization_retry_matches_oracle(max_ncorr):
     for tg, tr in zip(gpu.trace[:3], ref.trace[:3]):
         for key in ("obj", "inf_pr", "inf_du", "mu"):
             assert abs(tg[key] - tr[key]) <= 1e-6 * abs(tr[key]) + 1e-12, (tg["k"], key, tg[key], tr[key])
+
+
+@pytest.mark.parametrize("max_ncorr", [0, 2])
+@pytest.mark.parametrize("seed", [0, 1])
+def test_regularization_retry_midsize_matches_oracle(seed, max_ncorr):
+    """The same retry through fronts beyond the 5 x 5 system's micro / tiny path: a 150 x 400 LP with 15 %
+    free columns (pivot del_w where one is eliminated before its rows), del_w = 1e-12 rejected by
+    pivot_tol = 1e-9 twice per iteration.  With max_ncorr = 0 every iteration first solves on the failed
+    factor.  Prints the LDL^T plan's front classes (pytest -s): which kernels took the failures."""
+    from madipm_amd import SOLVE_SUCCEEDED
+    from madipm_amd.instances import random_lp
+    qp = random_lp(150, 400, density=0.03, seed=seed, free_frac=0.15)
+    info = {}
+    gpu, ref = _run_pair(qp, (1e-12, -1e-8), pivot_tol=1e-9, max_ncorr=max_ncorr, ldl_info=info)
+    print(f"\nretry seed={seed} max_ncorr={max_ncorr}: LDL^T plan " + ", ".join(
+        f"{k}={info[k]}" for k in ("n", "nsuper", "max_front", "nbig", "tree_fronts", "tree_medium", "fold_fronts",
+                                   "fold_leaves", "lb_groups", "lb_members", "root_tail_async")))
+    assert gpu.status == ref.status == SOLVE_SUCCEEDED, (gpu.status_name, ref.status)
+    assert gpu.iter == ref.iter
+    dw_g = [t["del_w"] for t in gpu.trace]
+    dw_r = [t["del_w"] for t in ref.trace]
+    assert dw_g == dw_r, (dw_g, dw_r)
+    assert all(abs(d - 1e-8) <= 1e-20 for d in dw_g[1:]) and len(dw_g) > 1
+    for tg, tr in zip(gpu.trace[:3], ref.trace[:3]):
+        for key in ("obj", "inf_pr", "inf_du", "mu"):
+            assert abs(tg[key] - tr[key]) <= 1e-6 * abs(tr[key]) + 1e-12, (tg["k"], key, tg[key], tr[key])
+    assert abs(gpu.objective - ref.objective) <= 1e-6 * abs(ref.objective), (gpu.objective, ref.objective)
 
 
 def test_all_trials_fail_is_internal_error():
