@@ -12,10 +12,6 @@
 // Quasi-definite KKT matrices (FixedRegularization(1e-8,-1e-8)) admit static
 // pivoting in any symmetric order; zero / non-finite pivots are reported (is_factorized=false).
 #include <algorithm>
-#include <atomic>
-#include <thread>
-#include <array>
-#include <map>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
@@ -24,9 +20,9 @@
 #include "ldl.hpp"
 
 namespace madipm {
+using namespace ldlconst;  // NT and the other constants shared with the planner (ldl_plan.hpp)
 namespace {
 
-constexpr int NT = 256;
 typedef double dbl4 __attribute__((ext_vector_type(4)));
 
 // Pin loaded values (an empty asm that "modifies" them) so the compiler keeps clamped loads
@@ -159,125 +155,6 @@ __global__ void k_status_init(LDLStatus* st, int all = 0) {
   st->fail_pivot = INT_MAX;
   st->npos = st->nneg = st->nzero = 0;
   if (all) st->err = 0;
-}
-
-// ------------------------------------------------------------------ small fronts (LDS)
-// Register-tiled right-looking LDL^T: the lower triangle of F is cut into 16 x 16 tiles of TS x TS
-// entries (TS = 8 for r <= 128, 4 for r <= 64); thread q < 136 owns tile q in registers.  Step t:
-// the owners of column t publish it through LDS (double-buffered), one barrier, every thread
-// applies the rank-1 update to its tile.  The column loop is unrolled by TS so register indices
-// are static.
-template <int TS>
-__global__ __launch_bounds__(NT) void k_small_factor(FrontTab T, const int32_t* __restrict__ fronts,
-                                                     const double* __restrict__ Kx, double* __restrict__ arena,
-                                                     const double* __restrict__ fscratch, double* __restrict__ D,
-                                                     LDLStatus* st, double tol) {
-  extern __shared__ __attribute__((aligned(16))) double F[];  // r x r, col-major, ld r (leaf fronts only)
-  __shared__ double cb[2][16 * TS];
-  __shared__ double dp[16 * TS];
-  const int s = fronts[blockIdx.x];
-  const int f0 = T.first[s];
-  const int w = T.first[s + 1] - f0;
-  const int r = T.nrows[s];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  // tile of this thread: q -> (ti, tj), tj <= ti, 136 lower tiles of a 16 x 16 grid
-  int ti = 0, tj = 0;
-  {
-    int q = tid;
-    while (q > ti) {
-      q -= ti + 1;
-      ++ti;
-    }
-    tj = q;
-  }
-  const bool act = tid < 136 && ti * TS < r;
-  const int i0 = ti * TS, j0 = tj * TS;
-  double a[TS][TS];
-  const int64_t fso = T.fs_off[s];
-  if (fso >= 0) {
-    // assembled by k_assemble (lower triangle, ld r): every thread loads its tile straight from HBM,
-    // TS*TS independent loads in flight (no serialised staging copy); entries above the diagonal
-    // are never read
-    const double* __restrict__ Fs = fscratch + fso;
-#pragma unroll
-    for (int k = 0; k < TS; ++k)
-#pragma unroll
-      for (int c = 0; c < TS; ++c) {
-        const int i = i0 + k, j = j0 + c;
-        a[k][c] = (act && i < r && j <= i) ? Fs[i + (int64_t)j * r] : 0.0;
-      }
-  } else {  // leaf: original entries only, scattered into LDS
-    for (int q = tid; q < r * r; q += NT) F[q] = 0.0;
-    __syncthreads();
-    for (int64_t q = T.asm_ptr[s] + tid; q < T.asm_ptr[s + 1]; q += NT) F[T.asm_dst[q]] = Kx[T.asm_src[q]];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < TS; ++k)
-#pragma unroll
-      for (int c = 0; c < TS; ++c) a[k][c] = (act && i0 + k < r && j0 + c < r) ? F[(i0 + k) + (j0 + c) * r] : 0.0;
-  }
-  for (int t8 = 0; t8 < w; t8 += TS) {
-#pragma unroll
-    for (int c = 0; c < TS; ++c) {
-      const int t = t8 + c;
-      if (t < w) {  // block-uniform
-        double* colb = cb[t & 1];
-        if (act && tj == (t8 / TS)) {
-#pragma unroll
-          for (int k = 0; k < TS; ++k) colb[i0 + k] = a[k][c];
-        }
-        __syncthreads();
-        const double dt = colb[t];
-        if (tid == 0) dp[t] = dt;
-        const double dinv = 1.0 / dt;
-        double li[TS], cj[TS];
-#pragma unroll
-        for (int k = 0; k < TS; ++k) li[k] = (i0 + k > t) ? colb[i0 + k] * dinv : 0.0;
-#pragma unroll
-        for (int cc = 0; cc < TS; ++cc) cj[cc] = (j0 + cc > t) ? colb[j0 + cc] : 0.0;
-#pragma unroll
-        for (int k = 0; k < TS; ++k)
-#pragma unroll
-          for (int cc = 0; cc < TS; ++cc) a[k][cc] = fma(-li[k], cj[cc], a[k][cc]);
-      }
-    }
-  }
-  __syncthreads();
-  // write-out: L panel (ld r; d on the diagonal, zeros above), D, lower triangle of U (ld r - w)
-  double* __restrict__ L = arena + T.l_off[s];
-  double* __restrict__ Uo = arena + T.u_off[s];
-  const int u = r - w;
-  if (act) {
-#pragma unroll
-    for (int c = 0; c < TS; ++c) {
-      const int j = j0 + c;
-      if (j >= r) continue;
-      if (j < w) {
-        const double dj = dp[j];
-        const double dinv = 1.0 / dj;
-#pragma unroll
-        for (int k = 0; k < TS; ++k) {
-          const int i = i0 + k;
-          if (i < r) L[i + (int64_t)j * r] = (i > j) ? a[k][c] * dinv : (i == j ? dj : 0.0);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < TS; ++k) {
-          const int i = i0 + k;
-          if (i < r && i >= j) Uo[(i - w) + (int64_t)(j - w) * u] = a[k][c];
-        }
-      }
-    }
-  }
-  // upper part of the L panel (rows above the tile grid's lower triangle): zeros, so the solves can
-  // read the r x w panel as stored
-  for (int j = wv; j < w; j += NT / 64)
-    for (int i = lane; i < j - (j % TS); i += 64) L[i + (int64_t)j * r] = 0.0;
-  if (tid < w) {
-    const double d = dp[tid];
-    D[f0 + tid] = d;
-    if (bad_pivot(d, tol)) atomicMin(&st->fail_pivot, f0 + tid + 1);
-  }
 }
 
 // ------------------------------------------------------------------ micro fronts (w <= 2, r <= 32)
@@ -549,7 +426,7 @@ constexpr int ANT = 1024;
 // sum to the next (the straddle branch below); MADIPM_ASM_LDS_WIN=n (tests) puts every tile of up to
 // n windows on this path, whatever its launch size.  kAsmLdsWinMax bounds n: the count rides in 16
 // bits of gchk, and the kernel checks it against FrontTab::asm_src_cap (kErrAsmSrc).
-constexpr int kAsmLdsSrc = 5 * ANT, kAsmLdsWin = 4, kAsmLdsWinMax = 12;
+static_assert(kAsmLdsSrc == 5 * ANT, "five sources per thread and window");
 static_assert(kAsmLdsSrc * kAsmLdsWinMax < 65536, "the tile's source count rides in 16 bits");
 // The tile's chunk sums into the LDS tile Ts (64 x 64, column-major, ld 64; zeroed first): the
 // tile's nonempty entries (its g_ptr list: ne, then position | first chunk << 12 per entry, then the
@@ -2558,7 +2435,7 @@ __device__ __forceinline__ void stF(double* p, double v) {
   if constexpr (SC) __hip_atomic_store((gdouble*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else *(gdouble*)p = v;
 }
-constexpr int BIG_MSZ = 4 * 16 * LDM;  // doubles of one panel's M_K blocks
+static_assert(BIG_MSZ == 4 * 16 * LDM, "one panel's M_K blocks");
 
 // the diagonal block of panel `step`, staged in A64: factorised; L11 (d on the diagonal), D and the
 // M_K blocks (to M: the front's slot in Mbuf, or the panel's slot in k_big_dag's Mch) written
@@ -3046,7 +2923,6 @@ __global__ __launch_bounds__(NT, SYRK_WAVES) void k_lb_syrk(const double* __rest
 // blockIdx.x % nsplit of tile blockIdx.x / nsplit's K range (16-column chunks), stores its partial
 // product write-through (psum), and the last part to take the tile's ticket sums the partials in part
 // order (fixed: bitwise reproducible), then runs the epilogue (and the lookahead of tile (0, 0)).
-constexpr int UPD_PART = 4 * 4 * 4 * NT;  // partial product doubles of one part (acc of every thread)
 constexpr int U128_LDS = 4 * SYK * SYLD;   // As[2] then Bs[2]
 // acc[a][b] += sum_{k in [k0, k1)} (L D)[I0 + rows, k] L[J0 + cols, k] on a 128 x 128 tile of front F (ld r):
 // four waves x 64 x 64 quadrants of f64 MFMA 16x16x4, K-chunks of 16 double-buffered through LDS (AB)
@@ -3366,8 +3242,6 @@ __global__ __launch_bounds__(NT, 2) void k_big_dag(FrontTab T, const DagTask* __
 
 // forward: s_j = b(c_j) / d_j, t = W s (two passes: column chunks of LBF_COLS -> partials, then the
 // chunks summed in order), the group's update vector = -t; the members' forward values are b(c_j)
-constexpr int LBF_COLS = 256;
-constexpr int LB_KCHUNK = 2048;  // members per SYRK launch (m x 2048 doubles of W stay cache-resident)
 __global__ __launch_bounds__(NT) void k_lb_fwd1(const double* __restrict__ W, const double* __restrict__ dlb,
                                                 const int32_t* __restrict__ mem, const int32_t* __restrict__ perm,
                                                 int m, int n, int64_t mem0, const double* __restrict__ b,
@@ -3531,7 +3405,6 @@ __device__ __forceinline__ void bwd_subst16(double (&v)[3], const double* Ls, in
 }
 
 // r <= SMALL_SOLVE_MAX rows (3 per lane of wave 0), panel r x w staged in LDS (ld r | 1)
-constexpr int SMALL_SOLVE_MAX = 192;
 
 __global__ __launch_bounds__(NT) void k_fwd_small(FrontTab T, const int32_t* __restrict__ fronts, int nf,
                                                   const double* __restrict__ arena, const double* __restrict__ b,
@@ -3718,7 +3591,8 @@ __global__ __launch_bounds__(NT) void k_bwd_tiny(FrontTab T, const int32_t* __re
 // initial forward vector of a big front (own b entries + children's update vectors), in HBM;
 // task = (front, chunk of GAT_ROWS rows), GAT_G lanes per row stride the row's gather list (children
 // in list order per lane, lanes combined by a fixed butterfly: deterministic)
-constexpr int GAT_G = 8, GAT_ROWS = NT / GAT_G;
+constexpr int GAT_G = 8;
+static_assert(GAT_ROWS == NT / GAT_G, "rows of a gather task");
 __global__ __launch_bounds__(NT) void k_fwd_gather(FrontTab T, const int32_t* __restrict__ list,
                                                    const double* __restrict__ b, const double* __restrict__ uvec,
                                                    double* __restrict__ vwork) {
@@ -3907,7 +3781,6 @@ __global__ __launch_bounds__(NT) void k_fwd_big(FrontTab T, const SolveTask* __r
 // Backward, big fronts, rows below the pivot block (independent of the panel chain): task =
 // (front, panel p, 256-row chunk); writes bpart[(bp_off[front] + p * nchunk + chunk) * 64 + col] =
 // sum over the chunk's rows of L(row, col) x(row).  The chain kernel sums the chunks in order.
-constexpr int BWD_CHUNK = 256;
 __global__ __launch_bounds__(NT) void k_bwd_below(FrontTab T, const int32_t* __restrict__ list,
                                                   const int32_t* __restrict__ bp_off, const double* __restrict__ arena,
                                                   const double* __restrict__ xi, double* __restrict__ bpart) {
@@ -4069,8 +3942,6 @@ __global__ __launch_bounds__(NT) void k_bwd_big(FrontTab T, const SolveTask* __r
 // block loads its L entries unconditionally (16-byte LDS reads, immediate offsets) and the
 // dependency chain is one readlane + one fma per pivot.
 // dynamic LDS of the tree solves (+ ~2 KB static): two 256-thread workgroups per CU
-constexpr int TREE_ROOT_LDS = 150 * 1024;  // the big etree roots' own forward launch (LDSolver: nroot_task_)
-constexpr int TREE_SOLVE_LDS = 76 * 1024;
 __device__ __forceinline__ int tree_ldt(int w) { return ((w + 15) & ~15) + 2; }  // forward: row-major ld
 __device__ __forceinline__ int tree_ldc(int r) { return ((r + 31) & ~31) + 2; }  // backward: col-major ld
 
@@ -4220,7 +4091,6 @@ __device__ __forceinline__ void bwd_subst_t(double (&v)[3], const double* LT, in
 // a level-1 front to retire).  The L panel is streamed in 16-column chunks, double-buffered: wave 0
 // substitutes chunk c while waves 1..3 stage chunk c +- 1.  v (forward) / x (backward) stay in wave 0's
 // registers, 4 rows per lane.
-constexpr int MED_SOLVE_MAX = SymbolicPlan::kFactTreeMedMax;
 constexpr int MCW = 16, MLDT = MCW + 2;           // forward chunk: pivot columns, row-major ld
 constexpr int MFBUF = MED_SOLVE_MAX * MLDT;       // doubles per forward chunk buffer
 constexpr int MLDC = MED_SOLVE_MAX + 2;           // backward chunk: col-major ld
@@ -4989,10 +4859,47 @@ __global__ __launch_bounds__(NT) void k_gather_scatter(const int32_t* gidx, int6
   }
 }
 
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// Upload of a host table; returns the device pointer for the FrontTab field (or kernel argument) it
+// feeds.  up: a one-element placeholder when the table is empty, so kernels never see a null table.
+template <class T, class V>
+T* put(DBuf<T>& d, const V& v) {
+  d.upload(v);
+  return d.p;
+}
+template <class T, class V>
+T* up(DBuf<T>& d, const V& v, T fill = T{}) {
+  if (v.empty())
+    d.upload(&fill, 1);
+  else
+    d.upload(v);
+  return d.p;
+}
+
+bool env_on(const char* k) {
+  const char* v = std::getenv(k);
+  return v && v[0] && v[0] != '0';
+}
+
+// static + dynamic LDS of a kernel must fit one CU (160 KB on gfx950)
+void check_lds_fit(const void* f, size_t dyn, const char* nm) {
+  int dev = 0, cu_lds = 0;
+  MADIPM_HIP(hipGetDevice(&dev));
+  MADIPM_HIP(hipDeviceGetAttribute(&cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
+  hipFuncAttributes fa{};
+  MADIPM_HIP(hipFuncGetAttributes(&fa, f));
+  MADIPM_REQUIRE(fa.sharedSizeBytes + dyn <= (size_t)cu_lds,
+                 std::string(nm) + ": LDS " + std::to_string(fa.sharedSizeBytes) + " + " + std::to_string(dyn) +
+                     " bytes exceeds the CU's " + std::to_string(cu_lds));
+}
+
+void set_max_dyn_lds(const void* f, int bytes) {
+  MADIPM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+}
 
 }  // namespace
 
+// symbolic_analyze -> read_ldl_knobs -> build_launch_plan (ldl_plan.cpp: every launch decision, on the
+// host) -> uploads -> workspace -> function attributes
 LDLSolver::LDLSolver(int n, const int64_t* colptr, const int32_t* rowval, const SymbolicOptions& sopt,
                      double ptol, const int32_t* user_perm, Comm* comm)
     : pivot_tol(ptol), comm_(comm) {
@@ -5002,334 +4909,73 @@ LDLSolver::LDLSolver(int n, const int64_t* colptr, const int32_t* rowval, const 
   const SymbolicPlan& S = S_;
   MADIPM_REQUIRE(S.nshards == 1 || comm == nullptr || (comm->size == S.nshards && comm->rank == S.shard),
                  "communicator does not match the shard layout");
-  first_.upload(S.first);
-  nrows_.upload(S.nrows);
-  row_ptr_.upload(S.row_ptr);
-  rows_.upload(S.rows);
-  l_off_.upload(S.l_off);
-  u_off_.upload(S.u_off);
-  {  // a small tree front whose parent is a tree front stores its update block packed lower
-     // (u (u + 1) / 2, column-major; u_ld 0 on the device): written by k_fact_tree's write-out and read
-     // only by its tree parent's push (or a medium parent's add) — about half the square block's lines
-    std::vector<int32_t> uld(S.u_ld);
-    for (int f = 0; f < S.nsuper; ++f) {
-      const int p = S.parent[f];
-      if (!S.ftree.empty() && S.ftree[f] && S.nrows[f] <= SymbolicPlan::kFactTreeMax && p >= 0 && S.ftree[p] &&
-          S.nrows[f] > S.first[f + 1] - S.first[f])
-        uld[f] = 0;
-    }
-    u_ld_.upload(uld);
-  }
-  uvec_off_.upload(S.uvec_off);
-  asm_ptr_.upload(S.asm_ptr);
-  asm_src_.upload(S.asm_src);
-  asm_dst64_.upload(S.asm_dst);
-  child_ptr_.upload(S.child_ptr);
-  child_list_.upload(S.child_list);
-  rel_ptr_.upload(S.rel_ptr);
-  rel_.upload(S.rel);
-  perm_.upload(S.perm);
-  T_.first = first_;
-  {
-    const char* ek = std::getenv("MADIPM_BIG_KPAN");  // panels per deferred big-front update group
-    big_kpan_ = ek ? std::max(1, std::min(8, std::atoi(ek))) : 4;
-    const char* es = std::getenv("MADIPM_UPD_SPLIT");  // A/B: 0 = one workgroup per k_big_upd128 tile
-    upd_split_ = !(es && es[0] == '0');
-    const char* ec = std::getenv("MADIPM_BIG_DAG");  // A/B: 0 = one launch per panel step and kind
-    big_dag_ = !(ec && ec[0] == '0');
-    // persistent workgroups of the big-front solve kernels (2 per CU; MADIPM_BIG_SOLVE_WG for A/B)
-    if (const char* eg = std::getenv("MADIPM_BIG_SOLVE_WG")) big_solve_wg_ = std::max(64, std::atoi(eg));
-    // pipelined in-LDS factorisation schedule (1, default); 0 = the barrier schedule, bitwise the same
-    // factor (test_ldl_fact_pipe_bitwise)
-    const char* ep = std::getenv("MADIPM_FACT_PIPE");
-    T_.fpipe = (ep && ep[0] == '0') ? 0 : 1;
-    const char* ef = std::getenv("MADIPM_DEBUG_PIPE_FAULT");  // tests: drop one hand-off (sticky error)
-    T_.pipe_fault = (ef && ef[0] == '1') ? 1 : 0;
-    // the assembly's device-side source-count check (MADIPM_DEBUG_ASM_SRC_CAP=<n>, tests only: a
-    // smaller bound, so the check fires)
-    T_.asm_src_cap = kAsmLdsSrc * kAsmLdsWinMax;
-    if (const char* e = std::getenv("MADIPM_DEBUG_ASM_SRC_CAP")) T_.asm_src_cap = std::atoi(e);
-  }
-  T_.nrows = nrows_;
-  T_.row_ptr = row_ptr_;
-  T_.rows = rows_;
-  T_.l_off = l_off_;
-  T_.u_off = u_off_;
-  T_.u_ld = u_ld_;
-  T_.uvec_off = uvec_off_;
-  T_.asm_ptr = asm_ptr_;
-  T_.asm_src = asm_src_;
-  T_.asm_dst = asm_dst64_;
-  T_.child_ptr = child_ptr_;
-  T_.child_list = child_list_;
-  T_.rel_ptr = rel_ptr_;
-  T_.rel = rel_;
-  T_.perm = perm_;
-  fs_off_.upload(S.fs_off);
-  sv_ptr_.upload(S.sv_ptr);
-  sv_src_.upload(S.sv_src);
-  sv_nt_.alloc(std::max<int64_t>(S.row_ptr[S.nsuper], 1));  // the tree solve's split (set with its tables)
-  sv_nt_.zero();
-  // g_ptr_, atiles_: with the big-child records below (bt renumbered, source-path tiles)
-  {
-    // int32 sources when every arena / K index fits (leaf update blocks stay materialised: forming
-    // them from the leaves' L panels in the gather was measured slower, r1 — 6 scattered loads per
-    // source instead of 1)
-    // (the check and the narrowing on the analysis threads: ~170 M sources on neos)
-    const int64_t ns = (int64_t)S.g_src.size();
-    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(analysis_threads(), ns / 4000000));
-    hvec<int32_t> g32(ns);
-    std::atomic<bool> fits{ns > 0};
-    {
-      std::vector<std::thread> th;
-      for (int t = 0; t < T; ++t)
-        th.emplace_back([&, t]() {
-          const int64_t q0 = ns * t / T, q1 = ns * (t + 1) / T;
-          bool ok = true;
-          for (int64_t q = q0; q < q1; ++q) {
-            const int64_t v = S.g_src[q];
-            ok = ok && v >= INT32_MIN && v < (1LL << 30);
-            g32[q] = (int32_t)v;
-          }
-          if (!ok) fits = false;
-        });
-      for (auto& x : th) x.join();
-    }
-    if (fits) {
-      g_src32_.upload(g32);
-    } else {
-      g_src_.upload(S.g_src);
-    }
-  }
+  knobs_ = read_ldl_knobs();
+  LaunchPlan P;  // host tables: they live until the uploads are done (the synchronisation at the end)
+  build_launch_plan(S, knobs_, P);
+  clk("launch plan (total)");
+  const int ns = S.nsuper, NL = S.nlevels;
+
+  // ---- front tables
+  T_.first = put(first_, S.first);
+  T_.nrows = put(nrows_, S.nrows);
+  T_.row_ptr = put(row_ptr_, S.row_ptr);
+  T_.rows = put(rows_, S.rows);
+  T_.l_off = put(l_off_, S.l_off);
+  T_.u_off = put(u_off_, S.u_off);
+  T_.u_ld = put(u_ld_, P.u_ld);
+  T_.uvec_off = put(uvec_off_, S.uvec_off);
+  T_.asm_ptr = put(asm_ptr_, S.asm_ptr);
+  T_.asm_src = put(asm_src_, S.asm_src);
+  T_.asm_dst = put(asm_dst64_, S.asm_dst);
+  T_.child_ptr = put(child_ptr_, S.child_ptr);
+  T_.child_list = put(child_list_, S.child_list);
+  T_.rel_ptr = put(rel_ptr_, S.rel_ptr);
+  T_.rel = put(rel_, S.rel);
+  T_.perm = put(perm_, S.perm);
+  T_.fs_off = put(fs_off_, S.fs_off);
+  T_.fs_img = put(fs_img_, P.fs_img);
+  T_.sv_ptr = put(sv_ptr_, S.sv_ptr);
+  T_.sv_src = put(sv_src_, P.sv_src);  // reordered: tree-task entries last, sv_nt of them per row
+  T_.sv_nt = put(sv_nt_, P.sv_nt);
+  T_.bigslot = put(bigslot_, P.bigslot);
+  T_.upos = put(upos_, P.upos);
+  T_.fpipe = knobs_.fact_pipe;
+  T_.pipe_fault = knobs_.pipe_fault;
+  T_.asm_src_cap = knobs_.asm_src_cap;
+  T_.lds_cap = P.lds_cap;
+  // ---- assembly: int32 sources when every arena / K index fits
+  if (P.g32_fits)
+    g_src32_.upload(P.g_src32);
+  else
+    g_src_.upload(S.g_src);
+  P.g_src32 = {};
   g_chunk_.upload(S.g_chunk);
   gpart_.alloc(std::max<size_t>(S.g_chunk.size(), 1));
-  std::vector<int64_t> asm_cid_off;  // per assembly group: its chunk-path chunks' range in chunk_ids_
-  {  // big-child records of the assembly tiles (BigChildRec): a bt entry's block, split into column
-     // ranges of <= kBigRecEntries entries; the tiles' bt0 / bt1 renumbered to the records
-    const int64_t nb = (int64_t)S.bt.size() / 5;
-    std::vector<int64_t> rptr(nb + 1, 0);
-    for (int64_t k = 0; k < nb; ++k) {
-      const int32_t* e = &S.bt[5 * k];
-      const int na = e[4] - e[3], nbt = e[2] - e[1], cpr = kBigRecEntries / na;
-      MADIPM_REQUIRE(na >= 1 && na <= 64 && nbt >= 1 && nbt <= 64, "assembly: big-child block outside its tile");
-      rptr[k + 1] = rptr[k] + (nbt + cpr - 1) / cpr;
-    }
-    MADIPM_REQUIRE(rptr[nb] < INT32_MAX, "assembly: too many big-child records");
-    std::vector<BigChildRec> br(std::max<int64_t>(rptr[nb], 1));
-    const int T = (int)std::min<int64_t>(analysis_threads(), std::max<int64_t>(1, nb / 4096));
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t)
-      th.emplace_back([&, t]() {
-        for (int64_t k = t; k < nb; k += T) {
-          const int32_t* e = &S.bt[5 * k];
-          const int c = e[0], b0 = e[1], b1 = e[2], a0 = e[3], a1 = e[4];
-          const int32_t* rel = S.rel.data() + S.rel_ptr[c];
-          const int I0 = rel[a0] & ~63, J0 = rel[b0] & ~63;
-          const int na = a1 - a0, cpr = kBigRecEntries / na;
-          for (int64_t q = rptr[k]; q < rptr[k + 1]; ++q) {
-            BigChildRec& R = br[q];
-            R = BigChildRec{};
-            R.u_off = S.u_off[c];
-            R.u_ld = S.u_ld[c];
-            R.a0 = a0;
-            R.b0 = b0 + (int)(q - rptr[k]) * cpr;
-            R.na = (uint16_t)na;
-            R.nb = (uint16_t)std::min(cpr, b1 - R.b0);
-            R.na_inv = (65536u + na - 1) / na;
-            for (int i = 0; i < na; ++i) R.rows[i] = (uint8_t)(rel[a0 + i] - I0);
-            for (int j = 0; j < R.nb; ++j) R.cols[j] = (uint8_t)(rel[R.b0 + j] - J0);
-          }
-        }
-      });
-    for (auto& x : th) x.join();
-    brec_.upload(br);
-    std::vector<SymbolicPlan::AsmTile> at(S.atiles);
-    for (auto& a : at) {
-      a.bt0 = (int32_t)rptr[a.bt0];
-      a.bt1 = (int32_t)rptr[a.bt1];
-      // the tile's nonempty-entry count rides in gptr's top 16 bits (asm_chunks_lds: no load of it)
-      MADIPM_REQUIRE(a.gptr < ((int64_t)1 << 47), "assembly: entry list offset past 2^47");
-      if (a.gptr >= 0) a.gptr |= (int64_t)S.g_ptr[a.gptr] << 48;
-    }
-    // Tiles of <= kAsmLdsWin windows of sources sum them from LDS (asm_chunks_lds): their entry lists point at
-    // sources (pos | first source << 12, then the count << 12), gptr bit 47 set, gchk = the first
-    // source | the count << 48; the chunk pass keeps only the other tiles' chunks (chunk_ids_, per
-    // assembly group).  MADIPM_ASM_LDS_SRC=0: every tile through the chunk pass (A/B).
-    const char* el = std::getenv("MADIPM_ASM_LDS_SRC");
-    const bool lds_src = !(el && el[0] == '0');
-    int force_win = 0;  // tests: every tile of <= n windows on the LDS source path (no launch-size rule)
-    if (const char* ew = std::getenv("MADIPM_ASM_LDS_WIN")) force_win = std::max(0, std::min(kAsmLdsWinMax, std::atoi(ew)));
-    std::vector<int32_t> gp2(S.g_ptr);
-    std::vector<int64_t> cids;
-    int64_t st_lds = 0, st_multi = 0, st_straddle = 0, st_chunk = 0, st_nsmax = 0;  // MADIPM_ASM_STATS
-    asm_cid_off.assign(S.atile_lev.size(), 0);
-    for (size_t g = 0; g + 1 < S.atile_lev.size(); ++g) {
-      asm_cid_off[g] = (int64_t)cids.size();
-      for (int32_t t = S.atile_lev[g]; t < S.atile_lev[g + 1]; ++t) {
-        const SymbolicPlan::AsmTile& a0 = S.atiles[t];
-        if (a0.gptr < 0) continue;
-        const int32_t ne = S.g_ptr[a0.gptr];
-        const int64_t nchk = S.g_ptr[a0.gptr + ne + 1] >> 12, cb = a0.gchk;
-        const int64_t sb = S.g_chunk[cb], ns = S.g_chunk[cb + nchk] - sb;
-        // one window in k_assemble's launches of < 256 tiles (LDLSolver::run_fact's one-tile-per-CU
-        // instance), kAsmLdsWin elsewhere (k_asm_update: the tiles past the group's fused-front mark)
-        const int32_t aend = (int)g < S.nlevels ? S.atile_fz1[g] : S.atile_lev[g + 1];
-        const int64_t nwin = force_win ? force_win : (t < aend && aend - S.atile_lev[g] < 256) ? 1 : kAsmLdsWin;
-        if (lds_src && ns <= kAsmLdsSrc * nwin && sb < ((int64_t)1 << 48)) {
-          for (int32_t k = 0; k < ne; ++k) {
-            const int32_t e = S.g_ptr[a0.gptr + 1 + k];
-            gp2[a0.gptr + 1 + k] = (e & 4095) | (int32_t)((S.g_chunk[cb + (e >> 12)] - sb) << 12);
-          }
-          gp2[a0.gptr + ne + 1] = (int32_t)(ns << 12);
-          at[t].gptr |= (int64_t)1 << 47;
-          at[t].gchk = sb | (ns << 48);
-          ++st_lds;
-          st_multi += ns > kAsmLdsSrc;
-          st_nsmax = std::max(st_nsmax, ns);
-          for (int32_t k = 0; k < ne; ++k) {  // entries whose sources cross a window boundary
-            const int64_t a = gp2[a0.gptr + 1 + k] >> 12, b = gp2[a0.gptr + 2 + k] >> 12;
-            st_straddle += b > a && a / kAsmLdsSrc != (b - 1) / kAsmLdsSrc;
-          }
-        } else {
-          for (int64_t c = cb; c < cb + nchk; ++c) cids.push_back(c);
-          ++st_chunk;
-        }
-      }
-    }
-    asm_cid_off.back() = (int64_t)cids.size();
-    if (std::getenv("MADIPM_ASM_STATS"))
-      fprintf(stderr, "asm lds-src: tiles %lld (multi-window %lld, straddling entries %lld, max sources %lld)  chunk-path tiles %lld\n",
-              (long long)st_lds, (long long)st_multi, (long long)st_straddle, (long long)st_nsmax, (long long)st_chunk);
-    g_ptr_.upload(gp2);
-    chunk_ids_.upload(cids);
-    atiles_.upload(at);
-  }
+  brec_.upload(P.brec);
+  g_ptr_.upload(P.g_ptr);
+  chunk_ids_.upload(P.chunk_ids);
+  atiles_.upload(P.atiles);
   fscratch_.alloc(std::max<int64_t>(S.fs_size, 1));
-  T_.fs_off = fs_off_;
-  {
-    // fronts staged into LDS by k_fact_tree (all sizes) and k_small_blocked (r > 32, not big, not a
-    // batched-leaf parent, whose SYRK writes ld r) are pre-assembled as their LDS image
-    std::vector<uint8_t> img(std::max<size_t>(S.nrows.size(), 1), 0);
-    std::vector<uint8_t> lbpar(S.nrows.size(), 0);
-    for (const auto& G : S.lb) lbpar[G.parent] = 1;
-    for (size_t f = 0; f < S.nrows.size(); ++f)
-      img[f] = (S.fs_off[f] >= 0 &&
-                (S.ftree[f] ? !S.absorb[f] : (!S.is_big[f] && !lbpar[f] && S.nrows[f] > 32))) ? 1 : 0;
-    fs_img_.upload(img);
-    T_.fs_img = fs_img_;
-  }
-  T_.sv_ptr = sv_ptr_;
-  T_.sv_src = sv_src_;
-  T_.sv_nt = sv_nt_;
-  const int ns = S.nsuper, NL = S.nlevels;
-  {
-    std::vector<int32_t> slot(std::max(ns, 1), -1);
-    int nslot = 0;
-    for (int s = 0; s < ns; ++s)
-      if (S.is_big[s]) slot[s] = nslot++;
-    bigslot_.upload(slot);
-    minv_.alloc((int64_t)std::max(nslot, 1) * 4096);
-    T_.bigslot = bigslot_;
-  }
-  // sharding tables (unsharded: xoff = -1, every x written, every column counted)
-  {
-    std::vector<int64_t> xo(std::max(ns, 1), -1);
-    std::vector<uint8_t> wo(std::max(ns, 1), 1), cm(std::max(S.N, 1), 1);
-    // solution exchange: every shard writes the top x it computes redundantly; the subtree x are
-    // all-gathered by shard slices (the partition is shard-independent, so every shard knows them all)
-    std::vector<int32_t> gi;
-    if (S.nshards > 1) {
-      std::vector<std::vector<int32_t>> own(S.nshards);
-      for (int s = 0; s < ns; ++s) {
-        xo[s] = S.xoff[s];
-        for (int j = S.first[s]; j < S.first[s + 1]; ++j) {
-          cm[j] = S.top(s) ? 2 : (S.mine(s) ? 1 : 0);
-          if (!S.top(s)) own[S.owner[s]].push_back(S.perm[j]);
-        }
-      }
-      for (const auto& o : own) gper_ = std::max<int64_t>(gper_, (int64_t)o.size());
-      gper_ = std::max<int64_t>(gper_, 1);
-      gi.assign((size_t)(S.nshards * gper_), -1);
-      for (int q = 0; q < S.nshards; ++q) std::copy(own[q].begin(), own[q].end(), gi.begin() + q * gper_);
-    }
-    gidx_.upload(gi.empty() ? std::vector<int32_t>{-1} : gi);
-    gsol_.alloc(std::max<int64_t>(S.nshards * gper_, 1));
-    xoff_.upload(xo);
-    wout_.upload(wo);
-    colmask_.upload(cm);
-    xch_.alloc(std::max<int64_t>(S.xlen, 1));
-    sx_ptr_.upload(S.sx_ptr.empty() ? std::vector<int64_t>{0} : S.sx_ptr);
-    sx_src_.upload(S.sx_src.empty() ? std::vector<int64_t>{0} : S.sx_src);
-    T_.xoff = xoff_;
-    T_.xch = xch_;
-    T_.wout = wout_;
-  }
-  auto lb_member = [&](int s) { return !S.lb_of.empty() && S.lb_of[s] >= 0; };
-  // solve classes: fronts up to SMALL_SOLVE_MAX rows whose L panel fits in LDS take the one-launch
-  // workgroup-per-front kernels; larger ones the dependency-driven big-front kernels
-  auto solve_small = [&](int s) {
-    const int r = S.nrows[s], w = S.first[s + 1] - S.first[s];
-    return r <= SMALL_SOLVE_MAX && 8 * (r | 1) * w <= 150 * 1024;
-  };
-  auto in_phase = [&](int s, int phase) {
-    if (lb_member(s)) return false;  // batched leaves: W build + the parent's SYRK + GEMV solves
-    return phase == 1 ? (!S.top(s) && S.mine(s)) : S.top(s);
-  };
-  auto tree_panel_doubles = [&](int s) {  // max(forward row-major, backward col-major) staged panel
-    const int r = S.nrows[s], w = S.first[s + 1] - S.first[s];
-    const int ldt = ((w + 15) & ~15) + 2, ldc = ((r + 31) & ~31) + 2;
-    return std::max<int64_t>((int64_t)r * ldt, (int64_t)w * ldc);
-  };
-  // tree solve set (k_fwd_tree / k_bwd_tree); MADIPM_TREE_SOLVE=0 disables it (A/B measurements)
-  std::vector<char> in_tree(std::max(ns, 1), 0);
-  {
-    const char* ev = std::getenv("MADIPM_TREE_SOLVE");
-    const bool on = !(ev && ev[0] == '0');
-    std::vector<char> lbpar(std::max(ns, 1), 0);
-    for (const auto& G : S.lb) lbpar[G.parent] = 1;
-    auto preleaf = [&](int c) { return S.child_ptr[c] == S.child_ptr[c + 1] && S.nrows[c] <= 32; };
-    // fronts whose whole panel (+ 8 KB of gather staging) does not fit TREE_SOLVE_LDS, medium fronts
-    // (SMALL_SOLVE_MAX < r <= MED_SOLVE_MAX) included, join with their panel streamed in chunks
-    for (int s = 0; on && s < ns; ++s) {  // postorder: children first
-      if (!in_phase(s, 1) || preleaf(s) || lbpar[s] || S.nrows[s] > MED_SOLVE_MAX) continue;
-      bool ok = true;
-      for (int q = S.child_ptr[s]; q < S.child_ptr[s + 1] && ok; ++q) {
-        const int c = S.child_list[q];
-        ok = in_tree[c] || (preleaf(c) && in_phase(c, 1));
-      }
-      in_tree[s] = ok;
-    }
-  }
-  // micro leaves (w <= 2, r <= 32, no children) under tree fronts, solved from precomputed leaf records
-  // (SolveLeaf) by the flat k_fwd_leaves / k_bwd_leaves launches (r3: solving them inside the tree tasks,
-  // or their backward only, measured slower: 1478 vs 1534 iters/s)
-  std::vector<char> sleaf(std::max(ns, 1), 0);
-  {
-    for (int c = 0; c < ns; ++c) {
-      const int p = S.parent[c];
-      sleaf[c] = p >= 0 && in_tree[p] && in_phase(c, 1) && S.child_ptr[c] == S.child_ptr[c + 1] && S.nrows[c] <= 32 &&
-                 S.first[c + 1] - S.first[c] <= 2;
-    }
-  }
+  minv_.alloc((int64_t)std::max(P.nbigslot, 1) * 4096);
+  // ---- sharding
+  gper_ = P.gper;
+  up(gidx_, P.gidx, -1);
+  gsol_.alloc(std::max<int64_t>(S.nshards * gper_, 1));
+  T_.xoff = put(xoff_, P.xoff);
+  T_.wout = put(wout_, P.wout);
+  colmask_.upload(P.colmask);
+  xch_.alloc(std::max<int64_t>(S.xlen, 1));
+  T_.xch = xch_;
+  up(sx_ptr_, S.sx_ptr);
+  up(sx_src_, S.sx_src);
   // ---- batched leaf columns
-  lb_at_level_.assign(std::max(NL, 1), {});
+  lb_at_level_ = std::move(P.lb_at_level);
   if (!S.lb.empty()) {
     lbg_.upload(S.lb);
     lbmem_.upload(S.lb_mem);
-    std::vector<int32_t> gid(S.lb_mem.size()), xrow;
-    std::vector<int64_t> poff;
-    int64_t np = 0;
-    for (size_t g = 0; g < S.lb.size(); ++g) {
-      const auto& G = S.lb[g];
-      for (int j = 0; j < G.n; ++j) gid[G.mem_off + j] = (int32_t)g;
-      for (int k = 0; k < G.m; ++k) xrow.push_back(S.rows[S.row_ptr[G.parent] + S.lb_gpos[G.gpos_off + k]]);
-      poff.push_back(np);
-      np += (int64_t)cdiv(G.n, LBF_COLS) * G.m;
-      lb_at_level_[S.level[G.parent]].push_back((int)g);
-    }
-    lbgid_.upload(gid);
-    lbxrow_.upload(xrow);
-    lbpoff_.upload(poff);
+    lbgid_.upload(P.lb_gid);
+    lbxrow_.upload(P.lb_xrow);
+    lbpoff_.upload(P.lb_poff);
     lbcs_.upload(S.lb_cs);
     lbce_.upload(S.lb_ce);
     lbwbase_.upload(S.lb_wbase);
@@ -5338,1044 +4984,157 @@ LDLSolver::LDLSolver(int n, const int64_t* colptr, const int32_t* rowval, const 
     lbW_.alloc(std::max<int64_t>(S.lb_wsize, 1));
     lbW_.zero();  // the pattern is fixed: entries outside it stay 0
     lbd_.alloc(2 * S.lb_mem.size());
-    lbpart_.alloc(std::max<int64_t>(np, 1));
+    lbpart_.alloc(std::max<int64_t>(P.lb_npart, 1));
   }
-
   clk("tables + uploads");
-  // ---- factorisation tree tables (k_fact_tree)
-  {
-    std::vector<int32_t> ord(S.ft_order), dptr{0}, dl;  // ticket order (SymbolicPlan::ft_order)
-    nftree_ = (int)ord.size();
-    for (int s : ord) {
-      for (int q = S.child_ptr[s]; q < S.child_ptr[s + 1]; ++q)
-        if (S.ftree[S.child_list[q]]) dl.push_back(S.child_list[q]);
-      dptr.push_back((int32_t)dl.size());
-      const int r = S.nrows[s], w = S.first[s + 1] - S.first[s], u = r - w;
-      const bool sq = r <= 128 && !S.fold_pk[s];
-      if (r > SymbolicPlan::kFactTreeMax)  // medium front: one panel (r | 1) x min(64, w) in LDS
-        ftree_lds_ = std::max<int>(ftree_lds_, 8 * (((r | 1) * std::min(64, w) + 1) & ~1));
-      else
-      ftree_lds_ = std::max<int>(ftree_lds_, (sq ? 8 * ((r * (r | 1) + 1) & ~1) : 8 * ((r * (r + 1) / 2 + 1) & ~1)) +
-                                                 (S.absorb[s] ? SymbolicPlan::kFoldRowBytes * S.fold_rmax[s] +
-                                                                    SymbolicPlan::kFoldLeafBytes * S.fold_lmax[s]
-                                                              : 0));
-      // folded leaves: their K entries read, their L entries written
-      for (int k = S.absorb[s] ? S.mc_ptr[s] : 0; k < (S.absorb[s] ? S.mc_ptr[s + 1] : 0); ++k) {
-        const int c = S.mc_list[k];
-        const double rc = S.nrows[c], wc = S.first[c + 1] - S.first[c];
-        ftree_bytes_ += 12.0 * (S.asm_ptr[c + 1] - S.asm_ptr[c]) + 8.0 * (rc * wc - wc * (wc - 1) / 2.0);
-        ftree_alg_ += fact_alg(c);
-        for (int t = 0; t < (int)wc; ++t) ftree_flops_ += (rc - t - 1) * (rc - t);
-      }
-      // staging model: the stored lower trapezoid of the panel written and the front's scatter list
-      // read (ftree_bytes_); SURVEY 8(d)'s algorithmic bytes (B_fact = 8 nnzL + 12 nnzK of the
-      // front's columns, exact column counts) in ftree_alg_
-      (void)u;
-      ftree_bytes_ += 8.0 * (r * (double)w - w * (w - 1) / 2.0) + 12.0 * (double)(S.asm_ptr[s + 1] - S.asm_ptr[s]);
-      ftree_alg_ += fact_alg(s);
-      for (int t = 0; t < w; ++t) ftree_flops_ += (double)(r - t - 1) * (r - t);
-    }
-    if (const char* ev = std::getenv("MADIPM_TREE_DEBUG"); ev && ev[0] == '1') {  // per-level front shapes
-      std::map<int, std::array<double, 7>> lv;  // count, sum r, max r, sum w, sum lds, max lds, sum leaves
-      for (int s : ord) {
-        const int r = S.nrows[s], w = S.first[s + 1] - S.first[s];
-        const bool sq = r <= 128 && !S.fold_pk[s];
-        const double lds = (sq ? 8.0 * r * (r | 1) : 4.0 * r * (r + 1)) +
-                           (S.absorb[s] ? SymbolicPlan::kFoldRowBytes * S.fold_rmax[s] + SymbolicPlan::kFoldLeafBytes * S.fold_lmax[s] : 0);
-        auto& a = lv[S.level[s]];
-        a[0] += 1, a[1] += r, a[2] = std::max<double>(a[2], r), a[3] += w, a[4] += lds, a[5] = std::max(a[5], lds);
-        a[6] += S.absorb[s] ? S.mc_ptr[s + 1] - S.mc_ptr[s] : 0;
-      }
-      for (auto& [l, a] : lv)
-        fprintf(stderr, "tree level %d: %4.0f fronts  r avg %.0f max %.0f  w avg %.1f  LDS avg %.0f max %.0f KB  leaves avg %.0f\n", l,
-                a[0], a[1] / a[0], a[2], a[3] / a[0], a[4] / a[0] / 1024, a[5] / 1024, a[6] / a[0]);
-    }
-    // the device-side carve check compares against this (MADIPM_DEBUG_LDS_SHRINK=<bytes>, tests only:
-    // pretend the launch has that much less, so the check fires)
-    T_.lds_cap = ftree_lds_;
-    if (const char* e = std::getenv("MADIPM_DEBUG_LDS_SHRINK")) T_.lds_cap -= std::atoi(e);
-    auto up = [](DBuf<int32_t>& d, const std::vector<int32_t>& v) { d.upload(v.empty() ? std::vector<int32_t>{0} : v); };
-    clk("  tree tables");
-    // fold helpers: a front with two or more leaf batches hands the first half of them to a helper
-    // ticket (before every front's; the helpers with the most batches first), folds the rest itself
-    // and adds the helper's image after its waits (MADIPM_FOLD_HELP=0: no helpers)
-    {
-      const char* eh = std::getenv("MADIPM_FOLD_HELP");
-      const bool on = !(eh && eh[0] == '0');
-      int min_nb = 3;  // fronts of at least this many batches get a helper (MADIPM_FOLD_HELP_MIN: A/B)
-      if (const char* em = std::getenv("MADIPM_FOLD_HELP_MIN")) min_nb = std::max(2, std::atoi(em));
-      int share4 = 2;  // the helper's share of the batches, in quarters (MADIPM_FOLD_HELP_SHARE: A/B)
-      if (const char* es = std::getenv("MADIPM_FOLD_HELP_SHARE")) share4 = std::max(1, std::min(3, std::atoi(es)));
-      std::vector<int32_t> help(std::max(ns, 1), -1);
-      std::vector<FoldStart> fst(std::max(ns, 1), FoldStart{0, 0, 0, 0, 0, 0, 0, 0, 0});
-      auto start = [&](int b0, int b1) {  // batches [b0, b1) and the first one's table entries
-        FoldStart F{b0, b1, 0, 0, 0, 0, 0, 0, 0};
-        if (b1 > b0) {
-          F.kq0 = S.fold_bat[b0];
-          F.kq1 = S.fold_bat[b0 + 1];
-          F.row0 = S.fold_row0[b0];
-          F.row1 = S.fold_row0[b0 + 1];
-          F.poff = S.fold_poff[b0];
-          F.plen = S.fold_plen[b0];
-        }
-        return F;
-      };
-      std::vector<FoldHelp> hv;
-      std::vector<uint16_t> hdst;  // per helper: the sorted LDS destinations its batches' products reach
-      int64_t img = 0;
-      // the run-end entries of a batch's product chunks name every destination it writes (a parked
-      // continuation ends at its run's destination too): the image holds exactly those, ascending.
-      // Helpers are independent: their lists are built on threads (marks over the 16-bit LDS space,
-      // then the distinct ones sorted), then appended in ticket order.
-      auto dests = [&](int b0, int b1, std::vector<uint8_t>& mark, std::vector<uint16_t>& out) {
-        for (int b = b0; b < b1; ++b) {
-          const int64_t po = S.fold_poff[b];
-          const int len = S.fold_plen[b];
-          for (int t = 0; t < SymbolicPlan::kFoldThreads; ++t) {
-            int d = (int)(S.fold_chead[(int64_t)b * SymbolicPlan::kFoldThreads + t] & 0xffffu);
-            for (int k = 0; k < len; ++k) {
-              const uint32_t e = S.fold_prod[po + (int64_t)SymbolicPlan::kFoldThreads * k + t];
-              d += (int)((e >> 24) & 127u);
-              if ((int32_t)e < 0) {
-                MADIPM_REQUIRE(d >= 0 && d < 65536, "fold helper: LDS destination beyond 16 bits");
-                if (!mark[d]) {
-                  mark[d] = 1;
-                  out.push_back((uint16_t)d);
-                }
-              }
-            }
-          }
-        }
-        std::sort(out.begin(), out.end());
-        for (uint16_t x : out) mark[x] = 0;
-      };
-      if (!S.fold_bptr.empty())
-        for (int f = 0; f < ns; ++f) fst[f] = start(S.fold_bptr[f], S.fold_bptr[f + 1]);
-      std::vector<std::array<int, 3>> cand;  // (front, first batch, end of the helper's batches), ticket order
-      for (int f : ord) {
-        if (!on || !S.absorb[f]) continue;
-        const int b0 = S.fold_bptr[f], nb = S.fold_bptr[f + 1] - b0;
-        if (nb < min_nb) continue;
-        cand.push_back({f, b0, b0 + std::max(1, std::min(nb - 1, nb * share4 / 4))});
-      }
-      std::vector<std::vector<uint16_t>> cd(cand.size());
-      {
-        std::atomic<size_t> next{0};
-        auto work = [&] {
-          std::vector<uint8_t> mark(65536, 0);
-          for (size_t k; (k = next.fetch_add(1)) < cand.size();) dests(cand[k][1], cand[k][2], mark, cd[k]);
-        };
-        const int nt = std::max(1, std::min<int>(analysis_threads(), (int)(cand.size() / 8)));
-        std::vector<std::thread> th;
-        for (int t = 1; t < nt; ++t) th.emplace_back(work);
-        work();
-        for (auto& x : th) x.join();
-      }
-      for (size_t k = 0; k < cand.size(); ++k) {
-        const int64_t dofs = (int64_t)hdst.size();
-        const int32_t nimg = (int32_t)cd[k].size();
-        hdst.insert(hdst.end(), cd[k].begin(), cd[k].end());
-        hv.push_back(FoldHelp{cand[k][0], 0, img, dofs, nimg, 0, start(cand[k][1], cand[k][2])});
-        img += (nimg + 1) & ~1LL;
-      }
-      std::stable_sort(hv.begin(), hv.end(),
-                       [](const FoldHelp& a, const FoldHelp& b) { return a.fs.b1 - a.fs.b0 > b.fs.b1 - b.fs.b0; });
-      nfhelp_ = (int)hv.size();
-      for (int h = 0; h < nfhelp_; ++h) {
-        hv[h].flag = ns + h;
-        help[hv[h].front] = h;
-        fst[hv[h].front] = start(hv[h].fs.b1, S.fold_bptr[hv[h].front + 1]);  // the front keeps the rest
-      }
-      fstart_.upload(fst);
-      fold_help_.upload(help);
-      fhelp_.upload(hv.empty() ? std::vector<FoldHelp>{FoldHelp{0, 0, 0, 0, 0, 0, FoldStart{0, 0, 0, 0, 0, 0, 0, 0, 0}}} : hv);
-      fimg_.alloc((size_t)std::max<int64_t>(img, 2));
-      fimg_dst_.upload(hdst.empty() ? std::vector<uint16_t>{0} : hdst);
-      T_.fimg_dst = fimg_dst_;
-      if (std::getenv("MADIPM_TREE_DEBUG"))
-        fprintf(stderr, "fold helpers: %d, image entries %lld (%.1f MB per factorisation, stored + read)\n", nfhelp_,
-                (long long)hdst.size(), 16e-6 * (double)hdst.size());
-      T_.fstart = fstart_;
-      T_.fold_help = fold_help_;
-      T_.fhelp = fhelp_;
-      T_.fimg = fimg_;
-      dptr.insert(dptr.begin(), (size_t)nfhelp_, 0);  // dep_ptr by ticket: the helpers' ranges are empty
-    }
-    clk("  fold helpers");
-    up(ft_order_, ord);
-    up(ft_dptr_, dptr);
-    up(ft_dep_, dl);
-    fflags_.alloc(std::max(ns + nfhelp_, 1));
-    fflags_.zero();
-    {
-      auto up8 = [](DBuf<uint8_t>& d, const std::vector<uint8_t>& v) { d.upload(v.empty() ? std::vector<uint8_t>{0} : v); };
-      auto up32 = [](DBuf<int32_t>& d, const std::vector<int32_t>& v) { d.upload(v.empty() ? std::vector<int32_t>{0} : v); };
-      auto up64 = [](DBuf<int64_t>& d, const std::vector<int64_t>& v) { d.upload(v.empty() ? std::vector<int64_t>{0} : v); };
-      up8(absorb_, S.absorb);
-      up8(fold_pk_, S.fold_pk);
-      up32(mc_ptr_, S.mc_ptr);
-      up64(ab_first_, S.ab_first);
-      up32(ab_src0_, S.ab_src0);
-      up32(ab_src1_, S.ab_src1);
-      up32(ab_k_, S.ab_k);
-      up32(ab_f0_, S.ab_f0);
-      up32(ab_wrc_, S.ab_wrc);
-      {
-        std::vector<int64_t> lo(S.mc_list.size() + 1, 0);
-        for (size_t k = 0; k < S.mc_list.size(); ++k) lo[k] = S.l_off[S.mc_list[k]];
-        ab_loff_.upload(lo);
-      }
-      up32(fold_bptr_, S.fold_bptr);
-      up32(fold_bat_, S.fold_bat);
-      up64(fold_row0_, S.fold_row0);
-      up64(fold_poff_, S.fold_poff);
-      up32(fold_plen_, S.fold_plen);
-      up32(fold_rmax_, S.fold_rmax);
-      up32(fold_lmax_, S.fold_lmax);
-      fold_prod_.upload(S.fold_prod.empty() ? std::vector<uint32_t>{SymbolicPlan::kFoldPad} : S.fold_prod);
-      fold_chead_.upload(S.fold_chead.empty() ? std::vector<uint32_t>{0u} : S.fold_chead);
-      T_.absorb = absorb_;
-      T_.fold_pk = fold_pk_;
-      T_.mc_ptr = mc_ptr_;
-      T_.ab_first = ab_first_;
-      T_.ab_src0 = ab_src0_;
-      T_.ab_src1 = ab_src1_;
-      T_.ab_k = ab_k_;
-      T_.ab_f0 = ab_f0_;
-      T_.ab_wrc = ab_wrc_;
-      T_.ab_loff = ab_loff_;
-      T_.fold_bptr = fold_bptr_;
-      T_.fold_bat = fold_bat_;
-      T_.fold_row0 = fold_row0_;
-      T_.fold_poff = fold_poff_;
-      T_.fold_plen = fold_plen_;
-      T_.fold_rmax = fold_rmax_;
-      T_.fold_lmax = fold_lmax_;
-      T_.fold_prod = fold_prod_.p;
-      T_.fold_chead = fold_chead_.p;
-    }
-    fcnt_.alloc(4);
-    fcnt_.zero();
-    const char* dv = std::getenv("MADIPM_TREE_DEBUG");
-    if (dv && dv[0] == '1' && nftree_) {
-      fdbg_.alloc((int64_t)24 * (nftree_ + nfhelp_));
-      fdbg_.zero();
-    }
-  }
 
-  // ---- factorisation launch schedules (phase 1: this shard's subtrees; phase 2: the top fronts)
-  clk("  fold table uploads");
-  std::vector<int32_t> sched;
-  auto align2 = [&]() {
-    if (sched.size() & 1) sched.push_back(0);
-  };
-  // phase-1 level groups: the fused fronts' tiles past their column block 0 wait for k_asm_update
-  auto asm_end = [&](int g) { return g < NL ? S.atile_fz1[g] : S.atile_lev[g + 1]; };
-  auto asm_launch = [&](int g, std::vector<Launch>& out) {
-    if (asm_end(g) <= S.atile_lev[g]) return;
-    Launch L{ASSEMBLE, 0, S.atile_lev[g], 0, asm_end(g) - S.atile_lev[g], asm_cid_off[g],
-             asm_cid_off[g + 1] - asm_cid_off[g]};  // the chunks of the group's chunk-path tiles
-    // algorithmic traffic: chunk pass reads (index, value) per source, writes one partial per chunk;
-    // the tile pass reads the entry offsets + partials (+ big-children blocks), writes the lower tile
-    const int64_t nsrc = S.g_chunk[S.chunk_lev[g + 1]] - S.g_chunk[S.chunk_lev[g]];
-    L.bytes2 = 16.0 * nsrc + 16.0 * L.nchunk;
-    L.flops2 = (double)nsrc;
-    for (int32_t t = S.atile_lev[g]; t < asm_end(g); ++t) {
-      const SymbolicPlan::AsmTile& at = S.atiles[t];
-      const int r = S.nrows[at.front], ti = at.tij & 0xffff, tj = (at.tij >> 16) & 0x7fff;
-      const double nr = std::min(64, r - 64 * ti), nc = std::min(64, r - 64 * tj);
-      L.bytes += 8.0 * (ti == tj ? nr * (nr + 1) / 2 : nr * nc) * (at.tij < 0 ? 2.0 : 1.0) +
-                 (at.gptr >= 0 ? 4.0 * (S.g_ptr[at.gptr] + 2) : 0.0);
-      for (int k = at.bt0; k < at.bt1; ++k) {
-        const int32_t* e = &S.bt[5 * k];
-        for (int b = e[1]; b < e[2]; ++b) L.bytes += 8.0 * std::max(0, e[4] - std::max(b, e[3]));
-      }
-    }
-    L.bytes += 8.0 * L.nchunk;
-    out.push_back(L);
-  };
-  auto lb_syrk_launch = [&](int g, std::vector<Launch>& out) {
-    const auto& G = S.lb[g];
-    Launch L{LB_SYRK, 0, g, 0, 0};
-    L.flops = (double)G.m * (G.m + 1) * (double)G.n;
-    // W once + the parent's lower triangle read-modify-written once per K-chunk
-    L.bytes = 8.0 * (double)G.m * G.n + 16.0 * (double)G.m * (G.m + 1) / 2.0 * cdiv(G.n, LB_KCHUNK);
-    out.push_back(L);
-  };
-  // The big fronts of a level in one k_big_dag launch: tasks in ticket order DIAG(0) | chain(0) feed(0) |
-  // chain(1) bulk(0) feed(1) | chain(2) bulk(1) feed(2) | ... | bulk(last) (k_big_dag's comment), every
-  // front of the level interleaved; each task's dependencies are the last earlier writers of the 64 x 64
-  // blocks of its front that it reads or read-modify-writes (every writer also reads what it writes, so
-  // the last writer stands for all earlier ones).  Then the fused fronts' k_asm_update.  The same tiles,
-  // operands and order of sums as the per-step launches with K unsplit.
-  std::vector<int32_t> dtask, ddptr{0}, ddlist;  // DagTask words, CSR of dependencies (launch-local tickets)
-  std::vector<int64_t> mslot(std::max(S.nsuper, 1), 0);
-  int64_t nmslot = 0;
-  for (int f = 0; f < S.nsuper; ++f)
-    if (S.is_big[f]) {
-      mslot[f] = nmslot;
-      nmslot += cdiv(S.first[f + 1] - S.first[f], 64) + 1;
-    }
-  auto dag_level = [&](const std::vector<int32_t>& big, int lev, int phase, std::vector<Launch>& out) {
-    const int kp = big_kpan_;
-    Launch L{BIG_DAG, 0, (int64_t)(dtask.size() / 4), 0, 0};
-    // per front, the live written rectangles bucketed by the 64 x 64 blocks they touch: a task depends on
-    // every live rectangle its reads or read-modify-writes intersect; a write drops the rectangles (per
-    // block) it covers — it depends on them, so it stands for them — and adds its own
-    struct Ent {
-      int r0, r1, c0, c1, w;
-    };
-    std::map<int, std::vector<std::vector<Ent>>> live;
-    std::vector<int32_t> deps;
-    std::vector<Ent> wr;
-    std::vector<int> wrs;
-    auto region = [&](int s, int r0, int r1, int c0, int c1, bool write) {
-      const int nb = (int)cdiv(S.nrows[s], 64);
-      auto& g = live[s];
-      if (g.empty()) g.resize((size_t)nb * nb);
-      r1 = std::min(r1, S.nrows[s]);
-      c1 = std::min(c1, S.nrows[s]);
-      if (r0 >= r1 || c0 >= c1) return;
-      for (int R = r0 >> 6; R <= (r1 - 1) >> 6; ++R)
-        for (int C = c0 >> 6; C <= std::min((c1 - 1) >> 6, R); ++C)
-          for (const Ent& e : g[(size_t)R * nb + C])
-            if (e.r0 < r1 && r0 < e.r1 && e.c0 < c1 && c0 < e.c1) deps.push_back(e.w);
-      if (write) {
-        wr.push_back(Ent{r0, r1, c0, c1, -1});
-        wrs.push_back(s);
-      }
-    };
-    auto emit = [&](int s, int step, int item, int kind) {
-      const int t = (int)L.items++;
-      std::sort(deps.begin(), deps.end());
-      deps.erase(std::unique(deps.begin(), deps.end()), deps.end());
-      for (int d : deps) ddlist.push_back(d);
-      ddptr.push_back((int32_t)ddlist.size());
-      for (size_t k = 0; k < wr.size(); ++k) {
-        const Ent q{wr[k].r0, wr[k].r1, wr[k].c0, wr[k].c1, t};
-        const int f = wrs[k], nb = (int)cdiv(S.nrows[f], 64);
-        auto& g = live[f];
-        for (int R = q.r0 >> 6; R <= (q.r1 - 1) >> 6; ++R)
-          for (int C = q.c0 >> 6; C <= std::min((q.c1 - 1) >> 6, R); ++C) {
-            auto& cell = g[(size_t)R * nb + C];
-            const int br0 = R * 64, br1 = br0 + 64, bc0 = C * 64, bc1 = bc0 + 64;
-            cell.erase(std::remove_if(cell.begin(), cell.end(), [&](const Ent& e) {
-                         const int a0 = std::max(e.r0, br0), a1 = std::min(e.r1, br1);
-                         const int b0 = std::max(e.c0, bc0), b1 = std::min(e.c1, bc1);
-                         return a0 >= q.r0 && a1 <= q.r1 && b0 >= q.c0 && b1 <= q.c1;  // covered here
-                       }),
-                       cell.end());
-            cell.push_back(q);
-          }
-      }
-      deps.clear();
-      wr.clear();
-      wrs.clear();
-      dtask.insert(dtask.end(), {s, step, item, kind});
-    };
-    int maxsteps = 0;
-    for (int s : big) maxsteps = std::max<int>(maxsteps, (int)cdiv(S.first[s + 1] - S.first[s], 64));
-    // first diagonal blocks
-    for (int s : big) {
-      const int w = S.first[s + 1] - S.first[s], kw = std::min(64, w);
-      region(s, 0, kw, 0, kw, true);
-      emit(s, 0, 0, 3);
-      L.bytes += 8.0 * (kw * (kw + 1.0) + 4 * 16 * 17);
-      L.flops += (double)kw * kw * kw / 3.0;
-    }
-    for (int s : big) L.alg += fact_alg(s);  // every column of the level's big fronts
-    auto bulk = [&](int g0) {  // 128 x 128 trailing tiles of group [g0, g0 + kp), columns past the feed tiles
-      for (int s : big) {
-        const int w = S.first[s + 1] - S.first[s], r = S.nrows[s];
-        if ((int)cdiv(w, 64) <= g0 || S.fused[s]) continue;
-        const int gend = std::min(64 * (g0 + kp), w), cb = gend + 64 * kp;
-        if (cb >= r) continue;
-        const int nt = (int)cdiv(r - cb, 128);
-        const double K = gend - 64 * g0, nbt = r - cb;
-        L.bytes += 8.0 * (nbt * (nbt + 1) + 2.0 * nbt * K);
-        L.flops += K * nbt * (nbt + 1);
-        // column by column: the first columns feed the next group's feed tiles (and its bulk's first
-        // columns), so their tickets come first and are done by the time those wait for them
-        for (int J = 0; J < nt; ++J)
-          for (int I = J; I < nt; ++I) {
-            const int i0 = cb + 128 * I, j0 = cb + 128 * J;
-            region(s, i0, i0 + 128, 64 * g0, gend, false);  // (L D)_I and L_J: the group's panels
-            region(s, j0, j0 + 128, 64 * g0, gend, false);
-            region(s, i0, i0 + 128, j0, j0 + 128, true);
-            emit(s, g0 + kp - 1, I | (J << 16), 2);
-          }
-      }
-    };
-    for (int g0 = 0; g0 < maxsteps; g0 += kp) {
-      // chain, per step: the critical tasks of every front first — trsm tiles 0 and 1 and the updates of
-      // tiles (0, 0) (with the next diagonal block), (1, 0) and (1, 1), which the next step's first
-      // tasks wait for — then the other trsm tiles and local updates
-      for (int p = g0; p < std::min(g0 + kp, maxsteps); ++p)
-        for (int phase2 = 0; phase2 < 2; ++phase2)
-          for (int kind = 0; kind < 2; ++kind)
-            for (int s : big) {
-              const int w = S.first[s + 1] - S.first[s], r = S.nrows[s];
-              const int npan = (int)cdiv(w, 64);
-              if (npan <= p) continue;
-              const int k0 = p * 64, kw = std::min(64, w - k0);
-              const int nt = (int)cdiv(r - k0 - kw, 64);
-              const double dk = kw, nb = r - k0 - kw;
-              const int gl = std::min(g0 + kp, npan) - 1, gend = std::min(64 * (gl + 1), w);
-              const bool local = !S.fused[s] && p < gl;  // local updates (then kw = 64, c0 = k0 + 64)
-              const int c0 = k0 + 64;
-              const int ncol = local ? (int)cdiv(gend - c0, 64) : 0;
-              auto trsm = [&](int rt) {
-                const int R0 = k0 + kw + 64 * rt;
-                region(s, k0, k0 + kw, k0, k0 + kw, false);  // L11, D, M_K
-                region(s, R0, R0 + 64, k0, k0 + kw, true);
-              };
-              auto upd = [&](int i, int j) {
-                region(s, c0 + 64 * i, c0 + 64 * i + 64, k0, k0 + 64, false);
-                region(s, c0 + 64 * j, c0 + 64 * j + 64, k0, k0 + 64, false);
-                region(s, c0 + 64 * i, c0 + 64 * i + 64, c0 + 64 * j, std::min(c0 + 64 * j + 64, gend), true);
-              };
-              const bool crit = phase2 == 0;
-              if (kind == 0) {
-                if (crit) {
-                  L.bytes += 8.0 * (2.0 * nb * dk + nt * (dk * (dk + 1) / 2 + 4 * 16 * 17));
-                  L.flops += nb * dk * dk;
-                  if (local) {
-                    const double nc = gend - c0;
-                    L.bytes += 8.0 * (2.0 * nb * nc + nb * dk + nc * dk);
-                    L.flops += 2.0 * dk * nc * (nb - 0.5 * nc);
-                  }
-                }
-                for (int rt = crit ? 0 : 2; rt < (crit ? std::min(nt, 2) : nt); ++rt) {
-                  trsm(rt);
-                  emit(s, p, rt, 0);
-                }
-              } else if (local) {
-                for (int j = 0; j < ncol; ++j)
-                  for (int i = j; i < nt; ++i) {
-                    const bool c = (i == 1 && j <= 1) || (i == 0 && j == 0);
-                    if (c != crit) continue;
-                    upd(i, j);
-                    emit(s, p, i | (j << 16), 1);
-                  }
-              }
-            }
-      if (g0 > 0) bulk(g0 - kp);
-      // feed: the trailing update of the next group's columns, 64 x 64 tiles (k_big_update trailing mode)
-      for (int s : big) {
-        const int w = S.first[s + 1] - S.first[s], r = S.nrows[s];
-        if ((int)cdiv(w, 64) <= g0 || S.fused[s]) continue;
-        const int gend = std::min(64 * (g0 + kp), w);
-        if (gend >= r) continue;
-        const int nt = (int)cdiv(r - gend, 64), ncb = std::min(kp, nt);
-        const double K = gend - 64 * g0, nbt = r - gend, nc = std::min(64.0 * kp, nbt);
-        L.bytes += 8.0 * (2.0 * nbt * nc + (nbt + nc) * K);
-        L.flops += 2.0 * K * nc * (nbt - 0.5 * nc);
-        for (int j = 0; j < ncb; ++j)
-          for (int i = j; i < nt; ++i) {
-            const int i0 = gend + 64 * i, j0 = gend + 64 * j;
-            region(s, i0, i0 + 64, 64 * g0, gend, false);
-            region(s, j0, j0 + 64, 64 * g0, gend, false);
-            region(s, i0, i0 + 64, j0, j0 + 64, true);
-            emit(s, g0 + kp - 1, (int)((uint32_t)i | ((uint32_t)j << 16) | 0x80000000u), 1);
-          }
-      }
-    }
-    bulk(((maxsteps - 1) / kp) * kp);
-    out.push_back(L);
-    if (phase == 1 && S.atile_fz0[lev] < S.atile_lev[lev + 1]) {
-      // the fused fronts' trailing tiles: assembled + updated after their panel (one launch)
-      const int32_t t0 = S.atile_fz0[lev], t1 = S.atile_lev[lev + 1];
-      Launch A{ASM_UPDATE, 0, t0, 4, t1 - t0};
-      for (int32_t t = t0; t < t1; ++t) {
-        const SymbolicPlan::AsmTile& at = S.atiles[t];
-        const int f = at.front, r = S.nrows[f], w = S.first[f + 1] - S.first[f];
-        A.nf = std::max(A.nf, (w + 3) & ~3);
-        const int ti = at.tij & 0xffff, tj = (at.tij >> 16) & 0x7fff;
-        const double nr = std::min(64, r - 64 * ti), nc = std::min(64, r - 64 * tj);
-        A.bytes += 8.0 * (ti == tj ? nr * (nr + 1) / 2 : nr * nc) + (at.gptr >= 0 ? 4.0 * (S.g_ptr[at.gptr] + 2) : 0.0) +
-                   8.0 * (nr + nc) * w;
-        for (int k = at.bt0; k < at.bt1; ++k) {
-          const int32_t* e = &S.bt[5 * k];
-          for (int b = e[1]; b < e[2]; ++b) A.bytes += 8.0 * std::max(0, e[4] - std::max(b, e[3]));
-        }
-        A.flops += 2.0 * nr * nc * w;
-      }
-      out.push_back(A);
-    }
-  };
-  auto build_fact = [&](int phase, std::vector<Launch>& out) {
-    if (phase == 1 && !S.lb.empty()) {
-      Launch L{LB_BUILD, 0, 0, 0, (int64_t)S.lb_mem.size()};
-      for (const auto& G : S.lb) L.bytes += 8.0 * (double)G.m * G.n * 2.0 + 12.0 * G.n * G.m;
-      for (int32_t c : S.lb_mem) L.alg += fact_alg_cols(c, c + 1);
-      out.push_back(L);
-    }
-    auto ftree_launch = [&]() {  // factorisation tree: after every level-0 launch (the pre-leaves)
-      asm_launch(2 * NL + 1, out);
-      Launch L{FTREE, 0, 0, nftree_, (int64_t)nftree_};
-      L.bytes = ftree_bytes_;
-      L.alg = ftree_alg_;
-      L.flops = ftree_flops_;
-      L.lds_bytes = ftree_lds_;
-      out.push_back(L);
-    };
-    for (int lev = 0; lev < NL; ++lev) {
-      if (phase == 1 && lev == 1 && nftree_) ftree_launch();
-      asm_launch(phase == 1 ? lev : NL + 1 + lev, out);
-      if (phase == 1)
-        for (int g : lb_at_level_[lev])
-          if (!S.top(S.lb[g].parent)) lb_syrk_launch(g, out);  // top parents: after their external part
-      std::vector<int32_t> cls[4], big, micro;
-      for (int q = S.level_ptr[lev]; q < S.level_ptr[lev + 1]; ++q) {
-        const int s = S.level_list[q];
-        if (!in_phase(s, phase) || S.ftree[s]) continue;
-        if (S.parent[s] >= 0 && S.absorb[S.parent[s]]) continue;  // factorised by its absorbing parent
-        const int r = S.nrows[s], w = S.first[s + 1] - S.first[s];
-        if (r <= 32 && w <= 2 && S.fs_off[s] < 0 && !S.is_big[s])
-          micro.push_back(s);
-        else if (!S.is_big[s])
-          cls[r <= 32 ? 0 : (r <= 64 ? 1 : (r <= 128 ? 2 : 3))].push_back(s);
-        else
-          big.push_back(s);
-      }
-      if (!micro.empty()) {
-        Launch L{MICRO, 0, (int64_t)sched.size(), (int)micro.size(), (int64_t)micro.size()};
-        for (int f : micro) {
-          const double r = S.nrows[f], w = S.first[f + 1] - S.first[f];
-          L.bytes += 8.0 * (r * w + (r - w) * (r - w + 1) / 2 + w) + 16.0 * (S.asm_ptr[f + 1] - S.asm_ptr[f]);
-          L.alg += fact_alg(f);
-          for (int t = 0; t < (int)w; ++t) L.flops += (r - t - 1) * (r - t);
-        }
-        out.push_back(L);
-        sched.insert(sched.end(), micro.begin(), micro.end());
-      }
-      for (int c = 0; c < 4; ++c)
-        if (!cls[c].empty()) {
-          Launch L{c == 3 ? SMALL192 : SMALL32 + c, 0, (int64_t)sched.size(), (int)cls[c].size(), (int64_t)cls[c].size()};
-          L.lds = false;
-          for (int f : cls[c]) {
-            L.lds = L.lds || S.fs_off[f] < 0;
-            const int r = S.nrows[f];
-            L.lds_bytes = std::max<int>(L.lds_bytes, c == 3 ? 8 * r * (r + 1) / 2 : 8 * r * (r | 1));
-          }
-          for (int f : cls[c]) {  // reads: K entries or the assembled front; writes: L panel, U block, D
-            const double r = S.nrows[f], w = S.first[f + 1] - S.first[f];
-            L.bytes += 8.0 * (r * w + (r - w) * (r - w) + w) +
-                       (S.fs_off[f] >= 0 ? 8.0 * r * (r + 1) / 2 : 16.0 * (S.asm_ptr[f + 1] - S.asm_ptr[f]));
-            L.alg += fact_alg(f);
-            for (int t = 0; t < (int)w; ++t) L.flops += (r - t - 1) * (r - t);
-          }
-          out.push_back(L);
-          sched.insert(sched.end(), cls[c].begin(), cls[c].end());
-        }
-      if (big.empty()) continue;
-      if (big_dag_) {
-        dag_level(big, lev, phase, out);
-        continue;
-      }
-      int maxsteps = 0;
-      for (int s : big) maxsteps = std::max<int>(maxsteps, (int)cdiv(S.first[s + 1] - S.first[s], 64));
-      int64_t last_upd = -1;  // the latest update launch (it factorised the next step's diagonal blocks)
-      for (int p = 0; p < maxsteps; ++p) {
-        std::vector<int32_t> td, tt, tu, tu128;  // (front, item) pairs
-        double kb[4] = {0, 0, 0, 0}, kf[4] = {0, 0, 0, 0}, ka = 0;
-        for (int s : big) {
-          const int w = S.first[s + 1] - S.first[s], r = S.nrows[s];
-          const int npan = (int)cdiv(w, 64);
-          if (npan <= p) continue;
-          const int k0 = p * 64, kw = std::min(64, w - k0);
-          const int nt = (int)cdiv(r - k0 - kw, 64);
-          const double dk = kw, nb = r - k0 - kw;
-          kb[0] += 8.0 * (dk * (dk + 1) + 4 * 16 * 17);  // diag: read + write lower, write the M blocks
-          ka += fact_alg_cols(S.first[s] + k0, S.first[s] + k0 + kw);  // 8(d): the panel's columns
-          kf[0] += dk * dk * dk / 3.0;
-          kb[1] += 8.0 * (2.0 * nb * dk + nt * (dk * (dk + 1) / 2 + 4 * 16 * 17));  // trsm: rows in/out + L11, M per tile
-          kf[1] += nb * dk * dk;
-          if (p == 0) td.insert(td.end(), {s, 0});  // later panels: the previous update's task (0, 0)
-          for (int i = 0; i < nt; ++i) tt.insert(tt.end(), {s, i});
-          if (S.fused[s]) continue;  // its trailing update: k_asm_update (below)
-          // deferred multi-panel update (k_big_update): panel groups of big_kpan_ panels; inside a
-          // group each panel updates the group's later panels only (local tiles), the group's last
-          // panel updates the rest of the front with K = the whole group (trailing tiles)
-          const int g0 = (p / big_kpan_) * big_kpan_, gl = std::min(g0 + big_kpan_, npan) - 1;
-          const int gend = std::min(64 * (gl + 1), w);
-          if (p < gl) {
-            const double nc = gend - (k0 + kw);  // the group's later columns
-            for (int j = 0; j < (int)cdiv((int)nc, 64); ++j)
-              for (int i = j; i < nt; ++i) tu.insert(tu.end(), {s, i | (j << 16)});
-            kb[2] += 8.0 * (2.0 * nb * nc + nb * dk + nc * dk);  // C in/out + the panel rows once
-            kf[2] += 2.0 * dk * nc * (nb - 0.5 * nc);
-          } else {  // 128 x 128 tiles (k_big_upd128)
-            const int c0 = gend, ntt = (int)cdiv(r - c0, 128);
-            const double K = gend - 64 * g0, nbt = r - c0;
-            for (int i = 0; i < ntt; ++i)
-              for (int j = 0; j <= i; ++j) tu128.insert(tu128.end(), {s, i | (j << 16)});
-            kb[3] += 8.0 * (nbt * (nbt + 1) + 2.0 * nbt * K);  // C in/out once per group + the group's panels
-            kf[3] += K * nbt * (nbt + 1);
-          }
-        }
-        const std::pair<int, std::vector<int32_t>*> kinds[4] = {
-            {BIG_DIAG, &td}, {BIG_TRSM, &tt}, {BIG_UPDATE, &tu}, {BIG_UPDATE128, &tu128}};
-        bool alg_done = false;  // the panels' 8(d) bytes ride on the step's first launch (k_big_diag at
-                                // step 0, k_big_trsm after: the diagonal blocks are factorised by the
-                                // previous step's update launch)
-        for (int q = 0; q < 4; ++q) {
-          const auto& kv = kinds[q];
-          if (kv.second->empty()) continue;
-          align2();
-          Launch L{kv.first, p, (int64_t)sched.size(), 0, (int64_t)kv.second->size() / 2};
-          L.bytes = kb[q];
-          L.alg = alg_done ? 0.0 : ka;
-          alg_done = true;
-          if (kv.first == BIG_UPDATE || kv.first == BIG_UPDATE128) last_upd = (int64_t)out.size();
-          if (kv.first == BIG_UPDATE128)  // K split over 2-4 workgroups per tile when the tiles alone
-                                          // would leave most CUs idle (k_big_upd128; nf = the split)
-            L.nf = !upd_split_ ? 1 : L.items <= 128 ? 4 : L.items <= 170 ? 3 : L.items <= 256 ? 2 : 1;
-          L.flops = kf[q];
-          out.push_back(L);
-          sched.insert(sched.end(), kv.second->begin(), kv.second->end());
-        }
-        // a last panel without rows below (r == w) launches nothing: its diagonal block was factorised
-        // by the previous step's update launch, which carries its bytes
-        if (!alg_done && ka > 0.0 && last_upd >= 0) out[last_upd].alg += ka;
-        if (p == 0 && phase == 1 && S.atile_fz0[lev] < S.atile_lev[lev + 1]) {
-          // the fused fronts' trailing tiles: assembled + updated after their panel (one launch)
-          const int32_t t0 = S.atile_fz0[lev], t1 = S.atile_lev[lev + 1];
-          Launch L{ASM_UPDATE, 0, t0, 4, t1 - t0};
-          for (int32_t t = t0; t < t1; ++t) {
-            const SymbolicPlan::AsmTile& at = S.atiles[t];
-            const int f = at.front, r = S.nrows[f], w = S.first[f + 1] - S.first[f];
-            L.nf = std::max(L.nf, (w + 3) & ~3);
-            const int ti = at.tij & 0xffff, tj = (at.tij >> 16) & 0x7fff;
-            const double nr = std::min(64, r - 64 * ti), nc = std::min(64, r - 64 * tj);
-            // the written entries + the chunk sums' offsets + the panel rows of I and J (+ big children)
-            L.bytes += 8.0 * (ti == tj ? nr * (nr + 1) / 2 : nr * nc) + (at.gptr >= 0 ? 4.0 * (S.g_ptr[at.gptr] + 2) : 0.0) +
-                       8.0 * (nr + nc) * w;
-            for (int k = at.bt0; k < at.bt1; ++k) {
-              const int32_t* e = &S.bt[5 * k];
-              for (int b = e[1]; b < e[2]; ++b) L.bytes += 8.0 * std::max(0, e[4] - std::max(b, e[3]));
-            }
-            L.flops += 2.0 * nr * nc * w;
-          }
-          out.push_back(L);
-        }
-      }
-    }
-    if (phase == 1 && NL == 1 && nftree_) ftree_launch();
-  };
-  clk("  launch plans (before build_fact)");
-  build_fact(1, fact1_);
-  if (S.nshards > 1) {
-    asm_launch(NL, fact1_);  // top fronts, external part (all-reduced next)
-    for (size_t g = 0; g < S.lb.size(); ++g)  // this shard's batched leaves under top fronts: into it
-      if (S.top(S.lb[g].parent)) lb_syrk_launch((int)g, fact1_);
-    build_fact(2, fact2_);
+  // ---- factorisation tree (k_fact_tree), fold helpers, leaf folding (SymbolicPlan::absorb / fold_* / ab_*)
+  nftree_ = P.nftree;
+  nfhelp_ = P.nfhelp;
+  up(ft_order_, P.ft_order);
+  up(ft_dptr_, P.ft_dptr);
+  up(ft_dep_, P.ft_dep);
+  T_.fstart = put(fstart_, P.fstart);
+  T_.fold_help = put(fold_help_, P.fold_help);
+  T_.fhelp = up(fhelp_, P.fhelp, FoldHelp{0, 0, 0, 0, 0, 0, FoldStart{0, 0, 0, 0, 0, 0, 0, 0, 0}});
+  fimg_.alloc((size_t)std::max<int64_t>(P.fimg_size, 2));
+  T_.fimg = fimg_;
+  T_.fimg_dst = up(fimg_dst_, P.fimg_dst);
+  fflags_.alloc(std::max(ns + nfhelp_, 1));
+  fflags_.zero();
+  T_.absorb = up(absorb_, S.absorb);
+  T_.fold_pk = up(fold_pk_, S.fold_pk);
+  T_.mc_ptr = up(mc_ptr_, S.mc_ptr);
+  T_.ab_first = up(ab_first_, S.ab_first);
+  T_.ab_src0 = up(ab_src0_, S.ab_src0);
+  T_.ab_src1 = up(ab_src1_, S.ab_src1);
+  T_.ab_k = up(ab_k_, S.ab_k);
+  T_.ab_f0 = up(ab_f0_, S.ab_f0);
+  T_.ab_wrc = up(ab_wrc_, S.ab_wrc);
+  T_.ab_loff = put(ab_loff_, P.ab_loff);
+  T_.fold_bptr = up(fold_bptr_, S.fold_bptr);
+  T_.fold_bat = up(fold_bat_, S.fold_bat);
+  T_.fold_row0 = up(fold_row0_, S.fold_row0);
+  T_.fold_poff = up(fold_poff_, S.fold_poff);
+  T_.fold_plen = up(fold_plen_, S.fold_plen);
+  T_.fold_rmax = up(fold_rmax_, S.fold_rmax);
+  T_.fold_lmax = up(fold_lmax_, S.fold_lmax);
+  T_.fold_prod = up(fold_prod_, S.fold_prod, SymbolicPlan::kFoldPad);
+  T_.fold_chead = up(fold_chead_, S.fold_chead);
+  fcnt_.alloc(4);
+  fcnt_.zero();
+  if (knobs_.tree_debug && nftree_) {
+    fdbg_.alloc((int64_t)24 * (nftree_ + nfhelp_));
+    fdbg_.zero();
   }
-  if (!dtask.empty()) {  // DAG tasks, dependencies, flags, counters, per-panel M_K slots
-    dag_tasks_.upload(dtask);
-    dag_dptr_.upload(ddptr);
-    dag_dlist_.upload(ddlist.empty() ? std::vector<int32_t>{0} : ddlist);
-    dag_flags_.alloc((int64_t)dtask.size() / 4);
+  clk("  fold table uploads");
+
+  // ---- factorisation launches (phase 1: this shard's subtrees; phase 2: the top fronts)
+  fact1_ = std::move(P.fact1);
+  fact2_ = std::move(P.fact2);
+  if (!P.dag_tasks.empty()) {  // DAG tasks, dependencies, flags, counters, per-panel M_K slots
+    dag_tasks_.upload(P.dag_tasks);
+    dag_dptr_.upload(P.dag_dptr);
+    up(dag_dlist_, P.dag_dlist);
+    dag_flags_.alloc((int64_t)P.dag_tasks.size() / 4);
     dag_flags_.zero();
     dag_cnt_.alloc(2);
     dag_cnt_.zero();
-    dag_m_.alloc(std::max<int64_t>(nmslot, 1) * BIG_MSZ);
-    dag_mslot_.upload(mslot);
+    dag_m_.alloc(std::max<int64_t>(P.nmslot, 1) * BIG_MSZ);
+    dag_mslot_.upload(P.mslot);
     int dev = 0, ncu = 0;
     MADIPM_HIP(hipGetDevice(&dev));
     MADIPM_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
     dag_grid_ = std::max(1, 2 * ncu);  // two workgroups per CU (80 KB of LDS, <= 256 registers)
-    if (const char* ed = std::getenv("MADIPM_DAG_DEBUG"); ed && ed[0] == '1') {  // per-task stamps (diagnostics)
-      dag_dbg_.alloc((int64_t)dtask.size());
+    if (knobs_.dag_debug) {  // per-task stamps (diagnostics)
+      dag_dbg_.alloc((int64_t)P.dag_tasks.size());
       dag_dbg_.zero();
-      dag_kind_ = dtask;
+      dag_kind_ = P.dag_tasks;
     }
   }
-  {  // k_big_upd128's split-K scratch: partial products and per-tile tickets of the largest split launch
-    int64_t np = 0, nt = 0;
-    for (const auto* V : {&fact1_, &fact2_})
-      for (const Launch& L : *V)
-        if (L.kind == BIG_UPDATE128 && L.nf > 1) {
-          np = std::max<int64_t>(np, L.items * L.nf);
-          nt = std::max<int64_t>(nt, L.items);
-        }
-    if (np) {
-      upsum_.alloc((size_t)np * UPD_PART);
-      uptick_.alloc((size_t)nt);
-      uptick_.zero();
-    }
+  if (P.upd_np) {  // k_big_upd128's split-K scratch
+    upsum_.alloc((size_t)P.upd_np * UPD_PART);
+    uptick_.alloc((size_t)P.upd_nt);
+    uptick_.zero();
   }
 
-  // ---- solve schedules: per level, small fronts (wave per front) and big fronts (task queues)
-  clk("  build_fact + dag tables");
-  std::vector<uint8_t> rootf(std::max(ns, 1), 0);  // roots solved by k_root_solve (1) / a k_fwd_tree task (2)
-  std::vector<int32_t> tfront;                      // tree-solve task -> its (top) front
-  {
-    std::vector<int32_t> flag_off(ns, 0);
-    int64_t nflags = 0;
-    for (int s = 0; s < ns; ++s)
-      if (!solve_small(s)) {
-        flag_off[s] = (int32_t)nflags;
-        nflags += cdiv(S.first[s + 1] - S.first[s], 64);
-      }
-    std::vector<int32_t> tasks, bp_off(ns, 0);
-    int64_t nbpart = 0;
-    auto build_solve = [&](int phase, std::vector<SolveLevel>& out) {
-      for (int lev = 0; lev < NL; ++lev) {
-        std::vector<int32_t> tiny, small, big, micro;
-        for (int q = S.level_ptr[lev]; q < S.level_ptr[lev + 1]; ++q) {
-          const int s = S.level_list[q];
-          if (!in_phase(s, phase) || (phase == 1 && (in_tree[s] || sleaf[s]))) continue;
-          const int r = S.nrows[s], w = S.first[s + 1] - S.first[s];
-          if (r <= 32 && w <= 2)
-            micro.push_back(s);
-          else if (solve_small(s))
-            (r > 32 ? small : tiny).push_back(s);
-          else
-            big.push_back(s);
-        }
-        SolveLevel L{};
-        L.micro_off = (int64_t)sched.size();
-        L.nmicro = (int)micro.size();
-        sched.insert(sched.end(), micro.begin(), micro.end());
-        for (int f : micro) {
-          const double r = S.nrows[f], w = S.first[f + 1] - S.first[f];
-          L.micro_bytes += 8.0 * (r * w + 3.0 * r);
-          L.micro_flops += 2.0 * (r * w - w * (w + 1) / 2);
-          L.micro_alg += solve_alg(f);
-        }
-        L.tiny_off = (int64_t)sched.size();
-        L.ntiny = (int)tiny.size();
-        sched.insert(sched.end(), tiny.begin(), tiny.end());
-        L.small_off = (int64_t)sched.size();
-        L.nsmall = (int)small.size();
-        sched.insert(sched.end(), small.begin(), small.end());
-        L.big_off = (int64_t)sched.size();
-        L.nbig = (int)big.size();
-        sched.insert(sched.end(), big.begin(), big.end());
-        align2();
-        L.gat_off = (int64_t)sched.size();
-        for (int s : big)
-          for (int c = 0; c < cdiv(S.nrows[s], GAT_ROWS); ++c) sched.insert(sched.end(), {s, c});
-        L.ngat = (int)(((int64_t)sched.size() - L.gat_off) / 2);
-        L.below_off = (int64_t)sched.size();
-        for (int s : big) {
-          const int w = S.first[s + 1] - S.first[s], r = S.nrows[s];
-          if (r == w) continue;
-          const int np = (int)cdiv(w, 64), nch = (int)cdiv(r - w, BWD_CHUNK);
-          bp_off[s] = (int32_t)nbpart;
-          nbpart += (int64_t)np * nch;
-          for (int p = 0; p < np; ++p)
-            for (int c = 0; c < nch; ++c) sched.insert(sched.end(), {s, p | (c << 16)});
-        }
-        L.nbelow = (int)(((int64_t)sched.size() - L.below_off) / 2);
-        int maxblk = 0, maxpan = 0;
-        for (int s : big) {
-          maxblk = std::max<int>(maxblk, (int)cdiv(S.nrows[s], 64));
-          maxpan = std::max<int>(maxpan, (int)cdiv(S.first[s + 1] - S.first[s], 64));
-        }
-        L.ftask_off = (int64_t)tasks.size() / 2;
-        for (int i = 0; i < maxblk; ++i)
-          for (int s : big)
-            if (i < cdiv(S.nrows[s], 64)) {
-              tasks.push_back(s);
-              tasks.push_back(i);
-            }
-        L.nftask = (int)((int64_t)tasks.size() / 2 - L.ftask_off);
-        L.btask_off = (int64_t)tasks.size() / 2;
-        for (int k = 0; k < maxpan; ++k)
-          for (int s : big) {
-            const int np = (int)cdiv(S.first[s + 1] - S.first[s], 64);
-            if (k < np) {
-              tasks.push_back(s);
-              tasks.push_back(np - 1 - k);
-            }
-          }
-        L.nbtask = (int)((int64_t)tasks.size() / 2 - L.btask_off);
-        // algorithmic traffic of one sweep: the L panel once (+ the vectors), 2 flops per panel entry
-        for (int f : small) {
-          const double r = S.nrows[f], w = S.first[f + 1] - S.first[f];
-          L.small_bytes += 8.0 * (r * w + 3.0 * r);
-          L.small_flops += 2.0 * (r * w - w * (w + 1) / 2);
-          L.small_alg += solve_alg(f);
-          L.small_lds = std::max<int>(L.small_lds, 8 * (S.nrows[f] | 1) * (S.first[f + 1] - S.first[f]));
-        }
-        for (int f : tiny) {
-          const double r = S.nrows[f], w = S.first[f + 1] - S.first[f];
-          L.tiny_bytes += 8.0 * (r * w + 3.0 * r);
-          L.tiny_flops += 2.0 * (r * w - w * (w + 1) / 2);
-          L.tiny_alg += solve_alg(f);
-        }
-        for (int f : big) {
-          const double r = S.nrows[f], w = S.first[f + 1] - S.first[f];
-          L.big_bytes += 8.0 * (r * w + 3.0 * r);
-          L.big_flops += 2.0 * (r * w - w * (w + 1) / 2);
-          L.below_bytes += 8.0 * (r - w) * w;
-          const double sa = solve_alg(f), da = std::min(sa, 4.0 * w * (w + 1));  // diagonal block / below it
-          L.big_alg += da;
-          L.below_alg += sa - da;
-          L.gat_bytes += 8.0 * (2.0 * r + 2.0 * (S.sv_ptr[S.row_ptr[f + 1]] - S.sv_ptr[S.row_ptr[f]]));
-        }
-        out.push_back(L);
-      }
-    };
-    build_solve(1, slev1_);
-    {  // tree solve tables
-      // elimination-tree roots (r == w, no parent) whose panel needs more LDS than the tree launches'
-      // TREE_SOLVE_LDS (two workgroups per CU) go last, into their own forward launch with the LDS they
-      // need (ex10's 120-column coupling root: 125 KB), solved forward and backward there in one pass
-      // (r3: the root sized every tree task's LDS; r4's first cut streamed it in chunks: slower)
-      auto big_root = [&](int s) {
-        const int r = S.nrows[s], w = S.first[s + 1] - S.first[s];
-        const int64_t need = 8 * tree_panel_doubles(s) + 8 * 1024;
-        return S.parent[s] < 0 && r == w && r <= SMALL_SOLVE_MAX && need > TREE_SOLVE_LDS && need <= TREE_ROOT_LDS;
-      };
-      std::vector<int32_t> ord, roots;
-      for (int lev = 0; lev < NL; ++lev)
-        for (int q = S.level_ptr[lev]; q < S.level_ptr[lev + 1]; ++q)
-          if (in_tree[S.level_list[q]]) (big_root(S.level_list[q]) ? roots : ord).push_back(S.level_list[q]);
-      nroot_task_ = (int)roots.size();
-      for (int s : roots) rootf[s] = 1;
-      rargs_.n = std::min(nroot_task_, kRootArgs);
-      for (int q = 0; q < rargs_.n; ++q) {
-        const int s = roots[q];
-        rargs_.s[q] = s;
-        rargs_.f0[q] = S.first[s];
-        rargs_.w[q] = S.first[s + 1] - S.first[s];
-        rargs_.r[q] = S.nrows[s];
-        rargs_.e0[q] = S.row_ptr[s];
-        rargs_.loff[q] = S.l_off[s];
-      }
-      ord.insert(ord.end(), roots.begin(), roots.end());
-      ntree_ = (int)ord.size();
-      // children of tree fronts scatter their forward update entries straight into the parent's
-      // gather range (sv order, gbuf); everyone else keeps its own update vector (uvec)
-      // each tree-front row's gather entries: those of fronts solved by earlier launches (the flat
-      // leaves, batched-leaf groups, level-path children) first, those of tree tasks (this launch)
-      // last, sv_nt[row] of them — k_fwd_tree sums the first part before it waits for its children
-      std::vector<int64_t> svs(S.sv_src);
-      {
-        std::vector<uint8_t> from_task((size_t)std::max<int64_t>(S.uvec_size, 1), 0);
-        for (int s : ord)
-          if (S.uvec_off[s] >= 0)
-            for (int a = 0; a < S.nrows[s] - (S.first[s + 1] - S.first[s]); ++a) from_task[S.uvec_off[s] + a] = 1;
-        std::vector<uint16_t> nt((size_t)std::max<int64_t>(S.row_ptr[ns], 1), 0);
-        std::vector<int64_t> tail;
-        for (int s : ord)
-          for (int i = 0; i < S.nrows[s]; ++i) {
-            const int64_t t = S.row_ptr[s] + i, p0 = S.sv_ptr[t], p1 = S.sv_ptr[t + 1];
-            tail.clear();
-            int64_t o = p0;
-            for (int64_t p = p0; p < p1; ++p)
-              if (from_task[S.sv_src[p]])
-                tail.push_back(S.sv_src[p]);
-              else
-                svs[o++] = S.sv_src[p];
-            for (int64_t v : tail) svs[o++] = v;
-            MADIPM_REQUIRE(tail.size() <= 65535, "tree solve: tree-task entries of one row beyond 16 bits");
-            nt[t] = (uint16_t)tail.size();
-          }
-        sv_src_.upload(svs);
-        sv_nt_.upload(nt);
-        MADIPM_HIP(hipStreamSynchronize(nullptr));  // the host vectors end with this block
-      }
-      std::vector<int64_t> inv((size_t)std::max<int64_t>(S.uvec_size, 1), -1), upm((size_t)std::max<int64_t>(S.rel_ptr[ns], 1), -1);
-      for (int s : ord)
-        for (int64_t p = S.sv_ptr[S.row_ptr[s]]; p < S.sv_ptr[S.row_ptr[s] + S.nrows[s]]; ++p) inv[svs[p]] = p;
-      for (int c = 0; c < ns; ++c)
-        if (S.parent[c] >= 0 && in_tree[S.parent[c]])
-          for (int64_t a = 0; a < S.rel_ptr[c + 1] - S.rel_ptr[c]; ++a) {
-            upm[S.rel_ptr[c] + a] = inv[S.uvec_off[c] + a];
-            MADIPM_REQUIRE(upm[S.rel_ptr[c] + a] >= 0, "tree gather map");
-          }
-      auto inv_pos = [&](int c, int a) { return upm[S.rel_ptr[c] + a]; };
-      tree_lds_ = 8 * 1024;
-      std::vector<uint8_t> chunk(std::max(ns, 1), 0);
-      for (int s : ord) {
-        const double r = S.nrows[s], w = S.first[s + 1] - S.first[s];
-        tree_bytes_ += 8.0 * (r * w + 3.0 * r);
-        tree_flops_ += 2.0 * (r * w - w * (w + 1) / 2);
-        tree_alg_ += solve_alg(s);
-        chunk[s] = !big_root(s) && (S.nrows[s] > SMALL_SOLVE_MAX || 8 * tree_panel_doubles(s) + 8 * 1024 > TREE_SOLVE_LDS);
-        if (big_root(s)) root_lds_ = std::max<int>(root_lds_, 8 * tree_panel_doubles(s));  // k_root_solve: the panel
-      }
-      tree_lds_ = TREE_SOLVE_LDS;  // the rest of the budget stages gather sources
-      tchunk_.upload(chunk);
-      // one task per tree front, in `ord` order (levels ascending): a task's forward dependencies (its
-      // tree children) have earlier tickets, and in reverse order the backward one (its tree parent)
-      // does.  (r3: chains of only-children solved back to back by one workgroup measured slower.)
-      std::vector<int32_t> cptr{0}, clist, dptr{0}, dl, tops;
-      std::vector<SolveLeaf> lv;
-      std::vector<int2> lrow;
-      for (int s : ord) {
-        clist.push_back(s);
-        for (int q = S.child_ptr[s]; q < S.child_ptr[s + 1]; ++q)
-          if (in_tree[S.child_list[q]]) dl.push_back(S.child_list[q]);
-        cptr.push_back((int32_t)clist.size());
-        dptr.push_back((int32_t)dl.size());
-        tops.push_back(s);
-      }
-      // the flat leaf launches: every folded leaf, in postorder (L panels in order)
-      for (int c = 0; c < ns; ++c) {
-        if (!sleaf[c]) continue;
-        const int r = S.nrows[c], w = S.first[c + 1] - S.first[c], f0 = S.first[c];
-        lv.push_back(SolveLeaf{S.l_off[c], f0, r | (w << 8), S.perm[f0], w == 2 ? S.perm[f0 + 1] : -1,
-                               (int32_t)lrow.size(), 0});
-        for (int a = 0; a < r - w; ++a) {
-          const int64_t g = inv_pos(c, a);
-          MADIPM_REQUIRE(g >= 0 && g < INT32_MAX, "tree solve: folded leaf gather position");
-          lrow.push_back(int2{(int32_t)g, S.rows[S.row_ptr[c] + w + a]});
-        }
-      }
-      ntask_ = (int)tops.size();
-      tfront = tops;
-      {  // elimination-tree roots (r == w, no parent) solved backward by k_fwd_tree right after their forward
-         // substitution, on the panel already in LDS (bitwise k_bwd_tree's x; r3: k_bwd_tree 52 -> 43 us)
-        std::vector<uint8_t> rbv(std::max(ntask_, 1), 0);
-        for (int t = 0; t < ntask_; ++t) {
-          const int f = tops[t];
-          rbv[t] = S.parent[f] < 0 && S.nrows[f] == S.first[f + 1] - S.first[f] && !chunk[f];
-          if (rbv[t] && !rootf[f]) rootf[f] = 2;  // solved forward and backward by its k_fwd_tree task
-        }
-        trootbwd_.upload(rbv);
-      }
-      std::vector<int32_t> par;  // backward ticket t -> task ntask - 1 - t: the tree parent of its top
-      for (int t = ntask_ - 1; t >= 0; --t) {
-        const int p = S.parent[tops[t]];
-        par.push_back(p >= 0 && in_tree[p] ? p : -1);
-      }
-      auto up = [](DBuf<int32_t>& d, const std::vector<int32_t>& v) { d.upload(v.empty() ? std::vector<int32_t>{0} : v); };
-      up(tc_ptr_, cptr);
-      up(tc_list_, clist);
-      up(tdep_ptr_, dptr);
-      up(tdep_, dl);
-      up(tpar_, par);
-      tleaf_.upload(lv.empty() ? std::vector<SolveLeaf>(1) : lv);
-      lrow.push_back(int2{0, 0});  // padding: the leaf kernels' clamped loads of a leaf without update rows
-      tlrow_.upload(lrow);
-      nsleaf_ = (int64_t)lv.size();
-      for (const SolveLeaf& L : lv) {
-        const double r = L.rw & 255, w = L.rw >> 8;
-        leaf_alg_ += 8.0 * (S.colcnt[L.f0] + (w == 2 ? S.colcnt[L.f0 + 1] : 0));
-        leaf_bytes_ += 8.0 * (r * w + 3.0 * r) + 32.0 + 8.0 * (r - w);
-        leaf_flops_ += 2.0 * (r * w - w * (w + 1) / 2);
-      }
-      tflags_.alloc(std::max(ns, 1));
-      tflags_.zero();
-      upos_.upload(upm);
-      gbuf_.alloc(std::max<int64_t>(S.sv_ptr[S.row_ptr[ns]], 1));
-      T_.upos = upos_;
-      T_.gbuf = gbuf_;
-      const char* dv = std::getenv("MADIPM_TREE_DEBUG");
-      if (dv && dv[0] == '1' && ntree_) tdbg_.alloc((int64_t)8 * ntree_);
-    }
-    if (S.nshards > 1) {
-      build_solve(2, slev2_);
-      align2();
-      xg_off_ = (int64_t)sched.size();
-      for (int s = 0; s < ns; ++s)
-        if (S.top(s))
-          for (int c = 0; c < cdiv(S.nrows[s], NT); ++c) sched.insert(sched.end(), {s, c});
-      nxg_ = (int)(((int64_t)sched.size() - xg_off_) / 2);
-    }
-    tasks_.upload(tasks.empty() ? std::vector<int32_t>{0, 0} : tasks);
-    flag_off_.upload(flag_off);
-    bp_off_.upload(bp_off);
-    bpart_.alloc(std::max<int64_t>(nbpart, 1) * 64);
-    flags_.alloc(std::max<int64_t>(nflags, 1));
-    flags_.zero();
-    // the big fronts' panel solutions as self-validating words (ll_put / ll_get): 64 values x 2 halves
-    // per panel flag
-    xll_.alloc(std::max<int64_t>(nflags, 1) * 128);
-    xll_.zero();
-    T_.xll = xll_;
-    counters_.alloc(4 * std::max(NL, 1) + 4);  // + the tree-solve tickets (4 NL, 4 NL + 1)
-    counters_.zero();
+  // ---- solve levels, tree-solve tables, big-front solve tasks
+  slev1_ = std::move(P.slev1);
+  slev2_ = std::move(P.slev2);
+  xg_off_ = P.xg_off;
+  nxg_ = P.nxg;
+  ntree_ = P.ntree;
+  ntask_ = P.ntask;
+  nroot_task_ = P.nroot_task;
+  rargs_ = P.rargs;
+  tree_lds_ = P.tree_lds;
+  root_lds_ = P.root_lds;
+  tree_bytes_ = P.tree_bytes, tree_flops_ = P.tree_flops, tree_alg_ = P.tree_alg;
+  nsleaf_ = P.nsleaf;
+  leaf_bytes_ = P.leaf_bytes, leaf_flops_ = P.leaf_flops, leaf_alg_ = P.leaf_alg;
+  tchunk_.upload(P.tchunk);
+  trootbwd_.upload(P.trootbwd);
+  up(tc_ptr_, P.tc_ptr);
+  up(tc_list_, P.tc_list);
+  up(tdep_ptr_, P.tdep_ptr);
+  up(tdep_, P.tdep);
+  up(tpar_, P.tpar);
+  up(tleaf_, P.tleaf);
+  tlrow_.upload(reinterpret_cast<const int2*>(P.tlrow.data()), P.tlrow.size());
+  tflags_.alloc(std::max(ns, 1));
+  tflags_.zero();
+  gbuf_.alloc(std::max<int64_t>(S.sv_ptr[S.row_ptr[ns]], 1));
+  T_.gbuf = gbuf_;
+  if (knobs_.tree_debug && ntree_) tdbg_.alloc((int64_t)8 * ntree_);
+  if (P.tasks.empty()) P.tasks = {0, 0};
+  tasks_.upload(P.tasks);
+  flag_off_.upload(P.flag_off);
+  bp_off_.upload(P.bp_off);
+  bpart_.alloc(std::max<int64_t>(P.nbpart, 1) * 64);
+  flags_.alloc(std::max<int64_t>(P.nflags, 1));
+  flags_.zero();
+  // the big fronts' panel solutions as self-validating words (ll_put / ll_get): 64 values x 2 halves
+  // per panel flag
+  xll_.alloc(std::max<int64_t>(P.nflags, 1) * 128);
+  xll_.zero();
+  T_.xll = xll_;
+  counters_.alloc(4 * std::max(NL, 1) + 4);  // + the tree-solve tickets (4 NL, 4 NL + 1)
+  counters_.zero();
+
+  // ---- the root tail (LaunchPlan::tail_ok: the launch lists allow it).  The tail's kernel waits on
+  // the device for a kernel of the caller's stream: never where kernels are serialised (counter
+  // collection — rocprofv3 --pmc dispatches one kernel at a time, and the waiting kernel would hold
+  // the GPU until its wait times out — AMD_SERIALIZE_KERNEL, HIP_LAUNCH_BLOCKING)
+  const bool serial = env_on("ROCPROF_COUNTER_COLLECTION") || env_on("ROCPROF_COUNTERS") ||
+                      env_on("AMD_SERIALIZE_KERNEL") || env_on("HIP_LAUNCH_BLOCKING");
+  root_async_ = P.tail_ok && !serial && knobs_.root_async != '0';
+  if (knobs_.root_async == '2')  // diagnostics: why (not)
+    fprintf(stderr, "root tail: async %d %s\n", (int)root_async_, P.tail_diag.c_str());
+  if (root_async_) {
+    side0_ = P.side0;
+    nroot_side_ = P.nroot_side;
+    asm_side_ = P.asm_side;
+    side_tree_ = P.side_tree;
+    int lo = 0, hi = 0;  // the tail is the critical path beside the forward solve: the higher priority
+    MADIPM_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    MADIPM_HIP(hipStreamCreateWithPriority(&side_, hipStreamNonBlocking, hi));
+    MADIPM_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
+    const int64_t ncb = asm_side_ ? cdiv(fact1_[side0_ - 1].nchunk, NT) : 0;
+    rflag_.alloc(2 + 64 + ncb);  // go, the assembly's tile counter, one done flag per root, chunk blocks
+    rflag_.zero();
+    tside_.upload(P.tside);
   }
-  {  // the root tail: the launches after the last tree launch factorise only k_root_solve's fronts
-    size_t ft = SIZE_MAX;
-    for (size_t i = 0; i < fact1_.size(); ++i)
-      if (fact1_[i].kind == FTREE) ft = i;
-    // after it: assembly launches, the last of which assembles the roots, then ONE factorisation
-    // launch (SMALL*) of <= 64 roots, all of them solved by k_root_solve
-    const size_t nl = fact1_.size();
-    bool ok = S.nshards == 1 && ntree_ > 0 && ft != SIZE_MAX && ft + 2 < nl && fact1_[nl - 2].kind == ASSEMBLE;
-    for (size_t i = ft + 1; ok && i + 1 < nl; ++i) ok = fact1_[i].kind == ASSEMBLE;
-    if (ok) {
-      const Launch& L = fact1_[nl - 1];
-      ok = (L.kind == SMALL64 || L.kind == SMALL128 || L.kind == SMALL192) && L.items <= 64;
-      for (int64_t k = 0; ok && k < L.items; ++k) ok = rootf[sched[L.off + k]] != 0;
-    }
-    const char* ra = std::getenv("MADIPM_ROOT_ASYNC");
-    // the tail's kernel waits on the device for a kernel of the caller's stream: never where kernels
-    // are serialised (counter collection — rocprofv3 --pmc dispatches one kernel at a time, and the
-    // waiting kernel would hold the GPU until its wait times out — AMD_SERIALIZE_KERNEL,
-    // HIP_LAUNCH_BLOCKING)
-    auto set = [](const char* k) {
-      const char* v = std::getenv(k);
-      return v && v[0] && v[0] != '0';
-    };
-    const bool serial = set("ROCPROF_COUNTER_COLLECTION") || set("ROCPROF_COUNTERS") || set("AMD_SERIALIZE_KERNEL") ||
-                        set("HIP_LAUNCH_BLOCKING");
-    root_async_ = ok && !serial && !(ra && ra[0] == '0');
-    if (ra && ra[0] == '2') {  // diagnostics: why (not)
-      std::string k;
-      for (const Launch& L : fact1_) k += std::to_string(L.kind) + "/" + std::to_string(L.items) + " ";
-      std::string rk;
-      if (nl > 0)
-        for (int64_t q = 0; q < std::min<int64_t>(fact1_[nl - 1].items, 8); ++q) {
-          const int f = sched[fact1_[nl - 1].off + q];
-          rk += std::to_string(f) + ":" + std::to_string(rootf[f]) + ":r" + std::to_string(S.nrows[f]) + " ";
-        }
-      fprintf(stderr, "root tail: async %d (roots %d, tree launch %lld, launches kind/items: %s; last launch fronts %s)\n",
-              (int)root_async_, nroot_task_, ft == SIZE_MAX ? -1LL : (long long)ft, k.c_str(), rk.c_str());
-    }
-    if (root_async_) {
-      side0_ = nl - 1;
-      nroot_side_ = (int)fact1_[nl - 1].items;
-      int lo = 0, hi = 0;  // the tail is the critical path beside the forward solve: the higher priority
-      MADIPM_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-      MADIPM_HIP(hipStreamCreateWithPriority(&side_, hipStreamNonBlocking, hi));
-      MADIPM_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-      // the roots' assembly tiles on the side stream too, behind the chunk pass's block flags
-      // (MADIPM_ROOT_ASM_SIDE=0: on the caller's stream)
-      const char* ea = std::getenv("MADIPM_ROOT_ASM_SIDE");
-      asm_side_ = fact1_[nl - 2].nchunk > 0 && !(ea && ea[0] == '0');
-      const int64_t ncb = asm_side_ ? cdiv(fact1_[nl - 2].nchunk, NT) : 0;
-      rflag_.alloc(2 + 64 + ncb);  // go, the assembly's tile counter, one done flag per root, chunk blocks
-      rflag_.zero();
-      // the k_fwd_tree tasks of the side roots wait for the tail themselves (supportcase10's root)
-      std::vector<uint8_t> ts(std::max(ntask_, 1), 0);
-      const Launch& L = fact1_[nl - 1];
-      for (int64_t k = 0; k < L.items; ++k) {
-        const int f = sched[L.off + k];
-        if (rootf[f] == 2)
-          for (int t = 0; t < ntask_; ++t)
-            if (tfront[t] == f) ts[t] = 1, side_tree_ = true;
-      }
-      tside_.upload(ts);
-    }
-  }
-  clk("  tree solve tables + root tail");
-  sched_.upload(sched.empty() ? std::vector<int32_t>{0} : sched);
+  clk("  launch + solve table uploads");
+  up(sched_, P.sched);
   arena_.alloc(std::max<int64_t>(S.arena_size, 2));
   if (S.nshards > 1) {  // top fronts: the strict upper triangles are never written, keep them 0
     MADIPM_HIP(hipMemset(arena_.p + S.top_lo, 0, sizeof(double) * (S.arena_size - S.top_lo)));
     // exchange buffer: the top fronts' lower triangles (column by column) + 4 status slots per shard
-    std::vector<int64_t> tc;
-    int64_t po = 0;
-    for (int s = 0; s < ns; ++s)
-      if (S.top(s)) {
-        const int64_t r = S.nrows[s];
-        for (int64_t c = 0; c < r; ++c) {
-          tc.insert(tc.end(), {S.l_off[s] + c * r + c, po, r - c});
-          po += r - c;
-        }
-      }
-    ntopcol_ = (int)(tc.size() / 3);
-    xpack_tri_ = po;
-    topcol_.upload(tc.empty() ? std::vector<int64_t>{0, 0, 0} : tc);
-    xpack_.alloc(po + 4 * S.nshards);
+    ntopcol_ = (int)(P.topcol.size() / 3);
+    xpack_tri_ = P.xpack_tri;
+    if (P.topcol.empty()) P.topcol = {0, 0, 0};
+    topcol_.upload(P.topcol);
+    xpack_.alloc(xpack_tri_ + 4 * S.nshards);
     xpack_.zero();
   }
   clk("  sched upload + arena");
@@ -6390,51 +5149,30 @@ LDLSolver::LDLSolver(int n, const int64_t* colptr, const int32_t* rowval, const 
   T_.err = &st_->err;
   status_.zero();
   h_st_->err = 0;
+  constexpr int asm_lds = 8 * kAsmLdsSrc, asm_upd_lds = 2 * 64 * AU_LDT * 8 + 8 * kAsmLdsSrc;
   static bool attr_done = false;
   if (!attr_done) {
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_small_factor<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   128 * 128 * 8));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_fwd_small, hipFuncAttributeMaxDynamicSharedMemorySize, 129 * 128 * 8));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_small_blocked<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   129 * 128 * 8));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_small_blocked<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   192 * 193 / 2 * 8));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_bwd_small, hipFuncAttributeMaxDynamicSharedMemorySize, 129 * 128 * 8));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_fwd_tree, hipFuncAttributeMaxDynamicSharedMemorySize, TREE_SOLVE_LDS));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_root_solve, hipFuncAttributeMaxDynamicSharedMemorySize, TREE_ROOT_LDS));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_fact_tree, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)SymbolicPlan::kFactTreeLdsMax));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_bwd_tree, hipFuncAttributeMaxDynamicSharedMemorySize, TREE_SOLVE_LDS));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_asm_update<int32_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   2 * 64 * AU_LDT * 8 + 8 * kAsmLdsSrc));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_asm_update<int64_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   2 * 64 * AU_LDT * 8 + 8 * kAsmLdsSrc));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_assemble<8, int32_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   8 * kAsmLdsSrc));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_assemble<8, int64_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   8 * kAsmLdsSrc));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_assemble<2, int32_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   8 * kAsmLdsSrc));
-    MADIPM_HIP(hipFuncSetAttribute((const void*)k_assemble<2, int64_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   8 * kAsmLdsSrc));
-    {  // static + dynamic LDS of the assembly kernels must fit one CU (160 KB on gfx950), as k_fact_tree's
-      int dev = 0, cu_lds = 0;
-      MADIPM_HIP(hipGetDevice(&dev));
-      MADIPM_HIP(hipDeviceGetAttribute(&cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
-      auto chk = [&](const void* f, size_t dyn, const char* nm) {
-        hipFuncAttributes fa{};
-        MADIPM_HIP(hipFuncGetAttributes(&fa, f));
-        MADIPM_REQUIRE(fa.sharedSizeBytes + dyn <= (size_t)cu_lds,
-                       std::string(nm) + ": LDS " + std::to_string(fa.sharedSizeBytes) + " + " + std::to_string(dyn) +
-                           " bytes exceeds the CU's " + std::to_string(cu_lds));
-      };
-      chk((const void*)k_assemble<2, int32_t>, 8 * kAsmLdsSrc, "k_assemble");
-      chk((const void*)k_assemble<8, int64_t>, 8 * kAsmLdsSrc, "k_assemble");
-      chk((const void*)k_asm_update<int32_t>, 2 * 64 * AU_LDT * 8 + 8 * kAsmLdsSrc, "k_asm_update");
-      chk((const void*)k_asm_update<int64_t>, 2 * 64 * AU_LDT * 8 + 8 * kAsmLdsSrc, "k_asm_update");
-    }
+    set_max_dyn_lds((const void*)k_fwd_small, kSolveSmallLds);
+    set_max_dyn_lds((const void*)k_bwd_small, kSolveSmallLds);
+    set_max_dyn_lds((const void*)k_small_blocked<false>, kSmall128Lds);
+    set_max_dyn_lds((const void*)k_small_blocked<true>, kSmall192Lds);
+    set_max_dyn_lds((const void*)k_fwd_tree, TREE_SOLVE_LDS);
+    set_max_dyn_lds((const void*)k_bwd_tree, TREE_SOLVE_LDS);
+    set_max_dyn_lds((const void*)k_root_solve, TREE_ROOT_LDS);
+    set_max_dyn_lds((const void*)k_fact_tree, (int)SymbolicPlan::kFactTreeLdsMax);
+    set_max_dyn_lds((const void*)k_asm_update<int32_t>, asm_upd_lds);
+    set_max_dyn_lds((const void*)k_asm_update<int64_t>, asm_upd_lds);
+    set_max_dyn_lds((const void*)k_assemble<8, int32_t>, asm_lds);
+    set_max_dyn_lds((const void*)k_assemble<8, int64_t>, asm_lds);
+    set_max_dyn_lds((const void*)k_assemble<2, int32_t>, asm_lds);
+    set_max_dyn_lds((const void*)k_assemble<2, int64_t>, asm_lds);
+    check_lds_fit((const void*)k_assemble<2, int32_t>, asm_lds, "k_assemble");
+    check_lds_fit((const void*)k_assemble<8, int64_t>, asm_lds, "k_assemble");
+    check_lds_fit((const void*)k_asm_update<int32_t>, asm_upd_lds, "k_asm_update");
+    check_lds_fit((const void*)k_asm_update<int64_t>, asm_upd_lds, "k_asm_update");
     attr_done = true;
   }
+  if (nftree_) check_lds_fit((const void*)k_fact_tree, (size_t)P.ftree_lds, "k_fact_tree");  // this plan's carve
   clk("  buffers + attributes");
   MADIPM_HIP(hipDeviceSynchronize());
   clk("schedules + workspace");
@@ -6532,7 +5270,7 @@ void LDLSolver::lb_fwd(const double* b, hipStream_t s) {
     const int nch = (int)cdiv(G.n, LBF_COLS);
     int64_t poff = 0;
     for (size_t h = 0; h < g; ++h) poff += cdiv(S_.lb[h].n, LBF_COLS) * S_.lb[h].m;
-    TIMED(KK_LB_GEMV, 8.0 * G.m * (double)G.n, lb_alg(g), 2.0 * G.m * (double)G.n,
+    TIMED(KK_LB_GEMV, 8.0 * G.m * (double)G.n, lb_alg(S_, g), 2.0 * G.m * (double)G.n,
           (k_lb_fwd1<<<dim3((unsigned)cdiv(G.m, NT), (unsigned)nch), NT, 0, s>>>(
               lbW_.p + G.w_off, lbd_, lbmem_, perm_, G.m, G.n, G.mem_off, b, xi_, lbpart_.p + poff)));
     k_lb_fwd2<<<(unsigned)cdiv(G.m, NT), NT, 0, s>>>(lbpart_.p + poff, G.m, nch, uvec_.p + G.uvec_off);
@@ -6543,28 +5281,11 @@ void LDLSolver::lb_bwd(int g, double* b, hipStream_t s) {
   const auto& G = S_.lb[g];
   int64_t xoff = 0;
   for (int h = 0; h < g; ++h) xoff += S_.lb[h].m;
-  TIMED(KK_LB_GEMV, 8.0 * G.m * (double)G.n, lb_alg(g), 2.0 * G.m * (double)G.n,
+  TIMED(KK_LB_GEMV, 8.0 * G.m * (double)G.n, lb_alg(S_, g), 2.0 * G.m * (double)G.n,
         (k_lb_bwd<<<(unsigned)cdiv(G.n, NT / 64), NT, 0, s>>>(lbW_.p + G.w_off, lbd_, lbmem_, perm_, lbxrow_.p + xoff,
                                                              G.m, G.n, G.mem_off, xi_, b)));
 }
 
-double LDLSolver::fact_alg_cols(int c0, int c1) const {
-  double b = 0.0;
-  for (int c = c0; c < c1; ++c) b += 8.0 * S_.colcnt[c] + 12.0 * S_.kcol[c];
-  return b;
-}
-double LDLSolver::lb_alg(size_t g) const {  // solve bytes of a batched-leaf group: 8 nnzL of its members
-  const auto& G = S_.lb[g];
-  double b = 0.0;
-  for (int64_t k = G.mem_off; k < G.mem_off + G.n; ++k) b += 8.0 * S_.colcnt[S_.lb_mem[k]];
-  return b;
-}
-double LDLSolver::fact_alg(int s) const { return fact_alg_cols(S_.first[s], S_.first[s + 1]); }
-double LDLSolver::solve_alg(int s) const {
-  double b = 0.0;
-  for (int c = S_.first[s]; c < S_.first[s + 1]; ++c) b += 8.0 * S_.colcnt[c];
-  return b;
-}
 
 void LDLSolver::run_fact(const std::vector<Launch>& LL, const double* Kx, hipStream_t s, size_t b, size_t e,
                          LDLStatus* stamp) {
@@ -6637,7 +5358,7 @@ void LDLSolver::run_fact(const std::vector<Launch>& LL, const double* Kx, hipStr
         break;
       case BIG_UPDATE:
         TIMED(KK_UPDATE, L.bytes, L.alg, L.flops,
-              (k_big_update<<<(unsigned)L.items, NT, 0, s>>>(T_, list, L.step, big_kpan_, arena_, D_, minv_, st_,
+              (k_big_update<<<(unsigned)L.items, NT, 0, s>>>(T_, list, L.step, knobs_.big_kpan, arena_, D_, minv_, st_,
                                                               pivot_tol)));
         break;
       case ASM_UPDATE:  // nf = the launch's K rows (the widest panel, rounded up to 4)
@@ -6651,14 +5372,14 @@ void LDLSolver::run_fact(const std::vector<Launch>& LL, const double* Kx, hipStr
         TIMED(KK_BIG_DAG, L.bytes, L.alg, L.flops,
               (k_big_dag<<<(unsigned)std::min<int64_t>(L.items, dag_grid_), NT, 0, s>>>(
                   T_, reinterpret_cast<const DagTask*>(dag_tasks_.p) + L.off, dag_dptr_.p + L.off, dag_dlist_.p,
-                  (int)L.items, dag_flags_.p + L.off, cepoch_, dag_cnt_.p, big_kpan_, arena_, D_, dag_m_, dag_mslot_,
+                  (int)L.items, dag_flags_.p + L.off, cepoch_, dag_cnt_.p, knobs_.big_kpan, arena_, D_, dag_m_, dag_mslot_,
                   st_, pivot_tol, &st_->err, dag_dbg_.p ? dag_dbg_.p + 4 * L.off : nullptr)));
         if (dag_dbg_.p) dag_debug_dump(s, L);
         break;
       case BIG_UPDATE128:
         TIMED(KK_UPDATE, L.bytes, L.alg, L.flops,
               (k_big_upd128<<<(unsigned)(L.items * std::max(1, L.nf)), NT, 0, s>>>(
-                  T_, list, L.step, big_kpan_, arena_, D_, minv_, st_, pivot_tol, std::max(1, L.nf), upsum_, uptick_)));
+                  T_, list, L.step, knobs_.big_kpan, arena_, D_, minv_, st_, pivot_tol, std::max(1, L.nf), upsum_, uptick_)));
         break;
       case LB_BUILD:
         TIMED(KK_LB_BUILD, L.bytes, L.alg, 0.0,
@@ -6669,14 +5390,6 @@ void LDLSolver::run_fact(const std::vector<Launch>& LL, const double* Kx, hipStr
         TIMED(KK_LB_SYRK, L.bytes, 0.0, L.flops, lb_syrk((int)L.off, s));
         break;
       case FTREE:
-        if (!ftree_checked_) {  // static + dynamic LDS must fit the CU (160 KB on gfx950)
-          hipFuncAttributes fa{};
-          MADIPM_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_fact_tree)));
-          MADIPM_REQUIRE(fa.sharedSizeBytes + (size_t)L.lds_bytes <= 160 * 1024,
-                         "k_fact_tree: LDS " + std::to_string(fa.sharedSizeBytes) + " + " +
-                             std::to_string(L.lds_bytes) + " bytes exceeds 160 KB");
-          ftree_checked_ = true;
-        }
         ++fepoch_;
         TIMED(KK_FACT_TREE, L.bytes, L.alg, L.flops,
               (k_fact_tree<<<(unsigned)(nftree_ + nfhelp_), FTN, L.lds_bytes, s>>>(
@@ -6976,7 +5689,7 @@ void LDLSolver::fwd_levels(const std::vector<SolveLevel>& V, int phase, double* 
       TIMED(KK_FWD_GATHER, L.gat_bytes, 0.0, 0.0,
             (k_fwd_gather<<<L.ngat, NT, 0, s>>>(T_, sched_.p + L.gat_off, b, uvec_, vwork_)));
       TIMED(KK_FWD_BIG, L.big_bytes, L.big_alg + L.below_alg, L.big_flops,
-            (k_fwd_big<<<std::min(L.nftask, big_solve_wg_), NT, 0, s>>>(T_, tasks + L.ftask_off, L.nftask, cnt + 2 * lev,
+            (k_fwd_big<<<std::min(L.nftask, knobs_.big_solve_wg), NT, 0, s>>>(T_, tasks + L.ftask_off, L.nftask, cnt + 2 * lev,
                                                                flags_, flag_off_, efwd, arena_, vwork_, xi_, uvec_, &st_->err)));
     }
     if (lev == 0 && phase == 0 && ntree_ && nsleaf_)
@@ -7038,7 +5751,7 @@ void LDLSolver::bwd_levels(const std::vector<SolveLevel>& V, int phase, double* 
             (k_bwd_below<<<L.nbelow, NT, 0, s>>>(T_, sched_.p + L.below_off, bp_off_, arena_, xi_, bpart_)));
     if (L.nbig)
       TIMED(KK_BWD_BIG, L.big_bytes - L.below_bytes, L.big_alg, L.big_flops - 0.25 * L.below_bytes,
-            (k_bwd_big<<<std::min(L.nbtask, big_solve_wg_), NT, 0, s>>>(T_, tasks + L.btask_off, L.nbtask, cnt + 2 * lev + 1,
+            (k_bwd_big<<<std::min(L.nbtask, knobs_.big_solve_wg), NT, 0, s>>>(T_, tasks + L.btask_off, L.nbtask, cnt + 2 * lev + 1,
                                                                flags_, flag_off_, ebwd, arena_, D_, xi_, b, bp_off_, bpart_,
                                                                &st_->err)));
     if (L.nsmall)

@@ -11,26 +11,10 @@
 #include <vector>
 
 #include "common.hpp"
+#include "ldl_plan.hpp"
 #include "symbolic.hpp"
 
 namespace madipm {
-
-// the batch range a k_fact_tree task folds and its first batch's table entries, in one record loaded
-// with the task's other per-front words (r5: the first batch's entries were a dependent round trip)
-struct FoldStart {
-  int32_t b0, b1;      // batches [b0, b1)
-  int32_t kq0, kq1;    // the first batch's leaves [kq0, kq1) (fold_bat)
-  int64_t row0, row1;  // its flat leaf rows (fold_row0)
-  int64_t poff;        // its product entries (fold_poff, fold_plen)
-  int32_t plen, pad;
-};
-struct FoldHelp {
-  int32_t front, flag;  // the front, the flag the helper publishes
-  int64_t img;          // its image in FrontTab::fimg: nimg doubles, entry k = LDS entry fimg_dst[dofs + k]
-  int64_t dofs;         // its destinations in FrontTab::fimg_dst (the LDS entries its batches' products reach)
-  int32_t nimg, pad;
-  FoldStart fs;         // its batches
-};
 
 // Device view of the front table (SoA, all device pointers).
 struct FrontTab {
@@ -107,30 +91,8 @@ constexpr int32_t kErrHandoff = 1;   // a dependency hand-off (flag poll) timed 
 constexpr int32_t kErrLdsCarve = 2;  // a k_fact_tree front or leaf batch did not fit its LDS carve
 constexpr int32_t kErrAsmSrc = 4;    // an assembly tile on the LDS source path has more sources than its windows
 
-// assembly: a big child's block on one 64x64 tile of its parent (SymbolicPlan::bt entry, split by
-// column ranges so that na * nb <= kBigRecEntries).  The child's update rows on the tile are the
-// consecutive rows a0 .. a0 + na - 1 (its rows are a sorted subset of the parent's), its columns
-// b0 .. b0 + nb - 1; rows[i] / cols[j] = their tile row / column.  Entry e < na nb of the record is
-// (i, j) = (e mod na, e div na), e div na = (e * na_inv) >> 16 (exact for e < 1024, na <= 64).
-constexpr int kBigRecEntries = 1024;
-struct BigChildRec {
-  int64_t u_off;
-  int32_t u_ld, a0, b0;
-  uint16_t na, nb;
-  uint32_t na_inv, pad;
-  uint8_t rows[64], cols[64];
-};
-
 struct SolveTask {
   int32_t front, blk;
-};
-
-// a micro leaf (w <= 2, r <= 32, no children) folded into a tree-solve chain task: its L panel, first
-// pivot, r | w << 8, the caller's indices of its two pivots, and the offset of its below rows' entries
-// in the row table (int2: gbuf position of the forward update entry, xi index of the row)
-struct SolveLeaf {
-  int64_t loff;
-  int32_t f0, rw, p0, p1, roff, pad;
 };
 
 struct LDLStatus {  // device-resident, read back by status()
@@ -232,15 +194,6 @@ class LinSolver {
   virtual void join(hipStream_t s) { (void)s; }
 };
 
-// k_root_solve's fronts (up to kRootArgs) by value: their shapes come with the launch instead of two
-// dependent table loads (front id, then first / nrows / row_ptr / l_off) before the gather
-constexpr int kRootArgs = 4;
-struct RootArgs {
-  int32_t n;
-  int32_t s[kRootArgs], f0[kRootArgs], w[kRootArgs], r[kRootArgs];
-  int64_t e0[kRootArgs], loff[kRootArgs];
-};
-
 class LDLSolver : public LinSolver {
  public:
   LDLSolver(int n, const int64_t* colptr, const int32_t* rowval, const SymbolicOptions& sopt,
@@ -299,47 +252,8 @@ class LDLSolver : public LinSolver {
   void kernel_stats(KernelStat out[KK_COUNT]) override;
 
  private:
-  enum Kind { ASSEMBLE = 0, SMALL32 = 1, SMALL64 = 2, SMALL128 = 3, BIG_DIAG = 4, BIG_TRSM = 5, BIG_UPDATE = 6,
-              LB_BUILD = 7, LB_SYRK = 8, MICRO = 9, SMALL192 = 10, FTREE = 11, BIG_UPDATE128 = 12,
-              ASM_UPDATE = 13, BIG_DAG = 14 };
-  struct Launch {
-    int kind;
-    int step;       // panel step for BIG_DIAG / BIG_TRSM / BIG_UPDATE
-    int64_t off;    // ASSEMBLE: first tile; SMALL*: front list in sched_; BIG_*: (front, item) pairs in sched_
-    int nf;         // number of fronts (SMALL*)
-    int64_t items;  // workgroups
-    int64_t chunk0 = 0, nchunk = 0;  // ASSEMBLE: chunk range of the level
-    double bytes = 0, flops = 0;       // staging traffic model / algorithmic work of the launch
-    double alg = 0;                    // SURVEY 8(d) bytes of the columns the launch factorises
-    double bytes2 = 0, flops2 = 0;     // ASSEMBLE: of the chunk pass
-    bool lds = true;                   // SMALL*: some front is a leaf (assembled in LDS)
-    int lds_bytes = 0;                 // SMALL*: dynamic LDS of the blocked kernel (largest front)
-  };
-  struct SolveLevel {
-    int64_t tiny_off;  // fronts with r <= 32 (half a wave each)
-    int ntiny;
-    int64_t micro_off;  // fronts with r <= 32, w <= 2 (16 lanes each)
-    int nmicro;
-    double micro_bytes = 0, micro_flops = 0, micro_alg = 0;
-    int64_t small_off;
-    int nsmall;
-    int64_t big_off;
-    int nbig;
-    int64_t gat_off;  // (front, 256-row chunk) pairs for k_fwd_gather
-    int ngat;
-    int64_t below_off;  // (front, panel | chunk << 16) pairs for k_bwd_below
-    int nbelow;
-    int64_t ftask_off;
-    int nftask;
-    int64_t btask_off;
-    int nbtask;
-    int small_lds = 0;  // dynamic LDS of the small-front solve kernels (largest panel, ld r | 1)
-    double tiny_bytes = 0, tiny_flops = 0;
-    double small_bytes = 0, small_flops = 0, big_bytes = 0, big_flops = 0, below_bytes = 0, gat_bytes = 0;
-    // SURVEY 8(d) bytes per direction: 8 nnzL of the fronts' columns (big: diagonal block / below it)
-    double tiny_alg = 0, small_alg = 0, big_alg = 0, below_alg = 0;
-  };
   SymbolicPlan S_;
+  LdlKnobs knobs_;  // the MADIPM_* environment, read once by the constructor
   FrontTab T_{};
   Comm* comm_ = nullptr;
   std::vector<Launch> fact1_, fact2_;      // phase 1 (this shard's subtrees; everything unsharded), phase 2 (top)
@@ -380,11 +294,6 @@ class LDLSolver : public LinSolver {
   // parent), between the level-0 launches and the remaining levels
   int ntree_ = 0, tree_lds_ = 0;
   double tree_bytes_ = 0, tree_flops_ = 0, tree_alg_ = 0;
-  // SURVEY 8(d) bytes of front s: factorisation 8 nnzL + 12 nnzK of its columns; solve 8 nnzL
-  double fact_alg(int s) const;
-  double fact_alg_cols(int c0, int c1) const;
-  double solve_alg(int s) const;
-  double lb_alg(size_t g) const;
   DBuf<int32_t> tc_ptr_, tc_list_, tdep_ptr_, tdep_, tpar_, tflags_;
   DBuf<uint8_t> trootbwd_;  // per forward task: an elimination-tree root solved backward by k_fwd_tree
   int nroot_task_ = 0, root_lds_ = 0;  // tree-solve tasks of big etree roots (last, own forward launch)
@@ -401,15 +310,11 @@ class LDLSolver : public LinSolver {
                        const char* p3, const char* p4, const char* p5, int stride);
   // factorisation tree (k_fact_tree): fronts in topological order, their tree children, flags
   // (per-factorisation epoch), ticket counters (reset by the launch's last workgroup)
-  int nftree_ = 0, ftree_lds_ = 0, fepoch_ = 0;
-  bool ftree_checked_ = false;
-  double ftree_bytes_ = 0, ftree_flops_ = 0, ftree_alg_ = 0;
+  int nftree_ = 0, fepoch_ = 0;
   DBuf<int32_t> ft_order_, ft_dptr_, ft_dep_, fflags_, fcnt_;
   DBuf<uint64_t> xll_;
   DBuf<uint16_t> sv_nt_;
   DBuf<int64_t> fdbg_, ab_first_, ab_loff_, fold_poff_, fold_row0_;
-  int big_kpan_ = 4;  // big fronts: panels per deferred trailing-update group (MADIPM_BIG_KPAN)
-  bool big_dag_ = true;  // a level's big fronts in one k_big_dag launch (MADIPM_BIG_DAG=0: per panel step and kind)
   DBuf<int32_t> dag_tasks_;  // DagTask (4 int32) per task of every DAG launch, in launch order
   DBuf<int32_t> dag_dptr_;   // per task: its first dependency in dag_dlist_ (launch-local tickets), + end
   DBuf<int32_t> dag_dlist_;
@@ -422,10 +327,8 @@ class LDLSolver : public LinSolver {
   DBuf<int64_t> dag_dbg_;          // MADIPM_DAG_DEBUG: 4 stamps per task
   std::vector<int32_t> dag_kind_;  // (its host copy of the task words)
   void dag_debug_dump(hipStream_t s, const Launch& L);
-  bool upd_split_ = true;  // k_big_upd128 split K on launches of few tiles (MADIPM_UPD_SPLIT=0: off)
-  DBuf<double> upsum_;    // its partial products
+  DBuf<double> upsum_;    // k_big_upd128 split K on launches of few tiles: its partial products
   DBuf<int32_t> uptick_;  // its per-tile tickets (reset by each tile's last part)
-  int big_solve_wg_ = 512;
   DBuf<int32_t> ab_src0_, ab_src1_, ab_k_, ab_f0_, ab_wrc_, fold_bptr_, fold_bat_, fold_plen_, fold_rmax_, fold_lmax_;
   DBuf<FoldStart> fstart_;
   DBuf<int32_t> fold_help_;
