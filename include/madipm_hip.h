@@ -427,6 +427,46 @@ int madipm_solver_update(madipm_solver_t s, const madipm_qp_update* u);
  * Any pointer may be NULL. */
 int madipm_solver_counters(madipm_solver_t s, int64_t* n_analyses, int64_t* n_updates, double* last_update_s);
 
+/* ------------------------------------------------------------------ the device route  [ABI 0.2.5, additive]
+ * The re-solve loop without the host: the update reads DEVICE arrays, the solution is written to DEVICE
+ * arrays, and everything the host update computes on the host (bound relaxation and push, the slack start
+ * A x, set_scaling!'s row maxima and gradient, the fixed variables' terms, the norms) is recomputed by
+ * kernels, every sum in the host loop's order and rounding: the refreshed solver holds exactly the bits a
+ * madipm_solver_create of the updated problem would hold.  (madipm_version() still returns 203.)
+ *
+ * madipm_solver_update_device: as madipm_solver_update, but every array pointer of `u` is a DEVICE pointer
+ * (c0 stays a host pointer); NULL = keep.  Needs madipm_solver_prepare_update first.
+ * Stream contract: `stream` is the stream the caller's arrays were produced on (NULL = the default
+ * stream).  The reads are ordered after the work already enqueued on it (an event wait: the caller's
+ * stream is not synchronised with the host).  The call returns with all its reads done and the solver's
+ * stream idle: the caller may then overwrite or free its arrays, which are never written.  Starts no
+ * solve, runs no analysis; n_updates and last_update_s count it.
+ * Rejections: those of madipm_solver_update, on the merged data (given fields over kept fields), with the
+ * same negative code and the same madipm_last_error() text (first offending index in the host's check
+ * order: row kinds, then variables, then ranged rows); the solver is untouched.
+ * Memory: the first call on a solver allocates, on top of madipm_solver_prepare_update's plan: 8 B per
+ * entry of A (row lists of the slack start and the row maxima) + 8 B per entry of A in a fixed column;
+ * 8 B per endpoint of a stored entry of H (16 B off the diagonal) + 8 B per entry between a fixed and a
+ * free variable + 12 B per entry between two fixed ones; 4 B per row and per variable for each list
+ * start; 8 B x (4 nvar + 3 ncon) of raw staging; 8 B x (3 (nvar + ranged rows) + nvar + ncon) of start
+ * vectors.  Later calls allocate nothing; a solver that never calls it, or calls only
+ * madipm_solver_prepare_update / madipm_solver_update, pays nothing.
+ * Mixing: madipm_solver_update, _update_device, _solve and _get_solution may follow each other in any
+ * order.  A host update after a device update first reads the device-installed numbers back, so that its
+ * "keep" fields and its classification check see them (madipm_solver_get_data does the same).
+ * madipm_solver_create_dist: every rank calls it with its own device copy of the same data. */
+int madipm_solver_update_device(madipm_solver_t s, const madipm_qp_update* u, madipm_stream_t stream);
+/* update_solution! into DEVICE arrays (any may be NULL): un-scaled, lengths and bits as
+ * madipm_solver_get_solution.  Does not block the host: the writes are ordered after the work already
+ * enqueued on `stream`, and work enqueued on `stream` after the call returns sees the results. */
+int madipm_solver_get_solution_device(madipm_solver_t s, double* d_x, double* d_y, double* d_zl, double* d_zu,
+                                      double* d_cons, madipm_stream_t stream);
+/* The raw problem numbers the solver currently holds (what was last installed by create / update /
+ * update_device), copied to HOST arrays; any pointer may be NULL.  Avals needs
+ * madipm_solver_prepare_update (the solver keeps no copy of A before it). */
+int madipm_solver_get_data(madipm_solver_t s, double* c, double* c0, double* Hvals, double* Avals, double* lcon,
+                           double* ucon, double* lvar, double* uvar, double* x0, double* y0);
+
 #ifdef __cplusplus
 }
 #endif

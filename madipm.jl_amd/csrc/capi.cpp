@@ -661,6 +661,32 @@ int madipm_solver_update(madipm_solver_t s, const madipm_qp_update* u) {
   MADIPM_API_END
 }
 
+int madipm_solver_update_device(madipm_solver_t s, const madipm_qp_update* u, madipm_stream_t stream) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s && u, "null argument");
+  s->s->update_device(*u, (hipStream_t)stream);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_get_solution_device(madipm_solver_t s, double* d_x, double* d_y, double* d_zl, double* d_zu,
+                                      double* d_cons, madipm_stream_t stream) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->get_solution_device(d_x, d_y, d_zl, d_zu, d_cons, (hipStream_t)stream);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_get_data(madipm_solver_t s, double* c, double* c0, double* Hvals, double* Avals, double* lcon,
+                           double* ucon, double* lvar, double* uvar, double* x0, double* y0) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->get_data(c, c0, Hvals, Avals, lcon, ucon, lvar, uvar, x0, y0);
+  return 0;
+  MADIPM_API_END
+}
+
 int madipm_solver_counters(madipm_solver_t s, int64_t* n_analyses, int64_t* n_updates, double* last_update_s) {
   MADIPM_API_BEGIN
   MADIPM_REQUIRE(s, "null handle");

@@ -70,6 +70,29 @@ struct UpdatePlan {
   int64_t nJ = 0, nH = 0;               // destination entries of J (= J^T) and H
 };
 
+// The device route (update_device), allocated by its first call: the raw problem numbers as last installed
+// (A's and H's are the plan's Araw / Hraw), the start vectors initialize() restarts from, and the lists
+// that give every host sum of numeric_host its input order: per destination [sp[i], sp[i + 1]) of
+// (input index, other index) pairs, 8 B each.  Per entry of A: 8 B (row lists) + 8 B per entry in a fixed
+// column; per stored entry of H: 8 B per endpoint (16 B off the diagonal), + 8 B per fixed / free cross
+// entry, + 12 B per entry between two fixed variables; 4 B per row and per variable for each sp.
+struct DevUpdate {
+  DBuf<double> c, lvar, uvar, lcon, ucon, x0, y0;  // raw staging (y0 is also the start y)
+  DBuf<double> x, xl, xu;                          // start vectors of [x; s], scaled
+  DBuf<double> xpre, ax, sc;                       // structural start before the push, A x, scalar block
+  DBuf<int32_t> chk, ineq;                         // the check's result block; ind_ineq
+  DBuf<uint8_t> vcls, ccls;                        // creation-time bound classes
+  DBuf<int32_t> asp, fsp, gsp, xsp, bfk;
+  DBuf<int2> ae, fe, ge, xe, bfrc;
+  int nbf = 0;
+  hipEvent_t ev = nullptr;
+  double* hsc = nullptr;  // pinned: SC_LEN scalars + the check block behind them
+  ~DevUpdate() {
+    if (ev) (void)hipEventDestroy(ev);
+    if (hsc) (void)hipHostFree(hsc);
+  }
+};
+
 namespace {
 
 constexpr int NT = 256;
@@ -1423,6 +1446,8 @@ MPCSolver::~MPCSolver() {
     }
   }
   if (hst_) (void)hipHostFree(hst_);
+  for (hipEvent_t e : sol_ev_)
+    if (e) (void)hipEventDestroy(e);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -2139,6 +2164,265 @@ __global__ void k_refresh_gather(int64_t nd, const int32_t* __restrict__ map, co
   GRID_LOOP(q, nd) to[q] = from[map[q]];
 }
 
+// ----------------------------------------------------------------- the device route (update_device)
+// numeric_host restated as kernels over device-resident raw data.  One thread per destination; a
+// destination's sources come from its list [sp[i], sp[i + 1]) of (input index, other index) pairs in
+// ascending input index, so every sum has the host loop's order; contraction is off, so every product is
+// rounded before it is added; the two maxima are integer maxima over the bit patterns of non-negative
+// doubles (order-free, hence deterministic).  std::min / std::max are restated with their own comparisons
+// (a NaN operand is kept or dropped exactly as on the host).
+__device__ __forceinline__ double smax(double a, double b) { return a < b ? b : a; }  // std::max(a, b)
+__device__ __forceinline__ double smin(double a, double b) { return b < a ? b : a; }  // std::min(a, b)
+__device__ __forceinline__ int dev_bound_class(double l, double u) {
+  return l == u ? 1 : (l != -INF ? 2 : 0) | (u != INF ? 4 : 0);
+}
+// after the loop every lane of the block is active again: one wave maximum, one integer atomic per wave
+__device__ __forceinline__ void publish_max(double a, double* slot) {
+  a = wave_reduce<OP_MAX>(a);
+  if ((threadIdx.x & 63) == 0 && a > 0.0)
+    atomicMax(reinterpret_cast<unsigned long long*>(slot), (unsigned long long)__double_as_longlong(a));
+}
+
+enum { SC_OS = 0, SC_OBJ = 1, SC_C0S = 2, SC_NORMB = 3, SC_GMAX = 4, SC_LEN = 8 };
+
+// The host's classification check on the merged data: out[0] = first row whose equality / ranged kind
+// changed, out[1] = first variable, out[2] = first ranged row whose bound class changed (INT32_MAX: none).
+// The classes were fixed at creation (vcls, ccls).
+__global__ void k_upd_check(int nx, int m, const double* __restrict__ lv, const double* __restrict__ uv,
+                            const double* __restrict__ lc, const double* __restrict__ uc,
+                            const uint8_t* __restrict__ vcls, const uint8_t* __restrict__ ccls,
+                            int32_t* __restrict__ out) {
+  GRID_LOOP(i, (nx > m ? nx : m)) {
+    if (i < m) {
+      const int was = ccls[i], is = dev_bound_class(lc[i], uc[i]);
+      if ((was == 1) != (is == 1))
+        atomicMin(&out[0], (int)i);
+      else if (was != is)
+        atomicMin(&out[2], (int)i);
+    }
+    if (i < nx && dev_bound_class(lv[i], uv[i]) != vcls[i]) atomicMin(&out[1], (int)i);
+  }
+}
+
+// raw_bounds + MadNLP.initialize!'s start and bound relaxation: xl / xu of [x; s], the structural start
+// (x0, a fixed variable at its value) as it is before the bound push
+__global__ void k_upd_bounds(int nx, int n, double tol, const double* __restrict__ lvar,
+                             const double* __restrict__ uvar, const double* __restrict__ lcon,
+                             const double* __restrict__ ucon, const double* __restrict__ x0,
+                             const int32_t* __restrict__ ineq, const uint8_t* __restrict__ fixed,
+                             double* __restrict__ xl, double* __restrict__ xu, double* __restrict__ xpre) {
+#pragma clang fp contract(off)
+  GRID_LOOP(i, n) {
+    const bool fx = fixed[i];
+    double l, u;
+    if (i < nx) {
+      l = lvar[i], u = uvar[i];
+      xpre[i] = fx ? l : x0[i];
+    } else {
+      const int r = ineq[i - nx];
+      l = lcon[r], u = ucon[r];
+    }
+    if (!fx) {
+      if (__builtin_isfinite(l)) l = l - tol * smax(1.0, fabs(l));
+      if (__builtin_isfinite(u)) u = u + tol * smax(1.0, fabs(u));
+    }
+    xl[i] = l;
+    xu[i] = u;
+  }
+}
+
+// per constraint row: the slack start (A x)_r over every entry of the row, the row maximum -> con_scale,
+// cfix over the row's fixed-column entries, rhs (scaled) and its part of norm_b
+__global__ __launch_bounds__(NT) void k_upd_rows(int m, int scaling, const int32_t* __restrict__ asp,
+                                                 const int2* __restrict__ ae, const int32_t* __restrict__ fsp,
+                                                 const int2* __restrict__ fe, const double* __restrict__ Av,
+                                                 const double* __restrict__ xpre, const double* __restrict__ lcon,
+                                                 const double* __restrict__ ucon, double* __restrict__ ax,
+                                                 double* __restrict__ cscale, double* __restrict__ cfix,
+                                                 double* __restrict__ rhs, double* __restrict__ sc) {
+#pragma clang fp contract(off)
+  double nb = 0.0;
+  GRID_LOOP(r, m) {
+    double s = 0.0, rm = 0.0;
+    const int a = asp[r], b = asp[r + 1];
+    for (int t = a; t < b; ++t) {
+      const int2 e = ae[t];
+      const double v = Av[e.x];
+      const double p = v * xpre[e.y];
+      s = s + p;
+      rm = smax(rm, fabs(v));
+    }
+    ax[r] = s;
+    const double cs = scaling ? smin(1.0, 100.0 / rm) : 1.0;
+    cscale[r] = cs;
+    double cf = 0.0;
+    for (int t = fsp[r]; t < fsp[r + 1]; ++t) {
+      const int2 e = fe[t];
+      const double v = cs * Av[e.x];
+      const double p = v * xpre[e.y];
+      cf = cf + p;
+    }
+    cfix[r] = cf;
+    const double l = lcon[r];
+    double h = l == ucon[r] ? l : 0.0;
+    if (scaling) h = h * cs;
+    rhs[r] = h;
+    nb = smax(nb, fabs(h));
+  }
+  publish_max(nb, sc + SC_NORMB);
+}
+
+// the slack start, initialize_variables!'s bound push, then the slack rows of x / xl / xu times con_scale
+__global__ void k_upd_start(int nx, int n, int scaling, double bp, double bf, const double* __restrict__ xpre,
+                            const double* __restrict__ ax, const double* __restrict__ cscale,
+                            const int32_t* __restrict__ ineq, const uint8_t* __restrict__ fixed,
+                            double* __restrict__ xl, double* __restrict__ xu, double* __restrict__ x) {
+#pragma clang fp contract(off)
+  GRID_LOOP(i, n) {
+    const int r = i < nx ? -1 : ineq[i - nx];
+    double v = i < nx ? xpre[i] : ax[r];
+    double l = xl[i], u = xu[i];
+    if (!fixed[i]) {
+      double lo = -INF, hi = INF;
+      if (__builtin_isfinite(l)) {
+        double pl = bp * smax(1.0, fabs(l));
+        if (__builtin_isfinite(u)) pl = smin(pl, bf * (u - l));
+        lo = l + pl;
+      }
+      if (__builtin_isfinite(u)) {
+        double pu = bp * smax(1.0, fabs(u));
+        if (__builtin_isfinite(l)) pu = smin(pu, bf * (u - l));
+        hi = u - pu;
+      }
+      v = smin(smax(v, lo), hi);
+    }
+    if (r >= 0 && scaling) {
+      const double cs = cscale[r];
+      xl[i] = l * cs;
+      xu[i] = u * cs;
+      v = v * cs;
+    }
+    x[i] = v;
+  }
+}
+
+// set_scaling!'s objective gradient at the start: g[i] = sgn c[i] + the H terms of variable i in input
+// order; its maximum magnitude -> sc[SC_GMAX]
+__global__ __launch_bounds__(NT) void k_upd_g(int nx, double sgn, const int32_t* __restrict__ gsp,
+                                              const int2* __restrict__ ge, const double* __restrict__ c,
+                                              const double* __restrict__ Hv, const double* __restrict__ x,
+                                              double* __restrict__ sc) {
+#pragma clang fp contract(off)
+  double gm = 0.0;
+  GRID_LOOP(i, nx) {
+    double g = sgn * c[i];
+    for (int t = gsp[i]; t < gsp[i + 1]; ++t) {
+      const int2 e = ge[t];
+      const double v = sgn * Hv[e.x];
+      const double p = v * x[e.y];
+      g = g + p;
+    }
+    gm = smax(gm, fabs(g));
+  }
+  publish_max(gm, sc + SC_GMAX);
+}
+
+// one thread: obj_scale, obj_scale * sgn, and c0s with const_fixed summed over the both-fixed H entries
+// (bf: input index, row, column) in input order
+__global__ void k_upd_scalars(int scaling, double sgn, double c0, int nbf, const int32_t* __restrict__ bfk,
+                              const int2* __restrict__ bfrc, const double* __restrict__ Hv,
+                              const double* __restrict__ x, double* __restrict__ sc) {
+#pragma clang fp contract(off)
+  if (blockIdx.x || threadIdx.x) return;
+  double os = 1.0;
+  if (scaling) {
+    const double gmax = sc[SC_GMAX];
+    os = gmax > 0 ? smin(1.0, 100.0 / gmax) : 1.0;
+  }
+  const double oss = os * sgn;
+  double cf = 0.0;
+  for (int t = 0; t < nbf; ++t) {
+    const int2 rc = bfrc[t];
+    const double v = oss * Hv[bfk[t]];
+    const double p = (((rc.x == rc.y ? 0.5 : 1.0) * v) * x[rc.x]) * x[rc.y];
+    cf = cf + p;
+  }
+  const double sc0 = sgn * c0;
+  const double t0 = os * sc0;
+  sc[SC_OBJ] = os;
+  sc[SC_OS] = oss;
+  sc[SC_C0S] = t0 + cf;
+}
+
+// cs = (obj_scale sgn) c, and gfix: the cross terms of the fixed variables into the free ones
+__global__ void k_upd_cs_gfix(int nx, int n, const int32_t* __restrict__ xsp, const int2* __restrict__ xe,
+                              const double* __restrict__ c, const double* __restrict__ Hv,
+                              const double* __restrict__ x, const double* __restrict__ sc, double* __restrict__ cs,
+                              double* __restrict__ gfix) {
+#pragma clang fp contract(off)
+  const double oss = sc[SC_OS];
+  GRID_LOOP(i, n) {
+    double gf = 0.0, cv = 0.0;
+    if (i < nx) {
+      cv = oss * c[i];
+      for (int t = xsp[i]; t < xsp[i + 1]; ++t) {
+        const int2 e = xe[t];
+        const double v = oss * Hv[e.x];
+        const double p = v * x[e.y];
+        gf = gf + p;
+      }
+    }
+    cs[i] = cv;
+    gfix[i] = gf;
+  }
+}
+
+// k_refresh_h with obj_scale * sgn read from the device scalar block
+__global__ void k_refresh_h_dev(int64_t nd, const int32_t* __restrict__ sp, const int32_t* __restrict__ src,
+                                const double* __restrict__ sc, const double* __restrict__ raw,
+                                const int32_t* __restrict__ kpos, double* __restrict__ Hv, double* __restrict__ Kx,
+                                double* __restrict__ K0) {
+#pragma clang fp contract(off)
+  const double os = sc[SC_OS];
+  GRID_LOOP(q, nd) {
+    const int a = sp[q], b = sp[q + 1];
+    if (a == b) continue;
+    double acc = os * raw[src[a]];
+    for (int t = a + 1; t < b; ++t) {
+      const double p = os * raw[src[t]];
+      acc = acc + p;
+    }
+    Hv[q] = acc;
+    const int kp = kpos[q];
+    if (kp >= 0) {
+      Kx[kp] = acc;
+      if (K0) K0[kp] = acc;
+    }
+  }
+}
+
+// update_solution! on the device: x, z_L / obj_scale, z_U / obj_scale, y con_scale / obj_scale, and the
+// constraint values k_cons left in `ax`, / con_scale (any output may be null)
+__global__ void k_unscale(int nx, int m, double os, const double* __restrict__ x, const double* __restrict__ y,
+                          const double* __restrict__ zl, const double* __restrict__ zu,
+                          const double* __restrict__ ax, const double* __restrict__ cscale, double* __restrict__ ox,
+                          double* __restrict__ oy, double* __restrict__ ozl, double* __restrict__ ozu,
+                          double* __restrict__ ocons) {
+#pragma clang fp contract(off)
+  GRID_LOOP(i, (nx > m ? nx : m)) {
+    if (i < nx) {
+      if (ox) ox[i] = x[i];
+      if (ozl) ozl[i] = zl[i] / os;
+      if (ozu) ozu[i] = zu[i] / os;
+    }
+    if (i < m) {
+      const double cs = cscale[i];
+      if (oy) oy[i] = y[i] * cs / os;
+      if (ocons) ocons[i] = ax[i] / cs;
+    }
+  }
+}
+
 // csr_from_coo's structure for the COO (r, c) without its values: destination entries sorted by
 // (row, column), each with the ids of its COO entries in input order (id < 0: a constant entry, no source)
 struct CooPlan {
@@ -2179,8 +2463,14 @@ CooPlan coo_plan(int nrow, const std::vector<int32_t>& r, const std::vector<int3
 
 // what setup_host derives from one coordinate's bounds: fixed, or finite lower (2) | finite upper (4)
 int bound_class(double l, double u) { return l == u ? 1 : (l != -INF ? 2 : 0) | (u != INF ? 4 : 0); }
-void require_same_class(const char* what, int idx, double l0, double u0, double l1, double u1) {
-  const int a = bound_class(l0, u0), b = bound_class(l1, u1);
+[[noreturn]] void throw_kind_change(int idx, bool was_equality) {
+  throw Error("madipm_solver_update: constraint " + std::to_string(idx) +
+                  (was_equality ? " was an equality (lcon == ucon) and would become ranged"
+                                : " was ranged (lcon != ucon) and would become an equality") +
+                  " (the classification of every bound is fixed at creation; nothing was changed)",
+              -3);
+}
+void require_same_class(const char* what, int idx, int a, int b) {
   if (a == b) return;
   std::string how;
   if ((a == 1) != (b == 1))
@@ -2195,6 +2485,9 @@ void require_same_class(const char* what, int idx, double l0, double u0, double 
   throw Error(std::string("madipm_solver_update: ") + what + " " + std::to_string(idx) + " " + how +
                   " (the classification of every bound is fixed at creation; nothing was changed)",
               -3);
+}
+void require_same_class(const char* what, int idx, double l0, double u0, double l1, double u1) {
+  require_same_class(what, idx, bound_class(l0, u0), bound_class(l1, u1));
 }
 
 }  // namespace
@@ -2319,6 +2612,7 @@ void MPCSolver::update(const madipm_qp_update& u) {
   QPHost& P = *H_;
   UpdatePlan& pl = *plan_;
   const int nx = P.nx, m = P.m, n = P.n;
+  refresh_host_mirrors();  // after a device update: the "keep" fields are the device-installed ones
   // ---- the classification setup_host derived must hold for the merged data; checked before anything changes
   const double* lv = u.lvar ? u.lvar : P.lvar.data();
   const double* uv = u.uvar ? u.uvar : P.uvar.data();
@@ -2326,12 +2620,7 @@ void MPCSolver::update(const madipm_qp_update& u) {
   const double* uc = u.ucon ? u.ucon : P.ucon.data();
   for (int i = 0; i < m; ++i) {
     const bool was = P.lcon[i] == P.ucon[i], is = lc[i] == uc[i];
-    if (was != is)
-      throw Error("madipm_solver_update: constraint " + std::to_string(i) +
-                      (was ? " was an equality (lcon == ucon) and would become ranged"
-                           : " was ranged (lcon != ucon) and would become an equality") +
-                      " (the classification of every bound is fixed at creation; nothing was changed)",
-                  -3);
+    if (was != is) throw_kind_change(i, was);
   }
   for (int i = 0; i < nx; ++i) require_same_class("variable", i, P.lvar[i], P.uvar[i], lv[i], uv[i]);
   for (int k = 0; k < P.ns; ++k) {
@@ -2381,8 +2670,314 @@ void MPCSolver::update(const madipm_qp_update& u) {
   MADIPM_HIP(hipStreamSynchronize(s));
   clk("uploads + kernels");
   initialized_ = false;  // the next solve() initialises from the new x0 / y0
+  start_on_device_ = false;
+  cscale_host_stale_ = false;
+  cscale_dev_ok_ = true;
+  dev_raw_stale_ = dev_ != nullptr;  // the device route's copies of c / bounds / x0 / y0 are refreshed on its next call
   ++n_updates_;
   last_update_s_ = now() - t0;
+}
+
+// ---- the device route
+enum { F_C = 1, F_H = 2, F_A = 4, F_LCON = 8, F_UCON = 16, F_LVAR = 32, F_UVAR = 64, F_X0 = 128, F_Y0 = 256 };
+
+// Host mirrors of the raw fields a device update installed (QPHost's vectors, the plan's Avals), read
+// back from the device staging; a no-op unless a device update ran since the last refresh.
+void MPCSolver::refresh_host_mirrors() {
+  if (!host_stale_) return;
+  QPHost& P = *H_;
+  DevUpdate& dv = *dev_;
+  UpdatePlan& pl = *plan_;
+  hipStream_t s = stream_;
+  auto get = [&](int bit, std::vector<double>& dst, const double* src) {
+    if ((host_stale_ & bit) && !dst.empty())
+      MADIPM_HIP(hipMemcpyAsync(dst.data(), src, dst.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  };
+  get(F_C, P.c, dv.c);
+  get(F_H, P.Hv, pl.Hraw);
+  get(F_A, pl.Av, pl.Araw);
+  get(F_LCON, P.lcon, dv.lcon);
+  get(F_UCON, P.ucon, dv.ucon);
+  get(F_LVAR, P.lvar, dv.lvar);
+  get(F_UVAR, P.uvar, dv.uvar);
+  get(F_X0, P.x0, dv.x0);
+  get(F_Y0, P.y0, dv.y0);
+  MADIPM_HIP(hipStreamSynchronize(s));
+  host_stale_ = 0;
+}
+
+void MPCSolver::get_data(double* c, double* c0, double* Hvals, double* Avals, double* lcon, double* ucon,
+                         double* lvar, double* uvar, double* x0, double* y0) {
+  QPHost& P = *H_;
+  MADIPM_REQUIRE(!Avals || P.nnzA == 0 || plan_,
+                 "madipm_solver_get_data: Avals needs madipm_solver_prepare_update first (the solver keeps no copy "
+                 "of A otherwise)");
+  refresh_host_mirrors();
+  auto out = [](double* dst, const std::vector<double>& v) {
+    if (dst) std::copy(v.begin(), v.end(), dst);
+  };
+  out(c, P.c);
+  if (c0) *c0 = P.c0;
+  out(Hvals, P.Hv);
+  if (Avals && plan_) out(Avals, plan_->Av);
+  out(lcon, P.lcon);
+  out(ucon, P.ucon);
+  out(lvar, P.lvar);
+  out(uvar, P.uvar);
+  out(x0, P.x0);
+  out(y0, P.y0);
+}
+
+// The first device update: the lists of the host sums (from the COO copy prepare_update keeps), the
+// staging of the raw fields (from the host mirrors, which are current: no device update ran yet), the
+// start vectors and the scalar block.  Every device allocation of the device route happens here.
+void MPCSolver::build_device_route() {
+  PhaseClock clk("build_device_route");
+  QPHost& P = *H_;
+  UpdatePlan& pl = *plan_;
+  const int nx = P.nx, m = P.m, n = P.n;
+  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
+  auto dv = std::make_unique<DevUpdate>();
+  hipStream_t s = stream_;
+  std::vector<std::vector<int32_t>> keep32;  // host sources of the asynchronous uploads
+  std::vector<std::vector<int2>> keep2;
+  // destinations dest[t] (in input order) with entries ent[t] -> per-destination lists, input order kept
+  auto lists = [&](int nd, const std::vector<int32_t>& dest, const std::vector<int2>& ent, DBuf<int32_t>& sp,
+                   DBuf<int2>& e) {
+    std::vector<int32_t> start(nd + 1, 0);
+    for (int32_t d : dest) start[d + 1]++;
+    for (int i = 0; i < nd; ++i) start[i + 1] += start[i];
+    std::vector<int2> out(ent.size());
+    std::vector<int32_t> fill(start.begin(), start.end() - 1);
+    for (size_t t = 0; t < dest.size(); ++t) out[fill[dest[t]]++] = ent[t];
+    sp.alloc(start.size());
+    sp.upload(start.data(), start.size(), s);
+    e.alloc(std::max<size_t>(out.size(), 1));
+    e.upload(out.data(), out.size(), s);
+    keep32.push_back(std::move(start));
+    keep2.push_back(std::move(out));
+  };
+  {
+    std::vector<int32_t> dest(na), fdest;
+    std::vector<int2> ent(na), fent;
+    for (int64_t k = 0; k < na; ++k) {
+      dest[k] = pl.Ar[k];
+      ent[k] = make_int2((int)k, pl.Ac[k]);
+      if (P.fixed[pl.Ac[k]]) {
+        fdest.push_back(pl.Ar[k]);
+        fent.push_back(ent[k]);
+      }
+    }
+    lists(m, dest, ent, dv->asp, dv->ae);
+    lists(m, fdest, fent, dv->fsp, dv->fe);
+  }
+  {
+    std::vector<int32_t> gdest, xdest, bfk;
+    std::vector<int2> gent, xent, bfrc;
+    for (int64_t k = 0; k < nh; ++k) {
+      const int r = P.Hr[k], c = P.Hc[k];
+      gdest.push_back(r);
+      gent.push_back(make_int2((int)k, c));
+      if (r != c) {
+        gdest.push_back(c);
+        gent.push_back(make_int2((int)k, r));
+      }
+      const bool fr = P.fixed[r], fc = P.fixed[c];
+      if (fr && fc) {
+        bfk.push_back((int32_t)k);
+        bfrc.push_back(make_int2(r, c));
+      } else if (fc) {
+        xdest.push_back(r);
+        xent.push_back(make_int2((int)k, c));
+      } else if (fr) {
+        xdest.push_back(c);
+        xent.push_back(make_int2((int)k, r));
+      }
+    }
+    lists(nx, gdest, gent, dv->gsp, dv->ge);
+    lists(nx, xdest, xent, dv->xsp, dv->xe);
+    dv->nbf = (int)bfk.size();
+    dv->bfk.alloc(std::max<size_t>(bfk.size(), 1));
+    dv->bfk.upload(bfk.data(), bfk.size(), s);
+    dv->bfrc.alloc(std::max<size_t>(bfrc.size(), 1));
+    dv->bfrc.upload(bfrc.data(), bfrc.size(), s);
+    keep32.push_back(std::move(bfk));
+    keep2.push_back(std::move(bfrc));
+  }
+  clk("lists");
+  std::vector<uint8_t> vcls(nx), ccls(m);
+  for (int i = 0; i < nx; ++i) vcls[i] = (uint8_t)bound_class(P.lvar[i], P.uvar[i]);
+  for (int i = 0; i < m; ++i) ccls[i] = (uint8_t)bound_class(P.lcon[i], P.ucon[i]);
+  auto up = [&](auto& buf, const auto& vec, size_t len) {
+    buf.alloc(std::max<size_t>(len, 1));
+    buf.upload(vec.data(), vec.size(), s);
+  };
+  up(dv->vcls, vcls, nx);
+  up(dv->ccls, ccls, m);
+  up(dv->ineq, P.ind_ineq, P.ns);
+  up(dv->c, P.c, nx);
+  up(dv->lvar, P.lvar, nx);
+  up(dv->uvar, P.uvar, nx);
+  up(dv->x0, P.x0, nx);
+  up(dv->lcon, P.lcon, m);
+  up(dv->ucon, P.ucon, m);
+  up(dv->y0, P.y0, m);
+  dv->x.alloc(std::max(n, 1));
+  dv->xl.alloc(std::max(n, 1));
+  dv->xu.alloc(std::max(n, 1));
+  dv->xpre.alloc(std::max(nx, 1));
+  dv->ax.alloc(std::max(m, 1));
+  dv->sc.alloc(SC_LEN);
+  dv->chk.alloc(4);
+  MADIPM_HIP(hipEventCreateWithFlags(&dv->ev, hipEventDisableTiming));
+  MADIPM_HIP(hipHostMalloc((void**)&dv->hsc, (SC_LEN + 2) * sizeof(double), hipHostMallocDefault));
+  MADIPM_HIP(hipStreamSynchronize(s));
+  dev_raw_stale_ = false;
+  dev_ = std::move(dv);
+  clk("staging + uploads");
+}
+
+void MPCSolver::update_device(const madipm_qp_update& u, hipStream_t caller) {
+  const double t0 = now();
+  PhaseClock clk("update_device");
+  MADIPM_REQUIRE(plan_, "madipm_solver_update_device: call madipm_solver_prepare_update on this solver first (it "
+                        "builds the refresh plan)");
+  QPHost& P = *H_;
+  UpdatePlan& pl = *plan_;
+  const int nx = P.nx, m = P.m, n = P.n;
+  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
+  if (!dev_) build_device_route();
+  DevUpdate& dv = *dev_;
+  hipStream_t s = stream_;
+  if (dev_raw_stale_) {  // a host update since: its c / bounds / x0 / y0 (Araw / Hraw it keeps itself)
+    auto send = [&](double* dst, const std::vector<double>& v) {
+      if (!v.empty()) MADIPM_HIP(hipMemcpyAsync(dst, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    };
+    send(dv.c, P.c), send(dv.lvar, P.lvar), send(dv.uvar, P.uvar), send(dv.x0, P.x0);
+    send(dv.lcon, P.lcon), send(dv.ucon, P.ucon), send(dv.y0, P.y0);
+    dev_raw_stale_ = false;
+  }
+  // ---- the caller's arrays are read after the work already enqueued on its stream
+  MADIPM_HIP(hipEventRecord(dv.ev, caller));
+  MADIPM_HIP(hipStreamWaitEvent(s, dv.ev, 0));
+  // ---- classification of the merged data, by a kernel, before anything is overwritten
+  const double* lv = u.lvar ? u.lvar : dv.lvar.p;
+  const double* uv = u.uvar ? u.uvar : dv.uvar.p;
+  const double* lc = u.lcon ? u.lcon : dv.lcon.p;
+  const double* uc = u.ucon ? u.ucon : dv.ucon.p;
+  int32_t* hchk = reinterpret_cast<int32_t*>(dv.hsc + SC_LEN);
+  if (u.lvar || u.uvar || u.lcon || u.ucon) {
+    MADIPM_HIP(hipMemsetAsync(dv.chk.p, 0x7f, 4 * sizeof(int32_t), s));
+    k_upd_check<<<blocks(std::max(nx, m)), NT, 0, s>>>(nx, m, lv, uv, lc, uc, dv.vcls, dv.ccls, dv.chk);
+    MADIPM_HIP(hipGetLastError());
+    MADIPM_HIP(hipMemcpyAsync(hchk, dv.chk.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    MADIPM_HIP(hipStreamSynchronize(s));
+    const int32_t none = 0x7f7f7f7f;
+    auto fetch = [&](const double* d, int i) {
+      double v = 0;
+      MADIPM_HIP(hipMemcpy(&v, d + i, sizeof(double), hipMemcpyDeviceToHost));
+      return v;
+    };
+    // the host path's order and text; the old class is the creation-time one, which the host mirrors
+    // still show whatever their age
+    if (hchk[0] != none) throw_kind_change(hchk[0], P.lcon[hchk[0]] == P.ucon[hchk[0]]);
+    if (hchk[1] != none) {
+      const int i = hchk[1];
+      require_same_class("variable", i, bound_class(P.lvar[i], P.uvar[i]), bound_class(fetch(lv, i), fetch(uv, i)));
+    }
+    if (hchk[2] != none) {
+      const int i = hchk[2];
+      require_same_class("constraint", i, bound_class(P.lcon[i], P.ucon[i]), bound_class(fetch(lc, i), fetch(uc, i)));
+    }
+  }
+  clk("classification check");
+  // ---- install the given fields into the staging
+  int given = 0;
+  auto put = [&](int bit, double* dst, const double* src, int64_t len) {
+    if (!src) return;
+    given |= bit;
+    if (src != dst && len) MADIPM_HIP(hipMemcpyAsync(dst, src, len * sizeof(double), hipMemcpyDeviceToDevice, s));
+  };
+  put(F_C, dv.c, u.c, nx);
+  put(F_H, pl.Hraw, u.Hvals, nh);
+  put(F_A, pl.Araw, u.Avals, na);
+  put(F_LCON, dv.lcon, u.lcon, m);
+  put(F_UCON, dv.ucon, u.ucon, m);
+  put(F_LVAR, dv.lvar, u.lvar, nx);
+  put(F_UVAR, dv.uvar, u.uvar, nx);
+  put(F_X0, dv.x0, u.x0, nx);
+  put(F_Y0, dv.y0, u.y0, m);
+  if (u.c0) P.c0 = *u.c0;
+  // ---- numeric_host, on the device
+  const int scaling = opt_.scaling ? 1 : 0;
+  MADIPM_HIP(hipMemsetAsync(dv.sc.p, 0, SC_LEN * sizeof(double), s));
+  if (n)
+    k_upd_bounds<<<blocks(n), NT, 0, s>>>(nx, n, opt_.bound_relax_factor, dv.lvar, dv.uvar, dv.lcon, dv.ucon, dv.x0,
+                                          dv.ineq, fixed_, dv.xl, dv.xu, dv.xpre);
+  if (m)
+    k_upd_rows<<<blocks(m), NT, 0, s>>>(m, scaling, dv.asp, dv.ae, dv.fsp, dv.fe, pl.Araw, dv.xpre, dv.lcon, dv.ucon,
+                                        dv.ax, pl.cscale, cfix_, rhs_, dv.sc);
+  if (n)
+    k_upd_start<<<blocks(n), NT, 0, s>>>(nx, n, scaling, opt_.bound_push, opt_.bound_fac, dv.xpre, dv.ax, pl.cscale,
+                                         dv.ineq, fixed_, dv.xl, dv.xu, dv.x);
+  if (scaling && nx) k_upd_g<<<blocks(nx), NT, 0, s>>>(nx, P.sgn, dv.gsp, dv.ge, dv.c, pl.Hraw, dv.x, dv.sc);
+  k_upd_scalars<<<1, 64, 0, s>>>(scaling, P.sgn, P.c0, dv.nbf, dv.bfk, dv.bfrc, pl.Hraw, dv.x, dv.sc);
+  if (n) k_upd_cs_gfix<<<blocks(n), NT, 0, s>>>(nx, n, dv.xsp, dv.xe, dv.c, pl.Hraw, dv.x, dv.sc, cs_, gfix_);
+  // ---- matrix values, as the host route
+  double* K0 = kkt_ == KKT_K25 ? K0_.p : nullptr;
+  if (pl.nJ) {
+    k_refresh_jt<<<blocks(pl.nJ), NT, 0, s>>>(pl.nJ, pl.tsp, pl.tsrc, JTci_, pl.cscale, pl.Araw, pl.jtk, JTv_, Kx_, K0);
+    k_refresh_gather<<<blocks(pl.nJ), NT, 0, s>>>(pl.nJ, pl.j2jt, JTv_, Jv_);
+  }
+  if (pl.nH)
+    k_refresh_h_dev<<<blocks(pl.nH), NT, 0, s>>>(pl.nH, pl.hsp, pl.hsrc, dv.sc, pl.Hraw, pl.hk, Hv_, Kx_, K0);
+  if (n) k_refresh_hdiag<<<blocks(n), NT, 0, s>>>(n, pl.hdpos, Hv_, Hdiag_);
+  MADIPM_HIP(hipGetLastError());
+  // ---- the host's scalars, read with the final synchronisation
+  MADIPM_HIP(hipMemcpyAsync(dv.hsc, dv.sc.p, SC_LEN * sizeof(double), hipMemcpyDeviceToHost, s));
+  MADIPM_HIP(hipStreamSynchronize(s));
+  clk("copies + kernels");
+  P.obj_scale = obj_scale_ = dv.hsc[SC_OBJ];
+  c0s_ = dv.hsc[SC_C0S];
+  norm_b_ = dv.hsc[SC_NORMB];
+  host_stale_ |= given;
+  start_on_device_ = true;
+  cscale_host_stale_ = true;
+  cscale_dev_ok_ = true;
+  initialized_ = false;
+  ++n_updates_;
+  last_update_s_ = now() - t0;
+}
+
+// con_scale on the device: the plan's once an update has written it, else a copy of the host's
+const double* MPCSolver::device_con_scale() {
+  if (plan_ && cscale_dev_ok_) return plan_->cscale.p;
+  if (!sol_cs_.p) {
+    sol_cs_.alloc(std::max(m_, 1));
+    sol_cs_.upload(H_->con_scale.data(), H_->con_scale.size(), stream_);
+  }
+  return sol_cs_.p;
+}
+
+void MPCSolver::get_solution_device(double* x, double* y, double* zl, double* zu, double* cons, hipStream_t caller) {
+  hipStream_t s = stream_;
+  if (!sol_ev_[0]) {
+    MADIPM_HIP(hipEventCreateWithFlags(&sol_ev_[0], hipEventDisableTiming));
+    MADIPM_HIP(hipEventCreateWithFlags(&sol_ev_[1], hipEventDisableTiming));
+    sol_ax_.alloc(std::max(m_, 1));
+  }
+  const double* cscale = device_con_scale();
+  // the outputs are written after the caller's earlier work on them, and read by its later work
+  MADIPM_HIP(hipEventRecord(sol_ev_[0], caller));
+  MADIPM_HIP(hipStreamWaitEvent(s, sol_ev_[0], 0));
+  if (cons && m_)
+    k_cons<<<(unsigned)((m_ + NT / 64 - 1) / (NT / 64)), NT, 0, s>>>(Jrp_, Jci_, Jv_, x_, cfix_, m_, nx_, sol_ax_);
+  if (std::max(nx_, m_))
+    k_unscale<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(nx_, m_, obj_scale_, x_, y_, zl_, zu_, sol_ax_, cscale, x, y,
+                                                        zl, zu, cons);
+  MADIPM_HIP(hipGetLastError());
+  MADIPM_HIP(hipEventRecord(sol_ev_[1], s));
+  MADIPM_HIP(hipStreamWaitEvent(caller, sol_ev_[1], 0));
 }
 
 // Launch helpers (the DV view is rebuilt from member buffers; cheap, host-only)
@@ -2670,10 +3265,21 @@ void MPCSolver::initialize() {
   hipStream_t s = stream_;
   {  // restart from the problem's initial point (solve! always restarts)
     const QPHost& P = *H_;
-    MADIPM_HIP(hipMemcpyAsync(x_.p, P.x.data(), sizeof(double) * n_, hipMemcpyHostToDevice, s));
-    MADIPM_HIP(hipMemcpyAsync(xl_.p, P.xl.data(), sizeof(double) * n_, hipMemcpyHostToDevice, s));
-    MADIPM_HIP(hipMemcpyAsync(xu_.p, P.xu.data(), sizeof(double) * n_, hipMemcpyHostToDevice, s));
-    if (m_) MADIPM_HIP(hipMemcpyAsync(y_.p, P.y.data(), sizeof(double) * m_, hipMemcpyHostToDevice, s));
+    if (start_on_device_) {  // the last update was a device update: its start vectors never left the device
+      const DevUpdate& dv = *dev_;
+      const auto d2d = hipMemcpyDeviceToDevice;
+      if (n_) {
+        MADIPM_HIP(hipMemcpyAsync(x_.p, dv.x.p, sizeof(double) * n_, d2d, s));
+        MADIPM_HIP(hipMemcpyAsync(xl_.p, dv.xl.p, sizeof(double) * n_, d2d, s));
+        MADIPM_HIP(hipMemcpyAsync(xu_.p, dv.xu.p, sizeof(double) * n_, d2d, s));
+      }
+      if (m_) MADIPM_HIP(hipMemcpyAsync(y_.p, dv.y0.p, sizeof(double) * m_, d2d, s));
+    } else {
+      MADIPM_HIP(hipMemcpyAsync(x_.p, P.x.data(), sizeof(double) * n_, hipMemcpyHostToDevice, s));
+      MADIPM_HIP(hipMemcpyAsync(xl_.p, P.xl.data(), sizeof(double) * n_, hipMemcpyHostToDevice, s));
+      MADIPM_HIP(hipMemcpyAsync(xu_.p, P.xu.data(), sizeof(double) * n_, hipMemcpyHostToDevice, s));
+      if (m_) MADIPM_HIP(hipMemcpyAsync(y_.p, P.y.data(), sizeof(double) * m_, hipMemcpyHostToDevice, s));
+    }
     zl_.zero(s);
     zu_.zero(s);
     d_.zero(s);
@@ -2958,7 +3564,11 @@ namespace madipm {
 // update_solution! (src/utils.jl:150-156) + MadNLP.update! [EXT]: un-scaled primal/dual solution
 void MPCSolver::get_solution(double* x, double* y, double* zl, double* zu, double* cons) {
   MADIPM_HIP(hipStreamSynchronize(stream_));
-  const QPHost& P = *H_;
+  QPHost& P = *H_;
+  if (cscale_host_stale_) {  // a device update computed con_scale on the device
+    if (m_) MADIPM_HIP(hipMemcpy(P.con_scale.data(), plan_->cscale.p, sizeof(double) * m_, hipMemcpyDeviceToHost));
+    cscale_host_stale_ = false;
+  }
   std::vector<double> xh(n_), yh(m_), zlh(n_), zuh(n_);
   if (n_) {
     MADIPM_HIP(hipMemcpy(xh.data(), x_.p, sizeof(double) * n_, hipMemcpyDeviceToHost));

@@ -43,6 +43,7 @@ struct DevState {
 struct QPHost;       // host copy of the problem (mpc.hip)
 struct HostNumeric;  // value-dependent host quantities of size O(n + m) (mpc.hip)
 struct UpdatePlan;   // index plans of the value refresh, built by prepare_update (mpc.hip)
+struct DevUpdate;    // staging, start vectors and sum-order lists of the device route (mpc.hip)
 
 class MPCSolver {
  public:
@@ -62,6 +63,15 @@ class MPCSolver {
   // without touching the linear solver and leaves the stream idle.
   void prepare_update(const madipm_qp& qp);
   void update(const madipm_qp_update& u);
+  // The device route (madipm_solver_update_device / _get_solution_device / _get_data): update_device reads
+  // DEVICE arrays after the work enqueued on `caller`, recomputes numeric_host's results with kernels and
+  // leaves the stream idle; its first call allocates everything it needs.  get_solution_device writes the
+  // un-scaled solution to device arrays without blocking the host; work enqueued on `caller` afterwards
+  // sees it.  get_data copies the raw numbers the solver holds to host arrays.
+  void update_device(const madipm_qp_update& u, hipStream_t caller);
+  void get_solution_device(double* x, double* y, double* zl, double* zu, double* cons, hipStream_t caller);
+  void get_data(double* c, double* c0, double* Hvals, double* Avals, double* lcon, double* ucon, double* lvar,
+                double* uvar, double* x0, double* y0);
   int64_t n_analyses() const { return n_analyses_; }
   int64_t n_updates() const { return n_updates_; }
   double last_update_s() const { return last_update_s_; }
@@ -72,6 +82,9 @@ class MPCSolver {
   // fixed variable only) receive the Jacobian's COO in the same pass that sums cfix
   void numeric_host(HostNumeric& o, std::vector<int32_t>* jr = nullptr, std::vector<int32_t>* jc = nullptr,
                     std::vector<double>* jv = nullptr);
+  void build_device_route();
+  void refresh_host_mirrors();
+  const double* device_con_scale();
   std::unique_ptr<LinSolver> make_linsolver(int n, const int64_t* cp, const int32_t* ri, const SymbolicOptions& so);
   void initialize();
   void init_starting_point();
@@ -151,6 +164,14 @@ class MPCSolver {
   double fs0_ = 0;  // device factorisation seconds at initialize! (cnt.linear_solver_time origin)
   DevState last_{};                // the state of the last termination test
   std::unique_ptr<UpdatePlan> plan_;  // null until prepare_update
+  std::unique_ptr<DevUpdate> dev_;     // null until the first update_device
+  int host_stale_ = 0;                 // raw fields whose host mirror is older than the device staging (bit mask)
+  bool dev_raw_stale_ = false;         // a host update ran since the device staging of c / bounds / x0 / y0 was written
+  bool start_on_device_ = false;       // initialize() restarts from dev_'s start vectors (last update: device)
+  bool cscale_host_stale_ = false;     // QPHost::con_scale is older than the plan's device con_scale
+  bool cscale_dev_ok_ = false;         // the plan's device con_scale has been written by an update
+  DBuf<double> sol_ax_, sol_cs_;       // get_solution_device: constraint values; con_scale when no update wrote it
+  hipEvent_t sol_ev_[2] = {nullptr, nullptr};
   int64_t n_analyses_ = 0, n_updates_ = 0;
   double last_update_s_ = 0;
 };

@@ -218,3 +218,50 @@ function solver_counters(h::Ptr{Cvoid})
                 h, na, nu, t), "madipm_solver_counters")
     return (n_analyses = na[], n_updates = nu[], last_update_s = t[])
 end
+
+# ---- the device route (ABI 0.2.5): the update reads DEVICE arrays, the solution is written to DEVICE arrays.
+# The arrays are Ptr{Float64} into device memory (e.g. pointer(::ROCArray{Float64})), or nothing = keep;
+# c0 stays a host number.  `stream` is the HIP stream the arrays were produced on (C_NULL: the default
+# stream): the reads are ordered after the work enqueued on it, and the call returns with its reads done.
+_dptr_or_null(a::Nothing) = Ptr{Float64}(C_NULL)
+_dptr_or_null(a::Ptr{Float64}) = a
+
+function solver_update_device(h::Ptr{Cvoid}; c=nothing, c0=nothing, Hvals=nothing, Avals=nothing, lcon=nothing,
+                              ucon=nothing, lvar=nothing, uvar=nothing, x0=nothing, y0=nothing,
+                              stream::Ptr{Cvoid}=C_NULL)
+    c0v = c0 === nothing ? nothing : Float64[c0]
+    GC.@preserve c0v begin
+        u = Ref(MadipmQPUpdate(_dptr_or_null(c), _ptr_or_null(c0v), _dptr_or_null(Hvals), _dptr_or_null(Avals),
+                               _dptr_or_null(lcon), _dptr_or_null(ucon), _dptr_or_null(lvar), _dptr_or_null(uvar),
+                               _dptr_or_null(x0), _dptr_or_null(y0)))
+        check(ccall((:madipm_solver_update_device, libmadipm), Cint, (Ptr{Cvoid}, Ref{MadipmQPUpdate}, Ptr{Cvoid}),
+                    h, u, stream), "madipm_solver_update_device")
+    end
+    return
+end
+
+# update_solution! into device arrays (any may be C_NULL); does not block the host, work enqueued on `stream`
+# afterwards sees the values
+function solver_get_solution_device(h::Ptr{Cvoid}, d_x::Ptr{Float64}, d_y::Ptr{Float64}, d_zl::Ptr{Float64},
+                                    d_zu::Ptr{Float64}, d_cons::Ptr{Float64}; stream::Ptr{Cvoid}=C_NULL)
+    check(ccall((:madipm_solver_get_solution_device, libmadipm), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                h, d_x, d_y, d_zl, d_zu, d_cons, stream), "madipm_solver_get_solution_device")
+    return
+end
+
+# the raw problem numbers the solver holds, into host vectors of the creation-time lengths (nothing = skip);
+# returns c0
+function solver_get_data(h::Ptr{Cvoid}; c=nothing, Hvals=nothing, Avals=nothing, lcon=nothing, ucon=nothing,
+                         lvar=nothing, uvar=nothing, x0=nothing, y0=nothing)
+    c0 = Ref{Float64}(0.0)
+    GC.@preserve c Hvals Avals lcon ucon lvar uvar x0 y0 begin
+        check(ccall((:madipm_solver_get_data, libmadipm), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    h, _ptr_or_null(c), c0, _ptr_or_null(Hvals), _ptr_or_null(Avals), _ptr_or_null(lcon),
+                    _ptr_or_null(ucon), _ptr_or_null(lvar), _ptr_or_null(uvar), _ptr_or_null(x0), _ptr_or_null(y0)),
+              "madipm_solver_get_data")
+    end
+    return c0[]
+end

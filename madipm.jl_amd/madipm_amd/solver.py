@@ -160,6 +160,29 @@ L._sig("madipm_solver_destroy", None, [L.vp])
 L._sig("madipm_solver_prepare_update", C.c_int, [L.vp, C.POINTER(QPStruct)])
 L._sig("madipm_solver_update", C.c_int, [L.vp, C.POINTER(QPUpdate)])
 L._sig("madipm_solver_counters", C.c_int, [L.vp, L.i64p, L.i64p, L.f64p])
+L._sig("madipm_solver_update_device", C.c_int, [L.vp, C.POINTER(QPUpdate), L.vp])
+L._sig("madipm_solver_get_solution_device", C.c_int, [L.vp, L.f64p, L.f64p, L.f64p, L.f64p, L.f64p, L.vp])
+L._sig("madipm_solver_get_data", C.c_int, [L.vp] + [L.f64p] * 10)
+
+
+def check_device_array(name: str, a, length: int, device=None):
+    """The argument check of MPCSolver.update_device, before any library call: `a` must be a torch tensor on
+    the GPU (on `device` when given), float64, contiguous, of shape (length,).  TypeError for a numpy array,
+    a CPU tensor or another dtype; ValueError for a non-contiguous tensor or another shape.  Returns `a`."""
+    import torch
+    if not isinstance(a, torch.Tensor):
+        raise TypeError(f"update_device: {name} must be a torch tensor on the GPU, not {type(a).__name__}")
+    if a.dtype != torch.float64:
+        raise TypeError(f"update_device: {name} has dtype {a.dtype}, expected torch.float64")
+    if not a.is_contiguous():  # a property of the tensor alone: checked before where it lives
+        raise ValueError(f"update_device: {name} is not contiguous")
+    if a.device.type != "cuda":
+        raise TypeError(f"update_device: {name} is on {a.device}, expected a GPU tensor")
+    if device is not None and a.device != device:
+        raise TypeError(f"update_device: {name} is on {a.device}, the solver is on {device}")
+    if tuple(a.shape) != (int(length),):
+        raise ValueError(f"update_device: {name} has shape {tuple(a.shape)}, expected ({int(length)},)")
+    return a
 
 
 class RCCLComm:
@@ -326,6 +349,8 @@ class MPCSolver:
         self.rethrow_error = bool(kwargs.get("rethrow_error", False))
         self._keep = []
         self._update_ready = False  # madipm_solver_prepare_update has run (update() calls it on first use)
+        self.qp_current = True      # self.qp's value arrays are the solver's (False after update_device)
+        self._device = None         # the solver's torch device, looked up by the first device-route call
         q = QPStruct()
         q.nvar, q.ncon = qp.nvar, qp.ncon
         q.nnzh, q.nnzj = qp.nnzh, qp.nnzj
@@ -463,12 +488,96 @@ class MPCSolver:
             c0v = C.c_double(float(c0))
             u.c0 = C.pointer(c0v)
             new["c0"] = float(c0)
+        self._prepare_update()
+        L.check(L.lib.madipm_solver_update(self.h, C.byref(u)), "update")
+        if self.qp_current:
+            self.qp = dataclasses.replace(qp, **new)
+        else:  # after update_device: the kept fields are the device-installed ones
+            self.fetch_qp()
+
+    def _prepare_update(self):
         if not self._update_ready:
             # the refresh plan, once: the creation-time arrays of self._q are alive in self._keep
             L.check(L.lib.madipm_solver_prepare_update(self.h, C.byref(self._q)), "prepare_update")
             self._update_ready = True
-        L.check(L.lib.madipm_solver_update(self.h, C.byref(u)), "update")
-        self.qp = dataclasses.replace(qp, **new)
+
+    def update_device(self, *, c=None, c0=None, Hvals=None, Avals=None, lcon=None, ucon=None, lvar=None,
+                      uvar=None, x0=None, y0=None, stream=None):
+        """update() from torch tensors on the solver's GPU (float64, contiguous, the shapes update() expects;
+        c0 is a Python number): nothing is copied to the host, and everything update() computes on the host
+        is recomputed by kernels, with the same bits.  `stream` is the torch.cuda.Stream the tensors were
+        produced on (None: the current stream); the reads are ordered after the work enqueued on it, and the
+        call returns with all its reads done, so the tensors may be overwritten right after it.  The same
+        changes of classification are refused, with the same message.  self.qp keeps its pattern and
+        dimensions, but its value arrays are no longer current (qp_current is False) until fetch_qp().
+        As wherever torch pointers or streams are handed to the library, `import torch` comes before this
+        package in the process, so that both use one HIP runtime."""
+        import torch
+        qp = self.qp
+        want = {"c": qp.nvar, "Hvals": qp.nnzh, "Avals": qp.nnzj, "lcon": qp.ncon, "ucon": qp.ncon,
+                "lvar": qp.nvar, "uvar": qp.nvar, "x0": qp.nvar, "y0": qp.ncon}
+        given = {"c": c, "Hvals": Hvals, "Avals": Avals, "lcon": lcon, "ucon": ucon, "lvar": lvar, "uvar": uvar,
+                 "x0": x0, "y0": y0}
+        if self._device is None:
+            self._device = torch.device("cuda", torch.cuda.current_device())
+        u, keep = QPUpdate(), []
+        for k, a in given.items():
+            if a is None:
+                continue
+            check_device_array(k, a, want[k], self._device)
+            keep.append(a)
+            setattr(u, k, C.cast(a.data_ptr(), L.f64p))  # an empty tensor's null pointer reads as "keep"
+        c0v = None
+        if c0 is not None:
+            c0v = C.c_double(float(c0))
+            u.c0 = C.pointer(c0v)
+        if stream is not None and not isinstance(stream, torch.cuda.Stream):
+            raise TypeError(f"update_device: stream must be a torch.cuda.Stream, not {type(stream).__name__}")
+        st = stream if stream is not None else torch.cuda.current_stream(self._device)
+        self._prepare_update()
+        # labelled as update(): a refused change of classification reads the same on both routes
+        L.check(L.lib.madipm_solver_update_device(self.h, C.byref(u), L.vp(st.cuda_stream)), "update")
+        self.qp_current = False
+
+    def fetch_qp(self) -> QuadraticModel:
+        """The problem the solver currently holds (madipm_solver_get_data), as an updated copy of self.qp;
+        self.qp is current again afterwards."""
+        qp = self.qp
+        self._prepare_update()  # the solver keeps A's values from then on
+        new = {"c": np.empty(qp.nvar), "Hvals": np.empty(qp.nnzh), "Avals": np.empty(qp.nnzj),
+               "lcon": np.empty(qp.ncon), "ucon": np.empty(qp.ncon), "lvar": np.empty(qp.nvar),
+               "uvar": np.empty(qp.nvar), "x0": np.empty(qp.nvar), "y0": np.empty(qp.ncon)}
+        c0 = C.c_double()
+        p = {k: L.ptr(a, C.c_double) for k, a in new.items()}
+        L.check(L.lib.madipm_solver_get_data(self.h, p["c"], C.byref(c0), p["Hvals"], p["Avals"], p["lcon"],
+                                             p["ucon"], p["lvar"], p["uvar"], p["x0"], p["y0"]), "get_data")
+        self.qp = dataclasses.replace(qp, c0=float(c0.value), **new)
+        self.qp_current = True
+        return self.qp
+
+    def solution_device(self, stream=None) -> dict:
+        """update_solution! into torch tensors on the GPU (madipm_solver_get_solution_device): the bits
+        solve() returns in host arrays, without a copy through the host and without blocking it.  Work
+        enqueued on `stream` (None: the current stream) afterwards sees the values."""
+        import torch
+        if self._device is None:
+            self._device = torch.device("cuda", torch.cuda.current_device())
+        if stream is not None and not isinstance(stream, torch.cuda.Stream):
+            raise TypeError(f"solution_device: stream must be a torch.cuda.Stream, not {type(stream).__name__}")
+        st = stream if stream is not None else torch.cuda.current_stream(self._device)
+        nx, m = self.qp.nvar, self.qp.ncon
+        with torch.cuda.stream(st):
+            out = {"solution": torch.empty(nx, dtype=torch.float64, device=self._device),
+                   "multipliers": torch.empty(m, dtype=torch.float64, device=self._device),
+                   "multipliers_L": torch.empty(nx, dtype=torch.float64, device=self._device),
+                   "multipliers_U": torch.empty(nx, dtype=torch.float64, device=self._device),
+                   "constraints": torch.empty(m, dtype=torch.float64, device=self._device)}
+        dp = {k: C.cast(t.data_ptr(), L.f64p) for k, t in out.items()}
+        L.check(L.lib.madipm_solver_get_solution_device(self.h, dp["solution"], dp["multipliers"],
+                                                        dp["multipliers_L"], dp["multipliers_U"],
+                                                        dp["constraints"], L.vp(st.cuda_stream)),
+                "get_solution_device")
+        return out
 
     def counters(self) -> dict:
         """n_analyses: linear-solver analyses run for this solver (stays 1); n_updates: successful update()

@@ -8,7 +8,13 @@ median of 10 after 2 warm-ups) and solve_s (initialize! + the MPC loop on the up
 median).  Every update installs c, the finite bounds and the values of A (and H) times 1 + 1e-3 U(-1, 1),
 seeded — lower and upper bound of a coordinate by the same factor, so the classification of every bound is
 the creation-time one.  The last updated solve is compared with a fresh solver on the same data
-(matches_fresh: same status, iterations, objective bits).  Ends with one JSON line."""
+(matches_fresh: same status, iterations, objective bits).
+
+The device route runs in the same process on the same sequence of perturbed data, held in torch tensors:
+update_device_s (counters()["last_update_s"] of MPCSolver.update_device, same median) beside the host
+update_s, and update + solve + solution_device() (the results left in device tensors, stream synchronised)
+against host update + solve with the host fetch; device_matches_fresh compares the last device-updated
+solve with the same fresh solver.  Ends with one JSON line."""
 import dataclasses
 import json
 import os
@@ -54,7 +60,7 @@ def run(name):
     s.update(**new)                            # the first update builds the plan
     first_update_s = time.perf_counter() - t
     prepare_update_s = first_update_s - s.counters()["last_update_s"]
-    upd, call, sol, its = [], [], [], []
+    upd, call, sol, its, hostloop = [], [], [], [], []
     for rep in range(WARMUP + REPS):
         new = perturb(qp, rng)
         t = time.perf_counter()
@@ -63,12 +69,41 @@ def run(name):
         t = time.perf_counter()
         st = s.solve(fetch_solution=False)
         t_solve = time.perf_counter() - t
+        t = time.perf_counter()
+        s.update(**new)
+        s.solve()                              # the whole host loop: update + solve + the host fetch
+        t_loop = time.perf_counter() - t
         if rep >= WARMUP:
             upd.append(s.counters()["last_update_s"])
             call.append(t_call)
             sol.append(t_solve)
             its.append(st.iter)
+            hostloop.append(t_loop)
     fresh = MPCSolver(dataclasses.replace(qp, **new), **opts).solve(fetch_solution=False)
+    # ---- the device route: the same sequence of data, in torch tensors
+    rng = np.random.default_rng(0)
+    perturb(qp, rng)                           # the first update's draw
+    s.update_device(**{k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()})  # allocates
+    rng = np.random.default_rng(0)
+    perturb(qp, rng)
+    dupd, dcall, devloop = [], [], []
+    for rep in range(WARMUP + REPS):
+        dnew = {k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()}
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        s.update_device(**dnew)
+        t_call = time.perf_counter() - t
+        dst = s.solve(fetch_solution=False)
+        t = time.perf_counter()
+        s.update_device(**dnew)
+        s.solve(fetch_solution=False)
+        s.solution_device()
+        torch.cuda.current_stream().synchronize()
+        t_loop = time.perf_counter() - t
+        if rep >= WARMUP:
+            dupd.append(s.counters()["last_update_s"])
+            dcall.append(t_call)
+            devloop.append(t_loop)
     c = s.counters()
     update_s, solve_s = statistics.median(upd), statistics.median(sol)
     return {"instance": name, "description": desc, "nvar": qp.nvar, "ncon": qp.ncon, "nnzj": qp.nnzj, "nnzh": qp.nnzh,
@@ -80,6 +115,12 @@ def run(name):
             "speedup": (construct_s + solve_s) / (update_s + solve_s),
             "matches_fresh": bool(fresh.status == st.status and fresh.iter == st.iter
                                   and np.float64(fresh.objective).tobytes() == np.float64(st.objective).tobytes()),
+            "update_device_s": statistics.median(dupd), "update_device_call_s": statistics.median(dcall),
+            "host_loop_s": statistics.median(hostloop),       # update + solve + get_solution (host arrays)
+            "device_loop_s": statistics.median(devloop),      # update_device + solve + solution_device + sync
+            "device_matches_fresh": bool(fresh.status == dst.status and fresh.iter == dst.iter
+                                         and np.float64(fresh.objective).tobytes()
+                                         == np.float64(dst.objective).tobytes()),
             "n_analyses": c["n_analyses"], "n_updates": c["n_updates"]}
 
 
@@ -94,6 +135,9 @@ def main():
               f"update_s {r['update_s']:.5f}  solve_s {r['solve_s']:.4f}  ->  update + solve "
               f"{r['update_plus_solve_s']:.4f} s against construct + solve {r['construct_plus_solve_s']:.4f} s "
               f"(x{r['speedup']:.1f}), matches_fresh {r['matches_fresh']}", flush=True)
+        print(f"{name}: device route: update_device_s {r['update_device_s']:.5f} (host update_s {r['update_s']:.5f})  "
+              f"update_device + solve + solution_device {r['device_loop_s']:.4f} s against update + solve + host "
+              f"fetch {r['host_loop_s']:.4f} s, device_matches_fresh {r['device_matches_fresh']}", flush=True)
         out.append(r)
     print(json.dumps({"resolve_bench": out, "warmup": WARMUP, "reps": REPS, "rel_noise": REL}))
 
