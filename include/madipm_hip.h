@@ -467,6 +467,53 @@ int madipm_solver_get_solution_device(madipm_solver_t s, double* d_x, double* d_
 int madipm_solver_get_data(madipm_solver_t s, double* c, double* c0, double* Hvals, double* Avals, double* lcon,
                            double* ucon, double* lvar, double* uvar, double* x0, double* y0);
 
+/* ------------------------------------------------------------------ warm start  [ABI 0.2.6, additive]
+ * A re-solve from a previous or caller-supplied point instead of the Mehrotra least-squares start alone.
+ * (madipm_version() still returns 203: these five symbols are the whole addition, no struct changed.)
+ *
+ * A warm point is (x, y, zl, zu) in the public, un-scaled space — what madipm_solver_get_solution and
+ * madipm_solver_get_solution_device return: lengths nvar, ncon, nvar, nvar.  Any of the four may be NULL
+ * (that block keeps its cold values; the slack values need x, the slack multipliers need y), not all four.
+ * While a point is set, madipm_solver_initialize / the initialisation inside madipm_solver_solve runs
+ * unchanged up to the end of init_starting_point!, then blends: x is clamped into the (relaxed) bounds,
+ * the slacks are the clamped scaled row values of it, y and z are scaled (z clamped at 0, the slack
+ * multipliers max(-y, 0) / max(y, 0)), every block becomes weight * warm + (1 - weight) * cold, a coordinate
+ * whose blended value is not strictly inside its bounds (or a multiplier that is not > 0) keeps its cold
+ * value, and the model is evaluated at the blended point.  The MPC loop is unchanged; it is the same rule
+ * for every KKT formulation, for a sharded solver and (every rank setting the same point) a distributed one.
+ * Without a point — never set, or cleared — initialisation is bit for bit the cold one: no extra kernel, no
+ * allocation.
+ * The point is kept on the device un-scaled (obj_scale and con_scale may change with the next update) and
+ * persists across solves and updates until it is replaced (a call replaces the whole point: the blocks it
+ * leaves NULL become absent) or cleared.  Memory: 8 B x (3 nvar + ncon) + 12 B per inequality row (+ 8 B x
+ * ncon for con_scale on a solver that never ran an update), allocated by the first call that sets a point
+ * and never again.
+ * weight must lie in the open interval (0, 1) (0.99 is the recommended value); a weight outside it or NaN,
+ * or four NULL pointers, is refused: negative code, the reason in madipm_last_error(), solver untouched.
+ * Non-finite entries of the point are NOT checked: they reach the iterate and the solve ends as any
+ * NaN does (INTERNAL_ERROR).
+ *
+ * madipm_solver_set_warm_start: HOST pointers, read during the call only. */
+int madipm_solver_set_warm_start(madipm_solver_t s, const double* x, const double* y, const double* zl,
+                                 const double* zu, double weight);
+/* DEVICE pointers, with the stream contract of madipm_solver_update_device: `stream` is the stream the
+ * arrays were produced on; the reads are ordered after the work already enqueued on it by an event wait,
+ * and the host is not synchronised.  The arrays are copied by the call: work enqueued on `stream` after it
+ * returns is ordered after the copies, so the caller may overwrite the arrays from that stream at once. */
+int madipm_solver_set_warm_start_device(madipm_solver_t s, const double* d_x, const double* d_y, const double* d_zl,
+                                        const double* d_zu, double weight, madipm_stream_t stream);
+/* The solver's own current iterate as the warm point: the bits madipm_solver_get_solution_device would
+ * write at the time of the call, without a trip through the host and without blocking it.  An error before
+ * the first solve.  The iterate is un-scaled with the solver's CURRENT obj_scale / con_scale: in a re-solve
+ * loop call it after the solve and BEFORE the next update, so that the solution is un-scaled with the
+ * scaling it was computed in (after an update the two differ when set_scaling! gives other factors). */
+int madipm_solver_warm_start_last(madipm_solver_t s, double weight);
+/* Back to cold starts; the device copy stays allocated for the next point. */
+int madipm_solver_clear_warm_start(madipm_solver_t s);
+/* active: a point is set; weight: its weight (0 when none); n_warm_inits: initialisations that blended.
+ * Any pointer may be NULL. */
+int madipm_solver_warm_info(madipm_solver_t s, int32_t* active, double* weight, int64_t* n_warm_inits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -697,6 +697,48 @@ int madipm_solver_counters(madipm_solver_t s, int64_t* n_analyses, int64_t* n_up
   MADIPM_API_END
 }
 
+int madipm_solver_set_warm_start(madipm_solver_t s, const double* x, const double* y, const double* zl,
+                                 const double* zu, double weight) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->set_warm_start(x, y, zl, zu, weight, false, nullptr);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_set_warm_start_device(madipm_solver_t s, const double* d_x, const double* d_y, const double* d_zl,
+                                        const double* d_zu, double weight, madipm_stream_t stream) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->set_warm_start(d_x, d_y, d_zl, d_zu, weight, true, (hipStream_t)stream);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_warm_start_last(madipm_solver_t s, double weight) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->warm_start_last(weight);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_clear_warm_start(madipm_solver_t s) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->clear_warm_start();
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_warm_info(madipm_solver_t s, int32_t* active, double* weight, int64_t* n_warm_inits) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->warm_info(active, weight, n_warm_inits);
+  return 0;
+  MADIPM_API_END
+}
+
 int madipm_update_step(int32_t rule, double tau, double mu, int32_t nlb, int32_t nub, const double* d_x_lr,
                        const double* d_xl_r, const double* d_zl_r, const double* d_dx_lr, const double* d_dzl,
                        const double* d_x_ur, const double* d_xu_r, const double* d_zu_r, const double* d_dx_ur,

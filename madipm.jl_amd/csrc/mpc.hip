@@ -93,6 +93,22 @@ struct DevUpdate {
   }
 };
 
+// The warm point (set_warm_start*), kept on the device in the public, un-scaled space: obj_scale and
+// con_scale may change with the next update.  8 B x (3 nvar + ncon) + 12 B per inequality row (the row
+// values of k_warm_rows and the slack -> row map), allocated by the first call that sets a point.
+struct WarmStart {
+  DBuf<double> x, y, zl, zu, rows;
+  DBuf<int32_t> ineq;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool has[4] = {false, false, false, false};  // x, y, zl, zu of the current point
+  bool active = false;
+  double weight = 0.0;
+  ~WarmStart() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 namespace {
 
 constexpr int NT = 256;
@@ -2423,6 +2439,83 @@ __global__ void k_unscale(int nx, int m, double os, const double* __restrict__ x
   }
 }
 
+// ---- warm start (madipm_solver_set_warm_start*): initialize() blends the cold start with a
+// caller-given point of the public, un-scaled space.  One thread (k_warm_rows: one lane group) per
+// destination, every sum in a fixed order, no atomics: the same bits from run to run.
+struct WarmArgs {
+  const double *wx, *wy, *wzl, *wzu;  // the warm point (null: the block is absent and keeps its cold values)
+  const double* cscale;               // con_scale
+  const int32_t* ineq;                // slack k -> its constraint row
+  double* rows;                       // per slack: the scaled row value of the clamped x (k_warm_rows)
+  double lam, os;                     // weight, obj_scale
+};
+
+// comparisons, not fmin / fmax: a NaN of the warm point is not hidden
+__device__ __forceinline__ double clampv(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// con_scale_i (A x~)_i of every inequality row, x~ = clamp(x, xl, xu) (a fixed variable: its value): J's
+// scaled entries of the structural columns + cfix (the fixed columns' terms), as k_cons forms the row for
+// get_solution.  A row per lane group of the solver's SpMV width; the lanes stride the row, then a butterfly.
+template <int G>
+__global__ __launch_bounds__(NT) void k_warm_rows(DV D, WarmArgs W) {
+  const int nx = D.nx, ns = D.n - D.nx;
+  const int gl = threadIdx.x & (G - 1);
+  GROUP_LOOP(k, ns, G) {
+    const int r = W.ineq[k];
+    const int64_t q1 = D.J.rp[r + 1];
+    double s = 0.0;
+    for (int64_t q = D.J.rp[r] + gl; q < q1; q += G) {
+      const int c = D.J.ci[q];
+      if (c < nx) s = fma(D.J.v[q], clampv(W.wx[c], D.xl[c], D.xu[c]), s);
+    }
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, G);
+    if (gl == 0) W.rows[k] = s + D.cfix[r];
+  }
+}
+
+// v = lam v~ + (1 - lam) v_cold on x and s (free coordinates), y, zl on ind_lb, zu on ind_ub, where
+//   x~ = clamp(x, xl, xu), s~ = clamp(row value, xl_s, xu_s), y~ = y obj_scale / con_scale,
+//   zl~ = max(zl obj_scale, 0), zu~ = max(zu obj_scale, 0), and for the slack of row i (stationarity of the
+//   slack coordinate, -y - zl_s + zu_s = 0) zl_s~ = max(-y~_i, 0), zu_s~ = max(y~_i, 0);
+// a coordinate whose blended value is not strictly interior (x <= xl, x >= xu, z <= 0) keeps its cold value,
+// so init_starting_point!'s interior assertions (solver.jl:120-123) still hold.  Each thread reads and
+// writes its own coordinate of the iterate only.
+__global__ __launch_bounds__(NT) void k_warm_blend(DV D, WarmArgs W) {
+#pragma clang fp contract(off)
+  const int n = D.n, nx = D.nx;
+  const double lam = W.lam, rest = 1.0 - W.lam;
+  GRID_LOOP(i, n + D.m) {
+    if (i < n) {
+      const bool lb = D.lbpos[i] >= 0, ub = D.ubpos[i] >= 0, slack = i >= nx;
+      if (W.wx && !D.fixed[i]) {
+        const double l = D.xl[i], u = D.xu[i];
+        const double xt = clampv(slack ? W.rows[i - nx] : W.wx[i], l, u);
+        const double v = lam * xt + rest * D.x[i];
+        if (!((lb && v <= l) || (ub && v >= u))) D.x[i] = v;
+      }
+      double ys = 0.0;
+      if (slack && W.wy) {
+        const int r = W.ineq[i - nx];
+        ys = W.wy[r] * W.os / W.cscale[r];
+      }
+      if (lb && (slack ? W.wy != nullptr : W.wzl != nullptr)) {
+        const double t = slack ? -ys : W.wzl[i] * W.os;
+        const double v = lam * (t < 0.0 ? 0.0 : t) + rest * D.zl[i];
+        if (!(v <= 0.0)) D.zl[i] = v;
+      }
+      if (ub && (slack ? W.wy != nullptr : W.wzu != nullptr)) {
+        const double t = slack ? ys : W.wzu[i] * W.os;
+        const double v = lam * (t < 0.0 ? 0.0 : t) + rest * D.zu[i];
+        if (!(v <= 0.0)) D.zu[i] = v;
+      }
+    } else if (W.wy) {
+      const int64_t j = i - n;
+      D.y[j] = lam * (W.wy[j] * W.os / W.cscale[j]) + rest * D.y[j];
+    }
+  }
+}
+
 // csr_from_coo's structure for the COO (r, c) without its values: destination entries sorted by
 // (row, column), each with the ids of its COO entries in input order (id < 0: a constant entry, no source)
 struct CooPlan {
@@ -3048,6 +3141,106 @@ void MPCSolver::get_solution_device(double* x, double* y, double* zl, double* zu
     }                                                                             \
   } while (0)
 
+// ---- warm start
+static void check_weight(double w) {
+  MADIPM_REQUIRE(w > 0.0 && w < 1.0, "warm start: weight must be in the open interval (0, 1), got " + std::to_string(w));
+}
+
+// the buffers, once (the first call that sets a point); nothing of the current point is touched
+WarmStart& MPCSolver::warm_buffers() {
+  if (!warm_) {
+    auto w = std::make_unique<WarmStart>();
+    w->x.alloc(std::max(nx_, 1));
+    w->y.alloc(std::max(m_, 1));
+    w->zl.alloc(std::max(nx_, 1));
+    w->zu.alloc(std::max(nx_, 1));
+    w->rows.alloc(std::max(ns_, 1));
+    w->ineq.alloc(std::max(ns_, 1));
+    w->ineq.upload(H_->ind_ineq.data(), H_->ind_ineq.size(), stream_);
+    MADIPM_HIP(hipEventCreateWithFlags(&w->ev[0], hipEventDisableTiming));
+    MADIPM_HIP(hipEventCreateWithFlags(&w->ev[1], hipEventDisableTiming));
+    device_con_scale();  // its one-off device copy (a solver without an update) now, not in initialize()
+    MADIPM_HIP(hipStreamSynchronize(stream_));
+    warm_ = std::move(w);
+  }
+  return *warm_;
+}
+
+void MPCSolver::set_warm_start(const double* x, const double* y, const double* zl, const double* zu, double weight,
+                               bool device, hipStream_t caller) {
+  check_weight(weight);
+  MADIPM_REQUIRE(x || y || zl || zu, "warm start: all four of x, y, zl, zu are NULL (madipm_solver_clear_warm_start "
+                                     "removes a warm point)");
+  WarmStart& w = warm_buffers();
+  hipStream_t s = stream_;
+  const auto kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (device) {  // the caller's arrays are read after the work already enqueued on its stream
+    MADIPM_HIP(hipEventRecord(w.ev[0], caller));
+    MADIPM_HIP(hipStreamWaitEvent(s, w.ev[0], 0));
+  }
+  const double* src[4] = {x, y, zl, zu};
+  double* dst[4] = {w.x.p, w.y.p, w.zl.p, w.zu.p};
+  const int64_t len[4] = {nx_, m_, nx_, nx_};
+  for (int k = 0; k < 4; ++k) {
+    w.has[k] = src[k] != nullptr;
+    if (src[k] && len[k]) MADIPM_HIP(hipMemcpyAsync(dst[k], src[k], len[k] * sizeof(double), kind, s));
+  }
+  if (device) {  // the caller's later work on its stream (overwriting the arrays) comes after the copies
+    MADIPM_HIP(hipEventRecord(w.ev[1], s));
+    MADIPM_HIP(hipStreamWaitEvent(caller, w.ev[1], 0));
+  } else {
+    MADIPM_HIP(hipStreamSynchronize(s));  // host arrays are read during the call only
+  }
+  w.weight = weight;
+  w.active = true;
+  initialized_ = false;
+}
+
+void MPCSolver::warm_start_last(double weight) {
+  check_weight(weight);
+  MADIPM_REQUIRE(solved_, "madipm_solver_warm_start_last: no solve has run on this solver yet");
+  WarmStart& w = warm_buffers();
+  const double* cscale = device_con_scale();
+  if (std::max(nx_, m_))
+    k_unscale<<<blocks(std::max(nx_, m_)), NT, 0, stream_>>>(nx_, m_, obj_scale_, x_, y_, zl_, zu_, nullptr, cscale, w.x,
+                                                              w.y, w.zl, w.zu, nullptr);
+  MADIPM_HIP(hipGetLastError());
+  for (bool& h : w.has) h = true;
+  w.weight = weight;
+  w.active = true;
+  initialized_ = false;
+}
+
+void MPCSolver::clear_warm_start() {
+  if (warm_ && warm_->active) initialized_ = false;
+  if (warm_) warm_->active = false;
+}
+
+void MPCSolver::warm_info(int32_t* active, double* weight, int64_t* n_warm_inits) const {
+  const bool on = warm_ && warm_->active;
+  if (active) *active = on ? 1 : 0;
+  if (weight) *weight = on ? warm_->weight : 0.0;
+  if (n_warm_inits) *n_warm_inits = n_warm_inits_;
+}
+
+// initialize()'s warm part, after init_starting_point(): the blend, then evaluate_model! at the blended
+// point (the cold path leaves the initial point's f, c and objective in place; the first termination test of
+// a warm solve sees the blended point's residuals)
+void MPCSolver::warm_blend() {
+  DV_ARGS;
+  hipStream_t s = stream_;
+  WarmStart& w = *warm_;
+  WarmArgs W{w.has[0] ? w.x.p : nullptr, w.has[1] ? w.y.p : nullptr, w.has[2] ? w.zl.p : nullptr,
+             w.has[3] ? w.zu.p : nullptr, device_con_scale(), w.ineq.p, w.rows.p, w.weight, obj_scale_};
+  if (W.wx && ns_) SPMV_LAUNCH(k_warm_rows, spmv_blocks(ns_), s, D, W);
+  const int nb = blocks(n_ + m_);
+  k_warm_blend<<<nb, NT, 0, s>>>(D, W);
+  SPMV_LAUNCH(k_eval, nb, s, D, 0);
+  launch_reduce_final(FIN_EVAL, nb);
+  MADIPM_HIP(hipGetLastError());
+  ++n_warm_inits_;
+}
+
 void MPCSolver::kkt_diag(double dw, double dc) {
   DV_ARGS;
   k_diag<<<blocks(n_ + m_), NT, 0, stream_>>>(D, dw, dc, fact_reset());
@@ -3309,6 +3502,7 @@ void MPCSolver::initialize() {
   norm_c_ = 0;
   for (double v : fh) norm_c_ = std::max(norm_c_, std::fabs(v));
   init_starting_point();
+  if (warm_ && warm_->active) warm_blend();
   k_set_mu<<<1, 1, 0, s>>>(st_, opt_.mu_init);  // solver.jl:179
   k_jtprod<<<blocks(n_), NT, 0, s>>>(D);        // solver.jl:187
   best_compl_ = INF;
@@ -3528,6 +3722,7 @@ int MPCSolver::solve(madipm_stats* stats) {
       throw;
   }
   MADIPM_HIP(hipStreamSynchronize(s));
+  solved_ = true;
   t_total_ = now() - tstart;
   status_ = status;
   t_linsol_ = ldl_->fact_seconds(s) - fs0_;

@@ -44,6 +44,7 @@ struct QPHost;       // host copy of the problem (mpc.hip)
 struct HostNumeric;  // value-dependent host quantities of size O(n + m) (mpc.hip)
 struct UpdatePlan;   // index plans of the value refresh, built by prepare_update (mpc.hip)
 struct DevUpdate;    // staging, start vectors and sum-order lists of the device route (mpc.hip)
+struct WarmStart;    // the warm point and its scratch, on the device (mpc.hip)
 
 class MPCSolver {
  public:
@@ -72,6 +73,15 @@ class MPCSolver {
   void get_solution_device(double* x, double* y, double* zl, double* zu, double* cons, hipStream_t caller);
   void get_data(double* c, double* c0, double* Hvals, double* Avals, double* lcon, double* ucon, double* lvar,
                 double* uvar, double* x0, double* y0);
+  // Warm start (madipm_solver_set_warm_start / _device / _warm_start_last / _clear_warm_start / _warm_info):
+  // a point (x, y, zl, zu) of the public space, any block absent (null), that initialize() blends with the
+  // cold start.  The first call that sets one allocates its device copy; a solver that never sets one, or
+  // cleared it, initializes exactly as before.  device: the pointers are device arrays produced on `caller`.
+  void set_warm_start(const double* x, const double* y, const double* zl, const double* zu, double weight,
+                      bool device, hipStream_t caller);
+  void warm_start_last(double weight);
+  void clear_warm_start();
+  void warm_info(int32_t* active, double* weight, int64_t* n_warm_inits) const;
   int64_t n_analyses() const { return n_analyses_; }
   int64_t n_updates() const { return n_updates_; }
   double last_update_s() const { return last_update_s_; }
@@ -83,6 +93,8 @@ class MPCSolver {
   void numeric_host(HostNumeric& o, std::vector<int32_t>* jr = nullptr, std::vector<int32_t>* jc = nullptr,
                     std::vector<double>* jv = nullptr);
   void build_device_route();
+  WarmStart& warm_buffers();
+  void warm_blend();
   void refresh_host_mirrors();
   const double* device_con_scale();
   std::unique_ptr<LinSolver> make_linsolver(int n, const int64_t* cp, const int32_t* ri, const SymbolicOptions& so);
@@ -172,6 +184,9 @@ class MPCSolver {
   bool cscale_dev_ok_ = false;         // the plan's device con_scale has been written by an update
   DBuf<double> sol_ax_, sol_cs_;       // get_solution_device: constraint values; con_scale when no update wrote it
   hipEvent_t sol_ev_[2] = {nullptr, nullptr};
+  std::unique_ptr<WarmStart> warm_;     // null until a warm point is set
+  int64_t n_warm_inits_ = 0;           // initialize() calls that blended
+  bool solved_ = false;                // a solve has run (warm_start_last needs its point)
   int64_t n_analyses_ = 0, n_updates_ = 0;
   double last_update_s_ = 0;
 };

@@ -265,3 +265,51 @@ function solver_get_data(h::Ptr{Cvoid}; c=nothing, Hvals=nothing, Avals=nothing,
     end
     return c0[]
 end
+
+# ---- warm start (ABI 0.2.6): the following solves start from a point (x, y, zl, zu) of the public, un-scaled
+# space (what solver_get_solution returns; lengths nvar, ncon, nvar, nvar; nothing = the block keeps its
+# cold values, not all four) blended into the cold start with `weight` in (0, 1).  The point persists across
+# solves and updates until it is replaced or cleared.  Non-finite entries are not checked.
+function solver_set_warm_start(h::Ptr{Cvoid}; x=nothing, y=nothing, zl=nothing, zu=nothing, weight::Real=0.99)
+    GC.@preserve x y zl zu begin
+        check(ccall((:madipm_solver_set_warm_start, libmadipm), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble),
+                    h, _ptr_or_null(x), _ptr_or_null(y), _ptr_or_null(zl), _ptr_or_null(zu), Float64(weight)),
+              "madipm_solver_set_warm_start")
+    end
+    return
+end
+
+# the same from DEVICE arrays (Ptr{Float64} into device memory, or nothing) produced on `stream`: the reads
+# are ordered after the work enqueued on it, the host is not synchronised, and work enqueued on `stream`
+# afterwards (overwriting the arrays) is ordered after the copies
+function solver_set_warm_start_device(h::Ptr{Cvoid}; x=nothing, y=nothing, zl=nothing, zu=nothing,
+                                      weight::Real=0.99, stream::Ptr{Cvoid}=C_NULL)
+    check(ccall((:madipm_solver_set_warm_start_device, libmadipm), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Cvoid}),
+                h, _dptr_or_null(x), _dptr_or_null(y), _dptr_or_null(zl), _dptr_or_null(zu), Float64(weight), stream),
+          "madipm_solver_set_warm_start_device")
+    return
+end
+
+# the solver's own current iterate as the warm point, without leaving the device (an error before the first
+# solve); in a re-solve loop: solve, solver_warm_start_last, update, solve
+function solver_warm_start_last(h::Ptr{Cvoid}; weight::Real=0.99)
+    check(ccall((:madipm_solver_warm_start_last, libmadipm), Cint, (Ptr{Cvoid}, Cdouble), h, Float64(weight)),
+          "madipm_solver_warm_start_last")
+    return
+end
+
+function solver_clear_warm_start(h::Ptr{Cvoid})
+    check(ccall((:madipm_solver_clear_warm_start, libmadipm), Cint, (Ptr{Cvoid},), h),
+          "madipm_solver_clear_warm_start")
+    return
+end
+
+# (active, weight, n_warm_inits): a point is set, its weight, initialisations that blended
+function solver_warm_info(h::Ptr{Cvoid})
+    a, w, k = Ref{Int32}(0), Ref{Float64}(0.0), Ref{Int64}(0)
+    check(ccall((:madipm_solver_warm_info, libmadipm), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Float64}, Ref{Int64}),
+                h, a, w, k), "madipm_solver_warm_info")
+    return (active = a[] != 0, weight = w[], n_warm_inits = k[])
+end

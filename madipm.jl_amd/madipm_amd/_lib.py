@@ -106,6 +106,12 @@ _sig("madipm_comm_allreduce", C.c_int, [vp, vp, C.c_int64, vp])
 _sig("madipm_comm_allgather", C.c_int, [vp, vp, C.c_int64, vp])
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, f64p, C.c_int64, vp)
 _sig("madipm_comm_create_host", C.c_int, [C.c_int32, C.c_int32, ALLREDUCE_FN, vp, C.POINTER(vp)])
+# warm start (ABI 0.2.6): host point, device point + stream, the solver's own iterate, clear, info
+_sig("madipm_solver_set_warm_start", C.c_int, [vp, f64p, f64p, f64p, f64p, C.c_double])
+_sig("madipm_solver_set_warm_start_device", C.c_int, [vp, f64p, f64p, f64p, f64p, C.c_double, vp])
+_sig("madipm_solver_warm_start_last", C.c_int, [vp, C.c_double])
+_sig("madipm_solver_clear_warm_start", C.c_int, [vp])
+_sig("madipm_solver_warm_info", C.c_int, [vp, i32p, f64p, i64p])
 
 
 class MadIPMError(RuntimeError):

@@ -579,6 +579,76 @@ class MPCSolver:
                 "get_solution_device")
         return out
 
+    # ------------------------------------------------------------ warm start
+    def warm_start(self, *, x=None, y=None, zl=None, zu=None, weight=0.99):
+        """Start the following solves from a point of the public space — what solve() returns as solution,
+        multipliers, multipliers_L, multipliers_U (lengths nvar, ncon, nvar, nvar) — instead of the cold
+        start alone: initialize! runs unchanged, then every block given here is blended into the cold start,
+        weight * warm + (1 - weight) * cold, after x is clamped into the bounds and the multipliers at 0; a
+        coordinate that would leave the strict interior keeps its cold value.  A block left None keeps its
+        cold values (the slack values follow x, the slack multipliers y).  The point replaces any earlier one
+        and stays, across solves and updates, until clear_warm_start().  0 < weight < 1; entries are not
+        checked for NaN / inf.  The arrays are read during the call only."""
+        want = {"x": self.qp.nvar, "y": self.qp.ncon, "zl": self.qp.nvar, "zu": self.qp.nvar}
+        p, keep = {}, []
+        for k, a in (("x", x), ("y", y), ("zl", zl), ("zu", zu)):
+            if a is None:
+                p[k] = None
+                continue
+            a = np.array(a, dtype=np.float64, order="C", ndmin=1)
+            if a.shape != (want[k],):
+                raise ValueError(f"warm_start: {k} has shape {a.shape}, expected ({want[k]},)")
+            # an empty block (ncon = 0) has nothing to read: any non-null address says "given"
+            a = a if a.size else np.zeros(1)
+            keep.append(a)
+            p[k] = L.ptr(a, C.c_double)
+        L.check(L.lib.madipm_solver_set_warm_start(self.h, p["x"], p["y"], p["zl"], p["zu"], float(weight)),
+                "warm_start")
+
+    def warm_start_device(self, *, x=None, y=None, zl=None, zu=None, weight=0.99, stream=None):
+        """warm_start() from torch tensors on the solver's GPU (float64, contiguous, the shapes warm_start()
+        expects), without a copy through the host.  `stream` is the torch.cuda.Stream the tensors were
+        produced on (None: the current stream): the reads are ordered after the work enqueued on it, the
+        host is not blocked, and work enqueued on it after the call is ordered after the copies, so the
+        tensors may be overwritten from that stream right away."""
+        import torch
+        want = {"x": self.qp.nvar, "y": self.qp.ncon, "zl": self.qp.nvar, "zu": self.qp.nvar}
+        if self._device is None:
+            self._device = torch.device("cuda", torch.cuda.current_device())
+        p, keep = {}, []
+        for k, a in (("x", x), ("y", y), ("zl", zl), ("zu", zu)):
+            if a is None:
+                p[k] = None
+                continue
+            check_device_array(k, a, want[k], self._device)
+            if a.numel() == 0:
+                a = torch.zeros(1, dtype=torch.float64, device=self._device)
+            keep.append(a)
+            p[k] = C.cast(a.data_ptr(), L.f64p)
+        if stream is not None and not isinstance(stream, torch.cuda.Stream):
+            raise TypeError(f"warm_start_device: stream must be a torch.cuda.Stream, not {type(stream).__name__}")
+        st = stream if stream is not None else torch.cuda.current_stream(self._device)
+        L.check(L.lib.madipm_solver_set_warm_start_device(self.h, p["x"], p["y"], p["zl"], p["zu"], float(weight),
+                                                          L.vp(st.cuda_stream)), "warm_start_device")
+
+    def warm_start_last(self, weight=0.99):
+        """The solver's own current iterate (the bits solution_device() would return now) as the warm point,
+        without leaving the GPU.  In a re-solve loop: solve() -> warm_start_last() -> update_device() ->
+        solve(), i.e. before the update, so that the solution is un-scaled with the scaling it was computed
+        in.  MadIPMError before the first solve."""
+        L.check(L.lib.madipm_solver_warm_start_last(self.h, float(weight)), "warm_start_last")
+
+    def clear_warm_start(self):
+        """Back to cold starts: the next solve() is bit for bit the one of a solver that never set a point."""
+        L.check(L.lib.madipm_solver_clear_warm_start(self.h), "clear_warm_start")
+
+    def warm_info(self) -> dict:
+        """active: a warm point is set; weight: its weight (0.0 when none); n_warm_inits: initialisations of
+        this solver that blended a warm point."""
+        a, w, k = C.c_int32(), C.c_double(), C.c_int64()
+        L.check(L.lib.madipm_solver_warm_info(self.h, C.byref(a), C.byref(w), C.byref(k)), "warm_info")
+        return {"active": bool(a.value), "weight": float(w.value), "n_warm_inits": int(k.value)}
+
     def counters(self) -> dict:
         """n_analyses: linear-solver analyses run for this solver (stays 1); n_updates: successful update()
         calls; last_update_s: host wall time of the last one (its stream synchronisation included)."""

@@ -14,7 +14,13 @@ The device route runs in the same process on the same sequence of perturbed data
 update_device_s (counters()["last_update_s"] of MPCSolver.update_device, same median) beside the host
 update_s, and update + solve + solution_device() (the results left in device tensors, stream synchronised)
 against host update + solve with the host fetch; device_matches_fresh compares the last device-updated
-solve with the same fresh solver.  Ends with one JSON line."""
+solve with the same fresh solver.  Ends with one JSON line.
+
+--warm WEIGHT adds the warm-started device loop on the same sequence of data, in the same process:
+warm_start_last(WEIGHT) after each solve (the previous solution, taken before the update), then update_device
++ solve + solution_device: warm_iters and warm_device_loop_s beside iters and device_loop_s, warm_status,
+and warm_obj_rel, the largest relative difference of a warm solve's objective from the cold solve's on the
+same data.  Without the option nothing of it runs and the output is as before."""
 import dataclasses
 import json
 import os
@@ -44,7 +50,7 @@ def perturb(qp, rng):
                 lvar=qp.lvar * fv, uvar=qp.uvar * fv, lcon=qp.lcon * fc, ucon=qp.ucon * fc)
 
 
-def run(name):
+def run(name, warm=None):
     qp, desc = bench.build_problem(name)
     opts = bench.solver_opts()
     MPCSolver(qp, **opts)                      # the first construction of a process pays one-off set-up
@@ -86,7 +92,7 @@ def run(name):
     s.update_device(**{k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()})  # allocates
     rng = np.random.default_rng(0)
     perturb(qp, rng)
-    dupd, dcall, devloop = [], [], []
+    dupd, dcall, devloop, dobj = [], [], [], []
     for rep in range(WARMUP + REPS):
         dnew = {k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()}
         torch.cuda.synchronize()
@@ -100,13 +106,38 @@ def run(name):
         s.solution_device()
         torch.cuda.current_stream().synchronize()
         t_loop = time.perf_counter() - t
+        dobj.append(dst.objective)
         if rep >= WARMUP:
             dupd.append(s.counters()["last_update_s"])
             dcall.append(t_call)
             devloop.append(t_loop)
     c = s.counters()
+    wres = {}
+    if warm is not None:   # the same data again, each solve started from the previous solution
+        rng = np.random.default_rng(0)
+        perturb(qp, rng)
+        wits, wloop, wstat, wrel = [], [], set(), 0.0
+        for rep in range(WARMUP + REPS):
+            dnew = {k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()}
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            s.warm_start_last(warm)
+            s.update_device(**dnew)
+            wst = s.solve(fetch_solution=False)
+            s.solution_device()
+            torch.cuda.current_stream().synchronize()
+            t_loop = time.perf_counter() - t
+            wrel = max(wrel, abs(wst.objective - dobj[rep]) / max(1.0, abs(dobj[rep])))
+            if rep >= WARMUP:
+                wits.append(wst.iter)
+                wloop.append(t_loop)
+                wstat.add(wst.status)
+        s.clear_warm_start()
+        wres = {"warm_weight": warm, "warm_iters": wits, "warm_device_loop_s": statistics.median(wloop),
+                "warm_status": sorted(wstat), "warm_obj_rel": wrel, "n_warm_inits": s.warm_info()["n_warm_inits"]}
+        c = s.counters()
     update_s, solve_s = statistics.median(upd), statistics.median(sol)
-    return {"instance": name, "description": desc, "nvar": qp.nvar, "ncon": qp.ncon, "nnzj": qp.nnzj, "nnzh": qp.nnzh,
+    return {**wres, "instance": name, "description": desc, "nvar": qp.nvar, "ncon": qp.ncon, "nnzj": qp.nnzj, "nnzh": qp.nnzh,
             "construct_s": construct_s, "prepare_update_s": prepare_update_s, "update_s": update_s,
             "update_call_s": statistics.median(call),   # MPCSolver.update: + the Python copies of the arrays
             "solve_s": solve_s, "first_solve_s": solve0_s, "status": st.status, "first_status": st0.status,
@@ -129,8 +160,13 @@ def main():
     _lib.check(_lib.madipm_set_device(0), "madipm_set_device")
     torch.zeros(1, device="cuda")
     out = []
-    for name in sys.argv[1:] or ["ex10", "supportcase10"]:
-        r = run(name)
+    args, warm = sys.argv[1:], None
+    if "--warm" in args:
+        k = args.index("--warm")
+        warm = float(args[k + 1])
+        del args[k:k + 2]
+    for name in args or ["ex10", "supportcase10"]:
+        r = run(name, warm)
         print(f"{name}: construct_s {r['construct_s']:.4f}  prepare_update_s {r['prepare_update_s']:.4f}  "
               f"update_s {r['update_s']:.5f}  solve_s {r['solve_s']:.4f}  ->  update + solve "
               f"{r['update_plus_solve_s']:.4f} s against construct + solve {r['construct_plus_solve_s']:.4f} s "
@@ -138,6 +174,11 @@ def main():
         print(f"{name}: device route: update_device_s {r['update_device_s']:.5f} (host update_s {r['update_s']:.5f})  "
               f"update_device + solve + solution_device {r['device_loop_s']:.4f} s against update + solve + host "
               f"fetch {r['host_loop_s']:.4f} s, device_matches_fresh {r['device_matches_fresh']}", flush=True)
+        if warm is not None:
+            print(f"{name}: warm start {warm}: iterations {statistics.median(r['warm_iters'])} (cold "
+                  f"{statistics.median(r['iters'])})  warm_start_last + update_device + solve + solution_device "
+                  f"{r['warm_device_loop_s']:.4f} s (cold {r['device_loop_s']:.4f} s), status {r['warm_status']}, "
+                  f"objective within {r['warm_obj_rel']:.1e} of the cold solve's", flush=True)
         out.append(r)
     print(json.dumps({"resolve_bench": out, "warmup": WARMUP, "reps": REPS, "rel_noise": REL}))
 
