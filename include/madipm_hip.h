@@ -514,6 +514,52 @@ int madipm_solver_clear_warm_start(madipm_solver_t s);
  * Any pointer may be NULL. */
 int madipm_solver_warm_info(madipm_solver_t s, int32_t* active, double* weight, int64_t* n_warm_inits);
 
+/* ------------------------------------------------------------------ adjoint gradients  [ABI 0.2.7, additive]
+ * The solver as a differentiable layer: for a loss l(x*) of the optimal x alone, given gx = dl/dx* (length
+ * nvar), the gradients of l with respect to the problem data.  (madipm_version() still returns 203: these
+ * three symbols and one struct are the whole addition, no existing struct changed.)
+ *
+ * Every non-NULL field of madipm_qp_gradients receives one gradient: c, lvar, uvar of length nvar, lcon, ucon of
+ * length ncon, Hvals of length nnzh and Avals of length nnzj in the creation-time COO order (a duplicated
+ * entry receives the full value in each copy).  Conventions: an infinite bound has gradient 0; for a fixed
+ * variable (lvar == uvar) and an equality row (lcon == ucon) the whole derivative with respect to the common
+ * value is in lvar / lcon and uvar / ucon is 0, so a caller that passes one array as both bounds adds the two
+ * and gets the right sum; c0 has no influence.  The derivation is DESIGN §13c.
+ * The call factorises the K2 matrix of the last solve's end point (kkt_diag + assemble + LDL^T, with the
+ * regularisation the options prescribe: none, the fixed pair, or the adaptive pair as the solve left it,
+ * and the loop's x100 retries, three trials) and runs one solve with it plus two steps of iterative refinement
+ * towards the matrix WITHOUT the regularisation, so that the gradients do not carry it (MADIPM_ADJ_REFINE =
+ * 0..8 sets the step count, for measurements); a later call on the same point (another gx) reuses the factor.  Nothing a later madipm_solver_initialize / _solve / _warm_start_last
+ * reads is changed: solve, adjoint, solve gives the second solve the bits of solve, solve.
+ * Refused (negative code, reason in madipm_last_error(), solver untouched): before the first solve; when the
+ * last solve did not end with MADIPM_SOLVE_SUCCEEDED; after a madipm_solver_update / _update_device /
+ * _initialize that no solve followed (the iterate no longer belongs to the data); kkt_system 1 or 2 (K2.5
+ * and the normal equations are left to a later release); a solver made by madipm_solver_create_dist; gx
+ * NULL; all seven outputs NULL.  A failure of all three factorisation trials is an error (-4).
+ * Memory, each part allocated by the first call that needs it and never again: 8 B x (3 nvar + 2 ncon +
+ * 2 inequality rows + 2) of right-hand side, solution and residual scratch; 4 B per row with lcon / ucon; 8 B per entry of
+ * A with Avals and 8 B per entry of H with Hvals (device copies of the COO indices); with lvar on a problem
+ * with fixed variables 8 B per entry of A in a fixed column and per entry of H between a fixed and a free
+ * variable; on the host route 8 B per entry of each output asked for.  Avals, Hvals and that lvar need
+ * madipm_solver_prepare_update first (the raw values and index arrays it keeps); c, the bounds of a problem
+ * without fixed variables, lcon and ucon need nothing per entry of A.
+ *
+ * madipm_solver_adjoint: HOST pointers, read / written during the call. */
+typedef struct madipm_qp_gradients { double *c, *Hvals, *Avals, *lcon, *ucon, *lvar, *uvar; } madipm_qp_gradients; /* NULL = not wanted */
+int madipm_solver_adjoint(madipm_solver_t s, const double* gx, const madipm_qp_gradients* out);
+/* DEVICE pointers.  d_gx has the stream contract of madipm_solver_set_warm_start_device: it is read after
+ * the work already enqueued on `stream` (an event wait; the host is not blocked on it).  The outputs have
+ * that of madipm_solver_get_solution_device: work enqueued on `stream` after the call returns sees them.
+ * The first call on a point waits, on the host, for the status of its factorisation. */
+int madipm_solver_adjoint_device(madipm_solver_t s, const double* d_gx, const madipm_qp_gradients* d_out,
+                                 madipm_stream_t stream);
+/* n_adjoints: successful adjoint calls; n_adjoint_factorizations: those that factorised (one per point);
+ * last_residual: ||g - K a||_inf / max(1, ||g||_inf) of the last call's refined solution, K the K2 matrix of
+ * the point without the regularisation (H, J, J^T and Sigma_l + Sigma_u); large on a degenerate point, whose
+ * gradients are then only as good as that (synchronises the solver's stream).  Any pointer may be NULL. */
+int madipm_solver_adjoint_info(madipm_solver_t s, int64_t* n_adjoints, int64_t* n_adjoint_factorizations,
+                               double* last_residual);
+
 #ifdef __cplusplus
 }
 #endif

@@ -739,6 +739,34 @@ int madipm_solver_warm_info(madipm_solver_t s, int32_t* active, double* weight, 
   MADIPM_API_END
 }
 
+int madipm_solver_adjoint(madipm_solver_t s, const double* gx, const madipm_qp_gradients* out) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(out, "madipm_solver_adjoint: null output struct");
+  s->s->adjoint(gx, *out, false, nullptr);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_adjoint_device(madipm_solver_t s, const double* d_gx, const madipm_qp_gradients* d_out,
+                                 madipm_stream_t stream) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(d_out, "madipm_solver_adjoint_device: null output struct");
+  s->s->adjoint(d_gx, *d_out, true, (hipStream_t)stream);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_adjoint_info(madipm_solver_t s, int64_t* n_adjoints, int64_t* n_adjoint_factorizations,
+                               double* last_residual) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->adjoint_info(n_adjoints, n_adjoint_factorizations, last_residual);
+  return 0;
+  MADIPM_API_END
+}
+
 int madipm_update_step(int32_t rule, double tau, double mu, int32_t nlb, int32_t nub, const double* d_x_lr,
                        const double* d_xl_r, const double* d_zl_r, const double* d_dx_lr, const double* d_dzl,
                        const double* d_x_ur, const double* d_xu_r, const double* d_zu_r, const double* d_dx_ur,

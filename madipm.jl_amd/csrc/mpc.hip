@@ -109,6 +109,30 @@ struct WarmStart {
   }
 };
 
+// The adjoint gradients (madipm_solver_adjoint*).  Everything here is allocated by the first
+// call that needs it: the right-hand side copy, the solution, the per-row residuals and the scalar block by
+// the first call (8 B x (nvar + 2 (n + m) + 2)); rowslack (4 B per row) with lcon / ucon; A's COO indices (8 B per entry)
+// with Avals; H's (8 B per entry) with Hvals; the fixed variables' entry lists (8 B per entry of A in a
+// fixed column and per entry of H between a fixed and a free variable, 4 B per fixed variable for each
+// list start) with lvar on a problem that has fixed variables; the host route's output staging (8 B per
+// output entry) with each output it is asked for.
+struct Adjoint {
+  DBuf<double> gx, sol, rowres, scal;     // host route's gx; a~ (refined); |g - K a~| per row; [residual ratio, unused]
+  DBuf<int32_t> rowslack;                 // row -> its slack (index into [nx, n)) or -1 (equality row)
+  DBuf<int32_t> Ar, Ac, Hr, Hc;           // COO indices, creation-time entry order
+  DBuf<int32_t> fix, fhsp, fasp;          // fixed variables; their list starts into fh / fa
+  DBuf<int2> fh, fa;                      // (entry of Hvals, free endpoint), (entry of Avals, row)
+  int nfix = -1;                          // -1: lists not built yet
+  DBuf<double> out[7];                    // host route: c, Hvals, Avals, lcon, ucon, lvar, uvar
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int64_t n_adjoints = 0, n_fact = 0;
+  int64_t fact_solve = -1;                // n_solves_ of the point the LDL^T currently holds the factor of
+  ~Adjoint() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 namespace {
 
 constexpr int NT = 256;
@@ -3567,6 +3591,7 @@ int MPCSolver::solve(madipm_stats* stats) {
   DV_ARGS;
   hipStream_t s = stream_;
   trace_.clear();
+  point_ok_ = false;
   int status = MADIPM_REGULAR;
   exception_ = MADIPM_EXC_NONE;
   double tstart = now();
@@ -3723,6 +3748,9 @@ int MPCSolver::solve(madipm_stats* stats) {
   }
   MADIPM_HIP(hipStreamSynchronize(s));
   solved_ = true;
+  point_ok_ = true;
+  ++n_solves_;
+  solve_updates_ = n_updates_;
   t_total_ = now() - tstart;
   status_ = status;
   t_linsol_ = ldl_->fact_seconds(s) - fs0_;
@@ -3787,6 +3815,376 @@ void MPCSolver::get_solution(double* x, double* y, double* zl, double* zu, doubl
     MADIPM_HIP(hipMemcpyAsync(h.data(), ax.p, sizeof(double) * m_, hipMemcpyDeviceToHost, stream_));
     MADIPM_HIP(hipStreamSynchronize(stream_));
     for (int j = 0; j < m_; ++j) cons[j] = h[j] / P.con_scale[j];
+  }
+}
+
+}  // namespace madipm
+
+// ======================================================================= adjoint gradients
+// madipm_solver_adjoint / _adjoint_device: with gx = dl/dx* at the end point of a successful solve, one
+// solve with the K2 matrix of that point, K a~ = [gx on the free variables; 0; 0] in the solver's scaled
+// space, gives a = (ax, as, ay) = (obj_scale a~x, obj_scale a~s / con_scale, con_scale a~y) of the public
+// space, and every gradient is a product of entries of a with entries of the solution.  One thread (the
+// residual: one lane group) per output, every sum in a fixed order, no atomics: the same bits run to run.
+namespace madipm {
+namespace {
+
+struct AdjArgs {
+  int n, m, nx;
+  double os, sgn;                                  // obj_scale; +1 minimize, -1 maximize
+  const double *d, *x, *xl, *xu, *zl, *zu, *y;     // a~ = [a~x; a~s; a~y]; the iterate (scaled space)
+  const double* cscale;                            // con_scale
+  const int32_t *lbpos, *ubpos;
+  const uint8_t* fixed;
+};
+
+__device__ __forceinline__ double adj_ax(const AdjArgs& A, int i) { return A.fixed[i] ? 0.0 : A.os * A.d[i]; }
+__device__ __forceinline__ double adj_ay(const AdjArgs& A, int r) { return A.cscale[r] * A.d[A.n + r]; }
+// Sigma_l, Sigma_u of coordinate i of [x; s] in the scaled space (k_diag's terms of pr_diag); 0 without the bound
+__device__ __forceinline__ double adj_sig_l(const AdjArgs& A, int i) {
+  return A.lbpos[i] >= 0 ? A.zl[i] / (A.x[i] - A.xl[i]) : 0.0;
+}
+__device__ __forceinline__ double adj_sig_u(const AdjArgs& A, int i) {
+  return A.ubpos[i] >= 0 ? A.zu[i] / (A.xu[i] - A.x[i]) : 0.0;
+}
+
+// gx into d's K2 layout (and into p, which keeps it for the residual): zero on fixed variables, slacks, rows
+// t1 != nullptr: the factorisation before this launch ended (LinSolver::lazy_inertia), as in k_rhs
+__global__ __launch_bounds__(NT) void k_adj_rhs(DV D, const double* __restrict__ gx, LDLStatus* t1) {
+  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  GRID_LOOP(i, D.n + D.m) {
+    const double v = (i < D.nx && !D.fixed[i]) ? gx[i] : 0.0;
+    D.d[i] = v;
+    D.p[i] = v;
+  }
+}
+
+// r = g - K v and |r| of every row, K the K2 matrix of the point WITHOUT the regularisation the factor carries:
+// H, J^T and Sigma_l + Sigma_u on a primal row, J on a dual row (k_residual's operator with the bound blocks
+// folded into Sigma).  v = the current a~; r (may be null) becomes the right-hand side of a refinement solve.
+template <int G>
+__global__ __launch_bounds__(NT) void k_adj_resid(DV D, AdjArgs A, const double* __restrict__ v, double* __restrict__ r,
+                                                  double* __restrict__ rowres) {
+  const int n = D.n, m = D.m;
+  const bool lead = (threadIdx.x & (G - 1)) == 0;
+  GROUP_LOOP(i, n + m, G) {
+    const double gi = D.p[i];
+    double kv;
+    if (i < n) {
+      double hd, jd;
+      gdot2<G>(D.H, i, v, D.JT, i, v + n, hd, jd);
+      kv = (hd + jd) + (adj_sig_l(A, (int)i) + adj_sig_u(A, (int)i)) * v[i];
+    } else {
+      kv = gdot<G>(D.J, i - n, v);
+    }
+    if (lead) {
+      const double ri = gi - kv;
+      if (r) r[i] = ri;
+      rowres[i] = fabs(ri);
+    }
+  }
+}
+
+// a~ = d (first) or a~ += d: the solve's result, then each refinement's correction
+__global__ __launch_bounds__(NT) void k_adj_acc(double* __restrict__ acc, const double* __restrict__ d, int64_t N,
+                                                int first) {
+  GRID_LOOP(i, N) acc[i] = first ? d[i] : acc[i] + d[i];
+}
+
+// out[0] = max_i rowres[i] / max(1, max_i |g_i|): one block, each thread a strided slice, then an LDS tree
+// (a maximum does not depend on the order; a NaN is kept)
+__global__ __launch_bounds__(NT) void k_adj_resmax(const double* __restrict__ rowres, const double* __restrict__ g,
+                                                   int64_t N, double* __restrict__ out) {
+  __shared__ double sw[NT], sg[NT];
+  const int t = threadIdx.x;
+  double w = 0.0, gm = 0.0;
+  for (int64_t i = t; i < N; i += NT) {
+    w = nmax(w, rowres[i]);
+    gm = nmax(gm, fabs(g[i]));
+  }
+  sw[t] = w;
+  sg[t] = gm;
+  __syncthreads();
+  for (int o = NT / 2; o > 0; o >>= 1) {
+    if (t < o) {
+      sw[t] = nmax(sw[t], sw[t + o]);
+      sg[t] = nmax(sg[t], sg[t + o]);
+    }
+    __syncthreads();
+  }
+  if (t == 0) out[0] = sw[0] / (sg[0] > 1.0 ? sg[0] : 1.0);
+}
+
+// The vector gradients (any output may be null).  Variable i: c_i = -sgn ax_i; a free one:
+// lvar_i = Sigma_l,i ax_i = Sigma~_l,i a~x_i and uvar_i likewise (the scalings cancel); a fixed one: uvar_i = 0
+// (lvar_i is k_adj_fix's).  Row i: an equality row lcon_i = ay_i, ucon_i = 0; a row with slack k:
+// lcon_i = Sigma_l,k as_k = con_scale_i Sigma~_l,k a~s_k and ucon_i likewise.
+__global__ __launch_bounds__(NT) void k_adj_vec(AdjArgs A, const int32_t* __restrict__ rowslack,
+                                                double* __restrict__ gc, double* __restrict__ glv,
+                                                double* __restrict__ guv, double* __restrict__ glc,
+                                                double* __restrict__ guc) {
+#pragma clang fp contract(off)
+  GRID_LOOP(i, (A.nx > A.m ? A.nx : A.m)) {
+    if (i < A.nx) {
+      const bool fx = A.fixed[i];
+      const double at = fx ? 0.0 : A.d[i];
+      if (gc) gc[i] = -(A.sgn * (A.os * at));
+      if (!fx) {
+        if (glv) glv[i] = adj_sig_l(A, (int)i) * at;
+        if (guv) guv[i] = adj_sig_u(A, (int)i) * at;
+      } else if (guv) {
+        guv[i] = 0.0;
+      }
+    }
+    if (i < A.m && (glc || guc)) {
+      const int k = rowslack[i];
+      const double cs = A.cscale[i];
+      if (k < 0) {
+        if (glc) glc[i] = cs * A.d[A.n + i];
+        if (guc) guc[i] = 0.0;
+      } else {
+        const double as = A.d[k];
+        if (glc) glc[i] = cs * (adj_sig_l(A, k) * as);
+        if (guc) guc[i] = cs * (adj_sig_u(A, k) * as);
+      }
+    }
+  }
+}
+
+// Avals[k], entry (r, c): -(ax_c y_r + ay_r x_c), y the public multiplier (k_unscale's rounding)
+__global__ __launch_bounds__(NT) void k_adj_avals(AdjArgs A, int64_t nnz, const int32_t* __restrict__ Ar,
+                                                  const int32_t* __restrict__ Ac, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  GRID_LOOP(k, nnz) {
+    const int r = Ar[k], c = Ac[k];
+    const double yr = A.y[r] * A.cscale[r] / A.os;
+    out[k] = -(adj_ax(A, c) * yr + adj_ay(A, r) * A.x[c]);
+  }
+}
+
+// Hvals[k], entry (r, c) of the lower triangle: -sgn ax_r x_r on the diagonal, -sgn (ax_r x_c + ax_c x_r) off it
+__global__ __launch_bounds__(NT) void k_adj_hvals(AdjArgs A, int64_t nnz, const int32_t* __restrict__ Hr,
+                                                  const int32_t* __restrict__ Hc, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  GRID_LOOP(k, nnz) {
+    const int r = Hr[k], c = Hc[k];
+    const double ar = adj_ax(A, r);
+    const double v = r == c ? ar * A.x[r] : ar * A.x[c] + adj_ax(A, c) * A.x[r];
+    out[k] = -(A.sgn * v);
+  }
+}
+
+// lvar_f of fixed variable f = gx_f - sgn (H ax)_f - (A^T ay)_f, from the raw values: the entries of Hvals
+// between f and a free variable, then the entries of Avals in column f, each list in input order
+__global__ __launch_bounds__(NT) void k_adj_fix(AdjArgs A, int nfix, const int32_t* __restrict__ fix,
+                                                const int32_t* __restrict__ fhsp, const int2* __restrict__ fh,
+                                                const int32_t* __restrict__ fasp, const int2* __restrict__ fa,
+                                                const double* __restrict__ Hraw, const double* __restrict__ Araw,
+                                                const double* __restrict__ gx, double* __restrict__ glv) {
+#pragma clang fp contract(off)
+  GRID_LOOP(t, nfix) {
+    double hs = 0.0, as = 0.0;
+    for (int q = fhsp[t]; q < fhsp[t + 1]; ++q) {
+      const int2 e = fh[q];
+      hs = hs + Hraw[e.x] * (A.os * A.d[e.y]);
+    }
+    for (int q = fasp[t]; q < fasp[t + 1]; ++q) {
+      const int2 e = fa[q];
+      as = as + Araw[e.x] * adj_ay(A, e.y);
+    }
+    const int f = fix[t];
+    glv[f] = gx[f] - A.sgn * hs - as;
+  }
+}
+
+}  // namespace
+
+// refinement solves per adjoint: 2, or MADIPM_ADJ_REFINE (0..8; A/B measurements of the refinement)
+static int adj_refine_steps() {
+  static const int k = [] {
+    const char* e = std::getenv("MADIPM_ADJ_REFINE");
+    const int v = e ? std::atoi(e) : 2;
+    return v < 0 ? 0 : (v > 8 ? 8 : v);
+  }();
+  return k;
+}
+
+void MPCSolver::adjoint(const double* gx, const madipm_qp_gradients& g, bool device, hipStream_t caller) {
+  const std::string who = device ? "madipm_solver_adjoint_device: " : "madipm_solver_adjoint: ";
+  QPHost& P = *H_;
+  // ---- refusals, before anything is allocated or enqueued
+  MADIPM_REQUIRE(solved_, who + "no solve has run on this solver yet");
+  MADIPM_REQUIRE(point_ok_ && !initialized_ && solve_updates_ == n_updates_,
+                 who + "an update, update_device or initialize ran since the last solve, so the iterate no longer "
+                       "belongs to the problem data (solve first)");
+  MADIPM_REQUIRE(status_ == MADIPM_SOLVE_SUCCEEDED, who + "the last solve ended with status " +
+                                                        std::to_string(status_) + ", not SOLVE_SUCCEEDED");
+  MADIPM_REQUIRE(kkt_ == KKT_K2, who + "only kkt_system = SparseKKTSystem (K2) is supported; the K2.5 and "
+                                       "normal-equations formulations are left to a later release");
+  MADIPM_REQUIRE(!comm_, who + "a solver created with a communicator (madipm_solver_create_dist) is not supported");
+  MADIPM_REQUIRE(gx, who + "gx is NULL");
+  double* const user[7] = {g.c, g.Hvals, g.Avals, g.lcon, g.ucon, g.lvar, g.uvar};
+  MADIPM_REQUIRE(g.c || g.Hvals || g.Avals || g.lcon || g.ucon || g.lvar || g.uvar,
+                 who + "all seven outputs are NULL");
+  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
+  const bool needA = g.Avals && na > 0, needH = g.Hvals && nh > 0, needFix = g.lvar && P.anyfix;
+  MADIPM_REQUIRE(plan_ || !(needA || needH || needFix),
+                 who + "Avals, Hvals (and lvar on a problem with fixed variables) need "
+                       "madipm_solver_prepare_update first (it keeps the index arrays and the raw values)");
+  hipStream_t s = stream_;
+  // ---- allocations, each by the first call that needs it
+  if (!adj_) {
+    auto a = std::make_unique<Adjoint>();
+    a->rowres.alloc(std::max(n_ + m_, 1));
+    a->sol.alloc(std::max(n_ + m_, 1));
+    a->scal.alloc(2);
+    a->scal.zero(s);
+    MADIPM_HIP(hipEventCreateWithFlags(&a->ev[0], hipEventDisableTiming));
+    MADIPM_HIP(hipEventCreateWithFlags(&a->ev[1], hipEventDisableTiming));
+    adj_ = std::move(a);
+  }
+  Adjoint& a = *adj_;
+  const double* cscale = device_con_scale();
+  if (!device && !a.gx.p) a.gx.alloc(std::max(nx_, 1));
+  if ((g.lcon || g.ucon) && !a.rowslack.p) {
+    std::vector<int32_t> rs(std::max(m_, 1), -1);
+    for (int k = 0; k < ns_; ++k) rs[P.ind_ineq[k]] = nx_ + k;
+    a.rowslack.upload(rs, s);
+    MADIPM_HIP(hipStreamSynchronize(s));
+  }
+  if (needA && !a.Ar.p) {
+    a.Ar.upload(plan_->Ar, s);
+    a.Ac.upload(plan_->Ac, s);
+  }
+  if (needH && !a.Hr.p) {
+    a.Hr.upload(P.Hr, s);
+    a.Hc.upload(P.Hc, s);
+  }
+  if (needFix && a.nfix < 0) {  // the fixed variables' entry lists, from the host COO copies
+    std::vector<int32_t> fix, tof(nx_, -1);
+    for (int i = 0; i < nx_; ++i)
+      if (P.fixed[i]) {
+        tof[i] = (int32_t)fix.size();
+        fix.push_back(i);
+      }
+    const int nf = (int)fix.size();
+    std::vector<int32_t> hsp(nf + 1, 0), asp(nf + 1, 0);
+    const std::vector<int32_t>&Ar = plan_->Ar, &Ac = plan_->Ac;
+    for (int64_t k = 0; k < nh; ++k) {
+      const int r = P.Hr[k], c = P.Hc[k];
+      if (P.fixed[r] != P.fixed[c]) hsp[tof[P.fixed[r] ? r : c] + 1]++;
+    }
+    for (int64_t k = 0; k < na; ++k)
+      if (P.fixed[Ac[k]]) asp[tof[Ac[k]] + 1]++;
+    for (int t = 0; t < nf; ++t) {
+      hsp[t + 1] += hsp[t];
+      asp[t + 1] += asp[t];
+    }
+    std::vector<int2> fh(std::max(hsp[nf], 1)), fa(std::max(asp[nf], 1));
+    std::vector<int32_t> hn(hsp.begin(), hsp.end() - 1), an(asp.begin(), asp.end() - 1);
+    for (int64_t k = 0; k < nh; ++k) {
+      const int r = P.Hr[k], c = P.Hc[k];
+      if (P.fixed[r] != P.fixed[c]) fh[hn[tof[P.fixed[r] ? r : c]]++] = make_int2((int)k, P.fixed[r] ? c : r);
+    }
+    for (int64_t k = 0; k < na; ++k)
+      if (P.fixed[Ac[k]]) fa[an[tof[Ac[k]]]++] = make_int2((int)k, Ar[k]);
+    a.fix.upload(fix, s);
+    a.fhsp.upload(hsp, s);
+    a.fasp.upload(asp, s);
+    a.fh.upload(fh, s);
+    a.fa.upload(fa, s);
+    MADIPM_HIP(hipStreamSynchronize(s));
+    a.nfix = nf;
+  }
+  const int64_t len[7] = {nx_, nh, na, m_, m_, nx_, nx_};
+  double* out[7];
+  for (int j = 0; j < 7; ++j) {
+    out[j] = user[j];
+    if (!device && user[j]) {
+      if (!a.out[j].p) a.out[j].alloc(std::max<int64_t>(len[j], 1));
+      out[j] = a.out[j].p;
+    }
+  }
+  // ---- the factor of the K2 matrix at the final iterate: once per solve
+  DV_ARGS;
+  if (a.fact_solve != n_solves_) {
+    a.fact_solve = -1;
+    double dw = 0.0, dc = 0.0;  // the options' regularisation; Adaptive: the current pair, not decayed
+    if (opt_.regularization == 1) {
+      dw = opt_.delta_p;
+      dc = opt_.delta_d;
+    } else if (opt_.regularization != 0) {
+      dw = adapt_dp_;
+      dc = adapt_dd_;
+    }
+    bool ok = false;
+    for (int trial = 0; trial < 3 && !ok; ++trial) {  // factorize_regularized_system!'s trials
+      if (trial) {
+        dw *= 100.0;
+        dc *= 100.0;
+      }
+      factor_enqueue(dw, dc);
+      ok = ldl_->status(s) == 0;
+    }
+    if (!ok) throw Error(who + "the factorisation of the KKT system at the solution failed in all three trials", -4);
+    a.fact_solve = n_solves_;
+    ++a.n_fact;
+  }
+  // ---- right-hand side, solve, residual
+  const double* dgx = gx;
+  if (device) {  // gx is read after the work already enqueued on the caller's stream
+    MADIPM_HIP(hipEventRecord(a.ev[0], caller));
+    MADIPM_HIP(hipStreamWaitEvent(s, a.ev[0], 0));
+  } else {
+    a.gx.upload(gx, nx_, s);
+    dgx = a.gx.p;
+  }
+  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
+  const int64_t N = (int64_t)n_ + m_;
+  const AdjArgs A{n_, m_, nx_, obj_scale_, P.sgn, a.sol.p, x_.p, xl_.p, xu_.p, zl_.p, zu_.p, y_.p,
+                  cscale, lbpos_.p, ubpos_.p, fixed_.p};
+  k_adj_rhs<<<nb, NT, 0, s>>>(D, dgx, take_fact_end());
+  kkt_solve();
+  k_adj_acc<<<nb, NT, 0, s>>>(a.sol.p, d_.p, N, 1);
+  // iterative refinement towards the system without the regularisation (the factor is the regularised
+  // matrix's: each step gains about -log10(delta |K^-1|) digits); a fixed count, so nothing is read back
+  for (int it = 0; it < adj_refine_steps(); ++it) {
+    SPMV_LAUNCH(k_adj_resid, nbs, s, D, A, a.sol.p, d_.p, a.rowres.p);
+    kkt_solve();
+    k_adj_acc<<<nb, NT, 0, s>>>(a.sol.p, d_.p, N, 0);
+  }
+  SPMV_LAUNCH(k_adj_resid, nbs, s, D, A, a.sol.p, (double*)nullptr, a.rowres.p);
+  k_adj_resmax<<<1, NT, 0, s>>>(a.rowres.p, p_.p, N, a.scal.p);
+  // ---- gradients
+  if ((out[0] || out[3] || out[4] || out[5] || out[6]) && std::max(nx_, m_))
+    k_adj_vec<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, a.rowslack.p, out[0], out[5], out[6], out[3], out[4]);
+  if (needFix && a.nfix > 0)
+    k_adj_fix<<<blocks(a.nfix), NT, 0, s>>>(A, a.nfix, a.fix.p, a.fhsp.p, a.fh.p, a.fasp.p, a.fa.p, plan_->Hraw.p,
+                                             plan_->Araw.p, dgx, out[5]);
+  if (needA) k_adj_avals<<<blocks(na), NT, 0, s>>>(A, na, a.Ar.p, a.Ac.p, out[2]);
+  if (needH) k_adj_hvals<<<blocks(nh), NT, 0, s>>>(A, nh, a.Hr.p, a.Hc.p, out[1]);
+  MADIPM_HIP(hipGetLastError());
+  if (device) {  // work enqueued on the caller's stream from now on sees the outputs
+    MADIPM_HIP(hipEventRecord(a.ev[1], s));
+    MADIPM_HIP(hipStreamWaitEvent(caller, a.ev[1], 0));
+  } else {
+    for (int j = 0; j < 7; ++j)
+      if (user[j] && len[j])
+        MADIPM_HIP(hipMemcpyAsync(user[j], out[j], len[j] * sizeof(double), hipMemcpyDeviceToHost, s));
+    MADIPM_HIP(hipStreamSynchronize(s));
+  }
+  ++a.n_adjoints;
+}
+
+void MPCSolver::adjoint_info(int64_t* n_adjoints, int64_t* n_adjoint_factorizations, double* last_residual) {
+  if (n_adjoints) *n_adjoints = adj_ ? adj_->n_adjoints : 0;
+  if (n_adjoint_factorizations) *n_adjoint_factorizations = adj_ ? adj_->n_fact : 0;
+  if (last_residual) {
+    *last_residual = 0.0;
+    if (adj_ && adj_->n_adjoints) {
+      MADIPM_HIP(hipMemcpyAsync(last_residual, adj_->scal.p, sizeof(double), hipMemcpyDeviceToHost, stream_));
+      MADIPM_HIP(hipStreamSynchronize(stream_));
+    }
   }
 }
 

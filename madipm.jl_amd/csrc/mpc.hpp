@@ -45,6 +45,7 @@ struct HostNumeric;  // value-dependent host quantities of size O(n + m) (mpc.hi
 struct UpdatePlan;   // index plans of the value refresh, built by prepare_update (mpc.hip)
 struct DevUpdate;    // staging, start vectors and sum-order lists of the device route (mpc.hip)
 struct WarmStart;    // the warm point and its scratch, on the device (mpc.hip)
+struct Adjoint;      // index copies, fixed-variable lists and scratch of the adjoint gradients (mpc.hip)
 
 class MPCSolver {
  public:
@@ -82,6 +83,13 @@ class MPCSolver {
   void warm_start_last(double weight);
   void clear_warm_start();
   void warm_info(int32_t* active, double* weight, int64_t* n_warm_inits) const;
+  // Adjoint gradients (madipm_solver_adjoint / _adjoint_device / _adjoint_info): given
+  // gx = dl/dx* at the point of the last successful solve, the gradients of l with respect to the problem
+  // data the caller asks for (non-null fields of `out`).  Factorises the K2 system at that point once per
+  // solve; further calls on the same point reuse the factor.  device: gx and the outputs are device arrays
+  // produced / consumed on `caller`.  Changes nothing a later initialize / solve / warm_start_last reads.
+  void adjoint(const double* gx, const madipm_qp_gradients& out, bool device, hipStream_t caller);
+  void adjoint_info(int64_t* n_adjoints, int64_t* n_adjoint_factorizations, double* last_residual);
   int64_t n_analyses() const { return n_analyses_; }
   int64_t n_updates() const { return n_updates_; }
   double last_update_s() const { return last_update_s_; }
@@ -187,6 +195,10 @@ class MPCSolver {
   std::unique_ptr<WarmStart> warm_;     // null until a warm point is set
   int64_t n_warm_inits_ = 0;           // initialize() calls that blended
   bool solved_ = false;                // a solve has run (warm_start_last needs its point)
+  std::unique_ptr<Adjoint> adj_;       // null until the first adjoint
+  bool point_ok_ = false;              // the iterate is the end point of a completed solve
+  int64_t n_solves_ = 0;               // completed solves (the adjoint's factor belongs to one of them)
+  int64_t solve_updates_ = 0;          // n_updates_ at the end of the last solve
   int64_t n_analyses_ = 0, n_updates_ = 0;
   double last_update_s_ = 0;
 };

@@ -313,3 +313,50 @@ function solver_warm_info(h::Ptr{Cvoid})
                 h, a, w, k), "madipm_solver_warm_info")
     return (active = a[] != 0, weight = w[], n_warm_inits = k[])
 end
+
+# ---- adjoint gradients (ABI 0.2.7): for a loss l(x*) of the last successful solve's x* alone, given
+# gx = dl/dx* (length nvar), the gradients of l with respect to the data.  madipm_qp_gradients: seven
+# pointers (c, Hvals, Avals, lcon, ucon, lvar, uvar; lengths nvar, nnzh, nnzj, ncon, ncon, nvar, nvar), a null
+# one = not wanted.  K2 only; refused before a solve, after an update no solve followed, on a failed solve.
+struct MadipmQPGradients
+    c::Ptr{Float64}
+    Hvals::Ptr{Float64}
+    Avals::Ptr{Float64}
+    lcon::Ptr{Float64}
+    ucon::Ptr{Float64}
+    lvar::Ptr{Float64}
+    uvar::Ptr{Float64}
+end
+
+# HOST vectors (or nothing); the outputs are written during the call
+function solver_adjoint(h::Ptr{Cvoid}, gx::Vector{Float64}; c=nothing, Hvals=nothing, Avals=nothing, lcon=nothing,
+                        ucon=nothing, lvar=nothing, uvar=nothing)
+    GC.@preserve gx c Hvals Avals lcon ucon lvar uvar begin
+        g = Ref(MadipmQPGradients(_ptr_or_null(c), _ptr_or_null(Hvals), _ptr_or_null(Avals), _ptr_or_null(lcon),
+                                  _ptr_or_null(ucon), _ptr_or_null(lvar), _ptr_or_null(uvar)))
+        check(ccall((:madipm_solver_adjoint, libmadipm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ref{MadipmQPGradients}),
+                    h, pointer(gx), g), "madipm_solver_adjoint")
+    end
+    return
+end
+
+# DEVICE arrays (Ptr{Float64} into device memory, or nothing): gx is read after the work enqueued on `stream`,
+# and work enqueued on `stream` after the call sees the outputs
+function solver_adjoint_device(h::Ptr{Cvoid}, gx::Ptr{Float64}; c=nothing, Hvals=nothing, Avals=nothing,
+                               lcon=nothing, ucon=nothing, lvar=nothing, uvar=nothing, stream::Ptr{Cvoid}=C_NULL)
+    g = Ref(MadipmQPGradients(_dptr_or_null(c), _dptr_or_null(Hvals), _dptr_or_null(Avals), _dptr_or_null(lcon),
+                              _dptr_or_null(ucon), _dptr_or_null(lvar), _dptr_or_null(uvar)))
+    check(ccall((:madipm_solver_adjoint_device, libmadipm), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ref{MadipmQPGradients}, Ptr{Cvoid}), h, gx, g, stream),
+          "madipm_solver_adjoint_device")
+    return
+end
+
+# (n_adjoints, n_adjoint_factorizations, last_residual): successful calls, those that factorised (one per
+# solved point), and the last call's ||g - K a||_inf / max(1, ||g||_inf)
+function solver_adjoint_info(h::Ptr{Cvoid})
+    na, nf, r = Ref{Int64}(0), Ref{Int64}(0), Ref{Float64}(0.0)
+    check(ccall((:madipm_solver_adjoint_info, libmadipm), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Float64}),
+                h, na, nf, r), "madipm_solver_adjoint_info")
+    return (n_adjoints = na[], n_adjoint_factorizations = nf[], last_residual = r[])
+end

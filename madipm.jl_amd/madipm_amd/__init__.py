@@ -22,6 +22,9 @@ def __getattr__(name):
                 "MadIPMError"):  # MadIPMError: what MPCSolver.update raises on a change of classification
         from . import solver
         return getattr(solver, name)
+    if name in ("QPLayer", "QPFunction"):  # the differentiable torch layer over MPCSolver.adjoint_device
+        from . import layer
+        return getattr(layer, name)
     if name == "HIPLDLSolver":
         from .linear_solver import HIPLDLSolver
         return HIPLDLSolver

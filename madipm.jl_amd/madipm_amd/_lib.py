@@ -114,6 +114,18 @@ _sig("madipm_solver_clear_warm_start", C.c_int, [vp])
 _sig("madipm_solver_warm_info", C.c_int, [vp, i32p, f64p, i64p])
 
 
+# adjoint gradients (ABI 0.2.7): host route, device route + stream, counters
+class QPGrad(C.Structure):
+    """madipm_qp_gradients: where each gradient goes; a NULL pointer means "not wanted"."""
+    _fields_ = [("c", f64p), ("Hvals", f64p), ("Avals", f64p), ("lcon", f64p), ("ucon", f64p), ("lvar", f64p),
+                ("uvar", f64p)]
+
+
+_sig("madipm_solver_adjoint", C.c_int, [vp, f64p, C.POINTER(QPGrad)])
+_sig("madipm_solver_adjoint_device", C.c_int, [vp, f64p, C.POINTER(QPGrad), vp])
+_sig("madipm_solver_adjoint_info", C.c_int, [vp, i64p, i64p, f64p])
+
+
 class MadIPMError(RuntimeError):
     pass
 

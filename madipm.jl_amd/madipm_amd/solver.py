@@ -165,24 +165,45 @@ L._sig("madipm_solver_get_solution_device", C.c_int, [L.vp, L.f64p, L.f64p, L.f6
 L._sig("madipm_solver_get_data", C.c_int, [L.vp] + [L.f64p] * 10)
 
 
-def check_device_array(name: str, a, length: int, device=None):
+def check_device_array(name: str, a, length: int, device=None, who: str = "update_device"):
     """The argument check of MPCSolver.update_device, before any library call: `a` must be a torch tensor on
     the GPU (on `device` when given), float64, contiguous, of shape (length,).  TypeError for a numpy array,
-    a CPU tensor or another dtype; ValueError for a non-contiguous tensor or another shape.  Returns `a`."""
+    a CPU tensor or another dtype; ValueError for a non-contiguous tensor or another shape.  Returns `a`.
+    `who` names the calling method in the message."""
     import torch
     if not isinstance(a, torch.Tensor):
-        raise TypeError(f"update_device: {name} must be a torch tensor on the GPU, not {type(a).__name__}")
+        raise TypeError(f"{who}: {name} must be a torch tensor on the GPU, not {type(a).__name__}")
     if a.dtype != torch.float64:
-        raise TypeError(f"update_device: {name} has dtype {a.dtype}, expected torch.float64")
+        raise TypeError(f"{who}: {name} has dtype {a.dtype}, expected torch.float64")
     if not a.is_contiguous():  # a property of the tensor alone: checked before where it lives
-        raise ValueError(f"update_device: {name} is not contiguous")
+        raise ValueError(f"{who}: {name} is not contiguous")
     if a.device.type != "cuda":
-        raise TypeError(f"update_device: {name} is on {a.device}, expected a GPU tensor")
+        raise TypeError(f"{who}: {name} is on {a.device}, expected a GPU tensor")
     if device is not None and a.device != device:
-        raise TypeError(f"update_device: {name} is on {a.device}, the solver is on {device}")
+        raise TypeError(f"{who}: {name} is on {a.device}, the solver is on {device}")
     if tuple(a.shape) != (int(length),):
-        raise ValueError(f"update_device: {name} has shape {tuple(a.shape)}, expected ({int(length)},)")
+        raise ValueError(f"{who}: {name} has shape {tuple(a.shape)}, expected ({int(length)},)")
     return a
+
+
+ADJOINT_NAMES = ("c", "Hvals", "Avals", "lcon", "ucon", "lvar", "uvar")
+
+
+def check_adjoint_want(want) -> tuple:
+    """The `want` argument of MPCSolver.adjoint / adjoint_device: None (all seven) or an iterable of names out
+    of ADJOINT_NAMES.  Returns the names in ADJOINT_NAMES order; ValueError for an unknown name or an empty
+    selection, TypeError for a bare string."""
+    if want is None:
+        return ADJOINT_NAMES
+    if isinstance(want, str):
+        raise TypeError(f"adjoint: want must be a collection of names, not the string {want!r}")
+    want = list(want)
+    unknown = [k for k in want if k not in ADJOINT_NAMES]
+    if unknown:
+        raise ValueError(f"adjoint: unknown name(s) {unknown} in want; the gradients are {list(ADJOINT_NAMES)}")
+    if not want:
+        raise ValueError("adjoint: want is empty")
+    return tuple(k for k in ADJOINT_NAMES if k in want)
 
 
 class RCCLComm:
@@ -648,6 +669,75 @@ class MPCSolver:
         a, w, k = C.c_int32(), C.c_double(), C.c_int64()
         L.check(L.lib.madipm_solver_warm_info(self.h, C.byref(a), C.byref(w), C.byref(k)), "warm_info")
         return {"active": bool(a.value), "weight": float(w.value), "n_warm_inits": int(k.value)}
+
+    # ------------------------------------------------------------ adjoint gradients
+    def _adjoint_sizes(self) -> dict:
+        qp = self.qp
+        return {"c": qp.nvar, "Hvals": qp.nnzh, "Avals": qp.nnzj, "lcon": qp.ncon, "ucon": qp.ncon,
+                "lvar": qp.nvar, "uvar": qp.nvar}
+
+    def _adjoint_prepare(self, names):
+        # Avals and Hvals read the index arrays and raw values prepare_update keeps, and so does lvar when a
+        # variable is fixed; the other gradients cost nothing per entry of A
+        if "Avals" in names or "Hvals" in names or ("lvar" in names and np.any(self.qp.lvar == self.qp.uvar)):
+            self._prepare_update()
+
+    def adjoint(self, gx, want=None) -> dict:
+        """Gradients of a loss l(x*) with respect to the problem data, given gx = dl/dx* (length nvar) at the
+        optimum the last solve() returned: a dict of numpy arrays over `want`, a subset of ADJOINT_NAMES
+        (None: all seven), Hvals / Avals in the creation-time COO order.  An infinite bound gets 0; a fixed
+        variable and an equality row carry their whole derivative in lvar / lcon (uvar / ucon are 0 there).
+        The first call after a solve factorises the KKT matrix of the optimum once; further calls on the same
+        point reuse the factor.  The solver's state is untouched: the next solve() is what it would have been.
+        MadIPMError when the last solve did not succeed, when an update or initialize ran since, for the
+        K2.5 / normal-equations formulations and for a solver created with `comm`."""
+        names = check_adjoint_want(want)
+        gx = np.array(gx, dtype=np.float64, order="C", ndmin=1)
+        if gx.shape != (self.qp.nvar,):
+            raise ValueError(f"adjoint: gx has shape {gx.shape}, expected ({self.qp.nvar},)")
+        size = self._adjoint_sizes()
+        buf = {k: np.empty(max(size[k], 1)) for k in names}  # an empty output still has a non-null address
+        g = L.QPGrad()
+        for k in names:
+            setattr(g, k, L.ptr(buf[k], C.c_double))
+        self._adjoint_prepare(names)
+        gxp = L.ptr(gx if gx.size else np.zeros(1), C.c_double)
+        L.check(L.lib.madipm_solver_adjoint(self.h, gxp, C.byref(g)), "adjoint")
+        return {k: buf[k][:size[k]] for k in names}
+
+    def adjoint_device(self, gx, want=None, stream=None) -> dict:
+        """adjoint() from and into torch tensors on the solver's GPU (gx: float64, contiguous, shape (nvar,)),
+        without a copy through the host.  `stream` is the torch.cuda.Stream gx was produced on (None: the
+        current stream): gx is read after the work enqueued on it, and work enqueued on it after the call
+        sees the returned tensors.  The arguments are checked before any library call."""
+        names = check_adjoint_want(want)
+        check_device_array("gx", gx, self.qp.nvar, self._device, who="adjoint_device")
+        import torch
+        if stream is not None and not isinstance(stream, torch.cuda.Stream):
+            raise TypeError(f"adjoint_device: stream must be a torch.cuda.Stream, not {type(stream).__name__}")
+        if self._device is None:
+            self._device = torch.device("cuda", torch.cuda.current_device())
+            check_device_array("gx", gx, self.qp.nvar, self._device, who="adjoint_device")
+        st = stream if stream is not None else torch.cuda.current_stream(self._device)
+        size = self._adjoint_sizes()
+        with torch.cuda.stream(st):
+            buf = {k: torch.empty(max(size[k], 1), dtype=torch.float64, device=self._device) for k in names}
+            gxd = gx if gx.numel() else torch.zeros(1, dtype=torch.float64, device=self._device)
+        g = L.QPGrad()
+        for k in names:
+            setattr(g, k, C.cast(buf[k].data_ptr(), L.f64p))
+        self._adjoint_prepare(names)
+        L.check(L.lib.madipm_solver_adjoint_device(self.h, C.cast(gxd.data_ptr(), L.f64p), C.byref(g),
+                                                   L.vp(st.cuda_stream)), "adjoint_device")
+        return {k: buf[k][:size[k]] for k in names}
+
+    def adjoint_info(self) -> dict:
+        """n_adjoints: successful adjoint calls; n_adjoint_factorizations: those that factorised (one per
+        solved point); last_residual: the last call's ||g - K a||_inf / max(1, ||g||_inf)."""
+        na, nf, r = C.c_int64(), C.c_int64(), C.c_double()
+        L.check(L.lib.madipm_solver_adjoint_info(self.h, C.byref(na), C.byref(nf), C.byref(r)), "adjoint_info")
+        return {"n_adjoints": int(na.value), "n_adjoint_factorizations": int(nf.value),
+                "last_residual": float(r.value)}
 
     def counters(self) -> dict:
         """n_analyses: linear-solver analyses run for this solver (stays 1); n_updates: successful update()

@@ -20,7 +20,13 @@ solve with the same fresh solver.  Ends with one JSON line.
 warm_start_last(WEIGHT) after each solve (the previous solution, taken before the update), then update_device
 + solve + solution_device: warm_iters and warm_device_loop_s beside iters and device_loop_s, warm_status,
 and warm_obj_rel, the largest relative difference of a warm solve's objective from the cold solve's on the
-same data.  Without the option nothing of it runs and the output is as before."""
+same data.  Without the option nothing of it runs and the output is as before.
+
+--adjoint adds, on the same sequence of data and in the same process, one adjoint per re-solve: after each
+update_device + solve, adjoint_device of a seeded gx for all seven gradients, stream synchronised:
+adjoint_s (the first adjoint on a point: the factorisation of its KKT matrix + one solve + the gradient
+kernels) beside adjoint_solve_s (the solve before it) and adjoint_again_s (a second gx on the same point,
+which reuses the factor), adjoint_residual (the largest last_residual) and adjoint_status."""
 import dataclasses
 import json
 import os
@@ -50,7 +56,7 @@ def perturb(qp, rng):
                 lvar=qp.lvar * fv, uvar=qp.uvar * fv, lcon=qp.lcon * fc, ucon=qp.ucon * fc)
 
 
-def run(name, warm=None):
+def run(name, warm=None, adjoint=False):
     qp, desc = bench.build_problem(name)
     opts = bench.solver_opts()
     MPCSolver(qp, **opts)                      # the first construction of a process pays one-off set-up
@@ -136,6 +142,40 @@ def run(name, warm=None):
         wres = {"warm_weight": warm, "warm_iters": wits, "warm_device_loop_s": statistics.median(wloop),
                 "warm_status": sorted(wstat), "warm_obj_rel": wrel, "n_warm_inits": s.warm_info()["n_warm_inits"]}
         c = s.counters()
+    if adjoint:   # the same data again: one adjoint (all seven gradients) per re-solve
+        rng = np.random.default_rng(0)
+        perturb(qp, rng)
+        grng = np.random.default_rng(1)
+        asol, afirst, aagain, astat, ares = [], [], [], set(), 0.0
+        for rep in range(WARMUP + REPS):
+            dnew = {k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()}
+            gx = torch.as_tensor(grng.standard_normal(qp.nvar), device="cuda")
+            gx2 = torch.as_tensor(grng.standard_normal(qp.nvar), device="cuda")
+            s.update_device(**dnew)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            ast = s.solve(fetch_solution=False)
+            t_solve = time.perf_counter() - t
+            astat.add(ast.status)
+            if ast.status != 1:
+                continue
+            t = time.perf_counter()
+            s.adjoint_device(gx)
+            torch.cuda.current_stream().synchronize()
+            t_first = time.perf_counter() - t
+            t = time.perf_counter()
+            s.adjoint_device(gx2)
+            torch.cuda.current_stream().synchronize()
+            t_again = time.perf_counter() - t
+            ares = max(ares, s.adjoint_info()["last_residual"])
+            if rep >= WARMUP:
+                asol.append(t_solve)
+                afirst.append(t_first)
+                aagain.append(t_again)
+        med = lambda v: statistics.median(v) if v else float("nan")  # noqa: E731
+        wres.update({"adjoint_s": med(afirst), "adjoint_again_s": med(aagain), "adjoint_solve_s": med(asol),
+                     "adjoint_residual": ares, "adjoint_status": sorted(astat), **s.adjoint_info()})
+        c = s.counters()
     update_s, solve_s = statistics.median(upd), statistics.median(sol)
     return {**wres, "instance": name, "description": desc, "nvar": qp.nvar, "ncon": qp.ncon, "nnzj": qp.nnzj, "nnzh": qp.nnzh,
             "construct_s": construct_s, "prepare_update_s": prepare_update_s, "update_s": update_s,
@@ -165,8 +205,11 @@ def main():
         k = args.index("--warm")
         warm = float(args[k + 1])
         del args[k:k + 2]
+    adjoint = "--adjoint" in args
+    if adjoint:
+        args.remove("--adjoint")
     for name in args or ["ex10", "supportcase10"]:
-        r = run(name, warm)
+        r = run(name, warm, adjoint)
         print(f"{name}: construct_s {r['construct_s']:.4f}  prepare_update_s {r['prepare_update_s']:.4f}  "
               f"update_s {r['update_s']:.5f}  solve_s {r['solve_s']:.4f}  ->  update + solve "
               f"{r['update_plus_solve_s']:.4f} s against construct + solve {r['construct_plus_solve_s']:.4f} s "
@@ -179,6 +222,10 @@ def main():
                   f"{statistics.median(r['iters'])})  warm_start_last + update_device + solve + solution_device "
                   f"{r['warm_device_loop_s']:.4f} s (cold {r['device_loop_s']:.4f} s), status {r['warm_status']}, "
                   f"objective within {r['warm_obj_rel']:.1e} of the cold solve's", flush=True)
+        if adjoint:
+            print(f"{name}: adjoint (seven gradients): {r['adjoint_s']:.4f} s after a solve of "
+                  f"{r['adjoint_solve_s']:.4f} s; a second gx on the same point {r['adjoint_again_s']:.4f} s; "
+                  f"residual <= {r['adjoint_residual']:.1e}, status {r['adjoint_status']}", flush=True)
         out.append(r)
     print(json.dumps({"resolve_bench": out, "warmup": WARMUP, "reps": REPS, "rel_noise": REL}))
 
