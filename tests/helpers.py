@@ -744,3 +744,245 @@ def signed_diagonal(n=20001, seed=7):
     Lw = sp.diags(d).tocsc()
     Lw.sort_indices()
     return Lw, d
+
+
+# ---------------------------------------------------------------- MPC reduction regimes
+# (test_step_gpu.py, test_mpc_regimes_gpu.py; pinned on the sources and the oracle in
+# test_regime_helpers_cpu.py)
+# The launch constants of csrc/mpc.hip and csrc/mpc.hpp that decide which path a reduction takes: the
+# regime tests derive every boundary from these and test_regime_helpers_cpu.py fails when a source changes.
+MPC_CONSTANTS = {"NT": 256, "FT1": 1024, "MAXB": 2048, "FG": 16, "FT": 128, "maxb_": 2048}
+MPC_NT, MPC_FT1, MPC_MAXB = MPC_CONSTANTS["NT"], MPC_CONSTANTS["FT1"], MPC_CONSTANTS["maxb_"]
+
+
+def mpc_blocks(n):
+    """MPCSolver::blocks: the producer blocks of a flat kernel over n elements."""
+    return max(1, min(MPC_MAXB, -(-int(n) // MPC_NT)))
+
+
+def mpc_spmv_blocks(rows, G):
+    """MPCSolver::spmv_blocks: the producer blocks of an SpMV-shaped kernel, one row per G lanes."""
+    return mpc_blocks(int(rows) * G)
+
+
+def mpc_regime(n, G=1):
+    """(producer blocks, finaliser 'one' | 'two', strided) of a kernel over n elements, G lanes each:
+    k_final's one-workgroup instance up to FT1 partial blocks, the two-level one past it; the producer's
+    loop strides once n G exceeds MAXB NT threads."""
+    nb = mpc_blocks(int(n) * G)
+    return nb, ("one" if nb <= MPC_FT1 else "two"), int(n) * G > MPC_MAXB * MPC_NT
+
+
+def regime_hot(m, n_ineq, where, boundary=None):
+    """The planted positions of regime_problem for a placement:
+      'first'     row 0 (a range row whenever n_ineq > 0: no coordinate can be planted beside it);
+      'last'      row m - 1, the last of n_ + m_, and its second column, the last lower-bounded column;
+      'boundary'  flat element `boundary` of [0, n_ + m_) — the first element of the block or of the
+                  stride trip under test, clamped to the last element — as a constraint row (an element
+                  below n_ wraps into the rows) and, as a position of ind_lb, as a coordinate."""
+    n_ = 2 * m + n_ineq
+    if where == "first":
+        return dict(row=0, coord=None if n_ineq > 0 else 0)
+    if where == "last":
+        return dict(row=m - 1, coord=-1)
+    assert where == "boundary" and boundary is not None
+    e = min(int(boundary), n_ + m - 1)
+    return dict(row=e - n_ if e >= n_ else e % m, coord=e)
+
+
+def regime_problem(m, n_ineq, seed, hess=False, hot=None):
+    """A separable LP / QP of any size for the reduction-regime tests: nx = 2 m columns, row i couples
+    columns 2 i and 2 i + 1 only (two entries of magnitude in [0.5, 2], random sign); the first n_ineq rows
+    are ranges (ucon = lcon + 1), the others equalities; no fixed and no free variable, so the solver has
+    n_ + m_ = 3 m + n_ineq rows.  Bounds: lower-only (50 %), both (40 %), upper-only (10 %, with c < 0
+    there), so nlb != nub and ind_lb, ind_ub are no identity.  lcon = A xint (ranges: a band around it)
+    for a strictly interior xint, and c = A^T y0 + zl0 - zu0 (- H xint) with zl0, zu0 >= 0 on their
+    bounds: feasible and bounded.  The start x0 = xint + 0.02 U(-1, 1).  hess=True: H = a positive
+    diagonal plus the off-diagonal of each pair (2 i, 2 i + 1), diagonally dominant: still separable.
+
+    hot = dict(row=r, coord=t or None) (regime_hot) plants the extreme element of the max-type reductions
+    through the start alone.  The reference's first Newton step uses the constraint residual c of x0
+    (initialize! evaluates the model before init_starting_point! moves x), so a column started away from
+    xint is moved by about that distance twice: by the starting point's projection and by the step.
+      coord  the lower-bounded column j of an equality row nearest to position t of ind_lb (t < 0: from the
+             end of the columns): lower-only, 0.5 above its bound, entry +-2 beside a partner entry -+0.5
+             whose sign moves the partner away from its bound, started 4 above xint_j (|c| = 8): the only
+             primal ratio below 1 at iteration 1.  Measured on the oracle, a larger offset is undone by the
+             Mehrotra corrector, and in a range row the projection pushes the slack out of its band (one
+             wide), whose repair (delta_x) lifts every coordinate off its bound: no column of a range row
+             and no slack can be planted this way, so positions there move to the next equality row.
+      row    |c_r| of x0 is the largest by a factor >= 4.  An equality row: the coordinate's row when t
+             lies in it; else both columns are lower-only, 50 above their bound, entries +-2 of one sign,
+             started 40 below xint (|c_r| = 160; they move away from their bounds).  A range row (no
+             coordinate then): one column started 4 above xint with entry +-2, |c_r| >= 6.8.
+    qp.hot = dict(row, coord: position in ind_lb or None, col: that column).
+    (The dual residual after init_starting_point! is -(1 + delta_s + delta_s2) on every lower-only
+    column, the same with + on every upper-only one and 0 on the boxed columns and slacks, and an LP's
+    stays a multiple of that: it has no unique maximum to plant; test_regime_helpers_cpu.py pins this.)"""
+    from madipm_amd.qp import QuadraticModel
+    rng = np.random.default_rng(seed)
+    nx = 2 * m
+    a = rng.uniform(0.5, 2.0, (m, 2)) * rng.choice([-1.0, 1.0], (m, 2))
+    u = rng.random(nx)
+    up_only, both = u < 0.1, (u >= 0.1) & (u < 0.5)
+    lvar = rng.uniform(-1.0, 1.0, nx)
+    uvar = np.where(both, lvar + rng.uniform(1.0, 5.0, nx), np.inf)
+    uvar[up_only] = lvar[up_only]
+    lvar[up_only] = -np.inf
+    pos = rng.uniform(0.2, 0.8, nx)
+    gap = rng.uniform(0.5, 2.0, nx)
+    noise = 0.02 * rng.uniform(-1.0, 1.0, nx)
+    start = {}                                          # column -> x0 - xint of the plants
+    if hot is not None:
+        r, t = int(hot["row"]), hot["coord"]
+        assert 0 <= r < m
+        for j in (2 * r, 2 * r + 1):
+            lvar[j], uvar[j], up_only[j], both[j] = 0.0, np.inf, False, False
+        q = j = None
+        if t is not None:
+            assert r >= n_ineq, "no coordinate can be planted beside a planted range row"
+            lb_cols = np.flatnonzero(np.isfinite(lvar))     # ind_lb: these columns, then the slacks
+            t = min(int(t), len(lb_cols) - 1) if t >= 0 else max(0, len(lb_cols) + int(t))
+            ok = np.flatnonzero(lb_cols // 2 >= n_ineq)     # positions in equality rows
+            t = int(ok[min(np.searchsorted(ok, t), len(ok) - 1)])
+            j = int(lb_cols[t])
+            p, q = j ^ 1, j // 2
+            uvar[j], both[j], gap[j] = np.inf, False, 0.5   # lower-only; lb_cols keeps its members
+            if np.isfinite(lvar[p]):
+                uvar[p], both[p] = np.inf, False
+            sj = np.sign(a[q, j & 1])
+            a[q, j & 1] = 2.0 * sj
+            a[q, p & 1] = (0.5 if up_only[p] else -0.5) * sj   # the partner moves away from its one bound
+            start[j] = 4.0
+        if r < n_ineq:
+            a[r, 0] = 2.0 * np.sign(a[r, 0])
+            start[2 * r] = 4.0
+        elif q != r:
+            a[r] = 2.0 * np.sign(a[r, 0])
+            gap[2 * r] = gap[2 * r + 1] = 50.0
+            start[2 * r] = start[2 * r + 1] = -40.0
+        hot = dict(row=r, coord=t, col=j)
+    with np.errstate(invalid="ignore"):
+        xint = np.where(both, lvar + pos * (uvar - lvar), np.where(up_only, uvar - gap, lvar + gap))
+    b = a[:, 0] * xint[0::2] + a[:, 1] * xint[1::2]
+    lcon, ucon = b.copy(), b.copy()
+    lcon[:n_ineq] = b[:n_ineq] - rng.uniform(0.2, 0.8, n_ineq)
+    ucon[:n_ineq] = lcon[:n_ineq] + 1.0
+    y0 = rng.uniform(-1.0, 1.0, m)
+    aty = (a * y0[:, None]).ravel()
+    zl0 = np.where(np.isfinite(lvar), rng.uniform(0.0, 1.0, nx), 0.0)
+    zu0 = np.where(both, rng.uniform(0.0, 1.0, nx), 0.0)
+    zu0[up_only] = np.abs(aty[up_only]) + rng.uniform(0.5, 1.5, int(up_only.sum()))
+    c = aty + zl0 - zu0
+    assert np.all(c[up_only] < 0.0)
+    Hr = Hc = Hv = []
+    if hess:
+        hd = rng.uniform(0.5, 2.0, nx)
+        ho = rng.uniform(-0.4, 0.4, m)
+        Hr = np.r_[np.arange(nx), np.arange(1, nx, 2)]
+        Hc = np.r_[np.arange(nx), np.arange(0, nx, 2)]
+        Hv = np.r_[hd, ho]
+        hx = hd * xint
+        hx[0::2] += ho * xint[1::2]
+        hx[1::2] += ho * xint[0::2]
+        c = c - hx
+        c[up_only] = np.minimum(c[up_only], -0.5)
+    x0 = xint + noise
+    for j, d in start.items():
+        x0[j] = xint[j] + d
+    qp = QuadraticModel(c=c, Hrows=Hr, Hcols=Hc, Hvals=Hv, Arows=np.repeat(np.arange(m), 2), Acols=np.arange(nx),
+                        Avals=a.ravel(), lcon=lcon, ucon=ucon, lvar=lvar, uvar=uvar, x0=x0,
+                        name=f"regime_{m}_{n_ineq}_s{seed}_{'qp' if hess else 'lp'}")
+    qp.hot = hot
+    return qp
+
+
+def regime_bounds(qp):
+    """(rows, nlb, nub) of the solver on a regime problem: n_ + m_ and the bounded coordinates, slacks
+    included (a range row's slack has both bounds)."""
+    ns = int(np.sum(qp.lcon != qp.ucon))
+    return (qp.nvar + ns + qp.ncon, int(np.sum(np.isfinite(qp.lvar))) + ns, int(np.sum(np.isfinite(qp.uvar))) + ns)
+
+
+def regime_name(m, n_ineq, hess, where, boundary=0):
+    """The cache key of a regime problem (seed = m + n_ineq): test_mpc_point_gpu._problem builds it."""
+    return f"regime:{m}:{n_ineq}:{int(hess)}:{where}:{boundary}"
+
+
+def regime_case(name):
+    tag, m, n_ineq, hess, where, boundary = name.split(":")
+    assert tag == "regime"
+    m, n_ineq = int(m), int(n_ineq)
+    return regime_problem(m, n_ineq, m + n_ineq, bool(int(hess)), regime_hot(m, n_ineq, where, int(boundary)))
+
+
+# SpMV-shaped kernels at G = 64 (NT / 64 = 4 rows per block): (m, n_ineq) -> rows = 3 m + n_ineq, with the
+# finaliser path and whether the row loop strides; `boundary` is the first row element of block FT1
+# (4 FT1) before the cap and of the second stride trip (4 MAXB) past it
+REGIME_G = 64
+REGIME_G64_SIZES = {(1300, 196): (4096, "one", False), (1300, 197): (4097, "two", False),
+                    (2600, 392): (8192, "two", False), (2600, 393): (8193, "two", True),
+                    (6000, 2001): (20001, "two", True)}
+REGIME_PLACES = ("first", "last", "boundary")
+REGIME_KS = (0, 1, 3)
+
+
+def regime_g64_boundary(rows):
+    per = MPC_NT // REGIME_G
+    return per * MPC_MAXB if rows > per * MPC_MAXB else per * MPC_FT1
+
+
+def regime_g64_cases():
+    """[(problem name, kkt, variant)] of the G = 64 sweep: per size the LP under K2, K2.5 and the normal
+    equations and the QP under K2 and K2.5 (default variant), MehrotraAdaptiveStep and max_ncorr = 3 on the
+    4097- and 8193-row LPs under K2; the placement of the plants cycles over the cases."""
+    out = []
+    for si, ((m, ni), (rows, _, _)) in enumerate(REGIME_G64_SIZES.items()):
+        combos = [(False, "K2", "default"), (False, "K25", "default"), (False, "normal", "default"),
+                  (True, "K2", "default"), (True, "K25", "default")]
+        if rows in (4097, 8193):
+            combos += [(False, "K2", "mehrotra"), (False, "K2", "ncorr3")]
+        for ci, (hess, kkt, variant) in enumerate(combos):
+            where = REGIME_PLACES[(si + ci) % 3]
+            out.append((regime_name(m, ni, hess, where, regime_g64_boundary(rows)), kkt, variant))
+    return out
+
+
+# flat kernels at the heuristic's own G: (m, n_ineq) -> (rows, finaliser, strided, placement, boundary, ks)
+REGIME_FLAT_SIZES = {(80000, 22144): (262144, "one", False, "last", 0, (2,)),
+                     (80000, 22145): (262145, "two", False, "last", 0, (2,)),
+                     (160000, 44588): (524588, "two", True, "boundary", MPC_MAXB * MPC_NT, (0, 2))}
+
+
+def regime_flat_cases():
+    return [(regime_name(m, ni, False, where, b), ks) for (m, ni), (_, _, _, where, b, ks) in REGIME_FLAT_SIZES.items()]
+
+
+def regime_launches(qp, G):
+    """The producer block counts of one MPC iteration on a regime problem, as (blocks, finaliser,
+    strided) per kernel family: 'flat' (k_rhs, k_term, k_apply, ... over n_ + m_), 'spmv' (k_residual,
+    k_eval, the normal-equation kernels: one row per G lanes) and 'step' (k_alpha, k_mu, the step-test
+    blocks of k_residual over max(nlb, nub))."""
+    rows, nlb, nub = regime_bounds(qp)
+    return dict(flat=mpc_regime(rows), spmv=mpc_regime(rows, G), step=mpc_regime(max(nlb, nub)))
+
+
+# the step test alone (madipm_update_step): max(nlb, nub) -> (blocks, finaliser, strided)
+REGIME_STEP_SIZES = {262144: (1024, "one", False), 262145: (1025, "two", False), 524288: (2048, "two", False),
+                     524289: (2048, "two", True), 1310797: (2048, "two", True)}
+
+
+def regime_step_ties(n):
+    """The tied index pairs of the step test at max(nlb, nub) = n, each of which must yield its last
+    index: across workgroups 0 and 1 of the two-level finaliser (FT blocks each), across blocks FT1 - 1
+    and FT1, the first and the last element, and past the cap one thread's two trips and the pair around
+    the first trip's end (the later index sits in block 0, which the finaliser combines first)."""
+    wg = MPC_CONSTANTS["FT"] * MPC_NT
+    ties = [(wg - 1, wg), (0, n - 1), (MPC_NT - 1, MPC_NT)]      # the last: blocks 0 | 1
+    if n > MPC_FT1 * MPC_NT:
+        ties.append((MPC_FT1 * MPC_NT - 1, MPC_FT1 * MPC_NT))
+    trip = MPC_MAXB * MPC_NT
+    if n > trip:
+        t = min(5, n - trip - 1)
+        ties += [(t, t + trip), (trip - 1, trip)]
+    return list(dict.fromkeys(ties))      # at n = MAXB NT + 1 the two-trip pair is (0, n - 1)
