@@ -22,44 +22,24 @@
 #include <thread>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <limits>
 #include <map>
 
 #include "mpc.hpp"
+#include "qp_model.hpp"
 
 namespace madipm {
 
-struct QPHost {
-  int nx = 0, m = 0, n = 0, ns = 0;
-  std::vector<double> c, lvar, uvar, lcon, ucon, x0, y0, Hv;
-  std::vector<int32_t> Hr, Hc;
-  // A's COO: the caller's arrays, read during construction only (no host copy: 8 GB for the dense QP)
-  const int32_t* Ar = nullptr;
-  const int32_t* Ac = nullptr;
-  const double* Av = nullptr;
-  int64_t nnzA = 0;
-  double c0 = 0, sgn = 1;
-  bool minimize = true;
-  std::vector<int32_t> ind_ineq, ind_fixed, ind_lb, ind_ub;
-  std::vector<uint8_t> fixed;
-  bool has_ineq = false;
-  std::vector<double> con_scale;
-  double obj_scale = 1;
-  std::vector<double> x, xl, xu, rhs, y;
-  bool anyfix = false;  // a fixed structural variable: J is built from a filtered COO, cfix is non-zero
-};
+// the model's index pairs are uploaded as the kernels' int2
+static_assert(sizeof(I2) == sizeof(int2) && alignof(I2) <= alignof(int2) && offsetof(I2, x) == offsetof(int2, x) &&
+                  offsetof(I2, y) == offsetof(int2, y),
+              "qp_model.hpp's I2 must have int2's layout");
+static const int2* as_int2(const std::vector<I2>& v) { return reinterpret_cast<const int2*>(v.data()); }
 
-// What numeric_host hands to the device besides QPHost's own vectors
-struct HostNumeric {
-  std::vector<double> gfix, cfix, cs;
-};
-
-// The refresh plan (prepare_update).  Every destination entry of a value array owns a list of COO
-// sources, [sp[q], sp[q + 1]) into src, in ascending input index: csr_from_coo's merge order.  J's lists
-// are kept once, in J^T's entry order (whose column-index array already names each entry's constraint
-// row, i.e. its con_scale); J's own values are gathered from J^T's through j2jt.  32-bit throughout.
+// The refresh plan on the device (prepare_update; the host arrays are qp_model.hpp's RefreshPlan)
 struct UpdatePlan {
   std::vector<int32_t> Ar, Ac;  // host copy of A's COO for the host passes (slack start, row maxima, cfix)
   std::vector<double> Av;
@@ -174,8 +154,6 @@ struct DV {
   double* Cx;               //   values of C = A Sigma^{-1} A^T (lower CSC)
   int64_t nnzC;
 };
-
-enum { KKT_K2 = 0, KKT_K25 = 1, KKT_NORMAL = 2 };
 
 enum { OP_SUM = 0, OP_MAX = 1, OP_MIN = 2 };
 
@@ -1500,128 +1478,6 @@ int MPCSolver::blocks(int64_t n) const {
 // of a dependent chain of rows (the row loads are latency-bound)
 int MPCSolver::spmv_blocks(int64_t rows) const { return blocks(rows * spmv_g_); }
 
-// ---- host construction helpers, threaded for the dense-QP config (5e8 entries in A): every O(nnz) pass
-// runs on analysis_threads() host threads over contiguous input chunks, with per-thread counts and
-// offsets in thread order, so the result is the one-thread result bit for bit (r3: 38 s of analysis_s
-// on the box, mostly single-threaded passes and growing vectors over the 5e8 entries).
-template <class F>
-static void par_range(int64_t n, F f, int64_t grain = (int64_t)1 << 20) {
-  const int T = (int)std::min<int64_t>(analysis_threads(), std::max<int64_t>(1, n / grain));
-  if (T <= 1) {
-    f(0, (int64_t)0, n);
-    return;
-  }
-  std::vector<std::thread> th;
-  for (int t = 0; t < T; ++t) th.emplace_back(f, t, n * t / T, n * (t + 1) / T);
-  for (auto& x : th) x.join();
-}
-static int par_threads(int64_t n, int64_t grain = (int64_t)1 << 20) {
-  return (int)std::min<int64_t>(analysis_threads(), std::max<int64_t>(1, n / grain));
-}
-
-// CSR (sorted by (row, col), duplicates summed in input order) of the COO (r, c, v): a stable counting
-// sort by row — per-thread row counts over input chunks, offsets in thread order — then each row's
-// run sorted by column only when it is not already (O(nnz) for the usual column- or row-major input;
-// a comparison sort of 1e9 dense-QP entries took minutes) and duplicates merged
-// entry k of the COO: row R(k), column C(k), value V(k) (accessors: the scaled Jacobian is read
-// straight from the caller's A, no COO copy); the CSR arrays are filled in full by the threads
-template <class R, class C, class V>
-static void csr_from_coo(int nrow, int64_t nnz, R r, C c, V v, std::vector<int64_t>& rp, hvec<int32_t>& ci,
-                         hvec<double>& cv) {
-  // per-thread row counts cost T (nrow + 1) int64: bound T so that they stay within the entries' own
-  // size (a tall sparse matrix with millions of rows would otherwise take gigabytes of scratch)
-  const int T = (int)std::max<int64_t>(1, std::min<int64_t>(par_threads(nnz), nnz / (4 * ((int64_t)nrow + 1))));
-  std::vector<std::vector<int64_t>> cnt(T, std::vector<int64_t>(nrow + 1, 0));
-  auto chunk = [&](int t) { return std::make_pair(nnz * t / T, nnz * (t + 1) / T); };
-  {
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t)
-      th.emplace_back([&, t] {
-        auto [k0, k1] = chunk(t);
-        int64_t* cn = cnt[t].data();
-        for (int64_t k = k0; k < k1; ++k) cn[r(k)]++;
-      });
-    for (auto& x : th) x.join();
-  }
-  std::vector<int64_t> start(nrow + 1, 0);
-  for (int i = 0; i < nrow; ++i) {
-    int64_t acc = start[i];
-    for (int t = 0; t < T; ++t) {
-      const int64_t c_ = cnt[t][i];
-      cnt[t][i] = acc;  // this thread's first slot in row i
-      acc += c_;
-    }
-    start[i + 1] = acc;
-  }
-  hvec<int32_t> tc(nnz);
-  hvec<double> tv(nnz);
-  {
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t)
-      th.emplace_back([&, t] {
-        auto [k0, k1] = chunk(t);
-        int64_t* off = cnt[t].data();
-        for (int64_t k = k0; k < k1; ++k) {
-          const int64_t q = off[r(k)]++;
-          tc[q] = c(k);
-          tv[q] = v(k);
-        }
-      });
-    for (auto& x : th) x.join();
-  }
-  // per row: sort if needed (stable: duplicates keep input order), count the distinct columns
-  std::vector<int64_t> uniq(nrow + 1, 0);
-  par_range(nrow, [&](int, int64_t i0, int64_t i1) {
-    std::vector<std::pair<int32_t, double>> buf;
-    for (int64_t i = i0; i < i1; ++i) {
-      const int64_t b = start[i], e = start[i + 1];
-      bool sorted = true;
-      for (int64_t q = b; q + 1 < e && sorted; ++q) sorted = tc[q] <= tc[q + 1];
-      if (!sorted) {
-        buf.clear();
-        for (int64_t q = b; q < e; ++q) buf.emplace_back(tc[q], tv[q]);
-        std::stable_sort(buf.begin(), buf.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-        for (int64_t q = b; q < e; ++q) tc[q] = buf[q - b].first, tv[q] = buf[q - b].second;
-      }
-      int64_t u = 0;
-      for (int64_t q = b; q < e; ++q) u += (q == b || tc[q] != tc[q - 1]);
-      uniq[i + 1] = u;
-    }
-  }, 4096);
-  for (int i = 0; i < nrow; ++i) uniq[i + 1] += uniq[i];
-  if (uniq[nrow] == nnz) {  // no duplicates: the sorted runs are the CSR
-    rp = std::move(start);
-    ci = std::move(tc);
-    cv = std::move(tv);
-    return;
-  }
-  rp = uniq;
-  ci.resize(uniq[nrow]);
-  cv.resize(uniq[nrow]);
-  par_range(nrow, [&](int, int64_t i0, int64_t i1) {
-    for (int64_t i = i0; i < i1; ++i) {
-      int64_t o = rp[i] - 1;
-      for (int64_t q = start[i]; q < start[i + 1]; ++q) {
-        if (q == start[i] || tc[q] != tc[q - 1]) {
-          ++o;
-          ci[o] = tc[q];
-          cv[o] = tv[q];
-        } else {
-          cv[o] += tv[q];
-        }
-      }
-    }
-  }, 4096);
-}
-static void csr_from_coo(int nrow, const std::vector<int32_t>& r, const std::vector<int32_t>& c,
-                         const std::vector<double>& v, std::vector<int64_t>& rp, hvec<int32_t>& ci, hvec<double>& cv) {
-  const int32_t *rr = r.data(), *cc = c.data();
-  const double* vv = v.data();
-  csr_from_coo(
-      nrow, (int64_t)r.size(), [=](int64_t k) { return rr[k]; }, [=](int64_t k) { return cc[k]; },
-      [=](int64_t k) { return vv[k]; }, rp, ci, cv);
-}
-
 MPCSolver::MPCSolver(const madipm_qp& qp, const madipm_options& opt, Comm* comm) : opt_(opt), comm_(comm) {
   const double t0 = now();
   PhaseClock clk("MPCSolver");
@@ -1654,222 +1510,22 @@ std::unique_ptr<LinSolver> MPCSolver::make_linsolver(int n, const int64_t* cp, c
   return std::make_unique<LDLSolver>(n, cp, ri, so, opt_.ldl.pivot_tol);
 }
 
-// xl / xu of [x; s] as given: the variables' bounds, then the ranged rows' (before relaxation and scaling)
-static void raw_bounds(QPHost& P) {
-  const int nx = P.nx;
-  P.xl.resize(P.n);
-  P.xu.resize(P.n);
-  for (int i = 0; i < nx; ++i) {
-    P.xl[i] = P.lvar[i];
-    P.xu[i] = P.uvar[i];
-  }
-  for (int k = 0; k < P.ns; ++k) {
-    P.xl[nx + k] = P.lcon[P.ind_ineq[k]];
-    P.xu[nx + k] = P.ucon[P.ind_ineq[k]];
-  }
-}
-
-// The numeric part of the construction: everything of size O(n + m) that depends on the problem's numbers
-// (and the O(nnz) host sums behind it), from QPHost's data, its index sets and A's COO.  The constructor
-// and update() both run it, so a refreshed solver holds the bits a fresh one would.
-void MPCSolver::numeric_host(HostNumeric& o, std::vector<int32_t>* jr, std::vector<int32_t>* jc,
-                             std::vector<double>* jv) {
-  PhaseClock clk("numeric_host");
-  QPHost& P = *H_;
-  const int nx = P.nx, m = P.m, n = P.n;
-  raw_bounds(P);
-  // ---- MadNLP.initialize!(cb, ...) [EXT]
-  P.x.assign(n, 0.0);
-  for (int i = 0; i < nx; ++i) P.x[i] = P.x0[i];
-  for (int i : P.ind_fixed) P.x[i] = P.xl[i];
-  P.y = P.y0;
-  P.rhs.assign(m, 0.0);
-  for (int i = 0; i < m; ++i) P.rhs[i] = (P.lcon[i] == P.ucon[i]) ? P.lcon[i] : 0.0;
-  const double tol = opt_.bound_relax_factor;
-  for (int i = 0; i < n; ++i) {
-    if (P.fixed[i]) continue;
-    if (std::isfinite(P.xl[i])) P.xl[i] = P.xl[i] - tol * std::max(1.0, std::fabs(P.xl[i]));
-    if (std::isfinite(P.xu[i])) P.xu[i] = P.xu[i] + tol * std::max(1.0, std::fabs(P.xu[i]));
-  }
-  if (P.ns) {
-    std::vector<double> ax(m, 0.0);
-    for (int64_t k = 0; k < P.nnzA; ++k) ax[P.Ar[k]] += P.Av[k] * P.x[P.Ac[k]];
-    for (int k = 0; k < P.ns; ++k) P.x[nx + k] = ax[P.ind_ineq[k]];
-  }
-  clk("bounds + slack start A x");
-  // initialize_variables! (Ipopt bound push) [EXT]
-  const double bp = opt_.bound_push, bf = opt_.bound_fac;
-  for (int i = 0; i < n; ++i) {
-    if (P.fixed[i]) continue;
-    const double l = P.xl[i], u = P.xu[i];
-    double lo = -INF, hi = INF;
-    if (std::isfinite(l)) {
-      double pl = bp * std::max(1.0, std::fabs(l));
-      if (std::isfinite(u)) pl = std::min(pl, bf * (u - l));
-      lo = l + pl;
-    }
-    if (std::isfinite(u)) {
-      double pu = bp * std::max(1.0, std::fabs(u));
-      if (std::isfinite(l)) pu = std::min(pu, bf * (u - l));
-      hi = u - pu;
-    }
-    P.x[i] = std::min(std::max(P.x[i], lo), hi);
-  }
-  // ---- set_scaling!(..., 100) [EXT] (solver.jl:148-159)
-  P.obj_scale = 1.0;
-  P.con_scale.assign(m, 1.0);
-  if (opt_.scaling) {
-    std::vector<double> g(nx);
-    for (int i = 0; i < nx; ++i) g[i] = P.sgn * P.c[i];
-    for (size_t k = 0; k < P.Hv.size(); ++k) {
-      const int r = P.Hr[k], c = P.Hc[k];
-      const double v = P.sgn * P.Hv[k];
-      g[r] += v * P.x[c];
-      if (r != c) g[c] += v * P.x[r];
-    }
-    double gmax = 0;
-    for (double v : g) gmax = std::max(gmax, std::fabs(v));
-    P.obj_scale = gmax > 0 ? std::min(1.0, 100.0 / gmax) : 1.0;
-    std::vector<double> rowmax(m, 0.0);
-    {  // per-thread row maxima, then their maximum (order-free)
-      const int64_t nz = P.nnzA;
-      // at most nz / (4 m) threads: their m-long maxima stay within the entries' own size
-      const int64_t tc = std::max<int64_t>(1, std::min<int64_t>(par_threads(nz), nz / (4 * std::max(m, 1))));
-      std::vector<std::vector<double>> rm(tc, std::vector<double>(m, 0.0));
-      par_range(nz, [&](int t, int64_t a, int64_t b) {
-        double* x = rm[t].data();
-        for (int64_t k = a; k < b; ++k) x[P.Ar[k]] = std::max(x[P.Ar[k]], std::fabs(P.Av[k]));
-      }, std::max<int64_t>((int64_t)1 << 20, (nz + tc - 1) / tc));
-      for (const auto& x : rm)
-        for (int i = 0; i < m; ++i) rowmax[i] = std::max(rowmax[i], x[i]);
-    }
-    for (int i = 0; i < m; ++i) P.con_scale[i] = std::min(1.0, 100.0 / rowmax[i]);
-    for (int k = 0; k < P.ns; ++k) {
-      const double cs = P.con_scale[P.ind_ineq[k]];
-      P.xl[nx + k] *= cs;
-      P.xu[nx + k] *= cs;
-      P.x[nx + k] *= cs;
-    }
-    for (int i = 0; i < m; ++i) P.rhs[i] *= P.con_scale[i];
-  }
-  obj_scale_ = P.obj_scale;
-  clk("bound push + scaling");
-  // fixed variables (MakeParameter): their Hessian terms -> objective constant / gradient shift ...
-  o.gfix.assign(n, 0.0);
-  o.cfix.assign(m, 0.0);
-  double const_fixed = 0.0;
-  for (size_t k = 0; k < P.Hv.size(); ++k) {
-    const int r = P.Hr[k], c = P.Hc[k];
-    const bool fr = P.fixed[r], fc = P.fixed[c];
-    if (!fr && !fc) continue;
-    const double v = P.obj_scale * P.sgn * P.Hv[k];
-    if (fr && fc) {
-      const_fixed += (r == c ? 0.5 : 1.0) * v * P.x[r] * P.x[c];
-      continue;
-    }
-    // cross term with a fixed variable -> constant gradient shift
-    if (!fr) o.gfix[r] += v * P.x[c];
-    if (!fc) o.gfix[c] += v * P.x[r];
-  }
-  // ... and their Jacobian columns -> cfix, summed in input order: the sequential pass (which, at
-  // construction, also collects the COO of the columns that stay)
-  if (P.anyfix) {
-    const int64_t nz = P.nnzA;
-    for (int64_t k = 0; k < nz; ++k) {
-      const int r = P.Ar[k], c = P.Ac[k];
-      const double v = P.con_scale[r] * P.Av[k];
-      if (P.fixed[c]) {
-        o.cfix[r] += v * P.x[c];
-        continue;
-      }
-      if (jr) {
-        jr->push_back(r);
-        jc->push_back(c);
-        jv->push_back(v);
-      }
-    }
-  }
-  o.cs.assign(n, 0.0);
-  for (int i = 0; i < nx; ++i) o.cs[i] = P.obj_scale * P.sgn * P.c[i];
-  c0s_ = P.obj_scale * (P.sgn * P.c0) + const_fixed;
-  // norm_b (solver.jl:173) on host
-  norm_b_ = 0;
-  for (double v : P.rhs) norm_b_ = std::max(norm_b_, std::fabs(v));
-  clk("fixed terms, cs, norms");
-}
-
-// Host-side construction: MPCSolver(...) (structure.jl:79-178), MadNLP.initialize!/set_scaling!
-// [EXT] and the K2 pattern of SparseKKTSystem [EXT].
+// Host-side construction: the problem model (qp_model.hpp) is built on the host, the linear solver is
+// analysed, everything is uploaded and the stream synchronised.
 void MPCSolver::setup_host(const madipm_qp& q) {
   PhaseClock clk("setup_host");
   H_ = std::make_unique<QPHost>();
   QPHost& P = *H_;
-  MADIPM_REQUIRE(q.nvar >= 0 && q.ncon >= 0, "negative dimensions");
-  P.nx = q.nvar;
-  P.m = q.ncon;
-  const int nx = P.nx, m = P.m;
-  auto cp = [](const double* a, int64_t n, double dflt = 0.0) {
-    std::vector<double> v(n, dflt);
-    if (a) std::copy(a, a + n, v.begin());
-    return v;
-  };
-  P.c = cp(q.c, nx);
-  P.lvar = cp(q.lvar, nx, -INF);
-  P.uvar = cp(q.uvar, nx, INF);
-  P.lcon = cp(q.lcon, m, -INF);
-  P.ucon = cp(q.ucon, m, INF);
-  P.x0 = cp(q.x0, nx);
-  P.y0 = cp(q.y0, m);
-  P.c0 = q.c0;
-  P.minimize = q.minimize != 0;
-  P.sgn = P.minimize ? 1.0 : -1.0;
-  P.Hr.assign(q.Hrows, q.Hrows + q.nnzh);
-  P.Hc.assign(q.Hcols, q.Hcols + q.nnzh);
-  P.Hv.assign(q.Hvals, q.Hvals + q.nnzh);
-  P.Ar = q.Arows;
-  P.Ac = q.Acols;
-  P.Av = q.Avals;
-  P.nnzA = q.nnzj;
-  for (int64_t k = 0; k < q.nnzh; ++k)
-    MADIPM_REQUIRE(P.Hr[k] >= P.Hc[k] && P.Hr[k] < nx && P.Hc[k] >= 0, "H must be lower-triangular COO in range");
-  {
-    std::atomic<bool> bad{false};
-    par_range(q.nnzj, [&](int, int64_t a, int64_t b) {
-      bool ok = true;
-      for (int64_t k = a; k < b; ++k) ok &= P.Ar[k] >= 0 && P.Ar[k] < m && P.Ac[k] >= 0 && P.Ac[k] < nx;
-      if (!ok) bad = true;
-    });
-    MADIPM_REQUIRE(!bad, "A index out of range");
-  }
-  clk("copy + validate");
-  // ---- index sets: MadNLP.get_index_constraints (EnforceEquality, MakeParameter) [EXT]
-  for (int i = 0; i < m; ++i)
-    if (P.lcon[i] != P.ucon[i]) P.ind_ineq.push_back(i);
-  P.ns = (int)P.ind_ineq.size();
-  const int n = nx + P.ns;
-  P.n = n;
-  raw_bounds(P);
-  P.fixed.assign(n, 0);
-  for (int i = 0; i < n; ++i) {
-    if (P.xl[i] == P.xu[i]) {
-      P.ind_fixed.push_back(i);
-      P.fixed[i] = 1;
-    } else {
-      if (P.xl[i] != -INF) P.ind_lb.push_back(i);
-      if (P.xu[i] != INF) P.ind_ub.push_back(i);
-    }
-  }
-  // structure.jl:172-173 field swap => update_barrier! tests nlb + nub > 0
-  P.has_ineq = (P.ind_lb.size() + P.ind_ub.size()) > 0;
-  for (int i = 0; i < nx && !P.anyfix; ++i) P.anyfix = P.fixed[i];
+  qp_intake(P, q, &clk);
   // ---- everything that depends on the numbers and is O(n + m) long: shared with update()
   HostNumeric num;
-  std::vector<int32_t> jr, jc;
-  std::vector<double> jv;
-  numeric_host(num, &jr, &jc, &jv);
+  JCoo jcoo;
+  numeric_host(P, opt_, num, &jcoo);
+  obj_scale_ = num.obj_scale;
+  c0s_ = num.c0s;
+  norm_b_ = num.norm_b;
   clk("initialize + scaling");
-
-  // ---- device problem data
+  const int nx = P.nx, m = P.m, n = P.n;
   nx_ = nx;
   ns_ = P.ns;
   n_ = n;
@@ -1877,102 +1533,17 @@ void MPCSolver::setup_host(const madipm_qp& q) {
   nlb_ = (int)P.ind_lb.size();
   nub_ = (int)P.ind_ub.size();
   L_ = (int64_t)n + m + nlb_ + nub_;
-  // scaled Hessian (full symmetric CSR over n; MakeParameter zeroes fixed rows/cols), diagonal apart
-  std::vector<int32_t> hr, hc;
-  std::vector<double> hv, Hdiag(n, 0.0);
-  for (size_t k = 0; k < P.Hv.size(); ++k) {
-    const int r = P.Hr[k], c = P.Hc[k];
-    const double v = P.obj_scale * P.sgn * P.Hv[k];
-    if (P.fixed[r] || P.fixed[c]) continue;  // numeric_host: const_fixed / gfix
-    if (r == c) {
-      Hdiag[r] += v;
-      hr.push_back(r);
-      hc.push_back(c);
-      hv.push_back(v);
-    } else {
-      hr.push_back(r);
-      hc.push_back(c);
-      hv.push_back(v);
-      hr.push_back(c);
-      hc.push_back(r);
-      hv.push_back(v);
-    }
-  }
-  std::vector<int64_t> Hrp;
-  hvec<int32_t> Hci;
-  hvec<double> Hcv;
-  csr_from_coo(n, hr, hc, hv, Hrp, Hci, Hcv);
-  // scaled Jacobian with slack columns (m x n); fixed columns zeroed (their term -> cfix).  Without a
-  // fixed column every entry is kept in input order and read straight from the caller's A; with one,
-  // numeric_host's cfix pass has filled the COO
-  const bool anyfix = P.anyfix;
-  if (anyfix)
-    for (int k = 0; k < P.ns; ++k) {
-      jr.push_back(P.ind_ineq[k]);
-      jc.push_back(nx + k);
-      jv.push_back(-1.0);
-    }
-  clk("H CSR + J COO");
-  std::vector<int64_t> Jrp, JTrp;
-  hvec<int32_t> Jci, JTci;
-  hvec<double> Jcv, JTcv;
-  if (anyfix) {
-    csr_from_coo(m, jr, jc, jv, Jrp, Jci, Jcv);
-    csr_from_coo(n, jc, jr, jv, JTrp, JTci, JTcv);
-    std::vector<int32_t>().swap(jr);
-    std::vector<int32_t>().swap(jc);
-    std::vector<double>().swap(jv);
-  } else {  // entries k < nnzA: A's (scaled); then one -1 per slack column
-    const int64_t na = P.nnzA, nj = na + P.ns;
-    const int32_t *Ar = P.Ar, *Ac = P.Ac, *ineq = P.ind_ineq.data();
-    const double *Av = P.Av, *cs = P.con_scale.data();
-    auto row = [=](int64_t k) { return k < na ? Ar[k] : ineq[k - na]; };
-    auto col = [=](int64_t k) { return k < na ? Ac[k] : (int32_t)(nx + (k - na)); };
-    auto val = [=](int64_t k) { return k < na ? cs[Ar[k]] * Av[k] : -1.0; };
-    csr_from_coo(m, nj, row, col, val, Jrp, Jci, Jcv);
-    csr_from_coo(n, nj, col, row, val, JTrp, JTci, JTcv);
-  }
-  clk("J, J^T CSR");
-  // K2 lower CSC: diag(n+m) + H strictly-lower + J at rows n+r  (SparseKKTSystem [EXT]), built by
-  // columns: column j < n = [j; H's rows i > j (row j of the symmetric CSR H, ascending); n + the rows r
-  // of column j of J (row j of J^T's CSR, ascending)], column j >= n = [j]
-  std::vector<int64_t> Kcp(n + m + 1, 0);
-  hvec<int32_t> Kri;
-  hvec<double> Kv;
-  {
-    std::vector<int64_t> hup(n, 0);  // per column: H entries below the diagonal
-    for (int i = 0; i < n; ++i)
-      for (int64_t q = Hrp[i]; q < Hrp[i + 1]; ++q) hup[i] += Hci[q] > i;
-    for (int j = 0; j < n + m; ++j) Kcp[j + 1] = Kcp[j] + 1 + (j < n ? hup[j] + (JTrp[j + 1] - JTrp[j]) : 0);
-    Kri.resize(Kcp[n + m]);
-    Kv.resize(Kcp[n + m]);
-    par_range(n + m, [&](int, int64_t j0, int64_t j1) {
-      for (int64_t j = j0; j < j1; ++j) {
-        int64_t o = Kcp[j];
-        Kri[o] = (int32_t)j;
-        Kv[o++] = 0.0;
-        if (j >= n) continue;
-        for (int64_t q = Hrp[j]; q < Hrp[j + 1]; ++q)
-          if (Hci[q] > j) {
-            Kri[o] = Hci[q];
-            Kv[o++] = Hcv[q];
-          }
-        for (int64_t q = JTrp[j]; q < JTrp[j + 1]; ++q) {
-          Kri[o] = n + JTci[q];
-          Kv[o++] = JTcv[q];
-        }
-      }
-    }, 1024);
-  }
-  nnzK_ = (int64_t)Kri.size();
-  clk("K2 CSC");
+  // ---- H, J, J^T CSR, the K2 pattern and (kkt_system 2) the normal equations' pattern
+  kkt_ = opt_.kkt_system;
+  QPStructure S = build_structure(P, opt_, jcoo, &clk);
+  nnzK_ = P.nnzK;
   if (const char* e = std::getenv("MADIPM_SPEC_NEAR")) spec_near_ = std::max(0.0, std::atof(e));
   if (const char* e = std::getenv("MADIPM_FINAL_DEBUG"); e && e[0] == '1') {
     fdbg_.alloc(8 * kFinDbg);
     MADIPM_HIP(hipMemset(fdbg_.p, 0, 8 * kFinDbg * sizeof(int64_t)));
   }
   {  // SpMV lane-group width: ~2 entries per lane on an average row of [H A^T; A]
-    const double avg = (double)(Hci.size() + 2 * Jci.size()) / std::max(1, n + m);
+    const double avg = (double)(P.nH + 2 * P.nJ) / std::max(1, n + m);
     spmv_g_ = 4;
     while (spmv_g_ < 64 && spmv_g_ * 2 < avg) spmv_g_ *= 2;
     if (const char* e = std::getenv("MADIPM_SPMV_G")) {  // tests / A-B: force the width (4..64, power of two)
@@ -1980,80 +1551,22 @@ void MPCSolver::setup_host(const madipm_qp& q) {
       if (g == 4 || g == 8 || g == 16 || g == 32 || g == 64) spmv_g_ = g;
     }
   }
-  std::vector<int64_t> diag_pos(Kcp.begin(), Kcp.end() - 1);  // the diagonal leads every column
-
-  // ---- KKT formulation + LDL^T symbolic analysis + device plan (linear-solver constructor)
-  kkt_ = opt_.kkt_system;
-  MADIPM_REQUIRE(kkt_ == KKT_K2 || kkt_ == KKT_K25 || kkt_ == KKT_NORMAL, "unknown kkt_system");
+  // ---- LDL^T symbolic analysis + device plan (linear-solver constructor)
   SymbolicOptions so;
   so.ordering = opt_.ldl.ordering;
   so.dense_alpha = opt_.ldl.dense_alpha;
   so.relax = opt_.ldl.relax;
   so.small_front_max = opt_.ldl.small_front_max;
-  std::vector<int64_t> Ccp, cpp;
-  std::vector<int32_t> Cri, cprod;
   if (kkt_ == KKT_NORMAL) {
-    // NormalKKTSystem constructor (normalkkt.jl:29-140): LP only; pattern of tril(A A^T) with A the
-    // scaled Jacobian with slack columns (build_normal_system, utils.jl:209-274), plus the product
-    // list of every entry for the assembly kernel (positions into J's CSR values).
-    MADIPM_REQUIRE(q.nnzh == 0,
-                   "The KKT system NormalKKTSystem supports only linear programs. "
-                   "The problem has a positive number of nonzero in its Hessian.");
-    std::vector<int64_t> colp(n + 1, 0);
-    for (int32_t k : Jci) colp[k + 1]++;
-    for (int k = 0; k < n; ++k) colp[k + 1] += colp[k];
-    std::vector<int32_t> crow(Jci.size()), cpos(Jci.size());
-    {
-      std::vector<int64_t> fill(colp.begin(), colp.end() - 1);
-      for (int i = 0; i < m; ++i)
-        for (int64_t p = Jrp[i]; p < Jrp[i + 1]; ++p) {
-          const int64_t t = fill[Jci[p]]++;
-          crow[t] = i;
-          cpos[t] = (int32_t)p;
-        }
-    }
-    Ccp.assign(m + 1, 0);
-    cpp.push_back(0);
-    struct Prod {
-      int32_t j, a, b;
-    };
-    std::vector<Prod> pr;
-    for (int i = 0; i < m; ++i) {
-      pr.clear();
-      for (int64_t p = Jrp[i]; p < Jrp[i + 1]; ++p) {
-        const int k = Jci[p];
-        for (int64_t t = colp[k]; t < colp[k + 1]; ++t)
-          if (crow[t] >= i) pr.push_back({crow[t], (int32_t)p, cpos[t]});
-      }
-      std::stable_sort(pr.begin(), pr.end(), [](const Prod& x, const Prod& y) { return x.j < y.j; });
-      for (size_t t = 0; t < pr.size(); ++t) {
-        if (t == 0 || pr[t].j != pr[t - 1].j) {
-          if (t) cpp.push_back((int64_t)cprod.size() / 2);
-          Cri.push_back(pr[t].j);
-        }
-        cprod.push_back(pr[t].a);
-        cprod.push_back(pr[t].b);
-      }
-      if (!pr.empty()) {
-        cpp.push_back((int64_t)cprod.size() / 2);
-      } else {  // empty row of A: structurally singular C; keep the (zero) diagonal entry
-        Cri.push_back(i);
-        cpp.push_back((int64_t)cprod.size() / 2);
-      }
-      Ccp[i + 1] = (int64_t)Cri.size();
-    }
-    nnzC_ = (int64_t)Cri.size();
-    ldl_ = make_linsolver(m, Ccp.data(), Cri.data(), so);
+    nnzC_ = (int64_t)S.Cri.size();
+    ldl_ = make_linsolver(m, S.Ccp.data(), S.Cri.data(), so);
     ldl_->spd = true;  // Cholesky semantics (test/test_gpu.jl:11): a non-positive pivot fails
   } else {
-    ldl_ = make_linsolver(n + m, Kcp.data(), Kri.data(), so);
+    ldl_ = make_linsolver(n + m, S.Kcp.data(), S.Kri.data(), so);
   }
 
   clk("linear solver (analysis + plan)");
   // ---- uploads
-  std::vector<int32_t> lbpos(n, -1), ubpos(n, -1);
-  for (int k = 0; k < nlb_; ++k) lbpos[P.ind_lb[k]] = k;
-  for (int k = 0; k < nub_; ++k) ubpos[P.ind_ub[k]] = k;
   hipStream_t s = stream_;
   auto up = [&](auto& buf, const auto& vec, size_t minlen = 1) {
     using T = typename std::decay_t<decltype(vec)>::value_type;
@@ -2065,26 +1578,26 @@ void MPCSolver::setup_host(const madipm_qp& q) {
   up(xu_, P.xu);
   up(y_, P.y);
   up(rhs_, P.rhs);
-  up(Hdiag_, Hdiag);
+  up(Hdiag_, S.Hdiag);
   up(cs_, num.cs);
   up(gfix_, num.gfix);
   up(cfix_, num.cfix);
-  up(diag_pos_, diag_pos);
-  up(Kx_, Kv);
+  up(diag_pos_, S.diag_pos);
+  up(Kx_, S.Kv);
   up(ind_lb_, P.ind_lb);
   up(ind_ub_, P.ind_ub);
-  up(lbpos_, lbpos);
-  up(ubpos_, ubpos);
+  up(lbpos_, S.lbpos);
+  up(ubpos_, S.ubpos);
   up(fixed_, P.fixed);
-  up(Hrp_, Hrp);
-  up(Hci_, Hci);
-  up(Hv_, Hcv);
-  up(Jrp_, Jrp);
-  up(Jci_, Jci);
-  up(Jv_, Jcv);
-  up(JTrp_, JTrp);
-  up(JTci_, JTci);
-  up(JTv_, JTcv);
+  up(Hrp_, S.Hrp);
+  up(Hci_, S.Hci);
+  up(Hv_, S.Hcv);
+  up(Jrp_, S.Jrp);
+  up(Jci_, S.Jci);
+  up(Jv_, S.Jcv);
+  up(JTrp_, S.JTrp);
+  up(JTci_, S.JTci);
+  up(JTv_, S.JTcv);
   auto zeros = [&](DBuf<double>& b, int64_t len) {
     b.alloc(std::max<int64_t>(len, 1));
     b.zero(s);
@@ -2105,20 +1618,16 @@ void MPCSolver::setup_host(const madipm_qp& q) {
   zeros(corr_lb_, nlb_);
   zeros(corr_ub_, nub_);
   if (kkt_ == KKT_NORMAL) {
-    up(cpp_, cpp);
-    up(cprod_, cprod, 2);
+    up(cpp_, S.cpp);
+    up(cprod_, S.cprod, 2);
     zeros(Cx_, nnzC_);
     zeros(Dinv_, n);
     zeros(bufm_, m);
   } else if (kkt_ == KKT_K25) {
-    hvec<int32_t> kcol(Kri.size());
-    par_range(n + m, [&](int, int64_t j0, int64_t j1) {
-      for (int64_t j = j0; j < j1; ++j)
-        for (int64_t q = Kcp[j]; q < Kcp[j + 1]; ++q) kcol[q] = (int32_t)j;
-    }, 1024);
-    up(Krow_, Kri);
+    const hvec<int32_t> kcol = k2_slot_columns(S.Kcp);
+    up(Krow_, S.Kri);
     up(Kcol_, kcol);
-    up(K0_, Kv);
+    up(K0_, S.Kv);
     zeros(sk_, n);
   }
   part_.alloc(MAXB * NPART + NL2 * FG + 8);  // + k_final's level-2 partials and ticket
@@ -2135,8 +1644,7 @@ void MPCSolver::setup_host(const madipm_qp& q) {
   clk("uploads");
   // the host copies of J, J^T and K2 (dense QP: ~18 GB) are released on a thread of their own: their
   // page-table teardown took 2.1 s of the construction on the box (r6) with nothing waiting for it
-  free_async(std::move(Jci), std::move(JTci), std::move(Jcv), std::move(JTcv), std::move(Kri), std::move(Kv),
-             std::move(Hci), std::move(Hcv));
+  free_async(std::move(S));
 }
 
 // ======================================================================= re-solve with new numbers
@@ -2540,179 +2048,35 @@ __global__ __launch_bounds__(NT) void k_warm_blend(DV D, WarmArgs W) {
   }
 }
 
-// csr_from_coo's structure for the COO (r, c) without its values: destination entries sorted by
-// (row, column), each with the ids of its COO entries in input order (id < 0: a constant entry, no source)
-struct CooPlan {
-  std::vector<int32_t> sp, src, drow, dcol;
-};
-CooPlan coo_plan(int nrow, const std::vector<int32_t>& r, const std::vector<int32_t>& c,
-                 const std::vector<int32_t>& id) {
-  const int64_t N = (int64_t)r.size();
-  std::vector<int64_t> start(nrow + 1, 0);
-  for (int64_t k = 0; k < N; ++k) start[r[k] + 1]++;
-  for (int i = 0; i < nrow; ++i) start[i + 1] += start[i];
-  std::vector<int32_t> ord(N);
-  {
-    std::vector<int64_t> fill(start.begin(), start.end() - 1);
-    for (int64_t k = 0; k < N; ++k) ord[fill[r[k]]++] = (int32_t)k;
-  }
-  CooPlan P;
-  P.sp.reserve(N + 1);
-  P.src.reserve(N);
-  P.drow.reserve(N);
-  P.dcol.reserve(N);
-  for (int i = 0; i < nrow; ++i) {
-    const auto b = ord.begin() + start[i], e = ord.begin() + start[i + 1];
-    if (!std::is_sorted(b, e, [&](int32_t x, int32_t y) { return c[x] < c[y]; }))
-      std::stable_sort(b, e, [&](int32_t x, int32_t y) { return c[x] < c[y]; });
-    for (auto it = b; it != e; ++it) {
-      if (it == b || c[*it] != c[*(it - 1)]) {
-        P.sp.push_back((int32_t)P.src.size());
-        P.drow.push_back(i);
-        P.dcol.push_back(c[*it]);
-      }
-      if (id[*it] >= 0) P.src.push_back(id[*it]);
-    }
-  }
-  P.sp.push_back((int32_t)P.src.size());
-  return P;
-}
-
-// what setup_host derives from one coordinate's bounds: fixed, or finite lower (2) | finite upper (4)
-int bound_class(double l, double u) { return l == u ? 1 : (l != -INF ? 2 : 0) | (u != INF ? 4 : 0); }
-[[noreturn]] void throw_kind_change(int idx, bool was_equality) {
-  throw Error("madipm_solver_update: constraint " + std::to_string(idx) +
-                  (was_equality ? " was an equality (lcon == ucon) and would become ranged"
-                                : " was ranged (lcon != ucon) and would become an equality") +
-                  " (the classification of every bound is fixed at creation; nothing was changed)",
-              -3);
-}
-void require_same_class(const char* what, int idx, int a, int b) {
-  if (a == b) return;
-  std::string how;
-  if ((a == 1) != (b == 1))
-    how = a == 1 ? "was fixed (lower == upper bound) and would become free"
-                 : "was free (lower != upper bound) and would become fixed";
-  else if ((a & 2) != (b & 2))
-    how = (a & 2) ? "had a finite lower bound that would become infinite"
-                  : "had an infinite lower bound that would become finite";
-  else
-    how = (a & 4) ? "had a finite upper bound that would become infinite"
-                  : "had an infinite upper bound that would become finite";
-  throw Error(std::string("madipm_solver_update: ") + what + " " + std::to_string(idx) + " " + how +
-                  " (the classification of every bound is fixed at creation; nothing was changed)",
-              -3);
-}
-void require_same_class(const char* what, int idx, double l0, double u0, double l1, double u1) {
-  require_same_class(what, idx, bound_class(l0, u0), bound_class(l1, u1));
-}
-
 }  // namespace
 
 void MPCSolver::prepare_update(const madipm_qp& q) {
   if (plan_) return;
   QPHost& P = *H_;
-  const int nx = P.nx, m = P.m, n = P.n;
-  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
-  MADIPM_REQUIRE(q.nvar == nx && q.ncon == m && q.nnzj == na && q.nnzh == nh,
-                 "madipm_solver_prepare_update: nvar / ncon / nnzj / nnzh differ from the problem the solver was "
-                 "created with");
-  MADIPM_REQUIRE(na == 0 || (q.Arows && q.Acols && q.Avals), "madipm_solver_prepare_update: null A arrays");
-  MADIPM_REQUIRE(na + P.ns < INT32_MAX && 2 * nh < INT32_MAX && nnzK_ < INT32_MAX,
-                 "madipm_solver_prepare_update: the refresh plan has 32-bit indices (nnz < 2^31)");
+  RefreshPlan R = build_refresh_plan(P, q);
   auto pl = std::make_unique<UpdatePlan>();
-  pl->Ar.assign(q.Arows, q.Arows + na);
-  pl->Ac.assign(q.Acols, q.Acols + na);
-  pl->Av.assign(q.Avals, q.Avals + na);
-  for (int64_t k = 0; k < na; ++k)
-    MADIPM_REQUIRE(pl->Ar[k] >= 0 && pl->Ar[k] < m && pl->Ac[k] >= 0 && pl->Ac[k] < nx,
-                   "madipm_solver_prepare_update: A index out of range");
-  // ---- J^T (n x m): the COO setup_host builds (fixed columns dropped, one -1 per slack column), transposed
-  std::vector<int32_t> er, ec, id;
-  er.reserve(na + P.ns);
-  ec.reserve(na + P.ns);
-  id.reserve(na + P.ns);
-  for (int64_t k = 0; k < na; ++k) {
-    if (P.fixed[pl->Ac[k]]) continue;
-    er.push_back(pl->Ar[k]);
-    ec.push_back(pl->Ac[k]);
-    id.push_back((int32_t)k);
-  }
-  for (int k = 0; k < P.ns; ++k) {
-    er.push_back(P.ind_ineq[k]);
-    ec.push_back(nx + k);
-    id.push_back(-1);
-  }
-  const CooPlan T = coo_plan(n, ec, er, id);
-  const int64_t nJ = (int64_t)T.drow.size();
-  std::vector<int32_t>().swap(er);
-  std::vector<int32_t>().swap(ec);
-  std::vector<int32_t>().swap(id);
-  // J's entries sorted by (row, column) = J^T's, bucketed by their column index in ascending order
-  std::vector<int32_t> j2jt(nJ);
-  {
-    std::vector<int64_t> rs(m + 1, 0);
-    for (int64_t t = 0; t < nJ; ++t) rs[T.dcol[t] + 1]++;
-    for (int i = 0; i < m; ++i) rs[i + 1] += rs[i];
-    for (int64_t t = 0; t < nJ; ++t) j2jt[rs[T.dcol[t]]++] = (int32_t)t;
-  }
-  // ---- H (n x n, symmetric): an off-diagonal source feeds (r, c) and (c, r); fixed rows / columns feed none
-  std::vector<int32_t> hr, hc, hid;
-  for (int64_t k = 0; k < nh; ++k) {
-    const int r = P.Hr[k], c = P.Hc[k];
-    if (P.fixed[r] || P.fixed[c]) continue;
-    hr.push_back(r);
-    hc.push_back(c);
-    hid.push_back((int32_t)k);
-    if (r != c) {
-      hr.push_back(c);
-      hc.push_back(r);
-      hid.push_back((int32_t)k);
-    }
-  }
-  const CooPlan Hp = coo_plan(n, hr, hc, hid);
-  const int64_t nH = (int64_t)Hp.drow.size();
-  // the plan must address exactly the arrays the constructor uploaded
-  MADIPM_REQUIRE((int64_t)Jv_.n == std::max<int64_t>(nJ, 1) && (int64_t)JTv_.n == std::max<int64_t>(nJ, 1) &&
-                     (int64_t)Hv_.n == std::max<int64_t>(nH, 1),
-                 "madipm_solver_prepare_update: the index arrays are not the ones the solver was created with");
-  // ---- K2's columns: [j; H's rows i > j; n + J^T's row j]
-  std::vector<int64_t> hup(n, 0), jtc(n, 0), Kcp(n + m + 1, 0);
-  for (int64_t t = 0; t < nH; ++t) hup[Hp.drow[t]] += Hp.dcol[t] > Hp.drow[t];
-  for (int64_t t = 0; t < nJ; ++t) jtc[T.drow[t]]++;
-  for (int j = 0; j < n + m; ++j) Kcp[j + 1] = Kcp[j] + 1 + (j < n ? hup[j] + jtc[j] : 0);
-  MADIPM_REQUIRE(Kcp[n + m] == nnzK_,
-                 "madipm_solver_prepare_update: the index arrays are not the ones the solver was created with");
-  std::vector<int32_t> hk(nH, -1), hdpos(n, -1), jtk(nJ);
-  {
-    std::vector<int64_t> nxt(n);
-    for (int j = 0; j < n; ++j) nxt[j] = Kcp[j] + 1;
-    for (int64_t t = 0; t < nH; ++t) {
-      const int i = Hp.drow[t], j = Hp.dcol[t];
-      if (j > i) hk[t] = (int32_t)nxt[i]++;
-      if (j == i) hdpos[i] = (int32_t)t;
-    }
-    for (int64_t t = 0; t < nJ; ++t) jtk[t] = (int32_t)nxt[T.drow[t]]++;
-  }
+  pl->Ar = std::move(R.Ar);
+  pl->Ac = std::move(R.Ac);
+  pl->Av = std::move(R.Av);
   // ---- device side: plans + staging (the only allocations of the refresh path)
   hipStream_t s = stream_;
   auto up = [&](auto& buf, const auto& vec) {
     buf.alloc(std::max<size_t>(vec.size(), 1));
     buf.upload(vec.data(), vec.size(), s);
   };
-  up(pl->tsp, T.sp);
-  up(pl->tsrc, T.src);
-  up(pl->jtk, jtk);
-  up(pl->j2jt, j2jt);
-  up(pl->hsp, Hp.sp);
-  up(pl->hsrc, Hp.src);
-  up(pl->hk, hk);
-  up(pl->hdpos, hdpos);
+  up(pl->tsp, R.tsp);
+  up(pl->tsrc, R.tsrc);
+  up(pl->jtk, R.jtk);
+  up(pl->j2jt, R.j2jt);
+  up(pl->hsp, R.hsp);
+  up(pl->hsrc, R.hsrc);
+  up(pl->hk, R.hk);
+  up(pl->hdpos, R.hdpos);
   up(pl->Araw, pl->Av);
   up(pl->Hraw, P.Hv);
-  pl->cscale.alloc(std::max(m, 1));
-  pl->nJ = nJ;
-  pl->nH = nH;
+  pl->cscale.alloc(std::max(P.m, 1));
+  pl->nJ = R.nJ;
+  pl->nH = R.nH;
   MADIPM_HIP(hipStreamSynchronize(s));
   // the host passes of numeric_host read A from the plan's copy from now on
   P.Ar = pl->Ar.data();
@@ -2728,22 +2092,14 @@ void MPCSolver::update(const madipm_qp_update& u) {
                         "the refresh plan)");
   QPHost& P = *H_;
   UpdatePlan& pl = *plan_;
-  const int nx = P.nx, m = P.m, n = P.n;
+  const int n = P.n;
   refresh_host_mirrors();  // after a device update: the "keep" fields are the device-installed ones
   // ---- the classification setup_host derived must hold for the merged data; checked before anything changes
   const double* lv = u.lvar ? u.lvar : P.lvar.data();
   const double* uv = u.uvar ? u.uvar : P.uvar.data();
   const double* lc = u.lcon ? u.lcon : P.lcon.data();
   const double* uc = u.ucon ? u.ucon : P.ucon.data();
-  for (int i = 0; i < m; ++i) {
-    const bool was = P.lcon[i] == P.ucon[i], is = lc[i] == uc[i];
-    if (was != is) throw_kind_change(i, was);
-  }
-  for (int i = 0; i < nx; ++i) require_same_class("variable", i, P.lvar[i], P.uvar[i], lv[i], uv[i]);
-  for (int k = 0; k < P.ns; ++k) {
-    const int r = P.ind_ineq[k];
-    require_same_class("constraint", r, P.lcon[r], P.ucon[r], lc[r], uc[r]);
-  }
+  require_same_classes(P, lv, uv, lc, uc);
   clk("classification check");
   // ---- install
   auto put = [](std::vector<double>& dst, const double* src) {
@@ -2761,7 +2117,10 @@ void MPCSolver::update(const madipm_qp_update& u) {
   put(P.y0, u.y0);
   clk("copy");
   HostNumeric num;
-  numeric_host(num);
+  numeric_host(P, opt_, num);
+  obj_scale_ = num.obj_scale;
+  c0s_ = num.c0s;
+  norm_b_ = num.norm_b;
   clk("numeric_host");
   hipStream_t s = stream_;
   auto send = [&](double* dst, const std::vector<double>& v) {
@@ -2851,86 +2210,32 @@ void MPCSolver::get_data(double* c, double* c0, double* Hvals, double* Avals, do
 void MPCSolver::build_device_route() {
   PhaseClock clk("build_device_route");
   QPHost& P = *H_;
-  UpdatePlan& pl = *plan_;
   const int nx = P.nx, m = P.m, n = P.n;
-  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
   auto dv = std::make_unique<DevUpdate>();
   hipStream_t s = stream_;
-  std::vector<std::vector<int32_t>> keep32;  // host sources of the asynchronous uploads
-  std::vector<std::vector<int2>> keep2;
-  // destinations dest[t] (in input order) with entries ent[t] -> per-destination lists, input order kept
-  auto lists = [&](int nd, const std::vector<int32_t>& dest, const std::vector<int2>& ent, DBuf<int32_t>& sp,
-                   DBuf<int2>& e) {
-    std::vector<int32_t> start(nd + 1, 0);
-    for (int32_t d : dest) start[d + 1]++;
-    for (int i = 0; i < nd; ++i) start[i + 1] += start[i];
-    std::vector<int2> out(ent.size());
-    std::vector<int32_t> fill(start.begin(), start.end() - 1);
-    for (size_t t = 0; t < dest.size(); ++t) out[fill[dest[t]]++] = ent[t];
-    sp.alloc(start.size());
-    sp.upload(start.data(), start.size(), s);
-    e.alloc(std::max<size_t>(out.size(), 1));
-    e.upload(out.data(), out.size(), s);
-    keep32.push_back(std::move(start));
-    keep2.push_back(std::move(out));
-  };
-  {
-    std::vector<int32_t> dest(na), fdest;
-    std::vector<int2> ent(na), fent;
-    for (int64_t k = 0; k < na; ++k) {
-      dest[k] = pl.Ar[k];
-      ent[k] = make_int2((int)k, pl.Ac[k]);
-      if (P.fixed[pl.Ac[k]]) {
-        fdest.push_back(pl.Ar[k]);
-        fent.push_back(ent[k]);
-      }
-    }
-    lists(m, dest, ent, dv->asp, dv->ae);
-    lists(m, fdest, fent, dv->fsp, dv->fe);
-  }
-  {
-    std::vector<int32_t> gdest, xdest, bfk;
-    std::vector<int2> gent, xent, bfrc;
-    for (int64_t k = 0; k < nh; ++k) {
-      const int r = P.Hr[k], c = P.Hc[k];
-      gdest.push_back(r);
-      gent.push_back(make_int2((int)k, c));
-      if (r != c) {
-        gdest.push_back(c);
-        gent.push_back(make_int2((int)k, r));
-      }
-      const bool fr = P.fixed[r], fc = P.fixed[c];
-      if (fr && fc) {
-        bfk.push_back((int32_t)k);
-        bfrc.push_back(make_int2(r, c));
-      } else if (fc) {
-        xdest.push_back(r);
-        xent.push_back(make_int2((int)k, c));
-      } else if (fr) {
-        xdest.push_back(c);
-        xent.push_back(make_int2((int)k, r));
-      }
-    }
-    lists(nx, gdest, gent, dv->gsp, dv->ge);
-    lists(nx, xdest, xent, dv->xsp, dv->xe);
-    dv->nbf = (int)bfk.size();
-    dv->bfk.alloc(std::max<size_t>(bfk.size(), 1));
-    dv->bfk.upload(bfk.data(), bfk.size(), s);
-    dv->bfrc.alloc(std::max<size_t>(bfrc.size(), 1));
-    dv->bfrc.upload(bfrc.data(), bfrc.size(), s);
-    keep32.push_back(std::move(bfk));
-    keep2.push_back(std::move(bfrc));
-  }
+  const RouteLists L = build_route_lists(P);  // alive until the synchronisation below
   clk("lists");
-  std::vector<uint8_t> vcls(nx), ccls(m);
-  for (int i = 0; i < nx; ++i) vcls[i] = (uint8_t)bound_class(P.lvar[i], P.uvar[i]);
-  for (int i = 0; i < m; ++i) ccls[i] = (uint8_t)bound_class(P.lcon[i], P.ucon[i]);
   auto up = [&](auto& buf, const auto& vec, size_t len) {
     buf.alloc(std::max<size_t>(len, 1));
     buf.upload(vec.data(), vec.size(), s);
   };
-  up(dv->vcls, vcls, nx);
-  up(dv->ccls, ccls, m);
+  auto up2 = [&](DBuf<int2>& buf, const std::vector<I2>& vec) {
+    buf.alloc(std::max<size_t>(vec.size(), 1));
+    buf.upload(as_int2(vec), vec.size(), s);
+  };
+  up(dv->asp, L.asp, L.asp.size());
+  up2(dv->ae, L.ae);
+  up(dv->fsp, L.fsp, L.fsp.size());
+  up2(dv->fe, L.fe);
+  up(dv->gsp, L.gsp, L.gsp.size());
+  up2(dv->ge, L.ge);
+  up(dv->xsp, L.xsp, L.xsp.size());
+  up2(dv->xe, L.xe);
+  dv->nbf = (int)L.bfk.size();
+  up(dv->bfk, L.bfk, L.bfk.size());
+  up2(dv->bfrc, L.bfrc);
+  up(dv->vcls, L.vcls, nx);
+  up(dv->ccls, L.ccls, m);
   up(dv->ineq, P.ind_ineq, P.ns);
   up(dv->c, P.c, nx);
   up(dv->lvar, P.lvar, nx);
@@ -4047,9 +3352,7 @@ void MPCSolver::adjoint(const double* gx, const madipm_qp_gradients& g, bool dev
   const double* cscale = device_con_scale();
   if (!device && !a.gx.p) a.gx.alloc(std::max(nx_, 1));
   if ((g.lcon || g.ucon) && !a.rowslack.p) {
-    std::vector<int32_t> rs(std::max(m_, 1), -1);
-    for (int k = 0; k < ns_; ++k) rs[P.ind_ineq[k]] = nx_ + k;
-    a.rowslack.upload(rs, s);
+    a.rowslack.upload(adjoint_rowslack(P), s);
     MADIPM_HIP(hipStreamSynchronize(s));
   }
   if (needA && !a.Ar.p) {
@@ -4061,40 +3364,16 @@ void MPCSolver::adjoint(const double* gx, const madipm_qp_gradients& g, bool dev
     a.Hc.upload(P.Hc, s);
   }
   if (needFix && a.nfix < 0) {  // the fixed variables' entry lists, from the host COO copies
-    std::vector<int32_t> fix, tof(nx_, -1);
-    for (int i = 0; i < nx_; ++i)
-      if (P.fixed[i]) {
-        tof[i] = (int32_t)fix.size();
-        fix.push_back(i);
-      }
-    const int nf = (int)fix.size();
-    std::vector<int32_t> hsp(nf + 1, 0), asp(nf + 1, 0);
-    const std::vector<int32_t>&Ar = plan_->Ar, &Ac = plan_->Ac;
-    for (int64_t k = 0; k < nh; ++k) {
-      const int r = P.Hr[k], c = P.Hc[k];
-      if (P.fixed[r] != P.fixed[c]) hsp[tof[P.fixed[r] ? r : c] + 1]++;
-    }
-    for (int64_t k = 0; k < na; ++k)
-      if (P.fixed[Ac[k]]) asp[tof[Ac[k]] + 1]++;
-    for (int t = 0; t < nf; ++t) {
-      hsp[t + 1] += hsp[t];
-      asp[t + 1] += asp[t];
-    }
-    std::vector<int2> fh(std::max(hsp[nf], 1)), fa(std::max(asp[nf], 1));
-    std::vector<int32_t> hn(hsp.begin(), hsp.end() - 1), an(asp.begin(), asp.end() - 1);
-    for (int64_t k = 0; k < nh; ++k) {
-      const int r = P.Hr[k], c = P.Hc[k];
-      if (P.fixed[r] != P.fixed[c]) fh[hn[tof[P.fixed[r] ? r : c]]++] = make_int2((int)k, P.fixed[r] ? c : r);
-    }
-    for (int64_t k = 0; k < na; ++k)
-      if (P.fixed[Ac[k]]) fa[an[tof[Ac[k]]]++] = make_int2((int)k, Ar[k]);
-    a.fix.upload(fix, s);
-    a.fhsp.upload(hsp, s);
-    a.fasp.upload(asp, s);
-    a.fh.upload(fh, s);
-    a.fa.upload(fa, s);
+    AdjointLists L = build_adjoint_lists(P);
+    L.fh.resize(std::max<size_t>(L.fh.size(), 1));  // the allocations are never empty
+    L.fa.resize(std::max<size_t>(L.fa.size(), 1));
+    a.fix.upload(L.fix, s);
+    a.fhsp.upload(L.fhsp, s);
+    a.fasp.upload(L.fasp, s);
+    a.fh.upload(as_int2(L.fh), L.fh.size(), s);
+    a.fa.upload(as_int2(L.fa), L.fa.size(), s);
     MADIPM_HIP(hipStreamSynchronize(s));
-    a.nfix = nf;
+    a.nfix = (int)L.fix.size();
   }
   const int64_t len[7] = {nx_, nh, na, m_, m_, nx_, nx_};
   double* out[7];

@@ -40,8 +40,7 @@ struct DevState {
   LDLStatus ldl_status;  // the linear solver's status (external_status): one read-back per iteration
 };
 
-struct QPHost;       // host copy of the problem (mpc.hip)
-struct HostNumeric;  // value-dependent host quantities of size O(n + m) (mpc.hip)
+struct QPHost;       // host copy of the problem (qp_model.hpp)
 struct UpdatePlan;   // index plans of the value refresh, built by prepare_update (mpc.hip)
 struct DevUpdate;    // staging, start vectors and sum-order lists of the device route (mpc.hip)
 struct WarmStart;    // the warm point and its scratch, on the device (mpc.hip)
@@ -96,10 +95,6 @@ class MPCSolver {
 
  private:
   void setup_host(const madipm_qp& qp);
-  // the value-dependent host part of the construction, shared with update(); jr/jc/jv (creation with a
-  // fixed variable only) receive the Jacobian's COO in the same pass that sums cfix
-  void numeric_host(HostNumeric& o, std::vector<int32_t>* jr = nullptr, std::vector<int32_t>* jc = nullptr,
-                    std::vector<double>* jv = nullptr);
   void build_device_route();
   WarmStart& warm_buffers();
   void warm_blend();
