@@ -560,6 +560,29 @@ int madipm_solver_adjoint_device(madipm_solver_t s, const double* d_gx, const ma
 int madipm_solver_adjoint_info(madipm_solver_t s, int64_t* n_adjoints, int64_t* n_adjoint_factorizations,
                                double* last_residual);
 
+/* ------------------------------------------------------------------ adjoint of all five blocks  [ABI 0.2.8, additive]
+ * The same gradients for a loss l(x, y, zl, zu, cons) of everything madipm_solver_get_solution returns: the
+ * row multipliers y (length ncon), the bound multipliers zl, zu (length nvar) and the constraint values
+ * cons = A x (length ncon), besides x.  (Two symbols and one struct; nothing above changed.)
+ * Every non-NULL field of madipm_qp_cotangents is the derivative of l with respect to that block, in the
+ * public un-scaled space; a NULL field is read as 0.  Constants, whose cotangents are ignored: zl_i / zu_i of
+ * a variable without that bound, and zl, zu of a fixed variable (all of them are returned as 0).  The slack
+ * multipliers max(-/+y, 0) are not separate arguments of the loss: it sees y.
+ * One more solve with the factor madipm_solver_adjoint uses (one factorisation per solved point serves both
+ * calls; the counters and the residual of madipm_solver_adjoint_info cover both), with a right-hand side in
+ * which the 1 / gap^2 terms of the active bounds are cancelled analytically: the bound
+ * gradients do not lose digits where Sigma = z / gap is 1e8 and more.  last_residual is that of this shifted
+ * system.  The outputs, their conventions, the stream contracts and the prerequisites (prepare_update for
+ * Avals, Hvals and lvar with fixed variables) are those of madipm_solver_adjoint / _adjoint_device.
+ * Refused as there, and when all five cotangents are NULL.  With x alone the call runs madipm_solver_adjoint's
+ * own path and returns its bits.
+ * Memory on top of madipm_solver_adjoint's, by the first call with a cotangent other than x: 8 B x (2 nvar +
+ * ncon + inequality rows); on the host route 8 B per entry of each cotangent given. */
+typedef struct madipm_qp_cotangents { const double *x, *y, *zl, *zu, *cons; } madipm_qp_cotangents; /* NULL = absent (0) */
+int madipm_solver_adjoint_full(madipm_solver_t s, const madipm_qp_cotangents* g, const madipm_qp_gradients* out);
+int madipm_solver_adjoint_full_device(madipm_solver_t s, const madipm_qp_cotangents* d_g,
+                                      const madipm_qp_gradients* d_out, madipm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

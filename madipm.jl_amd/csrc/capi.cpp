@@ -758,6 +758,27 @@ int madipm_solver_adjoint_device(madipm_solver_t s, const double* d_gx, const ma
   MADIPM_API_END
 }
 
+int madipm_solver_adjoint_full(madipm_solver_t s, const madipm_qp_cotangents* g, const madipm_qp_gradients* out) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(g, "madipm_solver_adjoint_full: null cotangent struct");
+  MADIPM_REQUIRE(out, "madipm_solver_adjoint_full: null output struct");
+  s->s->adjoint(*g, *out, false, nullptr, "madipm_solver_adjoint_full");
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_adjoint_full_device(madipm_solver_t s, const madipm_qp_cotangents* d_g,
+                                      const madipm_qp_gradients* d_out, madipm_stream_t stream) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(d_g, "madipm_solver_adjoint_full_device: null cotangent struct");
+  MADIPM_REQUIRE(d_out, "madipm_solver_adjoint_full_device: null output struct");
+  s->s->adjoint(*d_g, *d_out, true, (hipStream_t)stream, "madipm_solver_adjoint_full_device");
+  return 0;
+  MADIPM_API_END
+}
+
 int madipm_solver_adjoint_info(madipm_solver_t s, int64_t* n_adjoints, int64_t* n_adjoint_factorizations,
                                double* last_residual) {
   MADIPM_API_BEGIN

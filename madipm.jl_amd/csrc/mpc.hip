@@ -104,6 +104,9 @@ struct Adjoint {
   DBuf<int2> fh, fa;                      // (entry of Hvals, free endpoint), (entry of Avals, row)
   int nfix = -1;                          // -1: lists not built yet
   DBuf<double> out[7];                    // host route: c, Hvals, Avals, lcon, ucon, lvar, uvar
+  // the loss of all five blocks (§13d), by the first call with a cotangent other than gx: 8 B x (n + m + nvar)
+  DBuf<double> shift, apx;                // v = [q~; 0; gcons / con_scale]; a~'x of the shifted system
+  DBuf<double> ct[4];                     // host route's gy, gzl, gzu, gcons
   hipEvent_t ev[2] = {nullptr, nullptr};
   int64_t n_adjoints = 0, n_fact = 0;
   int64_t fact_solve = -1;                // n_solves_ of the point the LDL^T currently holds the factor of
@@ -3131,6 +3134,9 @@ void MPCSolver::get_solution(double* x, double* y, double* zl, double* zu, doubl
 // space, gives a = (ax, as, ay) = (obj_scale a~x, obj_scale a~s / con_scale, con_scale a~y) of the public
 // space, and every gradient is a product of entries of a with entries of the solution.  One thread (the
 // residual: one lane group) per output, every sum in a fixed order, no atomics: the same bits run to run.
+// madipm_solver_adjoint_full / _full_device: the loss also depends on y, zl, zu and A x.  The
+// same factor and refinement with the shifted right-hand side K a~' = g' (k_adj_shift, k_adj_rhs_full),
+// a~ = a~' - [q~; 0; 0] (k_adj_unshift), and the <true> instantiations of the gradient kernels.
 namespace madipm {
 namespace {
 
@@ -3151,6 +3157,79 @@ __device__ __forceinline__ double adj_sig_l(const AdjArgs& A, int i) {
 }
 __device__ __forceinline__ double adj_sig_u(const AdjArgs& A, int i) {
   return A.ubpos[i] >= 0 ? A.zu[i] / (A.xu[i] - A.x[i]) : 0.0;
+}
+
+// The loss of all five blocks: the cotangents besides gx (any may be null: 0), and a~'x, the
+// x part of the shifted system's solution, which the bound gradients of the free variables are formed from.
+struct AdjFull {
+  const double *gzl, *gzu, *gcons;
+  const double* apx;
+};
+// a bound the variable does not have makes its multiplier a constant: that cotangent is not read
+__device__ __forceinline__ double adj_gzl(const AdjArgs& A, const AdjFull& F, int i) {
+  return (F.gzl && A.lbpos[i] >= 0) ? F.gzl[i] : 0.0;
+}
+__device__ __forceinline__ double adj_gzu(const AdjArgs& A, const AdjFull& F, int i) {
+  return (F.gzu && A.ubpos[i] >= 0) ? F.gzu[i] : 0.0;
+}
+
+// v = [q~; 0; gcons / con_scale], the vector the shifted right-hand side applies K's blocks to:
+// q_i = (Sigma_l gzl - Sigma_u gzu)_i / (Sigma_l + Sigma_u)_i on a free variable with a bound, else 0 (the
+// scalings cancel in q), q~ = q / obj_scale.  The slack entries are written 0: their J~^T row is not empty.
+__global__ __launch_bounds__(NT) void k_adj_shift(AdjArgs A, AdjFull F, double* __restrict__ v, LDLStatus* t1) {
+#pragma clang fp contract(off)
+  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  GRID_LOOP(i, A.n + A.m) {
+    double o = 0.0;
+    if (i < A.nx) {
+      if (!A.fixed[i]) {
+        const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
+        if (sm > 0.0) o = ((sl * adj_gzl(A, F, (int)i) - su * adj_gzu(A, F, (int)i)) / sm) / A.os;
+      }
+    } else if (i >= A.n && F.gcons) {
+      o = F.gcons[i - A.n] / A.cscale[i - A.n];
+    }
+    v[i] = o;
+  }
+}
+
+// The shifted right-hand side into d (and p, which keeps it for the residual), k_adj_resid's access pattern
+// applied to v: gx + H~ q~ + J~^T (gcons / con_scale) on a free variable, 0 on a fixed one and on a slack,
+// con_scale_r gy_r / obj_scale + J~_r q~ on row r.  Every entry is of the cotangents' magnitude: the
+// Sigma terms of the plain form, 1e8 and more at an active bound, have cancelled in the algebra.
+template <int G>
+__global__ __launch_bounds__(NT) void k_adj_rhs_full(DV D, AdjArgs A, const double* __restrict__ gx,
+                                                     const double* __restrict__ gy, const double* __restrict__ v) {
+#pragma clang fp contract(off)
+  const int n = D.n, m = D.m;
+  const bool lead = (threadIdx.x & (G - 1)) == 0;
+  GROUP_LOOP(i, n + m, G) {
+    double g = 0.0;
+    if (i < n) {
+      if (i < D.nx && !D.fixed[i]) {
+        double hd, jd;
+        gdot2<G>(D.H, i, v, D.JT, i, v + n, hd, jd);
+        g = (gx ? gx[i] : 0.0) + (hd + jd);
+      }
+    } else {
+      const double jq = gdot<G>(D.J, i - n, v);
+      g = (gy ? A.cscale[i - n] * gy[i - n] / A.os : 0.0) + jq;
+    }
+    if (lead) {
+      D.d[i] = g;
+      D.p[i] = g;
+    }
+  }
+}
+
+// a~ = a~' - [q~; 0; 0], with a~'x kept for the bound gradients
+__global__ __launch_bounds__(NT) void k_adj_unshift(int nx, const double* __restrict__ v, double* __restrict__ sol,
+                                                    double* __restrict__ apx) {
+  GRID_LOOP(i, nx) {
+    const double ap = sol[i];
+    apx[i] = ap;
+    sol[i] = ap - v[i];
+  }
 }
 
 // gx into d's K2 layout (and into p, which keeps it for the residual): zero on fixed variables, slacks, rows
@@ -3224,7 +3303,11 @@ __global__ __launch_bounds__(NT) void k_adj_resmax(const double* __restrict__ ro
 // lvar_i = Sigma_l,i ax_i = Sigma~_l,i a~x_i and uvar_i likewise (the scalings cancel); a fixed one: uvar_i = 0
 // (lvar_i is k_adj_fix's).  Row i: an equality row lcon_i = ay_i, ucon_i = 0; a row with slack k:
 // lcon_i = Sigma_l,k as_k = con_scale_i Sigma~_l,k a~s_k and ucon_i likewise.
-__global__ __launch_bounds__(NT) void k_adj_vec(AdjArgs A, const int32_t* __restrict__ rowslack,
+// FULL (§13d; A.d is the un-shifted a~): a free variable's bounds in the shifted form,
+// lvar_i = Sigma~_l,i a~'x_i + h_i (gzl_i + gzu_i), uvar_i = Sigma~_u,i a~'x_i - h_i (gzl_i + gzu_i),
+// h_i = Sigma~_l Sigma~_u / (Sigma~_l + Sigma~_u) / obj_scale (0 where the sum is 0).
+template <bool FULL>
+__global__ __launch_bounds__(NT) void k_adj_vec(AdjArgs A, AdjFull F, const int32_t* __restrict__ rowslack,
                                                 double* __restrict__ gc, double* __restrict__ glv,
                                                 double* __restrict__ guv, double* __restrict__ glc,
                                                 double* __restrict__ guc) {
@@ -3235,8 +3318,16 @@ __global__ __launch_bounds__(NT) void k_adj_vec(AdjArgs A, const int32_t* __rest
       const double at = fx ? 0.0 : A.d[i];
       if (gc) gc[i] = -(A.sgn * (A.os * at));
       if (!fx) {
-        if (glv) glv[i] = adj_sig_l(A, (int)i) * at;
-        if (guv) guv[i] = adj_sig_u(A, (int)i) * at;
+        if constexpr (FULL) {
+          const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
+          const double ap = F.apx[i];
+          const double hg = sm > 0.0 ? (sl * su / sm) / A.os * (adj_gzl(A, F, (int)i) + adj_gzu(A, F, (int)i)) : 0.0;
+          if (glv) glv[i] = sl * ap + hg;
+          if (guv) guv[i] = su * ap - hg;
+        } else {
+          if (glv) glv[i] = adj_sig_l(A, (int)i) * at;
+          if (guv) guv[i] = adj_sig_u(A, (int)i) * at;
+        }
       } else if (guv) {
         guv[i] = 0.0;
       }
@@ -3257,13 +3348,19 @@ __global__ __launch_bounds__(NT) void k_adj_vec(AdjArgs A, const int32_t* __rest
 }
 
 // Avals[k], entry (r, c): -(ax_c y_r + ay_r x_c), y the public multiplier (k_unscale's rounding)
-__global__ __launch_bounds__(NT) void k_adj_avals(AdjArgs A, int64_t nnz, const int32_t* __restrict__ Ar,
+// FULL: + gcons_r x_c, the entry's own part of (A x)_r
+template <bool FULL>
+__global__ __launch_bounds__(NT) void k_adj_avals(AdjArgs A, AdjFull F, int64_t nnz, const int32_t* __restrict__ Ar,
                                                   const int32_t* __restrict__ Ac, double* __restrict__ out) {
 #pragma clang fp contract(off)
   GRID_LOOP(k, nnz) {
     const int r = Ar[k], c = Ac[k];
     const double yr = A.y[r] * A.cscale[r] / A.os;
-    out[k] = -(adj_ax(A, c) * yr + adj_ay(A, r) * A.x[c]);
+    const double v = -(adj_ax(A, c) * yr + adj_ay(A, r) * A.x[c]);
+    if constexpr (FULL)
+      out[k] = F.gcons ? v + F.gcons[r] * A.x[c] : v;
+    else
+      out[k] = v;
   }
 }
 
@@ -3281,7 +3378,10 @@ __global__ __launch_bounds__(NT) void k_adj_hvals(AdjArgs A, int64_t nnz, const 
 
 // lvar_f of fixed variable f = gx_f - sgn (H ax)_f - (A^T ay)_f, from the raw values: the entries of Hvals
 // between f and a free variable, then the entries of Avals in column f, each list in input order
-__global__ __launch_bounds__(NT) void k_adj_fix(AdjArgs A, int nfix, const int32_t* __restrict__ fix,
+// FULL: gxe_f = gx_f + (A^T gcons)_f in the place of gx_f, over the same list of column f (J~^T has no row
+// of a fixed variable), and gx may be null
+template <bool FULL>
+__global__ __launch_bounds__(NT) void k_adj_fix(AdjArgs A, AdjFull F, int nfix, const int32_t* __restrict__ fix,
                                                 const int32_t* __restrict__ fhsp, const int2* __restrict__ fh,
                                                 const int32_t* __restrict__ fasp, const int2* __restrict__ fa,
                                                 const double* __restrict__ Hraw, const double* __restrict__ Araw,
@@ -3298,7 +3398,17 @@ __global__ __launch_bounds__(NT) void k_adj_fix(AdjArgs A, int nfix, const int32
       as = as + Araw[e.x] * adj_ay(A, e.y);
     }
     const int f = fix[t];
-    glv[f] = gx[f] - A.sgn * hs - as;
+    if constexpr (FULL) {
+      double gs = 0.0;
+      if (F.gcons)
+        for (int q = fasp[t]; q < fasp[t + 1]; ++q) {
+          const int2 e = fa[q];
+          gs = gs + Araw[e.x] * F.gcons[e.y];
+        }
+      glv[f] = ((gx ? gx[f] : 0.0) + gs) - A.sgn * hs - as;
+    } else {
+      glv[f] = gx[f] - A.sgn * hs - as;
+    }
   }
 }
 
@@ -3315,7 +3425,18 @@ static int adj_refine_steps() {
 }
 
 void MPCSolver::adjoint(const double* gx, const madipm_qp_gradients& g, bool device, hipStream_t caller) {
-  const std::string who = device ? "madipm_solver_adjoint_device: " : "madipm_solver_adjoint: ";
+  adjoint(madipm_qp_cotangents{gx, nullptr, nullptr, nullptr, nullptr}, g, device, caller, nullptr);
+}
+
+// name == nullptr: madipm_solver_adjoint / _adjoint_device (gx alone, which must be given).  full: a
+// cotangent other than gx is given, and the shifted system of §13d is solved; without one the kernels and
+// their order are those of the gx-only call whichever entry point was taken.
+void MPCSolver::adjoint(const madipm_qp_cotangents& ct, const madipm_qp_gradients& g, bool device,
+                        hipStream_t caller, const char* name) {
+  const std::string who =
+      name ? std::string(name) + ": " : (device ? "madipm_solver_adjoint_device: " : "madipm_solver_adjoint: ");
+  const double* const gx = ct.x;
+  const bool full = ct.y || ct.zl || ct.zu || ct.cons;
   QPHost& P = *H_;
   // ---- refusals, before anything is allocated or enqueued
   MADIPM_REQUIRE(solved_, who + "no solve has run on this solver yet");
@@ -3327,7 +3448,10 @@ void MPCSolver::adjoint(const double* gx, const madipm_qp_gradients& g, bool dev
   MADIPM_REQUIRE(kkt_ == KKT_K2, who + "only kkt_system = SparseKKTSystem (K2) is supported; the K2.5 and "
                                        "normal-equations formulations are left to a later release");
   MADIPM_REQUIRE(!comm_, who + "a solver created with a communicator (madipm_solver_create_dist) is not supported");
-  MADIPM_REQUIRE(gx, who + "gx is NULL");
+  if (name)
+    MADIPM_REQUIRE(gx || full, who + "all five cotangents are NULL");
+  else
+    MADIPM_REQUIRE(gx, who + "gx is NULL");
   double* const user[7] = {g.c, g.Hvals, g.Avals, g.lcon, g.ucon, g.lvar, g.uvar};
   MADIPM_REQUIRE(g.c || g.Hvals || g.Avals || g.lcon || g.ucon || g.lvar || g.uvar,
                  who + "all seven outputs are NULL");
@@ -3350,7 +3474,17 @@ void MPCSolver::adjoint(const double* gx, const madipm_qp_gradients& g, bool dev
   }
   Adjoint& a = *adj_;
   const double* cscale = device_con_scale();
-  if (!device && !a.gx.p) a.gx.alloc(std::max(nx_, 1));
+  if (!device && gx && !a.gx.p) a.gx.alloc(std::max(nx_, 1));
+  const double* const cot[4] = {ct.y, ct.zl, ct.zu, ct.cons};
+  const int64_t clen[4] = {m_, nx_, nx_, m_};
+  if (full) {
+    if (!a.shift.p) {
+      a.shift.alloc(std::max(n_ + m_, 1));
+      a.apx.alloc(std::max(nx_, 1));
+    }
+    for (int j = 0; j < 4; ++j)
+      if (!device && cot[j] && !a.ct[j].p) a.ct[j].alloc(std::max<int64_t>(clen[j], 1));
+  }
   if ((g.lcon || g.ucon) && !a.rowslack.p) {
     a.rowslack.upload(adjoint_rowslack(P), s);
     MADIPM_HIP(hipStreamSynchronize(s));
@@ -3411,18 +3545,32 @@ void MPCSolver::adjoint(const double* gx, const madipm_qp_gradients& g, bool dev
   }
   // ---- right-hand side, solve, residual
   const double* dgx = gx;
-  if (device) {  // gx is read after the work already enqueued on the caller's stream
+  const double* dct[4] = {cot[0], cot[1], cot[2], cot[3]};  // gy, gzl, gzu, gcons on the device
+  if (device) {  // the cotangents are read after the work already enqueued on the caller's stream
     MADIPM_HIP(hipEventRecord(a.ev[0], caller));
     MADIPM_HIP(hipStreamWaitEvent(s, a.ev[0], 0));
   } else {
-    a.gx.upload(gx, nx_, s);
-    dgx = a.gx.p;
+    if (gx) {
+      a.gx.upload(gx, nx_, s);
+      dgx = a.gx.p;
+    }
+    for (int j = 0; j < 4; ++j)
+      if (cot[j]) {
+        if (clen[j]) a.ct[j].upload(cot[j], clen[j], s);
+        dct[j] = a.ct[j].p;
+      }
   }
   const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
   const int64_t N = (int64_t)n_ + m_;
   const AdjArgs A{n_, m_, nx_, obj_scale_, P.sgn, a.sol.p, x_.p, xl_.p, xu_.p, zl_.p, zu_.p, y_.p,
                   cscale, lbpos_.p, ubpos_.p, fixed_.p};
-  k_adj_rhs<<<nb, NT, 0, s>>>(D, dgx, take_fact_end());
+  const AdjFull F{dct[1], dct[2], dct[3], a.apx.p};
+  if (full) {  // the shifted system K a~' = g' (§13d); p keeps g' for the residual
+    k_adj_shift<<<nb, NT, 0, s>>>(A, F, a.shift.p, take_fact_end());
+    SPMV_LAUNCH(k_adj_rhs_full, nbs, s, D, A, dgx, dct[0], (const double*)a.shift.p);
+  } else {
+    k_adj_rhs<<<nb, NT, 0, s>>>(D, dgx, take_fact_end());
+  }
   kkt_solve();
   k_adj_acc<<<nb, NT, 0, s>>>(a.sol.p, d_.p, N, 1);
   // iterative refinement towards the system without the regularisation (the factor is the regularised
@@ -3434,13 +3582,27 @@ void MPCSolver::adjoint(const double* gx, const madipm_qp_gradients& g, bool dev
   }
   SPMV_LAUNCH(k_adj_resid, nbs, s, D, A, a.sol.p, (double*)nullptr, a.rowres.p);
   k_adj_resmax<<<1, NT, 0, s>>>(a.rowres.p, p_.p, N, a.scal.p);
+  if (full && nx_) k_adj_unshift<<<blocks(nx_), NT, 0, s>>>(nx_, a.shift.p, a.sol.p, a.apx.p);
   // ---- gradients
-  if ((out[0] || out[3] || out[4] || out[5] || out[6]) && std::max(nx_, m_))
-    k_adj_vec<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, a.rowslack.p, out[0], out[5], out[6], out[3], out[4]);
-  if (needFix && a.nfix > 0)
-    k_adj_fix<<<blocks(a.nfix), NT, 0, s>>>(A, a.nfix, a.fix.p, a.fhsp.p, a.fh.p, a.fasp.p, a.fa.p, plan_->Hraw.p,
-                                             plan_->Araw.p, dgx, out[5]);
-  if (needA) k_adj_avals<<<blocks(na), NT, 0, s>>>(A, na, a.Ar.p, a.Ac.p, out[2]);
+  const bool vec = (out[0] || out[3] || out[4] || out[5] || out[6]) && std::max(nx_, m_);
+  const bool fix = needFix && a.nfix > 0;
+  if (full) {
+    if (vec)
+      k_adj_vec<true><<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, F, a.rowslack.p, out[0], out[5], out[6], out[3],
+                                                                out[4]);
+    if (fix)
+      k_adj_fix<true><<<blocks(a.nfix), NT, 0, s>>>(A, F, a.nfix, a.fix.p, a.fhsp.p, a.fh.p, a.fasp.p, a.fa.p,
+                                                     plan_->Hraw.p, plan_->Araw.p, dgx, out[5]);
+    if (needA) k_adj_avals<true><<<blocks(na), NT, 0, s>>>(A, F, na, a.Ar.p, a.Ac.p, out[2]);
+  } else {
+    if (vec)
+      k_adj_vec<false><<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, F, a.rowslack.p, out[0], out[5], out[6], out[3],
+                                                                 out[4]);
+    if (fix)
+      k_adj_fix<false><<<blocks(a.nfix), NT, 0, s>>>(A, F, a.nfix, a.fix.p, a.fhsp.p, a.fh.p, a.fasp.p, a.fa.p,
+                                                      plan_->Hraw.p, plan_->Araw.p, dgx, out[5]);
+    if (needA) k_adj_avals<false><<<blocks(na), NT, 0, s>>>(A, F, na, a.Ar.p, a.Ac.p, out[2]);
+  }
   if (needH) k_adj_hvals<<<blocks(nh), NT, 0, s>>>(A, nh, a.Hr.p, a.Hc.p, out[1]);
   MADIPM_HIP(hipGetLastError());
   if (device) {  // work enqueued on the caller's stream from now on sees the outputs

@@ -88,6 +88,11 @@ class MPCSolver {
   // solve; further calls on the same point reuse the factor.  device: gx and the outputs are device arrays
   // produced / consumed on `caller`.  Changes nothing a later initialize / solve / warm_start_last reads.
   void adjoint(const double* gx, const madipm_qp_gradients& out, bool device, hipStream_t caller);
+  // The same for a loss of all five solution blocks (madipm_solver_adjoint_full / _full_device):
+  // non-null fields of `g` are the cotangents of x, y, zl, zu and A x.  `name`: the entry point, for the
+  // messages.  With g.x alone this is adjoint()'s path, bit for bit.
+  void adjoint(const madipm_qp_cotangents& g, const madipm_qp_gradients& out, bool device, hipStream_t caller,
+               const char* name);
   void adjoint_info(int64_t* n_adjoints, int64_t* n_adjoint_factorizations, double* last_residual);
   int64_t n_analyses() const { return n_analyses_; }
   int64_t n_updates() const { return n_updates_; }

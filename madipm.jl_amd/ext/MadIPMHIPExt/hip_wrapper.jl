@@ -360,3 +360,45 @@ function solver_adjoint_info(h::Ptr{Cvoid})
                 h, na, nf, r), "madipm_solver_adjoint_info")
     return (n_adjoints = na[], n_adjoint_factorizations = nf[], last_residual = r[])
 end
+
+# ---- adjoint of all five solution blocks (ABI 0.2.8): the loss is l(x, y, zl, zu, A x).  madipm_qp_cotangents:
+# five pointers (x, y, zl, zu, cons; lengths nvar, ncon, nvar, nvar, ncon), a null one = absent (0), not all
+# five.  zl / zu of a variable without that bound and of a fixed variable are constants: their cotangents are
+# not read.  Outputs, conventions and refusals are solver_adjoint's; with gx alone the bits are its bits.
+struct MadipmQPCotangents
+    x::Ptr{Float64}
+    y::Ptr{Float64}
+    zl::Ptr{Float64}
+    zu::Ptr{Float64}
+    cons::Ptr{Float64}
+end
+
+# HOST vectors (or nothing)
+function solver_adjoint_full(h::Ptr{Cvoid}; gx=nothing, gy=nothing, gzl=nothing, gzu=nothing, gcons=nothing,
+                             c=nothing, Hvals=nothing, Avals=nothing, lcon=nothing, ucon=nothing, lvar=nothing,
+                             uvar=nothing)
+    GC.@preserve gx gy gzl gzu gcons c Hvals Avals lcon ucon lvar uvar begin
+        ct = Ref(MadipmQPCotangents(_ptr_or_null(gx), _ptr_or_null(gy), _ptr_or_null(gzl), _ptr_or_null(gzu),
+                                    _ptr_or_null(gcons)))
+        g = Ref(MadipmQPGradients(_ptr_or_null(c), _ptr_or_null(Hvals), _ptr_or_null(Avals), _ptr_or_null(lcon),
+                                  _ptr_or_null(ucon), _ptr_or_null(lvar), _ptr_or_null(uvar)))
+        check(ccall((:madipm_solver_adjoint_full, libmadipm), Cint,
+                    (Ptr{Cvoid}, Ref{MadipmQPCotangents}, Ref{MadipmQPGradients}), h, ct, g),
+              "madipm_solver_adjoint_full")
+    end
+    return
+end
+
+# DEVICE arrays (Ptr{Float64} into device memory, or nothing), with solver_adjoint_device's stream contract
+function solver_adjoint_full_device(h::Ptr{Cvoid}; gx=nothing, gy=nothing, gzl=nothing, gzu=nothing, gcons=nothing,
+                                    c=nothing, Hvals=nothing, Avals=nothing, lcon=nothing, ucon=nothing,
+                                    lvar=nothing, uvar=nothing, stream::Ptr{Cvoid}=C_NULL)
+    ct = Ref(MadipmQPCotangents(_dptr_or_null(gx), _dptr_or_null(gy), _dptr_or_null(gzl), _dptr_or_null(gzu),
+                                _dptr_or_null(gcons)))
+    g = Ref(MadipmQPGradients(_dptr_or_null(c), _dptr_or_null(Hvals), _dptr_or_null(Avals), _dptr_or_null(lcon),
+                              _dptr_or_null(ucon), _dptr_or_null(lvar), _dptr_or_null(uvar)))
+    check(ccall((:madipm_solver_adjoint_full_device, libmadipm), Cint,
+                (Ptr{Cvoid}, Ref{MadipmQPCotangents}, Ref{MadipmQPGradients}, Ptr{Cvoid}), h, ct, g, stream),
+          "madipm_solver_adjoint_full_device")
+    return
+end

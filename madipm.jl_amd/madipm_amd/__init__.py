@@ -19,6 +19,7 @@ def __getattr__(name):
                 "SOLVE_SUCCEEDED", "INFEASIBLE_PROBLEM_DETECTED", "MAXIMUM_ITERATIONS_EXCEEDED",
                 "MAXIMUM_WALLTIME_EXCEEDED", "DIVERGING_ITERATES", "ERROR_IN_STEP_COMPUTATION", "INTERNAL_ERROR",
                 "STATUS_NAMES", "RCCLComm", "HostComm", "SolveException", "UnfactorizedSolveException",
+                "ADJOINT_NAMES", "COTANGENT_NAMES",  # MPCSolver.adjoint's gradients; its cotangents' blocks
                 "MadIPMError"):  # MadIPMError: what MPCSolver.update raises on a change of classification
         from . import solver
         return getattr(solver, name)

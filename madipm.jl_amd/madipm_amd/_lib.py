@@ -126,6 +126,16 @@ _sig("madipm_solver_adjoint_device", C.c_int, [vp, f64p, C.POINTER(QPGrad), vp])
 _sig("madipm_solver_adjoint_info", C.c_int, [vp, i64p, i64p, f64p])
 
 
+# adjoint of all five solution blocks (ABI 0.2.8)
+class QPCot(C.Structure):
+    """madipm_qp_cotangents: dl/dx, dl/dy, dl/dzl, dl/dzu, dl/d(A x); a NULL pointer means absent (0)."""
+    _fields_ = [("x", f64p), ("y", f64p), ("zl", f64p), ("zu", f64p), ("cons", f64p)]
+
+
+_sig("madipm_solver_adjoint_full", C.c_int, [vp, C.POINTER(QPCot), C.POINTER(QPGrad)])
+_sig("madipm_solver_adjoint_full_device", C.c_int, [vp, C.POINTER(QPCot), C.POINTER(QPGrad), vp])
+
+
 class MadIPMError(RuntimeError):
     pass
 

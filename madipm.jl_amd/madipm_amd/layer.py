@@ -4,24 +4,36 @@
     x = layer(c=c, lvar=lvar)        # update_device -> solve -> solution_device, all on the GPU
     loss(x).backward()               # adjoint_device: one factorisation + one solve with the LDL^T on the device
 
+    layer = QPLayer(solver, outputs=("x", "y", "cons"))
+    x, y, cons = layer(c=c)          # the row multipliers and A x* are differentiable too
+
 Forward and backward stay on the device (MPCSolver.update_device / solution_device / adjoint_device); the
-gradients are those of MPCSolver.adjoint: of a loss that depends on x alone, K2 formulation.
+gradients are those of MPCSolver.adjoint, K2 formulation.
 `import torch` comes before this package in the process, as for every device-route call.
 """
 from __future__ import annotations
 
 import torch
 
-from .solver import ADJOINT_NAMES, SOLVE_SUCCEEDED, STATUS_NAMES, MadIPMError
+from .solver import ADJOINT_NAMES, SOLVE_SUCCEEDED, STATUS_NAMES, MadIPMError, check_layer_outputs
+
+# output name -> (key of MPCSolver.solution_device(), cotangent keyword of MPCSolver.adjoint_device())
+_OUTPUTS = {"x": ("solution", "gx"), "y": ("multipliers", "gy"), "zl": ("multipliers_L", "gzl"),
+            "zu": ("multipliers_U", "gzu"), "cons": ("constraints", "gcons")}
 
 
 class QPFunction(torch.autograd.Function):
     """forward(solver, c, Hvals, Avals, lcon, ucon, lvar, uvar) -> x; a tensor left None keeps the solver's
     current data.  backward asks adjoint_device for exactly the gradients of the tensors that require grad,
-    and must run before the solver is updated or solved again (the adjoint belongs to the last solve)."""
+    and must run before the solver is updated or solved again (the adjoint belongs to the last solve).
+    A tuple of names from ("x", "y", "zl", "zu", "cons") as a ninth argument selects the outputs: forward then
+    returns that tuple of tensors, and backward passes on the cotangents of those the loss used."""
 
     @staticmethod
     def forward(ctx, solver, *data):
+        outputs = None
+        if len(data) > len(ADJOINT_NAMES):
+            data, outputs = data[:len(ADJOINT_NAMES)], data[len(ADJOINT_NAMES)]
         given = {k: t.detach() for k, t in zip(ADJOINT_NAMES, data) if t is not None}
         if given:
             solver.update_device(**given)
@@ -31,16 +43,28 @@ class QPFunction(torch.autograd.Function):
                               "not SOLVE_SUCCEEDED: no solution to differentiate")
         ctx.solver = solver
         ctx.names = ADJOINT_NAMES
-        return solver.solution_device()["solution"]
+        ctx.outputs = outputs
+        if outputs is None:
+            return solver.solution_device()["solution"]
+        ctx.set_materialize_grads(False)   # an output the loss did not use arrives as None and stays absent
+        sol = solver.solution_device()
+        return tuple(sol[_OUTPUTS[k][0]] for k in outputs)
 
     @staticmethod
-    def backward(ctx, gx):
-        # needs_input_grad[0] is the solver's; one entry per data tensor follows
+    def backward(ctx, *grads):
+        # needs_input_grad[0] is the solver's; one entry per data tensor follows (then the outputs' tuple)
+        nin = len(ctx.needs_input_grad)
         want = [k for k, need in zip(ctx.names, ctx.needs_input_grad[1:]) if need]
         if not want:
-            return (None,) * (1 + len(ctx.names))
-        g = ctx.solver.adjoint_device(gx.contiguous(), want=want)
-        return (None,) + tuple(g.get(k) for k in ctx.names)
+            return (None,) * nin
+        if ctx.outputs is None:
+            g = ctx.solver.adjoint_device(grads[0].contiguous(), want=want)
+        else:
+            cot = {_OUTPUTS[k][1]: t.contiguous() for k, t in zip(ctx.outputs, grads) if t is not None}
+            if not cot:
+                return (None,) * nin
+            g = ctx.solver.adjoint_device(cot.pop("gx", None), want=want, **cot)
+        return ((None,) + tuple(g.get(k) for k in ctx.names) + (None,) * nin)[:nin]
 
 
 class QPLayer(torch.nn.Module):
@@ -48,11 +72,20 @@ class QPLayer(torch.nn.Module):
     solver's GPU with the shapes MPCSolver.update_device expects; an argument left None keeps the solver's
     current numbers.  One tensor may be passed as both bounds of the equality rows (lcon and ucon) or of the
     fixed variables: the whole derivative arrives through the lower one and the upper one adds 0.  Raises
-    MadIPMError when the solve does not end with SOLVE_SUCCEEDED."""
+    MadIPMError when the solve does not end with SOLVE_SUCCEEDED.
 
-    def __init__(self, solver):
+    outputs: the default ("x",) returns the one tensor x*.  Any other ordered selection out of ("x", "y",
+    "zl", "zu", "cons") returns that tuple of MPCSolver.solution_device()'s solution, multipliers,
+    multipliers_L, multipliers_U and constraints, all differentiable; backward hands the solver the
+    cotangents of the outputs the loss used and no others.  zl / zu of a variable without that bound, and of
+    a fixed variable, are constants (0)."""
+
+    def __init__(self, solver, outputs=("x",)):
         super().__init__()
         self.solver = solver
+        self.outputs = check_layer_outputs(outputs)
 
     def forward(self, c=None, Hvals=None, Avals=None, lcon=None, ucon=None, lvar=None, uvar=None):
-        return QPFunction.apply(self.solver, c, Hvals, Avals, lcon, ucon, lvar, uvar)
+        if self.outputs == ("x",):
+            return QPFunction.apply(self.solver, c, Hvals, Avals, lcon, ucon, lvar, uvar)
+        return QPFunction.apply(self.solver, c, Hvals, Avals, lcon, ucon, lvar, uvar, self.outputs)

@@ -206,6 +206,49 @@ def check_adjoint_want(want) -> tuple:
     return tuple(k for k in ADJOINT_NAMES if k in want)
 
 
+COTANGENT_NAMES = ("x", "y", "zl", "zu", "cons")   # madipm_qp_cotangents' fields; gx, gy, gzl, gzu, gcons
+
+
+def check_adjoint_cotangents(nvar: int, ncon: int, gx=None, gy=None, gzl=None, gzu=None, gcons=None, *,
+                             on_device: bool = False, device=None, who: str = "adjoint") -> dict:
+    """The cotangent arguments of MPCSolver.adjoint / adjoint_device, before any library call: gx, gzl, gzu of
+    shape (nvar,), gy, gcons of shape (ncon,), each optional (None: 0) but not all five.  Host route: each is
+    converted to a C-contiguous float64 array.  Device route (on_device): each must pass check_device_array.
+    Returns {field of madipm_qp_cotangents: array} of those given, in COTANGENT_NAMES order."""
+    given = {}
+    for field, name, a, length in (("x", "gx", gx, nvar), ("y", "gy", gy, ncon), ("zl", "gzl", gzl, nvar),
+                                   ("zu", "gzu", gzu, nvar), ("cons", "gcons", gcons, ncon)):
+        if a is None:
+            continue
+        if on_device:
+            check_device_array(name, a, length, device, who=who)
+        else:
+            a = np.array(a, dtype=np.float64, order="C", ndmin=1)
+            if a.shape != (int(length),):
+                raise ValueError(f"{who}: {name} has shape {a.shape}, expected ({int(length)},)")
+        given[field] = a
+    if not given:
+        raise ValueError(f"{who}: no cotangent given; pass at least one of gx, gy, gzl, gzu, gcons")
+    return given
+
+
+def check_layer_outputs(outputs) -> tuple:
+    """The `outputs` argument of QPLayer: an ordered selection out of COTANGENT_NAMES without repeats.
+    Returns it as a tuple; TypeError for a bare string, ValueError for an unknown or repeated name or an
+    empty selection."""
+    if isinstance(outputs, str):
+        raise TypeError(f"QPLayer: outputs must be a collection of names, not the string {outputs!r}")
+    outputs = tuple(outputs)
+    unknown = [k for k in outputs if k not in COTANGENT_NAMES]
+    if unknown:
+        raise ValueError(f"QPLayer: unknown name(s) {unknown} in outputs; the blocks are {list(COTANGENT_NAMES)}")
+    if len(set(outputs)) != len(outputs):
+        raise ValueError(f"QPLayer: a name is repeated in outputs {list(outputs)}")
+    if not outputs:
+        raise ValueError("QPLayer: outputs is empty")
+    return outputs
+
+
 class RCCLComm:
     """RCCL communicator of the sharded factorisation (one process per GPU; madipm_comm_*).
 
@@ -682,7 +725,7 @@ class MPCSolver:
         if "Avals" in names or "Hvals" in names or ("lvar" in names and np.any(self.qp.lvar == self.qp.uvar)):
             self._prepare_update()
 
-    def adjoint(self, gx, want=None) -> dict:
+    def adjoint(self, gx=None, want=None, *, gy=None, gzl=None, gzu=None, gcons=None) -> dict:
         """Gradients of a loss l(x*) with respect to the problem data, given gx = dl/dx* (length nvar) at the
         optimum the last solve() returned: a dict of numpy arrays over `want`, a subset of ADJOINT_NAMES
         (None: all seven), Hvals / Avals in the creation-time COO order.  An infinite bound gets 0; a fixed
@@ -690,45 +733,65 @@ class MPCSolver:
         The first call after a solve factorises the KKT matrix of the optimum once; further calls on the same
         point reuse the factor.  The solver's state is untouched: the next solve() is what it would have been.
         MadIPMError when the last solve did not succeed, when an update or initialize ran since, for the
-        K2.5 / normal-equations formulations and for a solver created with `comm`."""
+        K2.5 / normal-equations formulations and for a solver created with `comm`.
+
+        A loss l(x, y, zl, zu, cons) of everything solve() returns: gy, gzl, gzu and gcons are
+        its derivatives with respect to multipliers, multipliers_L, multipliers_U and constraints (= A x),
+        lengths ncon, nvar, nvar, ncon; any of the five may be None (0), not all.  Constants, whose
+        cotangents are ignored: zl_i / zu_i of a variable without that bound and zl, zu of a fixed variable
+        (solve() returns 0 there).  With gx alone the call is the one above, bit for bit."""
         names = check_adjoint_want(want)
-        gx = np.array(gx, dtype=np.float64, order="C", ndmin=1)
-        if gx.shape != (self.qp.nvar,):
-            raise ValueError(f"adjoint: gx has shape {gx.shape}, expected ({self.qp.nvar},)")
+        given = check_adjoint_cotangents(self.qp.nvar, self.qp.ncon, gx, gy, gzl, gzu, gcons)
         size = self._adjoint_sizes()
         buf = {k: np.empty(max(size[k], 1)) for k in names}  # an empty output still has a non-null address
         g = L.QPGrad()
         for k in names:
             setattr(g, k, L.ptr(buf[k], C.c_double))
         self._adjoint_prepare(names)
-        gxp = L.ptr(gx if gx.size else np.zeros(1), C.c_double)
-        L.check(L.lib.madipm_solver_adjoint(self.h, gxp, C.byref(g)), "adjoint")
+        # an empty block (ncon = 0) has nothing to read: any non-null address says "given"
+        p = {k: L.ptr(a if a.size else np.zeros(1), C.c_double) for k, a in given.items()}
+        if list(given) == ["x"]:
+            L.check(L.lib.madipm_solver_adjoint(self.h, p["x"], C.byref(g)), "adjoint")
+        else:
+            ct = L.QPCot(**p)
+            L.check(L.lib.madipm_solver_adjoint_full(self.h, C.byref(ct), C.byref(g)), "adjoint")
         return {k: buf[k][:size[k]] for k in names}
 
-    def adjoint_device(self, gx, want=None, stream=None) -> dict:
-        """adjoint() from and into torch tensors on the solver's GPU (gx: float64, contiguous, shape (nvar,)),
-        without a copy through the host.  `stream` is the torch.cuda.Stream gx was produced on (None: the
-        current stream): gx is read after the work enqueued on it, and work enqueued on it after the call
-        sees the returned tensors.  The arguments are checked before any library call."""
+    def adjoint_device(self, gx=None, want=None, stream=None, *, gy=None, gzl=None, gzu=None, gcons=None) -> dict:
+        """adjoint() from and into torch tensors on the solver's GPU (every cotangent: float64, contiguous, the
+        shape adjoint() expects), without a copy through the host.  `stream` is the torch.cuda.Stream the
+        cotangents were produced on (None: the current stream): they are read after the work enqueued on it,
+        and work enqueued on it after the call sees the returned tensors.  The arguments are checked before
+        any library call."""
         names = check_adjoint_want(want)
-        check_device_array("gx", gx, self.qp.nvar, self._device, who="adjoint_device")
+        nvar, ncon = self.qp.nvar, self.qp.ncon
+        given = check_adjoint_cotangents(nvar, ncon, gx, gy, gzl, gzu, gcons, on_device=True, device=self._device,
+                                         who="adjoint_device")
         import torch
         if stream is not None and not isinstance(stream, torch.cuda.Stream):
             raise TypeError(f"adjoint_device: stream must be a torch.cuda.Stream, not {type(stream).__name__}")
         if self._device is None:
             self._device = torch.device("cuda", torch.cuda.current_device())
-            check_device_array("gx", gx, self.qp.nvar, self._device, who="adjoint_device")
+            check_adjoint_cotangents(nvar, ncon, gx, gy, gzl, gzu, gcons, on_device=True, device=self._device,
+                                     who="adjoint_device")
         st = stream if stream is not None else torch.cuda.current_stream(self._device)
         size = self._adjoint_sizes()
         with torch.cuda.stream(st):
             buf = {k: torch.empty(max(size[k], 1), dtype=torch.float64, device=self._device) for k in names}
-            gxd = gx if gx.numel() else torch.zeros(1, dtype=torch.float64, device=self._device)
+            keep = {k: a if a.numel() else torch.zeros(1, dtype=torch.float64, device=self._device)
+                    for k, a in given.items()}
         g = L.QPGrad()
         for k in names:
             setattr(g, k, C.cast(buf[k].data_ptr(), L.f64p))
         self._adjoint_prepare(names)
-        L.check(L.lib.madipm_solver_adjoint_device(self.h, C.cast(gxd.data_ptr(), L.f64p), C.byref(g),
-                                                   L.vp(st.cuda_stream)), "adjoint_device")
+        p = {k: C.cast(a.data_ptr(), L.f64p) for k, a in keep.items()}
+        if list(given) == ["x"]:
+            L.check(L.lib.madipm_solver_adjoint_device(self.h, p["x"], C.byref(g), L.vp(st.cuda_stream)),
+                    "adjoint_device")
+        else:
+            ct = L.QPCot(**p)
+            L.check(L.lib.madipm_solver_adjoint_full_device(self.h, C.byref(ct), C.byref(g), L.vp(st.cuda_stream)),
+                    "adjoint_device")
         return {k: buf[k][:size[k]] for k in names}
 
     def adjoint_info(self) -> dict:

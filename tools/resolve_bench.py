@@ -26,7 +26,12 @@ same data.  Without the option nothing of it runs and the output is as before.
 update_device + solve, adjoint_device of a seeded gx for all seven gradients, stream synchronised:
 adjoint_s (the first adjoint on a point: the factorisation of its KKT matrix + one solve + the gradient
 kernels) beside adjoint_solve_s (the solve before it) and adjoint_again_s (a second gx on the same point,
-which reuses the factor), adjoint_residual (the largest last_residual) and adjoint_status."""
+which reuses the factor), adjoint_residual (the largest last_residual) and adjoint_status.
+
+--adjoint-full is --adjoint with one more call per point, after the two above and on the same factor:
+adjoint_device with seeded cotangents of all five solution blocks (gx, gy, gzl, gzu, gcons), for all seven
+gradients: adjoint_full_s beside adjoint_again_s, and adjoint_full_residual, the largest last_residual of
+those calls (the residual of the shifted system)."""
 import dataclasses
 import json
 import os
@@ -56,7 +61,7 @@ def perturb(qp, rng):
                 lvar=qp.lvar * fv, uvar=qp.uvar * fv, lcon=qp.lcon * fc, ucon=qp.ucon * fc)
 
 
-def run(name, warm=None, adjoint=False):
+def run(name, warm=None, adjoint=False, adjoint_full=False):
     qp, desc = bench.build_problem(name)
     opts = bench.solver_opts()
     MPCSolver(qp, **opts)                      # the first construction of a process pays one-off set-up
@@ -147,6 +152,7 @@ def run(name, warm=None, adjoint=False):
         perturb(qp, rng)
         grng = np.random.default_rng(1)
         asol, afirst, aagain, astat, ares = [], [], [], set(), 0.0
+        afull, afres = [], 0.0
         for rep in range(WARMUP + REPS):
             dnew = {k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()}
             gx = torch.as_tensor(grng.standard_normal(qp.nvar), device="cuda")
@@ -168,6 +174,17 @@ def run(name, warm=None, adjoint=False):
             torch.cuda.current_stream().synchronize()
             t_again = time.perf_counter() - t
             ares = max(ares, s.adjoint_info()["last_residual"])
+            if adjoint_full:
+                draw = lambda k: torch.as_tensor(grng.standard_normal(k), device="cuda")  # noqa: E731
+                cot = dict(gy=draw(qp.ncon), gzl=draw(qp.nvar), gzu=draw(qp.nvar), gcons=draw(qp.ncon))
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                s.adjoint_device(gx, **cot)
+                torch.cuda.current_stream().synchronize()
+                t_full = time.perf_counter() - t
+                afres = max(afres, s.adjoint_info()["last_residual"])
+                if rep >= WARMUP:
+                    afull.append(t_full)
             if rep >= WARMUP:
                 asol.append(t_solve)
                 afirst.append(t_first)
@@ -175,6 +192,8 @@ def run(name, warm=None, adjoint=False):
         med = lambda v: statistics.median(v) if v else float("nan")  # noqa: E731
         wres.update({"adjoint_s": med(afirst), "adjoint_again_s": med(aagain), "adjoint_solve_s": med(asol),
                      "adjoint_residual": ares, "adjoint_status": sorted(astat), **s.adjoint_info()})
+        if adjoint_full:
+            wres.update({"adjoint_full_s": med(afull), "adjoint_full_residual": afres})
         c = s.counters()
     update_s, solve_s = statistics.median(upd), statistics.median(sol)
     return {**wres, "instance": name, "description": desc, "nvar": qp.nvar, "ncon": qp.ncon, "nnzj": qp.nnzj, "nnzh": qp.nnzh,
@@ -205,11 +224,14 @@ def main():
         k = args.index("--warm")
         warm = float(args[k + 1])
         del args[k:k + 2]
-    adjoint = "--adjoint" in args
-    if adjoint:
+    adjoint_full = "--adjoint-full" in args
+    if adjoint_full:
+        args.remove("--adjoint-full")
+    adjoint = "--adjoint" in args or adjoint_full
+    if "--adjoint" in args:
         args.remove("--adjoint")
     for name in args or ["ex10", "supportcase10"]:
-        r = run(name, warm, adjoint)
+        r = run(name, warm, adjoint, adjoint_full)
         print(f"{name}: construct_s {r['construct_s']:.4f}  prepare_update_s {r['prepare_update_s']:.4f}  "
               f"update_s {r['update_s']:.5f}  solve_s {r['solve_s']:.4f}  ->  update + solve "
               f"{r['update_plus_solve_s']:.4f} s against construct + solve {r['construct_plus_solve_s']:.4f} s "
@@ -226,6 +248,9 @@ def main():
             print(f"{name}: adjoint (seven gradients): {r['adjoint_s']:.4f} s after a solve of "
                   f"{r['adjoint_solve_s']:.4f} s; a second gx on the same point {r['adjoint_again_s']:.4f} s; "
                   f"residual <= {r['adjoint_residual']:.1e}, status {r['adjoint_status']}", flush=True)
+        if adjoint_full:
+            print(f"{name}: adjoint with all five cotangents on the same point {r['adjoint_full_s']:.4f} s, "
+                  f"residual <= {r['adjoint_full_residual']:.1e}", flush=True)
         out.append(r)
     print(json.dumps({"resolve_bench": out, "warmup": WARMUP, "reps": REPS, "rel_noise": REL}))
 
