@@ -583,6 +583,51 @@ int madipm_solver_adjoint_full(madipm_solver_t s, const madipm_qp_cotangents* g,
 int madipm_solver_adjoint_full_device(madipm_solver_t s, const madipm_qp_cotangents* d_g,
                                       const madipm_qp_gradients* d_out, madipm_stream_t stream);
 
+/* ------------------------------------------------------------------ forward-mode sensitivities  [ABI 0.2.9, additive]
+ * The transpose of the adjoint: given a DIRECTION in the data (dc, dHvals, dAvals, dlcon, ducon, dlvar, duvar),
+ * the directional derivative (dx, dy, dzl, dzu, dcons) of everything madipm_solver_get_solution returns, at
+ * the end point of the last successful solve: x*(theta + t d) = x* + t dx + O(t^2), the first-order prediction
+ * of a re-solve, or one column of the Jacobian per call.  (Three symbols and two structs; madipm_version()
+ * still returns 203; nothing above changed.)
+ * Every non-NULL field of madipm_qp_directions is one direction block, with the lengths and the COO order of
+ * madipm_qp_gradients; a NULL field is read as 0; duplicated COO entries are separate parameters that add.
+ * Conventions, the transposes of the adjoint's: an entry on an infinite bound is not read; for a fixed
+ * variable the common value moves by lvar's entry and uvar's is not read; for an equality row it moves by
+ * lcon's entry and ucon's is not read (so one array passed as both bounds stays right); c0 has no direction.
+ * Every non-NULL field of madipm_qp_point_tangents receives that block's derivative (x, zl, zu of length nvar;
+ * y, cons of length ncon); dzl_i / dzu_i is 0 for a variable without that bound and for a fixed variable.
+ * One solve with the factor madipm_solver_adjoint uses (one factorisation per solved point serves the adjoint
+ * and the tangent, in either order; n_adjoint_factorizations counts it), plus its two refinement steps
+ * towards the matrix without the regularisation, with the right-hand side and the outputs in a shifted form
+ * in which no product of Sigma = z / gap (1e8 and more at an active bound) with a direction remains (DESIGN
+ * §13e).  Nothing a later madipm_solver_initialize / _solve / _warm_start_last reads is changed.
+ * Refused as madipm_solver_adjoint refuses (before the first solve; a last status other than SOLVE_SUCCEEDED;
+ * an update / update_device / initialize that no solve followed; kkt_system 1 or 2; a solver made by
+ * madipm_solver_create_dist), and when all seven directions or all five outputs are NULL.  Directions in
+ * Hvals, Avals, and in lvar on a problem with fixed variables, need madipm_solver_prepare_update first (the raw
+ * values and index arrays it keeps).
+ * Memory, each part allocated by the first call that needs it and never again: madipm_solver_adjoint's scratch
+ * and that of its five-block call if no adjoint allocated them (8 B x (4 nvar + 3 ncon + 3 inequality rows + 2),
+ * 4 B per row), 8 B x (2 nvar + ncon + 2 inequality rows + 1) of its own; with a direction that needs
+ * prepare_update, 16 B per entry of A, 8 B per endpoint of a stored entry of H (16 B off the diagonal) and
+ * 4 B x (2 nvar + ncon + 3) of list starts; on the host route 8 B per entry of each direction given and each
+ * output asked for.  A solver that never calls it pays nothing.
+ *
+ * madipm_solver_tangent: HOST pointers, read / written during the call. */
+typedef struct madipm_qp_directions { const double *c, *Hvals, *Avals, *lcon, *ucon, *lvar, *uvar; } madipm_qp_directions; /* NULL = 0 */
+typedef struct madipm_qp_point_tangents { double *x, *y, *zl, *zu, *cons; } madipm_qp_point_tangents; /* NULL = not wanted */
+int madipm_solver_tangent(madipm_solver_t s, const madipm_qp_directions* d, const madipm_qp_point_tangents* out);
+/* DEVICE pointers.  The directions have the stream contract of madipm_solver_adjoint_device's cotangents (read
+ * after the work already enqueued on `stream`), the outputs that of its outputs (work enqueued on `stream`
+ * after the call returns sees them).  The first call on a point waits, on the host, for the status of its
+ * factorisation. */
+int madipm_solver_tangent_device(madipm_solver_t s, const madipm_qp_directions* d_d,
+                                 const madipm_qp_point_tangents* d_out, madipm_stream_t stream);
+/* n_tangents: successful tangent calls; last_residual: ||r - K w||_inf / max(1, ||r||_inf) of the last call's
+ * refined solution of the shifted system, as madipm_solver_adjoint_info reports it for the adjoint (the two
+ * do not overwrite each other; synchronises the solver's stream).  Any pointer may be NULL. */
+int madipm_solver_tangent_info(madipm_solver_t s, int64_t* n_tangents, double* last_residual);
+
 #ifdef __cplusplus
 }
 #endif

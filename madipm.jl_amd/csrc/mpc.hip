@@ -116,6 +116,21 @@ struct Adjoint {
   }
 };
 
+// The tangent (madipm_solver_tangent*) shares the adjoint's factor, solution, residual rows and
+// events.  Its own, each allocated by the first call that needs it: the data terms and the full dx
+// (8 B x (2 n + m + 1)); the shift vector is the adjoint's `shift`; rowslack as there; with Hvals / Avals (or
+// lvar on a problem with fixed variables) the entry lists of build_tangent_lists: 16 B per entry of A, 8 B per
+// endpoint of a stored entry of H, 4 B x (2 nvar + ncon) list starts; the host route's staging of the
+// directions given and the outputs wanted (8 B per entry).
+struct Tangent {
+  DBuf<double> base, dx, scal;            // data terms of the right-hand side; [dx; 0]; residual ratio
+  DBuf<int32_t> asp, csp, gsp;            // list starts: A per row, A per column, H per endpoint
+  DBuf<int2> ae, ce, ge;                  // (entry, column), (entry, row), (entry, other endpoint)
+  bool lists = false;
+  DBuf<double> dir[7], out[5];            // host route: c, Hvals, Avals, lcon, ucon, lvar, uvar; x, y, zl, zu, cons
+  int64_t n_tangents = 0;
+};
+
 namespace {
 
 constexpr int NT = 256;
@@ -3138,9 +3153,8 @@ void MPCSolver::get_solution(double* x, double* y, double* zl, double* zu, doubl
 // same factor and refinement with the shifted right-hand side K a~' = g' (k_adj_shift, k_adj_rhs_full),
 // a~ = a~' - [q~; 0; 0] (k_adj_unshift), and the <true> instantiations of the gradient kernels.
 namespace madipm {
-namespace {
 
-struct AdjArgs {
+struct AdjArgs {  // named in mpc.hpp (sens_solve)
   int n, m, nx;
   double os, sgn;                                  // obj_scale; +1 minimize, -1 maximize
   const double *d, *x, *xl, *xu, *zl, *zu, *y;     // a~ = [a~x; a~s; a~y]; the iterate (scaled space)
@@ -3148,6 +3162,8 @@ struct AdjArgs {
   const int32_t *lbpos, *ubpos;
   const uint8_t* fixed;
 };
+
+namespace {
 
 __device__ __forceinline__ double adj_ax(const AdjArgs& A, int i) { return A.fixed[i] ? 0.0 : A.os * A.d[i]; }
 __device__ __forceinline__ double adj_ay(const AdjArgs& A, int r) { return A.cscale[r] * A.d[A.n + r]; }
@@ -3424,6 +3440,79 @@ static int adj_refine_steps() {
   return k;
 }
 
+// ---- what the adjoint and the tangent (§13e) share: the refusals, the scratch, the factor, the solves
+void MPCSolver::sens_refuse(const std::string& who) const {
+  MADIPM_REQUIRE(solved_, who + "no solve has run on this solver yet");
+  MADIPM_REQUIRE(point_ok_ && !initialized_ && solve_updates_ == n_updates_,
+                 who + "an update, update_device or initialize ran since the last solve, so the iterate no longer "
+                       "belongs to the problem data (solve first)");
+  MADIPM_REQUIRE(status_ == MADIPM_SOLVE_SUCCEEDED, who + "the last solve ended with status " +
+                                                        std::to_string(status_) + ", not SOLVE_SUCCEEDED");
+  MADIPM_REQUIRE(kkt_ == KKT_K2, who + "only kkt_system = SparseKKTSystem (K2) is supported; the K2.5 and "
+                                       "normal-equations formulations are left to a later release");
+  MADIPM_REQUIRE(!comm_, who + "a solver created with a communicator (madipm_solver_create_dist) is not supported");
+}
+
+Adjoint& MPCSolver::sens_state() {
+  if (!adj_) {
+    auto a = std::make_unique<Adjoint>();
+    a->rowres.alloc(std::max(n_ + m_, 1));
+    a->sol.alloc(std::max(n_ + m_, 1));
+    a->scal.alloc(2);
+    a->scal.zero(stream_);
+    MADIPM_HIP(hipEventCreateWithFlags(&a->ev[0], hipEventDisableTiming));
+    MADIPM_HIP(hipEventCreateWithFlags(&a->ev[1], hipEventDisableTiming));
+    adj_ = std::move(a);
+  }
+  return *adj_;
+}
+
+// the factor of the K2 matrix at the final iterate: once per solve
+void MPCSolver::sens_factor(Adjoint& a, const std::string& who) {
+  if (a.fact_solve == n_solves_) return;
+  a.fact_solve = -1;
+  double dw = 0.0, dc = 0.0;  // the options' regularisation; Adaptive: the current pair, not decayed
+  if (opt_.regularization == 1) {
+    dw = opt_.delta_p;
+    dc = opt_.delta_d;
+  } else if (opt_.regularization != 0) {
+    dw = adapt_dp_;
+    dc = adapt_dd_;
+  }
+  bool ok = false;
+  for (int trial = 0; trial < 3 && !ok; ++trial) {  // factorize_regularized_system!'s trials
+    if (trial) {
+      dw *= 100.0;
+      dc *= 100.0;
+    }
+    factor_enqueue(dw, dc);
+    ok = ldl_->status(stream_) == 0;
+  }
+  if (!ok) throw Error(who + "the factorisation of the KKT system at the solution failed in all three trials", -4);
+  a.fact_solve = n_solves_;
+  ++a.n_fact;
+}
+
+// With the right-hand side in d (and in p, which keeps it): a.sol = K^-1 p, refined; the residual ratio
+// into resid[0]
+void MPCSolver::sens_solve(Adjoint& a, const AdjArgs& A, double* resid) {
+  DV_ARGS;
+  hipStream_t s = stream_;
+  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
+  const int64_t N = (int64_t)n_ + m_;
+  kkt_solve();
+  k_adj_acc<<<nb, NT, 0, s>>>(a.sol.p, d_.p, N, 1);
+  // iterative refinement towards the system without the regularisation (the factor is the regularised
+  // matrix's: each step gains about -log10(delta |K^-1|) digits); a fixed count, so nothing is read back
+  for (int it = 0; it < adj_refine_steps(); ++it) {
+    SPMV_LAUNCH(k_adj_resid, nbs, s, D, A, a.sol.p, d_.p, a.rowres.p);
+    kkt_solve();
+    k_adj_acc<<<nb, NT, 0, s>>>(a.sol.p, d_.p, N, 0);
+  }
+  SPMV_LAUNCH(k_adj_resid, nbs, s, D, A, a.sol.p, (double*)nullptr, a.rowres.p);
+  k_adj_resmax<<<1, NT, 0, s>>>(a.rowres.p, p_.p, N, resid);
+}
+
 void MPCSolver::adjoint(const double* gx, const madipm_qp_gradients& g, bool device, hipStream_t caller) {
   adjoint(madipm_qp_cotangents{gx, nullptr, nullptr, nullptr, nullptr}, g, device, caller, nullptr);
 }
@@ -3439,15 +3528,7 @@ void MPCSolver::adjoint(const madipm_qp_cotangents& ct, const madipm_qp_gradient
   const bool full = ct.y || ct.zl || ct.zu || ct.cons;
   QPHost& P = *H_;
   // ---- refusals, before anything is allocated or enqueued
-  MADIPM_REQUIRE(solved_, who + "no solve has run on this solver yet");
-  MADIPM_REQUIRE(point_ok_ && !initialized_ && solve_updates_ == n_updates_,
-                 who + "an update, update_device or initialize ran since the last solve, so the iterate no longer "
-                       "belongs to the problem data (solve first)");
-  MADIPM_REQUIRE(status_ == MADIPM_SOLVE_SUCCEEDED, who + "the last solve ended with status " +
-                                                        std::to_string(status_) + ", not SOLVE_SUCCEEDED");
-  MADIPM_REQUIRE(kkt_ == KKT_K2, who + "only kkt_system = SparseKKTSystem (K2) is supported; the K2.5 and "
-                                       "normal-equations formulations are left to a later release");
-  MADIPM_REQUIRE(!comm_, who + "a solver created with a communicator (madipm_solver_create_dist) is not supported");
+  sens_refuse(who);
   if (name)
     MADIPM_REQUIRE(gx || full, who + "all five cotangents are NULL");
   else
@@ -3462,17 +3543,7 @@ void MPCSolver::adjoint(const madipm_qp_cotangents& ct, const madipm_qp_gradient
                        "madipm_solver_prepare_update first (it keeps the index arrays and the raw values)");
   hipStream_t s = stream_;
   // ---- allocations, each by the first call that needs it
-  if (!adj_) {
-    auto a = std::make_unique<Adjoint>();
-    a->rowres.alloc(std::max(n_ + m_, 1));
-    a->sol.alloc(std::max(n_ + m_, 1));
-    a->scal.alloc(2);
-    a->scal.zero(s);
-    MADIPM_HIP(hipEventCreateWithFlags(&a->ev[0], hipEventDisableTiming));
-    MADIPM_HIP(hipEventCreateWithFlags(&a->ev[1], hipEventDisableTiming));
-    adj_ = std::move(a);
-  }
-  Adjoint& a = *adj_;
+  Adjoint& a = sens_state();
   const double* cscale = device_con_scale();
   if (!device && gx && !a.gx.p) a.gx.alloc(std::max(nx_, 1));
   const double* const cot[4] = {ct.y, ct.zl, ct.zu, ct.cons};
@@ -3520,29 +3591,7 @@ void MPCSolver::adjoint(const madipm_qp_cotangents& ct, const madipm_qp_gradient
   }
   // ---- the factor of the K2 matrix at the final iterate: once per solve
   DV_ARGS;
-  if (a.fact_solve != n_solves_) {
-    a.fact_solve = -1;
-    double dw = 0.0, dc = 0.0;  // the options' regularisation; Adaptive: the current pair, not decayed
-    if (opt_.regularization == 1) {
-      dw = opt_.delta_p;
-      dc = opt_.delta_d;
-    } else if (opt_.regularization != 0) {
-      dw = adapt_dp_;
-      dc = adapt_dd_;
-    }
-    bool ok = false;
-    for (int trial = 0; trial < 3 && !ok; ++trial) {  // factorize_regularized_system!'s trials
-      if (trial) {
-        dw *= 100.0;
-        dc *= 100.0;
-      }
-      factor_enqueue(dw, dc);
-      ok = ldl_->status(s) == 0;
-    }
-    if (!ok) throw Error(who + "the factorisation of the KKT system at the solution failed in all three trials", -4);
-    a.fact_solve = n_solves_;
-    ++a.n_fact;
-  }
+  sens_factor(a, who);
   // ---- right-hand side, solve, residual
   const double* dgx = gx;
   const double* dct[4] = {cot[0], cot[1], cot[2], cot[3]};  // gy, gzl, gzu, gcons on the device
@@ -3561,7 +3610,6 @@ void MPCSolver::adjoint(const madipm_qp_cotangents& ct, const madipm_qp_gradient
       }
   }
   const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
-  const int64_t N = (int64_t)n_ + m_;
   const AdjArgs A{n_, m_, nx_, obj_scale_, P.sgn, a.sol.p, x_.p, xl_.p, xu_.p, zl_.p, zu_.p, y_.p,
                   cscale, lbpos_.p, ubpos_.p, fixed_.p};
   const AdjFull F{dct[1], dct[2], dct[3], a.apx.p};
@@ -3571,17 +3619,7 @@ void MPCSolver::adjoint(const madipm_qp_cotangents& ct, const madipm_qp_gradient
   } else {
     k_adj_rhs<<<nb, NT, 0, s>>>(D, dgx, take_fact_end());
   }
-  kkt_solve();
-  k_adj_acc<<<nb, NT, 0, s>>>(a.sol.p, d_.p, N, 1);
-  // iterative refinement towards the system without the regularisation (the factor is the regularised
-  // matrix's: each step gains about -log10(delta |K^-1|) digits); a fixed count, so nothing is read back
-  for (int it = 0; it < adj_refine_steps(); ++it) {
-    SPMV_LAUNCH(k_adj_resid, nbs, s, D, A, a.sol.p, d_.p, a.rowres.p);
-    kkt_solve();
-    k_adj_acc<<<nb, NT, 0, s>>>(a.sol.p, d_.p, N, 0);
-  }
-  SPMV_LAUNCH(k_adj_resid, nbs, s, D, A, a.sol.p, (double*)nullptr, a.rowres.p);
-  k_adj_resmax<<<1, NT, 0, s>>>(a.rowres.p, p_.p, N, a.scal.p);
+  sens_solve(a, A, a.scal.p);
   if (full && nx_) k_adj_unshift<<<blocks(nx_), NT, 0, s>>>(nx_, a.shift.p, a.sol.p, a.apx.p);
   // ---- gradients
   const bool vec = (out[0] || out[3] || out[4] || out[5] || out[6]) && std::max(nx_, m_);
@@ -3624,6 +3662,297 @@ void MPCSolver::adjoint_info(int64_t* n_adjoints, int64_t* n_adjoint_factorizati
     *last_residual = 0.0;
     if (adj_ && adj_->n_adjoints) {
       MADIPM_HIP(hipMemcpyAsync(last_residual, adj_->scal.p, sizeof(double), hipMemcpyDeviceToHost, stream_));
+      MADIPM_HIP(hipStreamSynchronize(stream_));
+    }
+  }
+}
+
+}  // namespace madipm
+
+// ======================================================================= tangent
+// madipm_solver_tangent / _tangent_device: forward mode, the transpose of the adjoint.  A direction
+// (dc, dHvals, dAvals, dlcon, ducon, dlvar, duvar) of the data moves w = (x_F, s, y) by K dw = -(dF/dtheta) dtheta
+// with the K of §13c.  The system is solved in the shifted form, dx_F = dx' + p, ds = ds' + p_s, in which no
+// product of Sigma with a direction remains, with the adjoint's factor, refinement and residual.
+namespace madipm {
+namespace {
+
+struct TanDir {  // the direction blocks on the device (null: 0)
+  const double *c, *Hv, *Av, *lcon, *ucon, *lvar, *uvar;
+};
+// a direction entry of a bound the coordinate does not have is not read
+__device__ __forceinline__ double tan_dl(const AdjArgs& A, const TanDir& T, int i) {
+  return (T.lvar && A.lbpos[i] >= 0) ? T.lvar[i] : 0.0;
+}
+__device__ __forceinline__ double tan_du(const AdjArgs& A, const TanDir& T, int i) {
+  return (T.uvar && A.ubpos[i] >= 0) ? T.uvar[i] : 0.0;
+}
+
+// v = [p; p~_s; 0]: p_i = (Sigma_l dlvar + Sigma_u duvar)_i / (Sigma_l + Sigma_u)_i on a free variable with a
+// bound, else 0 (the scalings cancel in p); the slack k of row r: p~_s,k = con_scale_r (Sigma_l,k dlcon_r +
+// Sigma_u,k ducon_r) / (Sigma_l,k + Sigma_u,k).  One thread per variable and per row; a row's thread writes
+// its slack's entry.
+__global__ __launch_bounds__(NT) void k_tan_shift(AdjArgs A, TanDir T, const int32_t* __restrict__ rowslack,
+                                                  double* __restrict__ v, LDLStatus* t1) {
+#pragma clang fp contract(off)
+  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  GRID_LOOP(i, A.n + A.m) {
+    if (i < A.nx) {
+      double o = 0.0;
+      if (!A.fixed[i]) {
+        const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
+        if (sm > 0.0) o = (sl * tan_dl(A, T, (int)i) + su * tan_du(A, T, (int)i)) / sm;
+      }
+      v[i] = o;
+    } else if (i >= A.n) {
+      const int r = (int)(i - A.n), k = rowslack[r];
+      v[i] = 0.0;
+      if (k >= 0) {
+        const double sl = adj_sig_l(A, k), su = adj_sig_u(A, k), sm = sl + su;
+        const double dl = (T.lcon && A.lbpos[k] >= 0) ? T.lcon[r] : 0.0;
+        const double du = (T.ucon && A.ubpos[k] >= 0) ? T.ucon[r] : 0.0;
+        v[k] = sm > 0.0 ? A.cscale[r] * ((sl * dl + su * du) / sm) : 0.0;
+      }
+    }
+  }
+}
+
+// The data terms, one thread per destination, each list in ascending input index (build_tangent_lists).
+// A free variable i: base_i = -[ os sgn (dc_i + (dH x)_i + (H dxfix)_i) + os (dA^T y)_i ], y the public
+// multiplier, os y_r = con_scale_r y~_r; 0 on a fixed variable and a slack.  Row r (public space):
+// base_r = (dA x)_r + (A dxfix)_r.  dxfix = dlvar on the fixed variables.  Without lists (gsp == null) the
+// sums are empty: no Hvals / Avals direction and no fixed variable with an lvar direction.
+__global__ __launch_bounds__(NT) void k_tan_data(AdjArgs A, TanDir T, const int32_t* __restrict__ gsp,
+                                                 const int2* __restrict__ ge, const int32_t* __restrict__ csp,
+                                                 const int2* __restrict__ ce, const int32_t* __restrict__ asp,
+                                                 const int2* __restrict__ ae, const double* __restrict__ Hraw,
+                                                 const double* __restrict__ Araw, double* __restrict__ base) {
+#pragma clang fp contract(off)
+  GRID_LOOP(i, A.n + A.m) {
+    double o = 0.0;
+    if (i < A.nx) {
+      if (!A.fixed[i]) {
+        double hs = 0.0, as = 0.0;
+        if (gsp) {
+          for (int q = gsp[i]; q < gsp[i + 1]; ++q) {
+            const int2 e = ge[q];
+            if (T.Hv) hs = hs + T.Hv[e.x] * A.x[e.y];
+            if (T.lvar && A.fixed[e.y]) hs = hs + Hraw[e.x] * T.lvar[e.y];
+          }
+          if (T.Av)
+            for (int q = csp[i]; q < csp[i + 1]; ++q) {
+              const int2 e = ce[q];
+              as = as + T.Av[e.x] * (A.cscale[e.y] * A.y[e.y]);
+            }
+        }
+        const double dc = T.c ? T.c[i] : 0.0;
+        o = -((A.os * A.sgn) * (dc + hs) + as);
+      }
+    } else if (i >= A.n) {
+      const int r = (int)(i - A.n);
+      if (asp)
+        for (int q = asp[r]; q < asp[r + 1]; ++q) {
+          const int2 e = ae[q];
+          if (T.Av) o = o + T.Av[e.x] * A.x[e.y];
+          if (T.lvar && A.fixed[e.y]) o = o + Araw[e.x] * T.lvar[e.y];
+        }
+    }
+    base[i] = o;
+  }
+}
+
+// The shifted right-hand side into d (and p, which keeps it for the residual), k_adj_rhs_full's access
+// pattern applied to v: base_i - (H~ p)_i on a free variable (v's row part is 0: J~^T adds nothing), 0 on a
+// fixed one and on a slack, con_scale_r (db_r - base_r) - (J~ p - p~_s)_r on row r, db = dlcon on an equality
+// row.  Every entry is of the directions' magnitude.
+template <int G>
+__global__ __launch_bounds__(NT) void k_tan_rhs(DV D, AdjArgs A, TanDir T, const int32_t* __restrict__ rowslack,
+                                                const double* __restrict__ v, const double* __restrict__ base) {
+#pragma clang fp contract(off)
+  const int n = D.n, m = D.m;
+  const bool lead = (threadIdx.x & (G - 1)) == 0;
+  GROUP_LOOP(i, n + m, G) {
+    double g = 0.0;
+    if (i < n) {
+      if (i < D.nx && !D.fixed[i]) g = base[i] - gdot<G>(D.H, i, v);
+    } else {
+      const int r = (int)(i - n);
+      const double jq = gdot<G>(D.J, r, v);
+      const double db = (T.lcon && rowslack[r] < 0) ? T.lcon[r] : 0.0;
+      g = A.cscale[r] * (db - base[i]) - jq;
+    }
+    if (lead) {
+      D.d[i] = g;
+      D.p[i] = g;
+    }
+  }
+}
+
+// Un-shift and un-scale (A.d is the solution [dx'; ds~'; dy~] of the shifted system; any output may be null):
+// dx = dx' + p on a free variable, dlvar on a fixed one (also into dxs, with zeros on the slacks, for
+// k_tan_cons); dy = con_scale dy~ / obj_scale; dzl = -Sigma_l dx' + h (dlvar - duvar), dzu = Sigma_u dx' +
+// h (dlvar - duvar) with the public Sigma = Sigma~ / obj_scale and h = Sigma_l Sigma_u / (Sigma_l + Sigma_u);
+// 0 without that bound and on a fixed variable.
+__global__ __launch_bounds__(NT) void k_tan_out(AdjArgs A, TanDir T, const double* __restrict__ v,
+                                                double* __restrict__ dxs, double* __restrict__ ox,
+                                                double* __restrict__ oy, double* __restrict__ ozl,
+                                                double* __restrict__ ozu) {
+#pragma clang fp contract(off)
+  const int ns = A.n - A.nx;
+  const int top = A.nx > A.m ? A.nx : A.m;
+  GRID_LOOP(i, (top > ns ? top : ns)) {
+    if (i < A.nx) {
+      double dx, dzl = 0.0, dzu = 0.0;
+      if (A.fixed[i]) {
+        dx = T.lvar ? T.lvar[i] : 0.0;
+      } else {
+        const double dxp = A.d[i];
+        dx = dxp + v[i];
+        const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
+        const double hd = sm > 0.0 ? ((sl * su / sm) / A.os) * (tan_dl(A, T, (int)i) - tan_du(A, T, (int)i)) : 0.0;
+        if (A.lbpos[i] >= 0) dzl = hd - (sl / A.os) * dxp;
+        if (A.ubpos[i] >= 0) dzu = (su / A.os) * dxp + hd;
+      }
+      dxs[i] = dx;
+      if (ox) ox[i] = dx;
+      if (ozl) ozl[i] = dzl;
+      if (ozu) ozu[i] = dzu;
+    }
+    if (i < ns) dxs[A.nx + i] = 0.0;
+    if (i < A.m && oy) oy[i] = A.d[A.n + i] * A.cscale[i] / A.os;
+  }
+}
+
+// dcons_r = (A dx)_r + (dA x)_r: J~'s structural columns times dx / con_scale_r (J~ has no fixed column, and
+// dxs is 0 on the slacks), + base_r, which holds the fixed columns' part and dA x
+template <int G>
+__global__ __launch_bounds__(NT) void k_tan_cons(DV D, AdjArgs A, const double* __restrict__ dxs,
+                                                 const double* __restrict__ base, double* __restrict__ ocons) {
+#pragma clang fp contract(off)
+  const bool lead = (threadIdx.x & (G - 1)) == 0;
+  GROUP_LOOP(r, D.m, G) {
+    const double s = gdot<G>(D.J, r, dxs);
+    if (lead) ocons[r] = s / A.cscale[r] + base[D.n + r];
+  }
+}
+
+}  // namespace
+
+void MPCSolver::tangent(const madipm_qp_directions& dr, const madipm_qp_point_tangents& o, bool device,
+                        hipStream_t caller) {
+  const std::string who = device ? "madipm_solver_tangent_device: " : "madipm_solver_tangent: ";
+  QPHost& P = *H_;
+  // ---- refusals, before anything is allocated or enqueued
+  sens_refuse(who);
+  const double* const dir[7] = {dr.c, dr.Hvals, dr.Avals, dr.lcon, dr.ucon, dr.lvar, dr.uvar};
+  double* const user[5] = {o.x, o.y, o.zl, o.zu, o.cons};
+  MADIPM_REQUIRE(dr.c || dr.Hvals || dr.Avals || dr.lcon || dr.ucon || dr.lvar || dr.uvar,
+                 who + "all seven directions are NULL");
+  MADIPM_REQUIRE(o.x || o.y || o.zl || o.zu || o.cons, who + "all five outputs are NULL");
+  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
+  const bool needLists = (dr.Avals && na > 0) || (dr.Hvals && nh > 0) || (dr.lvar && P.anyfix);
+  MADIPM_REQUIRE(plan_ || !needLists,
+                 who + "Avals, Hvals (and lvar on a problem with fixed variables) need "
+                       "madipm_solver_prepare_update first (it keeps the index arrays and the raw values)");
+  hipStream_t s = stream_;
+  // ---- allocations, each by the first call that needs it
+  Adjoint& a = sens_state();
+  if (!tan_) {
+    auto t = std::make_unique<Tangent>();
+    t->base.alloc(std::max(n_ + m_, 1));
+    t->dx.alloc(std::max(n_, 1));
+    t->scal.alloc(1);
+    t->scal.zero(s);
+    tan_ = std::move(t);
+  }
+  Tangent& t = *tan_;
+  const double* cscale = device_con_scale();
+  if (!a.shift.p) {  // as the five-cotangent adjoint allocates them
+    a.shift.alloc(std::max(n_ + m_, 1));
+    a.apx.alloc(std::max(nx_, 1));
+  }
+  if (!a.rowslack.p) {
+    a.rowslack.upload(adjoint_rowslack(P), s);
+    MADIPM_HIP(hipStreamSynchronize(s));
+  }
+  if (needLists && !t.lists) {  // the entry lists, from the host COO copies
+    TangentLists L = build_tangent_lists(P);
+    L.ae.resize(std::max<size_t>(L.ae.size(), 1));  // the allocations are never empty
+    L.ce.resize(std::max<size_t>(L.ce.size(), 1));
+    L.ge.resize(std::max<size_t>(L.ge.size(), 1));
+    t.asp.upload(L.asp, s);
+    t.csp.upload(L.csp, s);
+    t.gsp.upload(L.gsp, s);
+    t.ae.upload(as_int2(L.ae), L.ae.size(), s);
+    t.ce.upload(as_int2(L.ce), L.ce.size(), s);
+    t.ge.upload(as_int2(L.ge), L.ge.size(), s);
+    MADIPM_HIP(hipStreamSynchronize(s));
+    t.lists = true;
+  }
+  const int64_t dlen[7] = {nx_, nh, na, m_, m_, nx_, nx_};
+  const int64_t olen[5] = {nx_, m_, nx_, nx_, m_};
+  const double* ddir[7];
+  double* out[5];
+  for (int j = 0; j < 7; ++j) {
+    ddir[j] = dir[j];
+    if (!device && dir[j]) {
+      if (!t.dir[j].p) t.dir[j].alloc(std::max<int64_t>(dlen[j], 1));
+      ddir[j] = t.dir[j].p;
+    }
+  }
+  for (int j = 0; j < 5; ++j) {
+    out[j] = user[j];
+    if (!device && user[j]) {
+      if (!t.out[j].p) t.out[j].alloc(std::max<int64_t>(olen[j], 1));
+      out[j] = t.out[j].p;
+    }
+  }
+  // ---- the factor of the K2 matrix at the final iterate: the adjoint's, once per solve
+  DV_ARGS;
+  sens_factor(a, who);
+  if (device) {  // the directions are read after the work already enqueued on the caller's stream
+    MADIPM_HIP(hipEventRecord(a.ev[0], caller));
+    MADIPM_HIP(hipStreamWaitEvent(s, a.ev[0], 0));
+  } else {
+    for (int j = 0; j < 7; ++j)
+      if (dir[j] && dlen[j]) t.dir[j].upload(dir[j], dlen[j], s);
+  }
+  // ---- right-hand side, solve, residual
+  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
+  const AdjArgs A{n_, m_, nx_, obj_scale_, P.sgn, a.sol.p, x_.p, xl_.p, xu_.p, zl_.p, zu_.p, y_.p,
+                  cscale, lbpos_.p, ubpos_.p, fixed_.p};
+  const TanDir T{ddir[0], ddir[1], ddir[2], ddir[3], ddir[4], ddir[5], ddir[6]};
+  const bool ls = needLists;  // lists built by an earlier call are not walked when this one has no use for them
+  k_tan_shift<<<nb, NT, 0, s>>>(A, T, a.rowslack.p, a.shift.p, take_fact_end());
+  k_tan_data<<<nb, NT, 0, s>>>(A, T, ls ? t.gsp.p : nullptr, t.ge.p, t.csp.p, t.ce.p, ls ? t.asp.p : nullptr, t.ae.p,
+                               plan_ ? plan_->Hraw.p : nullptr, plan_ ? plan_->Araw.p : nullptr, t.base.p);
+  SPMV_LAUNCH(k_tan_rhs, nbs, s, D, A, T, (const int32_t*)a.rowslack.p, (const double*)a.shift.p,
+              (const double*)t.base.p);
+  sens_solve(a, A, t.scal.p);
+  // ---- outputs
+  k_tan_out<<<blocks(std::max(std::max(nx_, m_), std::max(n_ - nx_, 1))), NT, 0, s>>>(
+      A, T, a.shift.p, t.dx.p, out[0], out[1], out[2], out[3]);
+  if (out[4] && m_)
+    SPMV_LAUNCH(k_tan_cons, spmv_blocks(m_), s, D, A, (const double*)t.dx.p, (const double*)t.base.p, out[4]);
+  MADIPM_HIP(hipGetLastError());
+  if (device) {  // work enqueued on the caller's stream from now on sees the outputs
+    MADIPM_HIP(hipEventRecord(a.ev[1], s));
+    MADIPM_HIP(hipStreamWaitEvent(caller, a.ev[1], 0));
+  } else {
+    for (int j = 0; j < 5; ++j)
+      if (user[j] && olen[j])
+        MADIPM_HIP(hipMemcpyAsync(user[j], out[j], olen[j] * sizeof(double), hipMemcpyDeviceToHost, s));
+    MADIPM_HIP(hipStreamSynchronize(s));
+  }
+  ++t.n_tangents;
+}
+
+void MPCSolver::tangent_info(int64_t* n_tangents, double* last_residual) {
+  if (n_tangents) *n_tangents = tan_ ? tan_->n_tangents : 0;
+  if (last_residual) {
+    *last_residual = 0.0;
+    if (tan_ && tan_->n_tangents) {
+      MADIPM_HIP(hipMemcpyAsync(last_residual, tan_->scal.p, sizeof(double), hipMemcpyDeviceToHost, stream_));
       MADIPM_HIP(hipStreamSynchronize(stream_));
     }
   }

@@ -45,6 +45,8 @@ struct UpdatePlan;   // index plans of the value refresh, built by prepare_updat
 struct DevUpdate;    // staging, start vectors and sum-order lists of the device route (mpc.hip)
 struct WarmStart;    // the warm point and its scratch, on the device (mpc.hip)
 struct Adjoint;      // index copies, fixed-variable lists and scratch of the adjoint gradients (mpc.hip)
+struct AdjArgs;      // the adjoint kernels' view of the point and the solution (mpc.hip)
+struct Tangent;      // entry lists and scratch of the forward-mode sensitivities (mpc.hip)
 
 class MPCSolver {
  public:
@@ -94,6 +96,12 @@ class MPCSolver {
   void adjoint(const madipm_qp_cotangents& g, const madipm_qp_gradients& out, bool device, hipStream_t caller,
                const char* name);
   void adjoint_info(int64_t* n_adjoints, int64_t* n_adjoint_factorizations, double* last_residual);
+  // Forward mode (madipm_solver_tangent / _tangent_device / _tangent_info): given a direction of
+  // the data (non-null fields of `d`), the directional derivative of the solution blocks the caller asks for
+  // (non-null fields of `out`) at the point of the last successful solve.  Shares the adjoint's factor (one
+  // factorisation per solved point serves both), refinement and residual; device and `caller` as there.
+  void tangent(const madipm_qp_directions& d, const madipm_qp_point_tangents& out, bool device, hipStream_t caller);
+  void tangent_info(int64_t* n_tangents, double* last_residual);
   int64_t n_analyses() const { return n_analyses_; }
   int64_t n_updates() const { return n_updates_; }
   double last_update_s() const { return last_update_s_; }
@@ -105,6 +113,11 @@ class MPCSolver {
   void warm_blend();
   void refresh_host_mirrors();
   const double* device_con_scale();
+  // shared by adjoint() and tangent(): the refusals, the scratch, the factor of the point, the refined solve
+  void sens_refuse(const std::string& who) const;
+  Adjoint& sens_state();
+  void sens_factor(Adjoint& a, const std::string& who);
+  void sens_solve(Adjoint& a, const AdjArgs& A, double* resid);
   std::unique_ptr<LinSolver> make_linsolver(int n, const int64_t* cp, const int32_t* ri, const SymbolicOptions& so);
   void initialize();
   void init_starting_point();
@@ -195,7 +208,8 @@ class MPCSolver {
   std::unique_ptr<WarmStart> warm_;     // null until a warm point is set
   int64_t n_warm_inits_ = 0;           // initialize() calls that blended
   bool solved_ = false;                // a solve has run (warm_start_last needs its point)
-  std::unique_ptr<Adjoint> adj_;       // null until the first adjoint
+  std::unique_ptr<Adjoint> adj_;       // null until the first adjoint or tangent
+  std::unique_ptr<Tangent> tan_;       // null until the first tangent
   bool point_ok_ = false;              // the iterate is the end point of a completed solve
   int64_t n_solves_ = 0;               // completed solves (the adjoint's factor belongs to one of them)
   int64_t solve_updates_ = 0;          // n_updates_ at the end of the last solve

@@ -785,4 +785,35 @@ AdjointLists build_adjoint_lists(const QPHost& P) {
   return L;
 }
 
+TangentLists build_tangent_lists(const QPHost& P) {
+  const int nx = P.nx, m = P.m;
+  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
+  TangentLists L;
+  {
+    std::vector<int32_t> rdest(na), cdest(na);
+    std::vector<I2> rent(na), cent(na);
+    for (int64_t k = 0; k < na; ++k) {
+      rdest[k] = P.Ar[k];
+      rent[k] = {(int32_t)k, P.Ac[k]};
+      cdest[k] = P.Ac[k];
+      cent[k] = {(int32_t)k, P.Ar[k]};
+    }
+    bucket(m, rdest, rent, L.asp, L.ae);
+    bucket(nx, cdest, cent, L.csp, L.ce);
+  }
+  std::vector<int32_t> gdest;
+  std::vector<I2> gent;
+  for (int64_t k = 0; k < nh; ++k) {
+    const int r = P.Hr[k], c = P.Hc[k];
+    gdest.push_back(r);
+    gent.push_back({(int32_t)k, c});
+    if (r != c) {
+      gdest.push_back(c);
+      gent.push_back({(int32_t)k, r});
+    }
+  }
+  bucket(nx, gdest, gent, L.gsp, L.ge);
+  return L;
+}
+
 }  // namespace madipm

@@ -3,8 +3,8 @@
 // Everything the solver derives on the host from the caller's QP before a byte is uploaded: the copy of
 // the problem and its index sets, the value-dependent vectors (numeric_host), the H / J / J^T CSR arrays,
 // the K2 and normal-equations patterns, the refresh plan of prepare_update, the sum-order lists of the
-// device route and the fixed-variable lists of the adjoint.  mpc.hip builds these, uploads them and
-// synchronises; tools/model_check.cpp builds and checks them on a machine without a GPU.
+// device route, the fixed-variable lists of the adjoint and the entry lists of the tangent.  mpc.hip builds
+// these, uploads them and synchronises; tools/model_check.cpp builds and checks them on a machine without a GPU.
 #pragma once
 
 #include <cstdint>
@@ -131,6 +131,17 @@ struct AdjointLists {
   std::vector<I2> fh, fa;
 };
 AdjointLists build_adjoint_lists(const QPHost& P);
+
+// The tangent's lists (forward-mode sensitivities): the entries of the COO input per destination as
+// (input index, other index) pairs in ascending input index, so every data product has a fixed order.
+// asp / ae: A's entries per row (entry, column); csp / ce: A's entries per column (entry, row); gsp / ge:
+// H's entries per endpoint (entry, other endpoint; a diagonal entry once).  Fixed columns and endpoints are
+// kept: their terms are the fixed variables' part of the right-hand side.  Reads A through P.Ar / P.Ac.
+struct TangentLists {
+  std::vector<int32_t> asp, csp, gsp;
+  std::vector<I2> ae, ce, ge;
+};
+TangentLists build_tangent_lists(const QPHost& P);
 
 // what qp_intake derives from one coordinate's bounds: fixed (1), or finite lower (2) | finite upper (4)
 int bound_class(double l, double u);

@@ -20,6 +20,7 @@ def __getattr__(name):
                 "MAXIMUM_WALLTIME_EXCEEDED", "DIVERGING_ITERATES", "ERROR_IN_STEP_COMPUTATION", "INTERNAL_ERROR",
                 "STATUS_NAMES", "RCCLComm", "HostComm", "SolveException", "UnfactorizedSolveException",
                 "ADJOINT_NAMES", "COTANGENT_NAMES",  # MPCSolver.adjoint's gradients; its cotangents' blocks
+                "TANGENT_NAMES",  # MPCSolver.tangent's output blocks (its directions' blocks are ADJOINT_NAMES)
                 "MadIPMError"):  # MadIPMError: what MPCSolver.update raises on a change of classification
         from . import solver
         return getattr(solver, name)

@@ -136,6 +136,23 @@ _sig("madipm_solver_adjoint_full", C.c_int, [vp, C.POINTER(QPCot), C.POINTER(QPG
 _sig("madipm_solver_adjoint_full_device", C.c_int, [vp, C.POINTER(QPCot), C.POINTER(QPGrad), vp])
 
 
+# forward-mode sensitivities (ABI 0.2.9): host route, device route + stream, counters
+class QPDir(C.Structure):
+    """madipm_qp_directions: the direction in each data block; a NULL pointer means 0."""
+    _fields_ = [("c", f64p), ("Hvals", f64p), ("Avals", f64p), ("lcon", f64p), ("ucon", f64p), ("lvar", f64p),
+                ("uvar", f64p)]
+
+
+class QPTan(C.Structure):
+    """madipm_qp_point_tangents: where dx, dy, dzl, dzu, d(A x) go; a NULL pointer means "not wanted"."""
+    _fields_ = [("x", f64p), ("y", f64p), ("zl", f64p), ("zu", f64p), ("cons", f64p)]
+
+
+_sig("madipm_solver_tangent", C.c_int, [vp, C.POINTER(QPDir), C.POINTER(QPTan)])
+_sig("madipm_solver_tangent_device", C.c_int, [vp, C.POINTER(QPDir), C.POINTER(QPTan), vp])
+_sig("madipm_solver_tangent_info", C.c_int, [vp, i64p, f64p])
+
+
 class MadIPMError(RuntimeError):
     pass
 

@@ -8,7 +8,9 @@
     x, y, cons = layer(c=c)          # the row multipliers and A x* are differentiable too
 
 Forward and backward stay on the device (MPCSolver.update_device / solution_device / adjoint_device); the
-gradients are those of MPCSolver.adjoint, K2 formulation.
+gradients are those of MPCSolver.adjoint, K2 formulation.  Forward-mode autograd
+(torch.autograd.forward_ad) goes through MPCSolver.tangent_device; the torch.func transforms
+ask a Function for the setup_context form of forward, which QPFunction does not have.
 `import torch` comes before this package in the process, as for every device-route call.
 """
 from __future__ import annotations
@@ -27,7 +29,10 @@ class QPFunction(torch.autograd.Function):
     current data.  backward asks adjoint_device for exactly the gradients of the tensors that require grad,
     and must run before the solver is updated or solved again (the adjoint belongs to the last solve).
     A tuple of names from ("x", "y", "zl", "zu", "cons") as a ninth argument selects the outputs: forward then
-    returns that tuple of tensors, and backward passes on the cotangents of those the loss used."""
+    returns that tuple of tensors, and backward passes on the cotangents of those the loss used.
+    jvp hands tangent_device the tangents of the data tensors that carry one and returns the tangents of the
+    selected outputs; like backward it must run before the solver is updated or solved again,
+    which forward-mode autograd does by calling it right after forward."""
 
     @staticmethod
     def forward(ctx, solver, *data):
@@ -65,6 +70,17 @@ class QPFunction(torch.autograd.Function):
                 return (None,) * nin
             g = ctx.solver.adjoint_device(cot.pop("gx", None), want=want, **cot)
         return ((None,) + tuple(g.get(k) for k in ctx.names) + (None,) * nin)[:nin]
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        # forward mode (torch.autograd.forward_ad): tangents[0] is the solver's (None); one
+        # entry per data tensor follows, None for a tensor without a tangent (then the outputs' tuple: None)
+        d = {k: t.contiguous() for k, t in zip(ctx.names, tangents[1:]) if t is not None}
+        keys = ("x",) if ctx.outputs is None else ctx.outputs
+        if not d:
+            return None if ctx.outputs is None else (None,) * len(keys)
+        t = ctx.solver.tangent_device(want=keys, **d)
+        return t["x"] if ctx.outputs is None else tuple(t[k] for k in keys)
 
 
 class QPLayer(torch.nn.Module):

@@ -232,6 +232,49 @@ def check_adjoint_cotangents(nvar: int, ncon: int, gx=None, gy=None, gzl=None, g
     return given
 
 
+TANGENT_NAMES = COTANGENT_NAMES   # MPCSolver.tangent's output blocks; its directions' blocks are ADJOINT_NAMES
+
+
+def check_tangent_want(want) -> tuple:
+    """The `want` argument of MPCSolver.tangent / tangent_device: None (all five) or an iterable of names out
+    of TANGENT_NAMES.  Returns the names in TANGENT_NAMES order; ValueError for an unknown name or an empty
+    selection, TypeError for a bare string."""
+    if want is None:
+        return TANGENT_NAMES
+    if isinstance(want, str):
+        raise TypeError(f"tangent: want must be a collection of names, not the string {want!r}")
+    want = list(want)
+    unknown = [k for k in want if k not in TANGENT_NAMES]
+    if unknown:
+        raise ValueError(f"tangent: unknown name(s) {unknown} in want; the blocks are {list(TANGENT_NAMES)}")
+    if not want:
+        raise ValueError("tangent: want is empty")
+    return tuple(k for k in TANGENT_NAMES if k in want)
+
+
+def check_tangent_directions(sizes: dict, directions: dict, *, on_device: bool = False, device=None,
+                             who: str = "tangent") -> dict:
+    """The direction arguments of MPCSolver.tangent / tangent_device, before any library call: `directions`
+    maps names out of ADJOINT_NAMES to arrays (None: 0) of the lengths in `sizes`, not all seven None.  Host
+    route: each is converted to a C-contiguous float64 array.  Device route (on_device): each must pass
+    check_device_array.  Returns {name: array} of those given, in ADJOINT_NAMES order."""
+    given = {}
+    for name in ADJOINT_NAMES:
+        a = directions.get(name)
+        if a is None:
+            continue
+        if on_device:
+            check_device_array(name, a, sizes[name], device, who=who)
+        else:
+            a = np.array(a, dtype=np.float64, order="C", ndmin=1)
+            if a.shape != (int(sizes[name]),):
+                raise ValueError(f"{who}: {name} has shape {a.shape}, expected ({int(sizes[name])},)")
+        given[name] = a
+    if not given:
+        raise ValueError(f"{who}: no direction given; pass at least one of {', '.join(ADJOINT_NAMES)}")
+    return given
+
+
 def check_layer_outputs(outputs) -> tuple:
     """The `outputs` argument of QPLayer: an ordered selection out of COTANGENT_NAMES without repeats.
     Returns it as a tuple; TypeError for a bare string, ValueError for an unknown or repeated name or an
@@ -801,6 +844,75 @@ class MPCSolver:
         L.check(L.lib.madipm_solver_adjoint_info(self.h, C.byref(na), C.byref(nf), C.byref(r)), "adjoint_info")
         return {"n_adjoints": int(na.value), "n_adjoint_factorizations": int(nf.value),
                 "last_residual": float(r.value)}
+
+    # ------------------------------------------------------------ forward-mode sensitivities
+    def tangent(self, want=None, *, c=None, Hvals=None, Avals=None, lcon=None, ucon=None, lvar=None,
+                uvar=None) -> dict:
+        """The directional derivative of the solution the last solve() returned along a direction of the
+        problem data: a dict of numpy arrays over `want`, a subset of TANGENT_NAMES (None: all five: x, y,
+        zl, zu and cons = A x).  The direction blocks have the data's shapes (Hvals / Avals in the
+        creation-time COO order); None is 0, not all seven.  An entry on an infinite bound is not read; a
+        fixed variable moves by lvar's entry and an equality row by lcon's (uvar's / ucon's is not read), so
+        one array passed as both bounds stays right.  x* + tangent is the first-order prediction of the
+        optimum after the data moved by the direction.  The call shares adjoint()'s factor of the point (one
+        factorisation serves both) and leaves the solver's state untouched.  MadIPMError as adjoint()."""
+        names = check_tangent_want(want)
+        size = self._adjoint_sizes()
+        given = check_tangent_directions(size, dict(c=c, Hvals=Hvals, Avals=Avals, lcon=lcon, ucon=ucon, lvar=lvar,
+                                                    uvar=uvar))
+        osize = self._tangent_sizes()
+        buf = {k: np.empty(max(osize[k], 1)) for k in names}  # an empty output still has a non-null address
+        o = L.QPTan()
+        for k in names:
+            setattr(o, k, L.ptr(buf[k], C.c_double))
+        self._adjoint_prepare(given)
+        # an empty block (nnzh = 0) has nothing to read: any non-null address says "given"
+        d = L.QPDir(**{k: L.ptr(a if a.size else np.zeros(1), C.c_double) for k, a in given.items()})
+        L.check(L.lib.madipm_solver_tangent(self.h, C.byref(d), C.byref(o)), "tangent")
+        return {k: buf[k][:osize[k]] for k in names}
+
+    def _tangent_sizes(self) -> dict:
+        qp = self.qp
+        return {"x": qp.nvar, "y": qp.ncon, "zl": qp.nvar, "zu": qp.nvar, "cons": qp.ncon}
+
+    def tangent_device(self, want=None, stream=None, *, c=None, Hvals=None, Avals=None, lcon=None, ucon=None,
+                       lvar=None, uvar=None) -> dict:
+        """tangent() from and into torch tensors on the solver's GPU (every direction: float64, contiguous, the
+        shape tangent() expects), without a copy through the host.  `stream` is the torch.cuda.Stream the
+        directions were produced on (None: the current stream): they are read after the work enqueued on it,
+        and work enqueued on it after the call sees the returned tensors.  The arguments are checked before
+        any library call."""
+        names = check_tangent_want(want)
+        size = self._adjoint_sizes()
+        dirs = dict(c=c, Hvals=Hvals, Avals=Avals, lcon=lcon, ucon=ucon, lvar=lvar, uvar=uvar)
+        given = check_tangent_directions(size, dirs, on_device=True, device=self._device, who="tangent_device")
+        import torch
+        if stream is not None and not isinstance(stream, torch.cuda.Stream):
+            raise TypeError(f"tangent_device: stream must be a torch.cuda.Stream, not {type(stream).__name__}")
+        if self._device is None:
+            self._device = torch.device("cuda", torch.cuda.current_device())
+            check_tangent_directions(size, dirs, on_device=True, device=self._device, who="tangent_device")
+        st = stream if stream is not None else torch.cuda.current_stream(self._device)
+        osize = self._tangent_sizes()
+        with torch.cuda.stream(st):
+            buf = {k: torch.empty(max(osize[k], 1), dtype=torch.float64, device=self._device) for k in names}
+            keep = {k: a if a.numel() else torch.zeros(1, dtype=torch.float64, device=self._device)
+                    for k, a in given.items()}
+        o = L.QPTan()
+        for k in names:
+            setattr(o, k, C.cast(buf[k].data_ptr(), L.f64p))
+        self._adjoint_prepare(given)
+        d = L.QPDir(**{k: C.cast(a.data_ptr(), L.f64p) for k, a in keep.items()})
+        L.check(L.lib.madipm_solver_tangent_device(self.h, C.byref(d), C.byref(o), L.vp(st.cuda_stream)),
+                "tangent_device")
+        return {k: buf[k][:osize[k]] for k in names}
+
+    def tangent_info(self) -> dict:
+        """n_tangents: successful tangent calls; last_residual: the last call's ||r - K w||_inf /
+        max(1, ||r||_inf) of the shifted system."""
+        nt, r = C.c_int64(), C.c_double()
+        L.check(L.lib.madipm_solver_tangent_info(self.h, C.byref(nt), C.byref(r)), "tangent_info")
+        return {"n_tangents": int(nt.value), "last_residual": float(r.value)}
 
     def counters(self) -> dict:
         """n_analyses: linear-solver analyses run for this solver (stays 1); n_updates: successful update()

@@ -7,7 +7,7 @@
 // Acols (nnzj int32 each), Avals (nnzj doubles), Hrows, Hcols (nnzh int32 each), Hvals (nnzh doubles).
 // --update FILE: raw lvar, uvar (nvar doubles each), lcon, ucon (ncon doubles each) of an update, run through
 // update()'s class-change checks after everything else.
-// Builds the model, the refresh plan, the device route's lists and the adjoint's lists, checks their
+// Builds the model, the refresh plan, the device route's lists, the adjoint's and the tangent's lists, checks their
 // invariants (exit status 1 with a message on the first violation; 2 with "error: <text>" when the model
 // itself refuses the problem or the update) and prints one line per array: "<name> <count> <FNV-1a 64>";
 // --dump DIR also writes each array raw to DIR/<name>.bin.  MADIPM_ANALYSIS_THREADS applies as in the solver.
@@ -174,6 +174,7 @@ int main(int argc, char** argv) try {
   const RouteLists L = build_route_lists(P);
   const std::vector<int32_t> rowslack = adjoint_rowslack(P);
   const AdjointLists G = build_adjoint_lists(P);
+  const TangentLists TL = build_tangent_lists(P);
   const int nx = P.nx, m = P.m, n = P.n;
   const int64_t nJ = R.nJ, nH = R.nH;
 
@@ -297,6 +298,19 @@ int main(int argc, char** argv) try {
         ++b;
       }
     CHECK(b == L.bfk.size(), "bfk length");
+  }
+  {  // the tangent's lists: every entry of A once per row and once per column, every entry of H per endpoint
+    std::vector<int> cov(na, 0);
+    check_lists("tangent asp/ae", m, TL.asp, TL.ae, [&](int d, I2 e) { return P.Ar[e.x] == d && P.Ac[e.x] == e.y; }, cov);
+    check_cover("tangent asp/ae", cov, [](int64_t) { return 1; });
+    cov.assign(na, 0);
+    check_lists("tangent csp/ce", nx, TL.csp, TL.ce, [&](int d, I2 e) { return P.Ac[e.x] == d && P.Ar[e.x] == e.y; }, cov);
+    check_cover("tangent csp/ce", cov, [](int64_t) { return 1; });
+    cov.assign(nh, 0);
+    check_lists("tangent gsp/ge", nx, TL.gsp, TL.ge, [&](int d, I2 e) {
+      return (P.Hr[e.x] == d && P.Hc[e.x] == e.y) || (P.Hc[e.x] == d && P.Hr[e.x] == e.y);
+    }, cov);
+    check_cover("tangent gsp/ge", cov, [&](int64_t k) { return hdiag(k) ? 1 : 2; });
   }
   CHECK((int)L.vcls.size() == nx && (int)L.ccls.size() == m, "class lengths");
   for (int i = 0; i < nx; ++i) CHECK(L.vcls[i] == bound_class(P.lvar[i], P.uvar[i]), at("vcls", i));

@@ -31,7 +31,16 @@ which reuses the factor), adjoint_residual (the largest last_residual) and adjoi
 --adjoint-full is --adjoint with one more call per point, after the two above and on the same factor:
 adjoint_device with seeded cotangents of all five solution blocks (gx, gy, gzl, gzu, gcons), for all seven
 gradients: adjoint_full_s beside adjoint_again_s, and adjoint_full_residual, the largest last_residual of
-those calls (the residual of the shifted system)."""
+those calls (the residual of the shifted system).
+
+--tangent adds, on the same sequence of data and in the same process, the forward-mode call: after each
+update_device + solve, tangent_device of a seeded direction in all seven data blocks for all five outputs,
+stream synchronised: tangent_s (the first call on a point: the factorisation + the solves) beside
+tangent_solve_s (the solve before it) and tangent_again_s (a second direction on the same point),
+tangent_residual (the largest last_residual) and tangent_status.  With --warm WEIGHT it also runs the
+sequence twice more, warm-started from the previous solution (warm_start_last) and from the first-order
+prediction solution + tangent along the actual next perturbation (warm_start_device):
+tangent_warm_iters_last and tangent_warm_iters_predicted."""
 import dataclasses
 import json
 import os
@@ -61,7 +70,7 @@ def perturb(qp, rng):
                 lvar=qp.lvar * fv, uvar=qp.uvar * fv, lcon=qp.lcon * fc, ucon=qp.ucon * fc)
 
 
-def run(name, warm=None, adjoint=False, adjoint_full=False):
+def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False):
     qp, desc = bench.build_problem(name)
     opts = bench.solver_opts()
     MPCSolver(qp, **opts)                      # the first construction of a process pays one-off set-up
@@ -195,6 +204,68 @@ def run(name, warm=None, adjoint=False, adjoint_full=False):
         if adjoint_full:
             wres.update({"adjoint_full_s": med(afull), "adjoint_full_residual": afres})
         c = s.counters()
+    if tangent:   # the same data again: the forward-mode call (all seven blocks, all five outputs) per re-solve
+        rng = np.random.default_rng(0)
+        perturb(qp, rng)
+        seq = [perturb(qp, rng) for _ in range(WARMUP + REPS + 1)]
+        drng = np.random.default_rng(2)
+        size = dict(c=qp.nvar, Hvals=qp.nnzh, Avals=qp.nnzj, lcon=qp.ncon, ucon=qp.ncon, lvar=qp.nvar, uvar=qp.nvar)
+        dev = lambda d: {k: torch.as_tensor(v, device="cuda") for k, v in d.items()}  # noqa: E731
+        draw = lambda: dev({k: drng.standard_normal(n) for k, n in size.items()})  # noqa: E731
+        tsol, tfirst, tagain, tstat, tres = [], [], [], set(), 0.0
+        for rep in range(WARMUP + REPS):
+            s.update_device(**dev(seq[rep]))
+            d1, d2 = draw(), draw()
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            tst = s.solve(fetch_solution=False)
+            t_solve = time.perf_counter() - t
+            tstat.add(tst.status)
+            if tst.status != 1:
+                continue
+            t = time.perf_counter()
+            s.tangent_device(**d1)
+            torch.cuda.current_stream().synchronize()
+            t_first = time.perf_counter() - t
+            t = time.perf_counter()
+            s.tangent_device(**d2)
+            torch.cuda.current_stream().synchronize()
+            t_again = time.perf_counter() - t
+            tres = max(tres, s.tangent_info()["last_residual"])
+            if rep >= WARMUP:
+                tsol.append(t_solve)
+                tfirst.append(t_first)
+                tagain.append(t_again)
+        med = lambda v: statistics.median(v) if v else float("nan")  # noqa: E731
+        wres.update({"tangent_s": med(tfirst), "tangent_again_s": med(tagain), "tangent_solve_s": med(tsol),
+                     "tangent_residual": tres, "tangent_status": sorted(tstat), **s.tangent_info()})
+        if warm is not None:   # the next solve started from the last solution, or from solution + tangent
+            for mode in ("last", "predicted"):
+                its_, stat_ = [], set()
+                s.clear_warm_start()
+                s.update_device(**dev(seq[0]))
+                ok = s.solve(fetch_solution=False).status == 1
+                for rep in range(1, WARMUP + REPS + 1):
+                    cur, nxt = dev(seq[rep - 1]), dev(seq[rep])
+                    if not ok:
+                        s.clear_warm_start()
+                    elif mode == "last":
+                        s.warm_start_last(warm)
+                    else:   # an infinite bound gives inf - inf = NaN, in an entry that is not read
+                        pt = s.solution_device()
+                        tg = s.tangent_device(want=("x", "y", "zl", "zu"), **{k: nxt[k] - cur[k] for k in nxt})
+                        s.warm_start_device(x=pt["solution"] + tg["x"], y=pt["multipliers"] + tg["y"],
+                                            zl=pt["multipliers_L"] + tg["zl"], zu=pt["multipliers_U"] + tg["zu"],
+                                            weight=warm)
+                    s.update_device(**nxt)
+                    wst = s.solve(fetch_solution=False)
+                    ok = wst.status == 1
+                    stat_.add(wst.status)
+                    if rep > WARMUP:
+                        its_.append(wst.iter)
+                wres.update({f"tangent_warm_iters_{mode}": its_, f"tangent_warm_status_{mode}": sorted(stat_)})
+            s.clear_warm_start()
+        c = s.counters()
     update_s, solve_s = statistics.median(upd), statistics.median(sol)
     return {**wres, "instance": name, "description": desc, "nvar": qp.nvar, "ncon": qp.ncon, "nnzj": qp.nnzj, "nnzh": qp.nnzh,
             "construct_s": construct_s, "prepare_update_s": prepare_update_s, "update_s": update_s,
@@ -230,8 +301,11 @@ def main():
     adjoint = "--adjoint" in args or adjoint_full
     if "--adjoint" in args:
         args.remove("--adjoint")
+    tangent = "--tangent" in args
+    if tangent:
+        args.remove("--tangent")
     for name in args or ["ex10", "supportcase10"]:
-        r = run(name, warm, adjoint, adjoint_full)
+        r = run(name, warm, adjoint, adjoint_full, tangent)
         print(f"{name}: construct_s {r['construct_s']:.4f}  prepare_update_s {r['prepare_update_s']:.4f}  "
               f"update_s {r['update_s']:.5f}  solve_s {r['solve_s']:.4f}  ->  update + solve "
               f"{r['update_plus_solve_s']:.4f} s against construct + solve {r['construct_plus_solve_s']:.4f} s "
@@ -251,6 +325,16 @@ def main():
         if adjoint_full:
             print(f"{name}: adjoint with all five cotangents on the same point {r['adjoint_full_s']:.4f} s, "
                   f"residual <= {r['adjoint_full_residual']:.1e}", flush=True)
+        if tangent:
+            print(f"{name}: tangent (seven direction blocks, five outputs): {r['tangent_s']:.4f} s after a solve of "
+                  f"{r['tangent_solve_s']:.4f} s; a second direction on the same point {r['tangent_again_s']:.4f} s; "
+                  f"residual <= {r['tangent_residual']:.1e}, status {r['tangent_status']}", flush=True)
+            if warm is not None:
+                med = lambda v: statistics.median(v) if v else float("nan")  # noqa: E731
+                print(f"{name}: warm start {warm} from solution + tangent: iterations "
+                      f"{med(r['tangent_warm_iters_predicted'])} (status {r['tangent_warm_status_predicted']}), "
+                      f"from the last solution alone {med(r['tangent_warm_iters_last'])} (status "
+                      f"{r['tangent_warm_status_last']}), cold {med(r['iters'])}", flush=True)
         out.append(r)
     print(json.dumps({"resolve_bench": out, "warmup": WARMUP, "reps": REPS, "rel_noise": REL}))
 
