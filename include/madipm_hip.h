@@ -628,6 +628,58 @@ int madipm_solver_tangent_device(madipm_solver_t s, const madipm_qp_directions* 
  * do not overwrite each other; synchronises the solver's stream).  Any pointer may be NULL. */
 int madipm_solver_tangent_info(madipm_solver_t s, int64_t* n_tangents, double* last_residual);
 
+/* ------------------------------------------------------------------ polish: exact active-set solve  [ABI 0.2.10, additive]
+ * madipm_solver_solve ends at a central-path point (mu about 1e-9): no bound is attained exactly and the
+ * multipliers of inactive bounds are about 1e-8.  The polish identifies the active set at that point (or takes
+ * the caller's), fixes the active coordinates of v = [x_free; s] (s = the inequality rows' values) at their
+ * bounds and solves the equality-constrained QP of that face to rounding level: one factorisation of the K2
+ * pattern (active coordinates penalised by sigma on the diagonal, no Sigma on the others) preconditions
+ * 1 + refine_steps solves with the EXACT reduced operator.  (Four symbols and three structs;
+ * madipm_version() still returns 203; nothing above changed.)
+ * The guess: coordinate j is lower-active when it has a lower bound and zl_j > v_j - lo_j, upper-active when it
+ * has an upper bound and zu_j > hi_j - v_j (both: the larger multiplier, lower on a tie), on the values
+ * madipm_solver_get_solution returns (a row's multipliers are max(-y, 0) and max(y, 0)).  A supplied set is one
+ * int8 per variable and one per row: -1 lower, +1 upper, 0 inactive; 0 on fixed variables and equality rows.
+ * The verdict (the larger number wins):
+ *   0 POLISHED: residual <= tol_resid (max-norm of the exact reduced residual at the final point, scaled space),
+ *     every active multiplier >= -tol_sign max(1, max |multiplier|), every inactive bound kept
+ *     (gap >= -tol_feas max(1, |bound|)).  The outputs are the polished point: an active variable equals its
+ *     bound, an inactive multiplier is 0, cons of an active row is the row's bound.
+ *   1 WRONG_SET: a sign or a bound is violated.   2 NO_CONVERGENCE: the residual is above tol_resid or not
+ *   finite (a degenerate face with dependent active constraints).   3 FACTORIZATION_FAILED: all three
+ *   regularisation trials failed.  In verdicts 1 - 3 the outputs are madipm_solver_get_solution's, bit for bit.
+ * info: verdict; n_active; residual; min_multiplier (the smallest active multiplier, +inf without one);
+ * min_gap (the smallest gap over the inactive bounds, +inf without one); the two counters.
+ * Refused as madipm_solver_adjoint refuses, and: exactly one of active_var / active_row given; a code other
+ * than -1, 0, +1, or one on a bound that does not exist, on a fixed variable or on an equality row; every
+ * output NULL; sigma, a tolerance or refine_steps (0..8) out of range.
+ * The call overwrites the KKT diagonal and the LDL^T factor: a later adjoint / tangent on the point
+ * factorises again (and a polish after those as well); a second polish of the same point with the same set
+ * and sigma does not.  Nothing a later madipm_solver_initialize / _solve reads is changed.
+ * Memory, allocated by the first call: madipm_solver_adjoint's scratch if no adjoint allocated it, 8 B x (4 n +
+ * 2 ncon) + 2 n bytes + 4 B per inequality row + 64 KiB of its own (n = nvar + inequality rows); on the host
+ * route 8 B per entry of each block and 1 B per code asked for or supplied. */
+enum { MADIPM_POLISHED = 0, MADIPM_POLISH_WRONG_SET = 1, MADIPM_POLISH_NO_CONVERGENCE = 2,
+       MADIPM_POLISH_FACTORIZATION_FAILED = 3 };
+typedef struct madipm_polish_opts { double sigma, tol_resid, tol_sign, tol_feas; int32_t refine_steps; } madipm_polish_opts;
+typedef struct madipm_polish_out { double *x, *y, *zl, *zu, *cons; int8_t *active_var, *active_row; } madipm_polish_out; /* any NULL */
+typedef struct madipm_polish_info {
+  int32_t verdict, n_active;
+  double residual, min_multiplier, min_gap;
+  int64_t n_polishes, n_polish_factorizations;
+} madipm_polish_info;
+void madipm_polish_default_opts(madipm_polish_opts* o); /* sigma 1e10, tolerances 1e-10, 1e-9, 1e-9, refine_steps 2 */
+/* HOST pointers.  opts NULL: the defaults; active_var and active_row both NULL: the guess; info may be NULL. */
+int madipm_solver_polish(madipm_solver_t s, const madipm_polish_opts* opts, const int8_t* active_var,
+                         const int8_t* active_row, const madipm_polish_out* out, madipm_polish_info* info);
+/* DEVICE pointers for the sets and `out` (info is a host struct), with the stream contract of
+ * madipm_solver_adjoint_device; the call waits, on the host, for the set's validation and the verdict. */
+int madipm_solver_polish_device(madipm_solver_t s, const madipm_polish_opts* opts, const int8_t* d_active_var,
+                                const int8_t* d_active_row, const madipm_polish_out* d_out, madipm_polish_info* info,
+                                madipm_stream_t stream);
+/* The last polish's info (zeros and verdict -1 before the first); no device access. */
+int madipm_solver_polish_info(madipm_solver_t s, madipm_polish_info* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -817,6 +817,50 @@ int madipm_solver_tangent_info(madipm_solver_t s, int64_t* n_tangents, double* l
   MADIPM_API_END
 }
 
+void madipm_polish_default_opts(madipm_polish_opts* o) {
+  if (!o) return;
+  o->sigma = 1e10;
+  o->tol_resid = 1e-10;
+  o->tol_sign = 1e-9;
+  o->tol_feas = 1e-9;
+  o->refine_steps = 2;
+}
+
+static madipm_polish_opts polish_opts(const madipm_polish_opts* o) {
+  madipm_polish_opts d;
+  madipm_polish_default_opts(&d);
+  return o ? *o : d;
+}
+
+int madipm_solver_polish(madipm_solver_t s, const madipm_polish_opts* opts, const int8_t* active_var,
+                         const int8_t* active_row, const madipm_polish_out* out, madipm_polish_info* info) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(out, "madipm_solver_polish: null output struct");
+  s->s->polish(polish_opts(opts), active_var, active_row, *out, info, false, nullptr);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_polish_device(madipm_solver_t s, const madipm_polish_opts* opts, const int8_t* d_active_var,
+                                const int8_t* d_active_row, const madipm_polish_out* d_out, madipm_polish_info* info,
+                                madipm_stream_t stream) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(d_out, "madipm_solver_polish_device: null output struct");
+  s->s->polish(polish_opts(opts), d_active_var, d_active_row, *d_out, info, true, (hipStream_t)stream);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_polish_info(madipm_solver_t s, madipm_polish_info* info) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->polish_info(info);
+  return 0;
+  MADIPM_API_END
+}
+
 int madipm_update_step(int32_t rule, double tau, double mu, int32_t nlb, int32_t nub, const double* d_x_lr,
                        const double* d_xl_r, const double* d_zl_r, const double* d_dx_lr, const double* d_dzl,
                        const double* d_x_ur, const double* d_xu_r, const double* d_zu_r, const double* d_dx_ur,

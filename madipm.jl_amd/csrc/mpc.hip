@@ -131,6 +131,28 @@ struct Tangent {
   int64_t n_tangents = 0;
 };
 
+// The polish (madipm_solver_polish*) shares the adjoint's residual rows, rowslack and events (and
+// overwrites its factor: sens_factor and polish() clear each other's tag).  Its own, allocated by the first
+// call: the scratch point [v; y], the gradient of the Lagrangian on [x; s], the raw bounds of [x; s] in the
+// public space, the partial measures and the row values (8 B x (4 n + 2 m)); the codes of this call and of the
+// factor held (2 n B); the slack -> row map (4 B per slack); the host route's staging of the set and the
+// outputs.
+struct PolMeasures {  // k_pol_verdict's result, read back with one copy
+  int32_t verdict, n_active;
+  double residual, min_multiplier, min_gap;
+};
+struct Polish {
+  DBuf<double> w, grad, lo, hi, part, ax;
+  DBuf<int8_t> codes, codes_fact, in_var, in_row, out_var, out_row;
+  DBuf<int32_t> ineq, flags;              // flags: [a bad code was supplied, the codes differ from the factor's]
+  DBuf<PolMeasures> meas;
+  DBuf<double> out[5];                    // host route: x, y, zl, zu, cons
+  int64_t bounds_updates = -1;            // n_updates_ of the bounds in lo / hi
+  int64_t fact_solve = -1;                // n_solves_ of the point the LDL^T holds the polish factor of
+  double fact_sigma = 0.0;
+  madipm_polish_info last{-1, 0, 0.0, 0.0, 0.0, 0, 0};
+};
+
 namespace {
 
 constexpr int NT = 256;
@@ -3471,6 +3493,7 @@ Adjoint& MPCSolver::sens_state() {
 void MPCSolver::sens_factor(Adjoint& a, const std::string& who) {
   if (a.fact_solve == n_solves_) return;
   a.fact_solve = -1;
+  if (pol_) pol_->fact_solve = -1;  // the polish's factor (§13f) is overwritten
   double dw = 0.0, dc = 0.0;  // the options' regularisation; Adaptive: the current pair, not decayed
   if (opt_.regularization == 1) {
     dw = opt_.delta_p;
@@ -3956,6 +3979,436 @@ void MPCSolver::tangent_info(int64_t* n_tangents, double* last_residual) {
       MADIPM_HIP(hipStreamSynchronize(stream_));
     }
   }
+}
+
+}  // namespace madipm
+
+// ======================================================================= polish
+// madipm_solver_polish / _polish_device: the active set the end point identifies (or the caller's), the active
+// coordinates of v = [x; s] at their bounds, and the equality-constrained QP of that face solved in delta form:
+// r = -[grad of the Lagrangian on the inactive coordinates; J v - b] at the scratch point w = [v; y], a solve
+// with the factor of the K2 pattern whose diagonal is H~_ii + delta_w (+ sigma on an active coordinate; no
+// Sigma), the correction masked on the active coordinates, a fixed number of times.  The factor is a
+// preconditioner: the residual is the exact masked operator's.  One thread (the residual: one lane group) per
+// output, every sum in a fixed order, no atomics but the integer maxima of the two flags.
+namespace madipm {
+namespace {
+
+struct PolArgs {
+  int n, m, nx;
+  double os;                                   // obj_scale
+  const double *x, *zl, *zu, *y;               // the iterate (scaled space); never written
+  const double* cscale;                        // con_scale
+  const int32_t *lbpos, *ubpos;
+  const uint8_t* fixed;
+  const double *lo, *hi;                       // raw bounds of [x; s], public space (lvar / lcon of the slack's row)
+  const int32_t *ineq, *rowslack;              // slack -> row; row -> slack coordinate or -1
+  int8_t* codes;                               // -1 lower-active, +1 upper-active, 0 inactive, per coordinate of [x; s]
+  const int8_t* codes_fact;                    // the codes the factor held was made with
+  double *w, *grad;                            // [v; y]; f + J~^T y on [x; s] at w
+  int32_t* flags;
+};
+
+// con_scale of coordinate i's row (1 on a variable), and its bounds in the scaled space
+__device__ __forceinline__ double pol_cs(const PolArgs& P, int i) { return i < P.nx ? 1.0 : P.cscale[P.ineq[i - P.nx]]; }
+// a multiplier of coordinate i, scaled space -> public (k_unscale's roundings: z / os, y cs / os)
+__device__ __forceinline__ double pol_mult(const PolArgs& P, int i, double z, double cs) {
+  return i < P.nx ? z / P.os : z * cs / P.os;
+}
+
+// The codes and the projected point.  av == null: the guess, on the values get_solution returns (multiplier
+// against gap, both un-scaled); else the supplied set, validated (flags[0]).  flags[1]: the codes differ from
+// those of the factor held.  Writes only scratch.  t1 as in k_adj_shift.
+__global__ __launch_bounds__(NT) void k_pol_classify(PolArgs P, const int8_t* __restrict__ av,
+                                                     const int8_t* __restrict__ ar, LDLStatus* t1) {
+#pragma clang fp contract(off)
+  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  const int top = P.n > P.m ? P.n : P.m;
+  GRID_LOOP(i, top) {
+    if (i < P.n) {
+      const bool fx = P.fixed[i], kl = P.lbpos[i] >= 0, ku = P.ubpos[i] >= 0;
+      const double cs = pol_cs(P, (int)i);
+      const double v = P.x[i];
+      const double ls = i < P.nx ? P.lo[i] : cs * P.lo[i], us = i < P.nx ? P.hi[i] : cs * P.hi[i];
+      int c = 0;
+      if (av) {
+        c = i < P.nx ? av[i] : ar[P.ineq[i - P.nx]];
+        if (c != 0 && (fx || (c != -1 && c != 1) || (c == -1 && !kl) || (c == 1 && !ku))) {
+          atomicMax(&P.flags[0], 1);
+          c = 0;
+        }
+      } else if (!fx) {
+        const double zl = kl ? pol_mult(P, (int)i, P.zl[i], cs) : 0.0, zu = ku ? pol_mult(P, (int)i, P.zu[i], cs) : 0.0;
+        const bool la = kl && zl > (v - ls) / cs, ua = ku && zu > (us - v) / cs;
+        c = (la && ua) ? (zu > zl ? 1 : -1) : (la ? -1 : (ua ? 1 : 0));
+      }
+      P.w[i] = c < 0 ? ls : (c > 0 ? us : v);
+      if (P.codes_fact[i] != c) atomicMax(&P.flags[1], 1);
+      P.codes[i] = (int8_t)c;
+    }
+    if (i < P.m) {
+      P.w[P.n + i] = P.y[i];
+      if (ar && P.rowslack[i] < 0 && ar[i] != 0) atomicMax(&P.flags[0], 1);
+    }
+  }
+}
+
+// The K2 diagonal of the polish factor: H~_ii + delta_w, + sigma on an active coordinate; delta_c on a row.
+// Only Kx's diagonal is written.  rs as in k_diag.
+__global__ __launch_bounds__(NT) void k_pol_diag(DV D, const int8_t* __restrict__ codes, double dw, double dc,
+                                                 double sigma, LDLStatus* rs) {
+#pragma clang fp contract(off)
+  if (rs && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_start(rs);
+  GRID_LOOP(i, D.n + D.m) {
+    if (i < D.n) {
+      const double h = D.Hdiag[i] + dw;
+      D.Kx[D.diag_pos[i]] = codes[i] ? h + sigma : h;
+    } else {
+      D.Kx[D.diag_pos[i]] = dc;
+    }
+  }
+}
+
+// The exact masked residual at w: on a coordinate of [x; s], t = (H~ v + c~ + gfix) + J~^T y (k_eval's f and
+// jacl), r = -t on an inactive free coordinate and 0 on an active or fixed one; on a row, r = -((J~ v - rhs) +
+// cfix).  r (may be null) becomes the right-hand side of the next solve; grad (may be null) keeps t.
+template <int G>
+__global__ __launch_bounds__(NT) void k_pol_resid(DV D, PolArgs P, double* __restrict__ r, double* __restrict__ rowres,
+                                                  double* __restrict__ grad, LDLStatus* t1) {
+#pragma clang fp contract(off)
+  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  const int n = D.n, m = D.m;
+  const bool lead = (threadIdx.x & (G - 1)) == 0;
+  const double* __restrict__ w = P.w;
+  GROUP_LOOP(i, n + m, G) {
+    double ri;
+    if (i < n) {
+      double hv, jy;
+      gdot2<G>(D.H, i, w, D.JT, i, w + n, hv, jy);
+      const double t = (hv + (D.cs[i] + D.gfix[i])) + jy;
+      ri = (P.codes[i] != 0 || D.fixed[i]) ? 0.0 : -t;
+      if (lead && grad) grad[i] = t;
+    } else {
+      const int64_t j = i - n;
+      const double jv = gdot<G>(D.J, j, w);
+      ri = -((jv - D.rhs[j]) + D.cfix[j]);
+    }
+    if (lead) {
+      if (r) r[i] = ri;
+      rowres[i] = fabs(ri);
+    }
+  }
+}
+
+// w += d, with the correction of an active or fixed coordinate dropped
+__global__ __launch_bounds__(NT) void k_pol_acc(PolArgs P, const double* __restrict__ d) {
+  GRID_LOOP(i, P.n + P.m) {
+    if (i < P.n && (P.codes[i] != 0 || P.fixed[i])) continue;
+    P.w[i] = P.w[i] + d[i];
+  }
+}
+
+// The checks as block partials (value-major, pidx): the smallest active multiplier, the largest |active
+// multiplier|, the smallest gap / max(1, |bound|) and the smallest gap over the inactive bounds, all in the
+// public space
+__global__ __launch_bounds__(NT) void k_pol_meas(PolArgs P, double* __restrict__ part) {
+#pragma clang fp contract(off)
+  double mn = INF, ma = 0.0, gp = INF, gr = INF;
+  GRID_LOOP(i, P.n) {
+    if (P.fixed[i]) continue;
+    const int c = P.codes[i];
+    const double cs = pol_cs(P, (int)i);
+    if (c != 0) {
+      const double t = pol_mult(P, (int)i, P.grad[i], cs);
+      const double z = c < 0 ? t : -t;
+      mn = fmin(mn, z);
+      ma = nmax(ma, fabs(z));
+    }
+    const double v = P.w[i];
+    if (P.lbpos[i] >= 0 && c != -1) {
+      const double b = P.lo[i], bs = i < P.nx ? b : cs * b;
+      const double g = (v - bs) / cs;
+      gr = fmin(gr, g);
+      gp = fmin(gp, g / fmax(1.0, fabs(b)));
+    }
+    if (P.ubpos[i] >= 0 && c != 1) {
+      const double b = P.hi[i], bs = i < P.nx ? b : cs * b;
+      const double g = (bs - v) / cs;
+      gr = fmin(gr, g);
+      gp = fmin(gp, g / fmax(1.0, fabs(b)));
+    }
+  }
+  double v[4] = {mn, ma, gp, gr};
+  const int ops[4] = {OP_MIN, OP_MAX, OP_MIN, OP_MIN};
+  block_partials<4>(v, ops, part);
+}
+
+// The verdict: one block, each thread a strided slice, then an LDS tree (k_adj_resmax's shape; maxima and
+// minima do not depend on the order, the count is an integer sum).  failed: all three factorisations failed.
+__global__ __launch_bounds__(NT) void k_pol_verdict(const double* __restrict__ rowres, int64_t N,
+                                                    const double* __restrict__ part, int nb,
+                                                    const int8_t* __restrict__ codes, int n, double tol_resid,
+                                                    double tol_sign, double tol_feas, int failed,
+                                                    PolMeasures* __restrict__ out) {
+  __shared__ double sr[NT], smn[NT], sma[NT], sgp[NT], sgr[NT];
+  __shared__ int sc[NT];
+  const int t = threadIdx.x;
+  double r = 0.0, mn = INF, ma = 0.0, gp = INF, gr = INF;
+  int cnt = 0;
+  for (int64_t i = t; i < N; i += NT) r = nmax(r, rowres[i]);
+  for (int b = t; b < nb; b += NT) {
+    mn = fmin(mn, part[pidx(b, 0)]);
+    ma = nmax(ma, part[pidx(b, 1)]);
+    gp = fmin(gp, part[pidx(b, 2)]);
+    gr = fmin(gr, part[pidx(b, 3)]);
+  }
+  for (int i = t; i < n; i += NT) cnt += codes[i] != 0;
+  sr[t] = r, smn[t] = mn, sma[t] = ma, sgp[t] = gp, sgr[t] = gr, sc[t] = cnt;
+  __syncthreads();
+  for (int o = NT / 2; o > 0; o >>= 1) {
+    if (t < o) {
+      sr[t] = nmax(sr[t], sr[t + o]);
+      smn[t] = fmin(smn[t], smn[t + o]);
+      sma[t] = nmax(sma[t], sma[t + o]);
+      sgp[t] = fmin(sgp[t], sgp[t + o]);
+      sgr[t] = fmin(sgr[t], sgr[t + o]);
+      sc[t] += sc[t + o];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    int v = MADIPM_POLISHED;
+    if (smn[0] < -tol_sign * (sma[0] > 1.0 ? sma[0] : 1.0) || sgp[0] < -tol_feas) v = MADIPM_POLISH_WRONG_SET;
+    if (!(sr[0] <= tol_resid)) v = MADIPM_POLISH_NO_CONVERGENCE;  // a NaN lands here
+    if (failed) v = MADIPM_POLISH_FACTORIZATION_FAILED;
+    out->verdict = v;
+    out->n_active = sc[0];
+    out->residual = sr[0];
+    out->min_multiplier = smn[0];
+    out->min_gap = sgr[0];
+  }
+}
+
+// The polished point, un-scaled (any output may be null): x = v; y = y~ cs / os; zl = t / os on a lower-active
+// variable, zu = -t / os on an upper-active one, 0 elsewhere; cons = (A x) / cs from k_cons' row values, the
+// bound itself on an active row
+__global__ __launch_bounds__(NT) void k_pol_out(PolArgs P, const double* __restrict__ ax, double* __restrict__ ox,
+                                                double* __restrict__ oy, double* __restrict__ ozl,
+                                                double* __restrict__ ozu, double* __restrict__ ocons) {
+#pragma clang fp contract(off)
+  GRID_LOOP(i, (P.nx > P.m ? P.nx : P.m)) {
+    if (i < P.nx) {
+      const int c = P.codes[i];
+      const double t = c != 0 ? P.grad[i] / P.os : 0.0;
+      if (ox) ox[i] = P.w[i];
+      if (ozl) ozl[i] = c < 0 ? t : 0.0;
+      if (ozu) ozu[i] = c > 0 ? -t : 0.0;
+    }
+    if (i < P.m) {
+      const double cs = P.cscale[i];
+      if (oy) oy[i] = P.w[P.n + i] * cs / P.os;
+      if (ocons) {
+        const int k = P.rowslack[i], c = k >= 0 ? P.codes[k] : 0;
+        ocons[i] = c < 0 ? P.lo[k] : (c > 0 ? P.hi[k] : ax[i] / cs);
+      }
+    }
+  }
+}
+
+// The codes as the caller sees them: one per variable, one per row (0 on an equality row)
+__global__ __launch_bounds__(NT) void k_pol_codes(PolArgs P, int8_t* __restrict__ ovar, int8_t* __restrict__ orow) {
+  GRID_LOOP(i, (P.nx > P.m ? P.nx : P.m)) {
+    if (i < P.nx && ovar) ovar[i] = P.codes[i];
+    if (i < P.m && orow) {
+      const int k = P.rowslack[i];
+      orow[i] = k >= 0 ? P.codes[k] : (int8_t)0;
+    }
+  }
+}
+
+}  // namespace
+
+void MPCSolver::polish(const madipm_polish_opts& o, const int8_t* av, const int8_t* ar, const madipm_polish_out& po,
+                       madipm_polish_info* info, bool device, hipStream_t caller) {
+  const std::string who = device ? "madipm_solver_polish_device: " : "madipm_solver_polish: ";
+  QPHost& P = *H_;
+  // ---- refusals, before anything is allocated or enqueued
+  sens_refuse(who);
+  MADIPM_REQUIRE((av == nullptr) == (ar == nullptr),
+                 who + "exactly one of active_var and active_row is given (pass both, or neither for the guess)");
+  double* const user[5] = {po.x, po.y, po.zl, po.zu, po.cons};
+  MADIPM_REQUIRE(po.x || po.y || po.zl || po.zu || po.cons || po.active_var || po.active_row,
+                 who + "all seven outputs are NULL");
+  auto tol_ok = [](double t) { return t >= 0.0 && std::isfinite(t); };
+  MADIPM_REQUIRE(o.sigma > 0.0 && std::isfinite(o.sigma), who + "sigma must be positive and finite");
+  MADIPM_REQUIRE(tol_ok(o.tol_resid) && tol_ok(o.tol_sign) && tol_ok(o.tol_feas),
+                 who + "tol_resid, tol_sign and tol_feas must be finite and not negative");
+  MADIPM_REQUIRE(o.refine_steps >= 0 && o.refine_steps <= 8,
+                 who + "refine_steps must be in 0..8, got " + std::to_string(o.refine_steps));
+  hipStream_t s = stream_;
+  // ---- allocations, by the first call
+  Adjoint& a = sens_state();
+  const double* cscale = device_con_scale();
+  if (!a.rowslack.p) {
+    a.rowslack.upload(adjoint_rowslack(P), s);
+    MADIPM_HIP(hipStreamSynchronize(s));
+  }
+  const int ns = n_ - nx_;
+  if (!pol_) {
+    auto p = std::make_unique<Polish>();
+    p->w.alloc(std::max(n_ + m_, 1));
+    p->grad.alloc(std::max(n_, 1));
+    p->lo.alloc(std::max(n_, 1));
+    p->hi.alloc(std::max(n_, 1));
+    p->part.alloc((size_t)4 * MAXB);
+    p->ax.alloc(std::max(m_, 1));
+    p->codes.alloc(std::max(n_, 1));
+    p->codes_fact.alloc(std::max(n_, 1));
+    p->codes_fact.zero(s);
+    p->ineq.alloc(std::max(ns, 1));
+    p->ineq.upload(P.ind_ineq.data(), P.ind_ineq.size(), s);
+    p->flags.alloc(2);
+    p->meas.alloc(1);
+    pol_ = std::move(p);
+  }
+  Polish& p = *pol_;
+  if (p.bounds_updates != n_updates_) {  // the raw bounds of [x; s], as the last update left them
+    refresh_host_mirrors();
+    std::vector<double> lo(std::max(n_, 1)), hi(std::max(n_, 1));
+    for (int i = 0; i < nx_; ++i) lo[i] = P.lvar[i], hi[i] = P.uvar[i];
+    for (int k = 0; k < ns; ++k) lo[nx_ + k] = P.lcon[P.ind_ineq[k]], hi[nx_ + k] = P.ucon[P.ind_ineq[k]];
+    p.lo.upload(lo, s);
+    p.hi.upload(hi, s);
+    MADIPM_HIP(hipStreamSynchronize(s));  // lo / hi are this scope's
+    p.bounds_updates = n_updates_;
+  }
+  const int64_t olen[5] = {nx_, m_, nx_, nx_, m_};
+  double* out[5];
+  for (int j = 0; j < 5; ++j) {
+    out[j] = user[j];
+    if (!device && user[j]) {
+      if (!p.out[j].p) p.out[j].alloc(std::max<int64_t>(olen[j], 1));
+      out[j] = p.out[j].p;
+    }
+  }
+  int8_t *ovar = po.active_var, *orow = po.active_row;
+  const int8_t *dav = av, *dar = ar;
+  if (!device) {
+    if (ovar && !p.out_var.p) p.out_var.alloc(std::max(nx_, 1));
+    if (orow && !p.out_row.p) p.out_row.alloc(std::max(m_, 1));
+    if (ovar) ovar = p.out_var.p;
+    if (orow) orow = p.out_row.p;
+    if (av) {
+      if (!p.in_var.p) {
+        p.in_var.alloc(std::max(nx_, 1));
+        p.in_row.alloc(std::max(m_, 1));
+      }
+      p.in_var.upload(av, nx_, s);
+      p.in_row.upload(ar, m_, s);
+      dav = p.in_var.p;
+      dar = p.in_row.p;
+    }
+  } else {  // the set is read, and the outputs written, after the work already enqueued on the caller's stream
+    MADIPM_HIP(hipEventRecord(a.ev[0], caller));
+    MADIPM_HIP(hipStreamWaitEvent(s, a.ev[0], 0));
+  }
+  // ---- the codes and the projected point
+  DV_ARGS;
+  const PolArgs A{n_, m_, nx_, obj_scale_, x_.p, zl_.p, zu_.p, y_.p, cscale, lbpos_.p, ubpos_.p, fixed_.p,
+                  p.lo.p, p.hi.p, p.ineq.p, a.rowslack.p, p.codes.p, p.codes_fact.p, p.w.p, p.grad.p, p.flags.p};
+  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_), nbn = blocks(std::max(n_, 1));
+  const int64_t N = (int64_t)n_ + m_;
+  p.flags.zero(s);
+  k_pol_classify<<<blocks(std::max(std::max(n_, m_), 1)), NT, 0, s>>>(A, dav, dar, take_fact_end());
+  MADIPM_HIP(hipGetLastError());
+  int32_t hflags[2] = {0, 0};
+  MADIPM_HIP(hipMemcpyAsync(hflags, p.flags.p, sizeof(hflags), hipMemcpyDeviceToHost, s));
+  MADIPM_HIP(hipStreamSynchronize(s));
+  MADIPM_REQUIRE(!hflags[0], who + "the supplied set has a code other than -1, 0, +1, or a code on a bound that does "
+                                   "not exist, on a fixed variable or on an equality row");
+  // ---- the factor: once per point, set and sigma
+  bool ok = true;
+  if (p.fact_solve != n_solves_ || p.fact_sigma != o.sigma || hflags[1]) {
+    p.fact_solve = -1;
+    a.fact_solve = -1;  // the adjoint's factor and KKT diagonal are overwritten
+    double dw = 0.0, dc = 0.0;  // sens_factor's regularisation and trials
+    if (opt_.regularization == 1) {
+      dw = opt_.delta_p;
+      dc = opt_.delta_d;
+    } else if (opt_.regularization != 0) {
+      dw = adapt_dp_;
+      dc = adapt_dd_;
+    }
+    ok = false;
+    for (int trial = 0; trial < 3 && !ok; ++trial) {
+      if (trial) {
+        dw *= 100.0;
+        dc *= 100.0;
+      }
+      k_pol_diag<<<nb, NT, 0, s>>>(D, p.codes.p, dw, dc, o.sigma, fact_reset());
+      timed_factorize();
+      ok = ldl_->status(s) == 0;
+    }
+    if (ok) {
+      if (n_) MADIPM_HIP(hipMemcpyAsync(p.codes_fact.p, p.codes.p, (size_t)n_, hipMemcpyDeviceToDevice, s));
+      p.fact_solve = n_solves_;
+      p.fact_sigma = o.sigma;
+      ++p.last.n_polish_factorizations;
+    }
+  }
+  // ---- 1 + refine_steps solves in delta form, the final residual, the verdict
+  if (ok)
+    for (int it = 0; it <= o.refine_steps; ++it) {
+      SPMV_LAUNCH(k_pol_resid, nbs, s, D, A, d_.p, a.rowres.p, (double*)nullptr, take_fact_end());
+      kkt_solve();
+      k_pol_acc<<<nb, NT, 0, s>>>(A, d_.p);
+    }
+  SPMV_LAUNCH(k_pol_resid, nbs, s, D, A, (double*)nullptr, a.rowres.p, p.grad.p, take_fact_end());
+  k_pol_meas<<<nbn, NT, 0, s>>>(A, p.part.p);
+  k_pol_verdict<<<1, NT, 0, s>>>(a.rowres.p, N, p.part.p, nbn, p.codes.p, n_, o.tol_resid, o.tol_sign, o.tol_feas,
+                                 ok ? 0 : 1, p.meas.p);
+  MADIPM_HIP(hipGetLastError());
+  PolMeasures hm{};
+  MADIPM_HIP(hipMemcpyAsync(&hm, p.meas.p, sizeof(hm), hipMemcpyDeviceToHost, s));
+  MADIPM_HIP(hipStreamSynchronize(s));
+  // ---- outputs: the polished point, or get_solution's bits
+  const bool any5 = out[0] || out[1] || out[2] || out[3] || out[4];
+  const unsigned nbc = (unsigned)((m_ + NT / 64 - 1) / (NT / 64));
+  if (any5 && std::max(nx_, m_)) {
+    if (hm.verdict == MADIPM_POLISHED) {
+      if (out[4] && m_) k_cons<<<nbc, NT, 0, s>>>(Jrp_, Jci_, Jv_, p.w.p, cfix_, m_, nx_, p.ax.p);
+      k_pol_out<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, p.ax.p, out[0], out[1], out[2], out[3], out[4]);
+    } else {
+      if (out[4] && m_) k_cons<<<nbc, NT, 0, s>>>(Jrp_, Jci_, Jv_, x_, cfix_, m_, nx_, p.ax.p);
+      k_unscale<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(nx_, m_, obj_scale_, x_, y_, zl_, zu_, p.ax.p, cscale, out[0],
+                                                          out[1], out[2], out[3], out[4]);
+    }
+  }
+  if ((ovar || orow) && std::max(nx_, m_)) k_pol_codes<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, ovar, orow);
+  MADIPM_HIP(hipGetLastError());
+  if (device) {  // work enqueued on the caller's stream from now on sees the outputs
+    MADIPM_HIP(hipEventRecord(a.ev[1], s));
+    MADIPM_HIP(hipStreamWaitEvent(caller, a.ev[1], 0));
+  } else {
+    for (int j = 0; j < 5; ++j)
+      if (user[j] && olen[j])
+        MADIPM_HIP(hipMemcpyAsync(user[j], out[j], olen[j] * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (po.active_var && nx_) MADIPM_HIP(hipMemcpyAsync(po.active_var, ovar, (size_t)nx_, hipMemcpyDeviceToHost, s));
+    if (po.active_row && m_) MADIPM_HIP(hipMemcpyAsync(po.active_row, orow, (size_t)m_, hipMemcpyDeviceToHost, s));
+    MADIPM_HIP(hipStreamSynchronize(s));
+  }
+  ++p.last.n_polishes;
+  p.last.verdict = hm.verdict;
+  p.last.n_active = hm.n_active;
+  p.last.residual = hm.residual;
+  p.last.min_multiplier = hm.min_multiplier;
+  p.last.min_gap = hm.min_gap;
+  if (info) *info = p.last;
+}
+
+void MPCSolver::polish_info(madipm_polish_info* info) const {
+  if (!info) return;
+  *info = pol_ ? pol_->last : madipm_polish_info{-1, 0, 0.0, 0.0, 0.0, 0, 0};
 }
 
 }  // namespace madipm

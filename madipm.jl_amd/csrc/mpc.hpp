@@ -47,6 +47,7 @@ struct WarmStart;    // the warm point and its scratch, on the device (mpc.hip)
 struct Adjoint;      // index copies, fixed-variable lists and scratch of the adjoint gradients (mpc.hip)
 struct AdjArgs;      // the adjoint kernels' view of the point and the solution (mpc.hip)
 struct Tangent;      // entry lists and scratch of the forward-mode sensitivities (mpc.hip)
+struct Polish;       // scratch, set codes and counters of the active-set polish (mpc.hip)
 
 class MPCSolver {
  public:
@@ -102,6 +103,12 @@ class MPCSolver {
   // factorisation per solved point serves both), refinement and residual; device and `caller` as there.
   void tangent(const madipm_qp_directions& d, const madipm_qp_point_tangents& out, bool device, hipStream_t caller);
   void tangent_info(int64_t* n_tangents, double* last_residual);
+  // The exact active-set solve after the interior-point method (madipm_solver_polish / _polish_device /
+  // _polish_info).  av / ar: the supplied set (both null: the guess); device: every pointer but
+  // `info` is a device pointer, ordered against `caller` as in adjoint().
+  void polish(const madipm_polish_opts& o, const int8_t* av, const int8_t* ar, const madipm_polish_out& out,
+              madipm_polish_info* info, bool device, hipStream_t caller);
+  void polish_info(madipm_polish_info* info) const;
   int64_t n_analyses() const { return n_analyses_; }
   int64_t n_updates() const { return n_updates_; }
   double last_update_s() const { return last_update_s_; }
@@ -210,6 +217,7 @@ class MPCSolver {
   bool solved_ = false;                // a solve has run (warm_start_last needs its point)
   std::unique_ptr<Adjoint> adj_;       // null until the first adjoint or tangent
   std::unique_ptr<Tangent> tan_;       // null until the first tangent
+  std::unique_ptr<Polish> pol_;        // null until the first polish
   bool point_ok_ = false;              // the iterate is the end point of a completed solve
   int64_t n_solves_ = 0;               // completed solves (the adjoint's factor belongs to one of them)
   int64_t solve_updates_ = 0;          // n_updates_ at the end of the last solve

@@ -402,3 +402,86 @@ function solver_adjoint_full_device(h::Ptr{Cvoid}; gx=nothing, gy=nothing, gzl=n
           "madipm_solver_adjoint_full_device")
     return
 end
+
+# ---- polish: the exact active-set solve after the interior-point method (ABI 0.2.10).  The active set the end
+# point identifies (or the caller's: one Int8 per variable and one per row, -1 lower, +1 upper, 0 inactive), the
+# active coordinates at their bounds, the equality-constrained QP of that face solved to rounding level.
+# madipm_polish_out: seven pointers (x, y, zl, zu, cons: Float64; active_var, active_row: Int8), a null one = not
+# wanted, not all seven.  The verdict (0 polished, 1 wrong set, 2 no convergence, 3 factorisation failed) comes
+# back in the info; with a verdict other than 0 the blocks are solver_get_solution's.
+struct MadipmPolishOpts
+    sigma::Float64
+    tol_resid::Float64
+    tol_sign::Float64
+    tol_feas::Float64
+    refine_steps::Int32
+end
+struct MadipmPolishOut
+    x::Ptr{Float64}
+    y::Ptr{Float64}
+    zl::Ptr{Float64}
+    zu::Ptr{Float64}
+    cons::Ptr{Float64}
+    active_var::Ptr{Int8}
+    active_row::Ptr{Int8}
+end
+struct MadipmPolishInfo
+    verdict::Int32
+    n_active::Int32
+    residual::Float64
+    min_multiplier::Float64
+    min_gap::Float64
+    n_polishes::Int64
+    n_polish_factorizations::Int64
+end
+MadipmPolishInfo() = MadipmPolishInfo(-1, 0, 0.0, 0.0, 0.0, 0, 0)
+
+function polish_default_opts()
+    o = Ref(MadipmPolishOpts(0.0, 0.0, 0.0, 0.0, 0))
+    ccall((:madipm_polish_default_opts, libmadipm), Cvoid, (Ref{MadipmPolishOpts},), o)
+    return o[]
+end
+
+_i8ptr_or_null(a::Nothing) = Ptr{Int8}(C_NULL)
+_i8ptr_or_null(a::Vector{Int8}) = pointer(a)
+_i8ptr_or_null(a::Ptr{Int8}) = a
+
+# host arrays: Vector{Float64} / Vector{Int8} of the right lengths, or nothing
+function solver_polish(h::Ptr{Cvoid}; opts::MadipmPolishOpts=polish_default_opts(), active_var=nothing,
+                       active_row=nothing, x=nothing, y=nothing, zl=nothing, zu=nothing, cons=nothing,
+                       out_active_var=nothing, out_active_row=nothing)
+    info = Ref(MadipmPolishInfo())
+    GC.@preserve active_var active_row x y zl zu cons out_active_var out_active_row begin
+        o = Ref(MadipmPolishOut(_ptr_or_null(x), _ptr_or_null(y), _ptr_or_null(zl), _ptr_or_null(zu),
+                                _ptr_or_null(cons), _i8ptr_or_null(out_active_var), _i8ptr_or_null(out_active_row)))
+        check(ccall((:madipm_solver_polish, libmadipm), Cint,
+                    (Ptr{Cvoid}, Ref{MadipmPolishOpts}, Ptr{Int8}, Ptr{Int8}, Ref{MadipmPolishOut},
+                     Ref{MadipmPolishInfo}),
+                    h, Ref(opts), _i8ptr_or_null(active_var), _i8ptr_or_null(active_row), o, info),
+              "madipm_solver_polish")
+    end
+    return info[]
+end
+
+# device arrays: Ptr{Float64} / Ptr{Int8} into device memory, or nothing; the stream contract of
+# solver_adjoint_device.  The info comes back on the host.
+function solver_polish_device(h::Ptr{Cvoid}; opts::MadipmPolishOpts=polish_default_opts(), active_var=nothing,
+                              active_row=nothing, x=nothing, y=nothing, zl=nothing, zu=nothing, cons=nothing,
+                              out_active_var=nothing, out_active_row=nothing, stream::Ptr{Cvoid}=C_NULL)
+    info = Ref(MadipmPolishInfo())
+    o = Ref(MadipmPolishOut(_dptr_or_null(x), _dptr_or_null(y), _dptr_or_null(zl), _dptr_or_null(zu),
+                            _dptr_or_null(cons), _i8ptr_or_null(out_active_var), _i8ptr_or_null(out_active_row)))
+    check(ccall((:madipm_solver_polish_device, libmadipm), Cint,
+                (Ptr{Cvoid}, Ref{MadipmPolishOpts}, Ptr{Int8}, Ptr{Int8}, Ref{MadipmPolishOut}, Ref{MadipmPolishInfo},
+                 Ptr{Cvoid}),
+                h, Ref(opts), _i8ptr_or_null(active_var), _i8ptr_or_null(active_row), o, info, stream),
+          "madipm_solver_polish_device")
+    return info[]
+end
+
+function solver_polish_info(h::Ptr{Cvoid})
+    info = Ref(MadipmPolishInfo())
+    check(ccall((:madipm_solver_polish_info, libmadipm), Cint, (Ptr{Cvoid}, Ref{MadipmPolishInfo}), h, info),
+          "madipm_solver_polish_info")
+    return info[]
+end

@@ -21,6 +21,7 @@ def __getattr__(name):
                 "STATUS_NAMES", "RCCLComm", "HostComm", "SolveException", "UnfactorizedSolveException",
                 "ADJOINT_NAMES", "COTANGENT_NAMES",  # MPCSolver.adjoint's gradients; its cotangents' blocks
                 "TANGENT_NAMES",  # MPCSolver.tangent's output blocks (its directions' blocks are ADJOINT_NAMES)
+                "POLISH_NAMES", "PolishVerdict",  # MPCSolver.polish's blocks; its verdict
                 "MadIPMError"):  # MadIPMError: what MPCSolver.update raises on a change of classification
         from . import solver
         return getattr(solver, name)

@@ -153,6 +153,37 @@ _sig("madipm_solver_tangent_device", C.c_int, [vp, C.POINTER(QPDir), C.POINTER(Q
 _sig("madipm_solver_tangent_info", C.c_int, [vp, i64p, f64p])
 
 
+# polish: the exact active-set solve after the interior-point method (ABI 0.2.10)
+i8p = C.POINTER(C.c_int8)
+
+
+class PolishOpts(C.Structure):
+    """madipm_polish_opts."""
+    _fields_ = [("sigma", C.c_double), ("tol_resid", C.c_double), ("tol_sign", C.c_double), ("tol_feas", C.c_double),
+                ("refine_steps", C.c_int32)]
+
+
+class PolishOut(C.Structure):
+    """madipm_polish_out: where the polished blocks and the set's codes go; a NULL pointer means "not wanted"."""
+    _fields_ = [("x", f64p), ("y", f64p), ("zl", f64p), ("zu", f64p), ("cons", f64p), ("active_var", i8p),
+                ("active_row", i8p)]
+
+
+class PolishInfo(C.Structure):
+    """madipm_polish_info."""
+    _fields_ = [("verdict", C.c_int32), ("n_active", C.c_int32), ("residual", C.c_double),
+                ("min_multiplier", C.c_double), ("min_gap", C.c_double), ("n_polishes", C.c_int64),
+                ("n_polish_factorizations", C.c_int64)]
+
+
+_sig("madipm_polish_default_opts", None, [C.POINTER(PolishOpts)])
+_sig("madipm_solver_polish", C.c_int, [vp, C.POINTER(PolishOpts), i8p, i8p, C.POINTER(PolishOut),
+                                       C.POINTER(PolishInfo)])
+_sig("madipm_solver_polish_device", C.c_int, [vp, C.POINTER(PolishOpts), i8p, i8p, C.POINTER(PolishOut),
+                                              C.POINTER(PolishInfo), vp])
+_sig("madipm_solver_polish_info", C.c_int, [vp, C.POINTER(PolishInfo)])
+
+
 class MadIPMError(RuntimeError):
     pass
 

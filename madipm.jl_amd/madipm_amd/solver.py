@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import enum
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -273,6 +274,108 @@ def check_tangent_directions(sizes: dict, directions: dict, *, on_device: bool =
     if not given:
         raise ValueError(f"{who}: no direction given; pass at least one of {', '.join(ADJOINT_NAMES)}")
     return given
+
+
+POLISH_NAMES = ("x", "y", "zl", "zu", "cons", "active_var", "active_row")   # madipm_polish_out's fields
+
+
+class PolishVerdict(enum.IntEnum):
+    """madipm_polish_info.verdict: the larger number wins."""
+    POLISHED = 0
+    WRONG_SET = 1
+    NO_CONVERGENCE = 2
+    FACTORIZATION_FAILED = 3
+
+
+def check_polish_want(want) -> tuple:
+    """The `want` argument of MPCSolver.polish / polish_device: None (all seven) or an iterable of names out of
+    POLISH_NAMES.  Returns the names in POLISH_NAMES order; ValueError for an unknown name or an empty
+    selection, TypeError for a bare string."""
+    if want is None:
+        return POLISH_NAMES
+    if isinstance(want, str):
+        raise TypeError(f"polish: want must be a collection of names, not the string {want!r}")
+    want = list(want)
+    unknown = [k for k in want if k not in POLISH_NAMES]
+    if unknown:
+        raise ValueError(f"polish: unknown name(s) {unknown} in want; the blocks are {list(POLISH_NAMES)}")
+    if not want:
+        raise ValueError("polish: want is empty")
+    return tuple(k for k in POLISH_NAMES if k in want)
+
+
+def check_polish_opts(sigma=None, tol_resid=None, tol_sign=None, tol_feas=None, refine_steps=None) -> tuple:
+    """The options of MPCSolver.polish / polish_device, before any library call; None is the library's default
+    (madipm_polish_default_opts: 1e10, 1e-10, 1e-9, 1e-9, 2).  sigma must be positive and finite, the
+    tolerances finite and not negative, refine_steps an integer in 0..8.  Returns the five values in
+    madipm_polish_opts' order."""
+    d = L.PolishOpts()
+    L.lib.madipm_polish_default_opts(C.byref(d))
+    sigma = d.sigma if sigma is None else float(sigma)
+    if not (sigma > 0.0 and np.isfinite(sigma)):
+        raise ValueError(f"polish: sigma must be positive and finite, got {sigma}")
+    tols = []
+    for name, v, dv in (("tol_resid", tol_resid, d.tol_resid), ("tol_sign", tol_sign, d.tol_sign),
+                        ("tol_feas", tol_feas, d.tol_feas)):
+        v = dv if v is None else float(v)
+        if not (v >= 0.0 and np.isfinite(v)):
+            raise ValueError(f"polish: {name} must be finite and not negative, got {v}")
+        tols.append(v)
+    if refine_steps is None:
+        refine_steps = d.refine_steps
+    if isinstance(refine_steps, bool) or not isinstance(refine_steps, (int, np.integer)):
+        raise TypeError(f"polish: refine_steps must be an integer, not {type(refine_steps).__name__}")
+    if not 0 <= int(refine_steps) <= 8:
+        raise ValueError(f"polish: refine_steps must be in 0..8, got {int(refine_steps)}")
+    return (sigma, *tols, int(refine_steps))
+
+
+def check_polish_set(nvar: int, ncon: int, active_var=None, active_row=None, *, on_device: bool = False,
+                     device=None) -> tuple:
+    """The supplied active set of MPCSolver.polish / polish_device, before any library call: both None (the
+    guess: returns ()) or both given, of shapes (nvar,) and (ncon,).  Host route: integer arrays with values
+    that fit int8, converted to C-contiguous int8.  Device route (on_device): contiguous torch.int8 tensors on
+    the GPU (on `device` when given).  Which codes a variable or a row may carry is the library's check."""
+    who = "polish_device" if on_device else "polish"
+    if active_var is None and active_row is None:
+        return ()
+    if active_var is None or active_row is None:
+        raise ValueError(f"{who}: active_var and active_row go together; pass both, or neither for the guess")
+    out = []
+    for name, a, length in (("active_var", active_var, nvar), ("active_row", active_row, ncon)):
+        if on_device:
+            import torch
+            if not isinstance(a, torch.Tensor):
+                raise TypeError(f"{who}: {name} must be a torch tensor on the GPU, not {type(a).__name__}")
+            if a.dtype != torch.int8:
+                raise TypeError(f"{who}: {name} has dtype {a.dtype}, expected torch.int8")
+            if not a.is_contiguous():
+                raise ValueError(f"{who}: {name} is not contiguous")
+            if a.device.type != "cuda":
+                raise TypeError(f"{who}: {name} is on {a.device}, expected a GPU tensor")
+            if device is not None and a.device != device:
+                raise TypeError(f"{who}: {name} is on {a.device}, the solver is on {device}")
+            if tuple(a.shape) != (int(length),):
+                raise ValueError(f"{who}: {name} has shape {tuple(a.shape)}, expected ({int(length)},)")
+        else:
+            a = np.array(a, ndmin=1)
+            if a.size and a.dtype.kind not in "iu":
+                raise TypeError(f"{who}: {name} has dtype {a.dtype}, expected integers (-1, 0, +1)")
+            if a.shape != (int(length),):
+                raise ValueError(f"{who}: {name} has shape {a.shape}, expected ({int(length)},)")
+            if a.size and (a.min() < -128 or a.max() > 127):
+                raise ValueError(f"{who}: {name} has a value that does not fit int8")
+            a = np.ascontiguousarray(a, dtype=np.int8)
+        out.append(a)
+    return tuple(out)
+
+
+def _polish_info_dict(info) -> dict:
+    v = int(info.verdict)
+    return {"verdict": PolishVerdict(v) if v >= 0 else None, "n_active": int(info.n_active),
+            "residual": float(info.residual), "min_multiplier": float(info.min_multiplier),
+            "min_gap": float(info.min_gap), "n_polishes": int(info.n_polishes),
+            "n_polish_factorizations": int(info.n_polish_factorizations)}
 
 
 def check_layer_outputs(outputs) -> tuple:
@@ -913,6 +1016,82 @@ class MPCSolver:
         nt, r = C.c_int64(), C.c_double()
         L.check(L.lib.madipm_solver_tangent_info(self.h, C.byref(nt), C.byref(r)), "tangent_info")
         return {"n_tangents": int(nt.value), "last_residual": float(r.value)}
+
+    # ------------------------------------------------------------ polish
+    def _polish_sizes(self) -> dict:
+        qp = self.qp
+        return {"x": qp.nvar, "y": qp.ncon, "zl": qp.nvar, "zu": qp.nvar, "cons": qp.ncon, "active_var": qp.nvar,
+                "active_row": qp.ncon}
+
+    def polish(self, want=None, *, active_var=None, active_row=None, sigma=None, tol_resid=None, tol_sign=None,
+               tol_feas=None, refine_steps=None) -> dict:
+        """The exact solution on the active set the last solve()'s end point identifies: active bounds
+        attained bitwise, inactive multipliers exactly 0, the KKT conditions at rounding level.  Returns a
+        dict over `want`, a subset of POLISH_NAMES (None: all seven: x, y, zl, zu, cons and the set as
+        active_var / active_row, int8: -1 lower-active, +1 upper-active, 0 inactive), plus "info": verdict (a
+        PolishVerdict), n_active, residual, min_multiplier, min_gap and the two counters.  active_var and
+        active_row (both or neither) supply the set instead of the guess.  With a verdict other than POLISHED
+        the blocks are solve()'s, bit for bit.  The call overwrites the factor adjoint() / tangent() share (they
+        factorise again), and leaves the next solve() untouched.  MadIPMError as adjoint(), and for a code on
+        a bound that does not exist, on a fixed variable or on an equality row."""
+        names = check_polish_want(want)
+        opts = check_polish_opts(sigma, tol_resid, tol_sign, tol_feas, refine_steps)
+        size = self._polish_sizes()
+        sets = check_polish_set(size["active_var"], size["active_row"], active_var, active_row)
+        buf = {k: np.empty(max(size[k], 1), np.int8 if k.startswith("active") else np.float64) for k in names}
+        o = L.PolishOut()
+        for k in names:
+            setattr(o, k, L.ptr(buf[k], C.c_int8 if k.startswith("active") else C.c_double))
+        po = L.PolishOpts(*opts)
+        info = L.PolishInfo()
+        # an empty block (ncon = 0) has nothing to read: any non-null address says "given"
+        p = [L.ptr(a if a.size else np.zeros(1, np.int8), C.c_int8) for a in sets] if sets else [None, None]
+        L.check(L.lib.madipm_solver_polish(self.h, C.byref(po), p[0], p[1], C.byref(o), C.byref(info)), "polish")
+        res = {k: buf[k][:size[k]] for k in names}
+        res["info"] = _polish_info_dict(info)
+        return res
+
+    def polish_device(self, want=None, stream=None, *, active_var=None, active_row=None, sigma=None, tol_resid=None,
+                      tol_sign=None, tol_feas=None, refine_steps=None) -> dict:
+        """polish() into torch tensors on the solver's GPU (float64; the set's codes int8), without a copy
+        through the host; a supplied set is a pair of contiguous int8 tensors on that GPU.  `stream` is the
+        torch.cuda.Stream the set was produced on (None: the current stream): it is read after the work
+        enqueued on it, and work enqueued on it after the call sees the returned tensors.  "info" is a host
+        dict.  The arguments are checked before any library call."""
+        names = check_polish_want(want)
+        opts = check_polish_opts(sigma, tol_resid, tol_sign, tol_feas, refine_steps)
+        size = self._polish_sizes()
+        sets = check_polish_set(size["active_var"], size["active_row"], active_var, active_row, on_device=True,
+                                device=self._device)
+        import torch
+        if stream is not None and not isinstance(stream, torch.cuda.Stream):
+            raise TypeError(f"polish_device: stream must be a torch.cuda.Stream, not {type(stream).__name__}")
+        if self._device is None:
+            self._device = torch.device("cuda", torch.cuda.current_device())
+            check_polish_set(size["active_var"], size["active_row"], active_var, active_row, on_device=True,
+                             device=self._device)
+        st = stream if stream is not None else torch.cuda.current_stream(self._device)
+        with torch.cuda.stream(st):
+            buf = {k: torch.empty(max(size[k], 1), dtype=torch.int8 if k.startswith("active") else torch.float64,
+                                  device=self._device) for k in names}
+            keep = [a if a.numel() else torch.zeros(1, dtype=torch.int8, device=self._device) for a in sets]
+        o = L.PolishOut()
+        for k in names:
+            setattr(o, k, C.cast(buf[k].data_ptr(), L.i8p if k.startswith("active") else L.f64p))
+        po = L.PolishOpts(*opts)
+        info = L.PolishInfo()
+        p = [C.cast(a.data_ptr(), L.i8p) for a in keep] if keep else [None, None]
+        L.check(L.lib.madipm_solver_polish_device(self.h, C.byref(po), p[0], p[1], C.byref(o), C.byref(info),
+                                                  L.vp(st.cuda_stream)), "polish_device")
+        res = {k: buf[k][:size[k]] for k in names}
+        res["info"] = _polish_info_dict(info)
+        return res
+
+    def polish_info(self) -> dict:
+        """The last polish()'s info (verdict None before the first); no device access."""
+        info = L.PolishInfo()
+        L.check(L.lib.madipm_solver_polish_info(self.h, C.byref(info)), "polish_info")
+        return _polish_info_dict(info)
 
     def counters(self) -> dict:
         """n_analyses: linear-solver analyses run for this solver (stays 1); n_updates: successful update()

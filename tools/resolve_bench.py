@@ -40,7 +40,13 @@ tangent_solve_s (the solve before it) and tangent_again_s (a second direction on
 tangent_residual (the largest last_residual) and tangent_status.  With --warm WEIGHT it also runs the
 sequence twice more, warm-started from the previous solution (warm_start_last) and from the first-order
 prediction solution + tangent along the actual next perturbation (warm_start_device):
-tangent_warm_iters_last and tangent_warm_iters_predicted."""
+tangent_warm_iters_last and tangent_warm_iters_predicted.
+
+--polish adds, on the same sequence of data and in the same process, the exact active-set solve: after each
+update_device + solve, polish_device for all seven blocks, stream synchronised: polish_s (the first call on a
+point: classification, factorisation, three solves, the verdict's read-back) beside polish_solve_s (the solve
+before it) and polish_again_s (a second call with the returned set supplied: no factorisation), polish_verdicts
+(how often each verdict came back), polish_residual (the largest) and the counters."""
 import dataclasses
 import json
 import os
@@ -70,7 +76,7 @@ def perturb(qp, rng):
                 lvar=qp.lvar * fv, uvar=qp.uvar * fv, lcon=qp.lcon * fc, ucon=qp.ucon * fc)
 
 
-def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False):
+def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polish=False):
     qp, desc = bench.build_problem(name)
     opts = bench.solver_opts()
     MPCSolver(qp, **opts)                      # the first construction of a process pays one-off set-up
@@ -266,6 +272,43 @@ def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False):
                 wres.update({f"tangent_warm_iters_{mode}": its_, f"tangent_warm_status_{mode}": sorted(stat_)})
             s.clear_warm_start()
         c = s.counters()
+    if polish:   # the same data again: the exact active-set solve per re-solve, then again with its set supplied
+        rng = np.random.default_rng(0)
+        perturb(qp, rng)
+        psol, pfirst, pagain, pstat, pverd, pres = [], [], [], set(), {}, 0.0
+        for rep in range(WARMUP + REPS):
+            s.update_device(**{k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()})
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            pst = s.solve(fetch_solution=False)
+            t_solve = time.perf_counter() - t
+            pstat.add(pst.status)
+            if pst.status != 1:
+                continue
+            t = time.perf_counter()
+            p1 = s.polish_device()
+            torch.cuda.current_stream().synchronize()
+            t_first = time.perf_counter() - t
+            t = time.perf_counter()
+            p2 = s.polish_device(active_var=p1["active_var"], active_row=p1["active_row"])
+            torch.cuda.current_stream().synchronize()
+            t_again = time.perf_counter() - t
+            v = p1["info"]["verdict"].name
+            pverd[v] = pverd.get(v, 0) + 1
+            if np.isfinite(p1["info"]["residual"]):
+                pres = max(pres, p1["info"]["residual"])
+            assert p2["info"]["verdict"] == p1["info"]["verdict"]
+            if rep >= WARMUP:
+                psol.append(t_solve)
+                pfirst.append(t_first)
+                pagain.append(t_again)
+        med = lambda v: statistics.median(v) if v else float("nan")  # noqa: E731
+        info = s.polish_info()
+        wres.update({"polish_s": med(pfirst), "polish_again_s": med(pagain), "polish_solve_s": med(psol),
+                     "polish_verdicts": pverd, "polish_residual": pres, "polish_status": sorted(pstat),
+                     "polish_n_active": info["n_active"], "n_polishes": info["n_polishes"],
+                     "n_polish_factorizations": info["n_polish_factorizations"]})
+        c = s.counters()
     update_s, solve_s = statistics.median(upd), statistics.median(sol)
     return {**wres, "instance": name, "description": desc, "nvar": qp.nvar, "ncon": qp.ncon, "nnzj": qp.nnzj, "nnzh": qp.nnzh,
             "construct_s": construct_s, "prepare_update_s": prepare_update_s, "update_s": update_s,
@@ -304,8 +347,11 @@ def main():
     tangent = "--tangent" in args
     if tangent:
         args.remove("--tangent")
+    polish = "--polish" in args
+    if polish:
+        args.remove("--polish")
     for name in args or ["ex10", "supportcase10"]:
-        r = run(name, warm, adjoint, adjoint_full, tangent)
+        r = run(name, warm, adjoint, adjoint_full, tangent, polish)
         print(f"{name}: construct_s {r['construct_s']:.4f}  prepare_update_s {r['prepare_update_s']:.4f}  "
               f"update_s {r['update_s']:.5f}  solve_s {r['solve_s']:.4f}  ->  update + solve "
               f"{r['update_plus_solve_s']:.4f} s against construct + solve {r['construct_plus_solve_s']:.4f} s "
@@ -335,6 +381,11 @@ def main():
                       f"{med(r['tangent_warm_iters_predicted'])} (status {r['tangent_warm_status_predicted']}), "
                       f"from the last solution alone {med(r['tangent_warm_iters_last'])} (status "
                       f"{r['tangent_warm_status_last']}), cold {med(r['iters'])}", flush=True)
+        if polish:
+            print(f"{name}: polish (seven blocks): {r['polish_s']:.4f} s after a solve of {r['polish_solve_s']:.4f} s; "
+                  f"again with the returned set supplied {r['polish_again_s']:.4f} s; verdicts {r['polish_verdicts']}, "
+                  f"residual <= {r['polish_residual']:.1e}, {r['polish_n_active']} active in the last set, "
+                  f"{r['n_polish_factorizations']} factorisations in {r['n_polishes']} calls", flush=True)
         out.append(r)
     print(json.dumps({"resolve_bench": out, "warmup": WARMUP, "reps": REPS, "rel_noise": REL}))
 
