@@ -76,6 +76,34 @@ struct DBuf {
   operator T*() const { return p; }
 };
 
+// Work enqueued on `to` from now on runs after the work already enqueued on `from`
+inline void stream_after(hipEvent_t e, hipStream_t from, hipStream_t to) {
+  MADIPM_HIP(hipEventRecord(e, from));
+  MADIPM_HIP(hipStreamWaitEvent(to, e, 0));
+}
+
+// A call that reads and writes a caller's device arrays from a stream of our own: begin() before the first
+// access (ours waits for the caller's earlier work), end() after the last (the caller's later work waits for
+// ours).  The two events are created by the first begin().
+struct StreamHandoff {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  StreamHandoff() = default;
+  StreamHandoff(const StreamHandoff&) = delete;
+  StreamHandoff& operator=(const StreamHandoff&) = delete;
+  ~StreamHandoff() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  void begin(hipStream_t caller, hipStream_t ours) {
+    if (!ev[0]) {
+      MADIPM_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
+      MADIPM_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
+    }
+    stream_after(ev[0], caller, ours);
+  }
+  void end(hipStream_t ours, hipStream_t caller) { stream_after(ev[1], ours, caller); }
+};
+
 // MADIPM_SYMBOLIC_TIMING=1: wall time of each construction phase on stderr (diagnostics: the dense
 // QP's analysis_s breakdown)
 struct PhaseClock {

@@ -28,27 +28,9 @@
 #include <limits>
 #include <map>
 
-#include "mpc.hpp"
-#include "qp_model.hpp"
+#include "mpc_kernels.hpp"
 
 namespace madipm {
-
-// the model's index pairs are uploaded as the kernels' int2
-static_assert(sizeof(I2) == sizeof(int2) && alignof(I2) <= alignof(int2) && offsetof(I2, x) == offsetof(int2, x) &&
-                  offsetof(I2, y) == offsetof(int2, y),
-              "qp_model.hpp's I2 must have int2's layout");
-static const int2* as_int2(const std::vector<I2>& v) { return reinterpret_cast<const int2*>(v.data()); }
-
-// The refresh plan on the device (prepare_update; the host arrays are qp_model.hpp's RefreshPlan)
-struct UpdatePlan {
-  std::vector<int32_t> Ar, Ac;  // host copy of A's COO for the host passes (slack start, row maxima, cfix)
-  std::vector<double> Av;
-  DBuf<double> Araw, Hraw, cscale;      // device staging: raw Avals / Hvals, con_scale
-  DBuf<int32_t> tsp, tsrc, jtk, j2jt;   // J^T entry -> sources, -> its Kx_ slot; J entry -> J^T entry
-  DBuf<int32_t> hsp, hsrc, hk, hdpos;   // H entry -> sources, -> its Kx_ slot (-1: upper triangle);
-                                        // hdpos[i] = H's entry (i, i) or -1
-  int64_t nJ = 0, nH = 0;               // destination entries of J (= J^T) and H
-};
 
 // The device route (update_device), allocated by its first call: the raw problem numbers as last installed
 // (A's and H's are the plan's Araw / Hraw), the start vectors initialize() restarts from, and the lists
@@ -79,186 +61,18 @@ struct DevUpdate {
 struct WarmStart {
   DBuf<double> x, y, zl, zu, rows;
   DBuf<int32_t> ineq;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  StreamHandoff sync;
   bool has[4] = {false, false, false, false};  // x, y, zl, zu of the current point
   bool active = false;
   double weight = 0.0;
-  ~WarmStart() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
-// The adjoint gradients (madipm_solver_adjoint*).  Everything here is allocated by the first
-// call that needs it: the right-hand side copy, the solution, the per-row residuals and the scalar block by
-// the first call (8 B x (nvar + 2 (n + m) + 2)); rowslack (4 B per row) with lcon / ucon; A's COO indices (8 B per entry)
-// with Avals; H's (8 B per entry) with Hvals; the fixed variables' entry lists (8 B per entry of A in a
-// fixed column and per entry of H between a fixed and a free variable, 4 B per fixed variable for each
-// list start) with lvar on a problem that has fixed variables; the host route's output staging (8 B per
-// output entry) with each output it is asked for.
-struct Adjoint {
-  DBuf<double> gx, sol, rowres, scal;     // host route's gx; a~ (refined); |g - K a~| per row; [residual ratio, unused]
-  DBuf<int32_t> rowslack;                 // row -> its slack (index into [nx, n)) or -1 (equality row)
-  DBuf<int32_t> Ar, Ac, Hr, Hc;           // COO indices, creation-time entry order
-  DBuf<int32_t> fix, fhsp, fasp;          // fixed variables; their list starts into fh / fa
-  DBuf<int2> fh, fa;                      // (entry of Hvals, free endpoint), (entry of Avals, row)
-  int nfix = -1;                          // -1: lists not built yet
-  DBuf<double> out[7];                    // host route: c, Hvals, Avals, lcon, ucon, lvar, uvar
-  // the loss of all five blocks (§13d), by the first call with a cotangent other than gx: 8 B x (n + m + nvar)
-  DBuf<double> shift, apx;                // v = [q~; 0; gcons / con_scale]; a~'x of the shifted system
-  DBuf<double> ct[4];                     // host route's gy, gzl, gzu, gcons
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int64_t n_adjoints = 0, n_fact = 0;
-  int64_t fact_solve = -1;                // n_solves_ of the point the LDL^T currently holds the factor of
-  ~Adjoint() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
-// The tangent (madipm_solver_tangent*) shares the adjoint's factor, solution, residual rows and
-// events.  Its own, each allocated by the first call that needs it: the data terms and the full dx
-// (8 B x (2 n + m + 1)); the shift vector is the adjoint's `shift`; rowslack as there; with Hvals / Avals (or
-// lvar on a problem with fixed variables) the entry lists of build_tangent_lists: 16 B per entry of A, 8 B per
-// endpoint of a stored entry of H, 4 B x (2 nvar + ncon) list starts; the host route's staging of the
-// directions given and the outputs wanted (8 B per entry).
-struct Tangent {
-  DBuf<double> base, dx, scal;            // data terms of the right-hand side; [dx; 0]; residual ratio
-  DBuf<int32_t> asp, csp, gsp;            // list starts: A per row, A per column, H per endpoint
-  DBuf<int2> ae, ce, ge;                  // (entry, column), (entry, row), (entry, other endpoint)
-  bool lists = false;
-  DBuf<double> dir[7], out[5];            // host route: c, Hvals, Avals, lcon, ucon, lvar, uvar; x, y, zl, zu, cons
-  int64_t n_tangents = 0;
-};
-
-// The polish (madipm_solver_polish*) shares the adjoint's residual rows, rowslack and events (and
-// overwrites its factor: sens_factor and polish() clear each other's tag).  Its own, allocated by the first
-// call: the scratch point [v; y], the gradient of the Lagrangian on [x; s], the raw bounds of [x; s] in the
-// public space, the partial measures and the row values (8 B x (4 n + 2 m)); the codes of this call and of the
-// factor held (2 n B); the slack -> row map (4 B per slack); the host route's staging of the set and the
-// outputs.
-struct PolMeasures {  // k_pol_verdict's result, read back with one copy
-  int32_t verdict, n_active;
-  double residual, min_multiplier, min_gap;
-};
-struct Polish {
-  DBuf<double> w, grad, lo, hi, part, ax;
-  DBuf<int8_t> codes, codes_fact, in_var, in_row, out_var, out_row;
-  DBuf<int32_t> ineq, flags;              // flags: [a bad code was supplied, the codes differ from the factor's]
-  DBuf<PolMeasures> meas;
-  DBuf<double> out[5];                    // host route: x, y, zl, zu, cons
-  int64_t bounds_updates = -1;            // n_updates_ of the bounds in lo / hi
-  int64_t fact_solve = -1;                // n_solves_ of the point the LDL^T holds the polish factor of
-  double fact_sigma = 0.0;
-  madipm_polish_info last{-1, 0, 0.0, 0.0, 0.0, 0, 0};
 };
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int NPART = 16;
-constexpr int MAXB = 2048;  // partial-reduction blocks (part_ holds NPART x MAXB, value-major)
-// partial k of block b: value-major so k_final's loads of one value are coalesced
-__device__ __forceinline__ int pidx(int b, int k) { return k * MAXB + b; }
-constexpr double INF = std::numeric_limits<double>::infinity();
-
-struct DCsr {
-  const int64_t* rp;
-  const int32_t* ci;
-  const double* v;
-};
-
-struct DV {
-  int n, m, nx, nlb, nub;
-  double *x, *xl, *xu, *zl, *zu, *f, *jacl, *c, *y, *rhs;
-  double *pr_diag, *l_diag, *u_diag, *l_lower, *u_lower;
-  double *d, *p, *corr_lb, *corr_ub;
-  double* Kx;
-  const int64_t* diag_pos;
-  const double *Hdiag, *cs, *gfix, *cfix;
-  const int32_t *ind_lb, *ind_ub, *lbpos, *ubpos;
-  const uint8_t* fixed;
-  DCsr H, J, JT;
-  double* part;
-  DevState* st;
-  // KKT formulation (madipm_options.kkt_system): K2 / K2.5 (scaled) / normal equations
-  int kkt;
-  double* sk;               // K2.5: primal scaling s_i = sqrt(dist_l * dist_u)
-  const int32_t *Krow, *Kcol;
-  const double* K0;         // K2.5: unscaled K2 values (off-diagonal entries are constant)
-  int64_t nnzK;
-  double* Dinv;             // normal: 1 ./ pr_diag
-  double* bufm;             // normal: right-hand side / solution of the m x m system
-  const int64_t* cpp;       // normal: C entry e = sum over products [cpp[e], cpp[e+1])
-  const int2* cprod;        //   product = (position of A_ik, position of A_jk) in J's values
-  double* Cx;               //   values of C = A Sigma^{-1} A^T (lower CSC)
-  int64_t nnzC;
-};
-
-enum { OP_SUM = 0, OP_MAX = 1, OP_MIN = 2 };
-
-__device__ __forceinline__ double nmax(double a, double b) { return ((b > a) | (b != b)) ? b : a; }
-__device__ __forceinline__ double comb(double a, double b, int op) {
-  return op == OP_SUM ? a + b : (op == OP_MAX ? nmax(a, b) : fmin(a, b));
-}
 __device__ __forceinline__ double csr_dot(const DCsr& A, int row, const double* __restrict__ x) {
   double s = 0.0;
   for (int64_t q = A.rp[row]; q < A.rp[row + 1]; ++q) s += A.v[q] * x[A.ci[q]];
   return s;
-}
-
-// Wave reductions with the pairing of the `for (o = 32; o; o >>= 1) a = op(a, __shfl_down(a, o))` tree
-// (lane i combines lane i + o; lane 0 ends with the same value bit for bit), without the LDS crossbar:
-// o = 32 / 16 by the gfx950 half-row swaps (v_permlane32_swap / v_permlane16_swap: the swapped-in half
-// is lane i + o for the lanes the tree reads), o = 8, 4, 2, 1 by DPP row_shl:o inside each 16-lane row.
-// (ds_bpermute costs an LDS round trip per step: k_final's level-1 tree took ~2 us, MADIPM_FINAL_DEBUG.)
-template <int O>
-__device__ __forceinline__ int lane_down_i32(int v) {
-  if constexpr (O == 32) {
-    const auto p = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return (int)p[1];
-  } else if constexpr (O == 16) {
-    const auto p = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    return (int)p[1];
-  } else {
-    return __builtin_amdgcn_update_dpp(v, v, 0x100 + O, 0xf, 0xf, false);  // row_shl:O
-  }
-}
-template <int O>
-__device__ __forceinline__ double lane_down(double v) {
-  return __hiloint2double(lane_down_i32<O>(__double2hiint(v)), lane_down_i32<O>(__double2loint(v)));
-}
-template <int OP>
-__device__ __forceinline__ double wave_reduce(double a) {
-  a = comb(a, lane_down<32>(a), OP);
-  a = comb(a, lane_down<16>(a), OP);
-  a = comb(a, lane_down<8>(a), OP);
-  a = comb(a, lane_down<4>(a), OP);
-  a = comb(a, lane_down<2>(a), OP);
-  return comb(a, lane_down<1>(a), OP);
-}
-template <int O>
-__device__ __forceinline__ void argmin_step(double& a, int& b);
-__device__ __forceinline__ double wave_reduce_op(double a, int op) {
-  return op == OP_SUM ? wave_reduce<OP_SUM>(a) : (op == OP_MAX ? wave_reduce<OP_MAX>(a) : wave_reduce<OP_MIN>(a));
-}
-
-template <int NV>
-__device__ void block_partials(double (&v)[NV], const int (&ops)[NV], double* part, int base = 0, int bid = -1) {
-  __shared__ double sh[NV][NT / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const double a = wave_reduce_op(v[k], ops[k]);
-    if (lane == 0) sh[k][wv] = a;
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    const int k = threadIdx.x;
-    double a = sh[k][0];
-    for (int w = 1; w < NT / 64; ++w) a = comb(a, sh[k][w], ops[k]);
-    part[pidx(bid >= 0 ? bid : (int)blockIdx.x, base + k)] = a;
-  }
 }
 
 // (value, index) argmin in the order of the reference's left fold (kernels.jl:226-272:
@@ -285,84 +99,6 @@ __device__ __forceinline__ void wave_argmin(double& a, int& b) {
   argmin_step<4>(a, b);
   argmin_step<2>(a, b);
   argmin_step<1>(a, b);
-}
-
-#define GRID_LOOP(i, N) for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (N); i += (int64_t)gridDim.x * blockDim.x)
-
-// SpMV rows in groups of G lanes (G | 64): the group's lanes stride the row's entries (coalesced),
-// then a G-wide butterfly sums them (every lane of the group holds the row sum).  G is chosen per
-// problem from the mean row length (MPCSolver::spmv_group).
-#define GROUP_LOOP(i, N, G) \
-  for (int64_t i = (blockIdx.x * (int64_t)NT + threadIdx.x) / (G); i < (N); i += (int64_t)gridDim.x * (NT / (G)))
-// the same loops over a sub-grid of nblk blocks (block bid of it): kernels whose blocks split into roles
-#define GROUP_LOOP_B(i, N, G, bid, nblk) \
-  for (int64_t i = ((bid) * (int64_t)NT + threadIdx.x) / (G); i < (N); i += (int64_t)(nblk) * (NT / (G)))
-#define GRID_LOOP_B(i, N, bid, nblk) \
-  for (int64_t i = (bid) * (int64_t)blockDim.x + threadIdx.x; i < (N); i += (int64_t)(nblk) * blockDim.x)
-
-template <int G>
-__device__ __forceinline__ double gdot(const DCsr& A, int64_t row, const double* __restrict__ x) {
-  const int gl = threadIdx.x & (G - 1);
-  double s = 0.0;
-  const int64_t q1 = A.rp[row + 1];
-  // two entries per lane and trip, both issued before either is summed (clamped index, the second
-  // masked): the gathers of consecutive trips no longer wait for each other; same summation order
-  for (int64_t q = A.rp[row] + gl; q < q1; q += 2 * G) {
-    const int64_t qb = min(q + G, q1 - 1);
-    const double va = A.v[q], vb = A.v[qb];
-    const double xa = x[A.ci[q]], xb = x[A.ci[qb]];
-    s = fma(va, xa, s);
-    s = fma((q + G < q1) ? vb : 0.0, xb, s);
-  }
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, G);
-  return s;
-}
-
-// gdot<G>(A, ra, xa) and gdot<G>(B, rb, xb) at once (a primal row's H and J^T parts): both rows'
-// extents, then each trip's entries and gathers of both, issued before either is summed — one chain
-// of dependent loads instead of two back to back.  Each sum in gdot's own order (same bits).
-template <int G>
-__device__ __forceinline__ void gdot2(const DCsr& A, int64_t ra, const double* __restrict__ xa, const DCsr& B,
-                                      int64_t rb, const double* __restrict__ xb, double& sa, double& sb) {
-  const int gl = threadIdx.x & (G - 1);
-  const int64_t a1 = A.rp[ra + 1], b1 = B.rp[rb + 1];
-  int64_t qa = A.rp[ra] + gl, qb = B.rp[rb] + gl;
-  sa = 0.0;
-  sb = 0.0;
-  while (qa < a1 || qb < b1) {
-    const bool ta = qa < a1, tb = qb < b1;
-    double va = 0.0, va2 = 0.0, ya = 0.0, ya2 = 0.0, vb = 0.0, vb2 = 0.0, yb = 0.0, yb2 = 0.0;
-    if (ta) {
-      const int64_t q2 = min(qa + G, a1 - 1);
-      va = A.v[qa];
-      va2 = A.v[q2];
-      ya = xa[A.ci[qa]];
-      ya2 = xa[A.ci[q2]];
-    }
-    if (tb) {
-      const int64_t q2 = min(qb + G, b1 - 1);
-      vb = B.v[qb];
-      vb2 = B.v[q2];
-      yb = xb[B.ci[qb]];
-      yb2 = xb[B.ci[q2]];
-    }
-    if (ta) {
-      sa = fma(va, ya, sa);
-      sa = fma((qa + G < a1) ? va2 : 0.0, ya2, sa);
-      qa += 2 * G;
-    }
-    if (tb) {
-      sb = fma(vb, yb, sb);
-      sb = fma((qb + G < b1) ? vb2 : 0.0, yb2, sb);
-      qb += 2 * G;
-    }
-  }
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) {
-    sa += __shfl_xor(sa, o, G);
-    sb += __shfl_xor(sb, o, G);
-  }
 }
 
 // ------------------------------------------------------------------ KKT diagonal (kernels.jl:124-149)
@@ -1504,8 +1240,6 @@ MPCSolver::~MPCSolver() {
     }
   }
   if (hst_) (void)hipHostFree(hst_);
-  for (hipEvent_t e : sol_ev_)
-    if (e) (void)hipEventDestroy(e);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -2320,8 +2054,7 @@ void MPCSolver::update_device(const madipm_qp_update& u, hipStream_t caller) {
     dev_raw_stale_ = false;
   }
   // ---- the caller's arrays are read after the work already enqueued on its stream
-  MADIPM_HIP(hipEventRecord(dv.ev, caller));
-  MADIPM_HIP(hipStreamWaitEvent(s, dv.ev, 0));
+  stream_after(dv.ev, caller, s);
   // ---- classification of the merged data, by a kernel, before anything is overwritten
   const double* lv = u.lvar ? u.lvar : dv.lvar.p;
   const double* uv = u.uvar ? u.uvar : dv.uvar.p;
@@ -2422,93 +2155,46 @@ const double* MPCSolver::device_con_scale() {
 }
 
 void MPCSolver::get_solution_device(double* x, double* y, double* zl, double* zu, double* cons, hipStream_t caller) {
-  hipStream_t s = stream_;
-  if (!sol_ev_[0]) {
-    MADIPM_HIP(hipEventCreateWithFlags(&sol_ev_[0], hipEventDisableTiming));
-    MADIPM_HIP(hipEventCreateWithFlags(&sol_ev_[1], hipEventDisableTiming));
-    sol_ax_.alloc(std::max(m_, 1));
-  }
+  if (!sol_ax_.p) sol_ax_.alloc(std::max(m_, 1));
   const double* cscale = device_con_scale();
   // the outputs are written after the caller's earlier work on them, and read by its later work
-  MADIPM_HIP(hipEventRecord(sol_ev_[0], caller));
-  MADIPM_HIP(hipStreamWaitEvent(s, sol_ev_[0], 0));
-  if (cons && m_)
-    k_cons<<<(unsigned)((m_ + NT / 64 - 1) / (NT / 64)), NT, 0, s>>>(Jrp_, Jci_, Jv_, x_, cfix_, m_, nx_, sol_ax_);
-  if (std::max(nx_, m_))
-    k_unscale<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(nx_, m_, obj_scale_, x_, y_, zl_, zu_, sol_ax_, cscale, x, y,
-                                                        zl, zu, cons);
+  sol_sync_.begin(caller, stream_);
+  unscale_point(cscale, sol_ax_, x, y, zl, zu, cons);
   MADIPM_HIP(hipGetLastError());
-  MADIPM_HIP(hipEventRecord(sol_ev_[1], s));
-  MADIPM_HIP(hipStreamWaitEvent(caller, sol_ev_[1], 0));
+  sol_sync_.end(stream_, caller);
 }
 
-// Launch helpers (the DV view is rebuilt from member buffers; cheap, host-only)
-#define DV_ARGS                                                                                         \
-  DV D;                                                                                                 \
-  D.n = n_;                                                                                             \
-  D.m = m_;                                                                                             \
-  D.nx = nx_;                                                                                           \
-  D.nlb = nlb_;                                                                                         \
-  D.nub = nub_;                                                                                         \
-  D.x = x_;                                                                                             \
-  D.xl = xl_;                                                                                           \
-  D.xu = xu_;                                                                                           \
-  D.zl = zl_;                                                                                           \
-  D.zu = zu_;                                                                                           \
-  D.f = f_;                                                                                             \
-  D.jacl = jacl_;                                                                                       \
-  D.c = c_;                                                                                             \
-  D.y = y_;                                                                                             \
-  D.rhs = rhs_;                                                                                         \
-  D.pr_diag = pr_diag_;                                                                                 \
-  D.l_diag = l_diag_;                                                                                   \
-  D.u_diag = u_diag_;                                                                                   \
-  D.l_lower = l_lower_;                                                                                 \
-  D.u_lower = u_lower_;                                                                                 \
-  D.d = d_;                                                                                             \
-  D.p = p_;                                                                                             \
-  D.corr_lb = corr_lb_;                                                                                 \
-  D.corr_ub = corr_ub_;                                                                                 \
-  D.Kx = Kx_;                                                                                           \
-  D.diag_pos = diag_pos_;                                                                               \
-  D.Hdiag = Hdiag_;                                                                                     \
-  D.cs = cs_;                                                                                           \
-  D.gfix = gfix_;                                                                                       \
-  D.cfix = cfix_;                                                                                       \
-  D.ind_lb = ind_lb_;                                                                                   \
-  D.ind_ub = ind_ub_;                                                                                   \
-  D.lbpos = lbpos_;                                                                                     \
-  D.ubpos = ubpos_;                                                                                     \
-  D.fixed = fixed_;                                                                                     \
-  D.H = DCsr{Hrp_, Hci_, Hv_};                                                                          \
-  D.J = DCsr{Jrp_, Jci_, Jv_};                                                                          \
-  D.JT = DCsr{JTrp_, JTci_, JTv_};                                                                      \
-  D.part = part_;                                                                                       \
-  D.st = st_;                                                                                           \
-  D.kkt = kkt_;                                                                                         \
-  D.sk = sk_;                                                                                           \
-  D.Krow = Krow_;                                                                                       \
-  D.Kcol = Kcol_;                                                                                       \
-  D.K0 = K0_;                                                                                           \
-  D.nnzK = nnzK_;                                                                                       \
-  D.Dinv = Dinv_;                                                                                       \
-  D.bufm = bufm_;                                                                                       \
-  D.cpp = cpp_;                                                                                         \
-  D.cprod = reinterpret_cast<const int2*>(cprod_.p);                                                    \
-  D.Cx = Cx_;                                                                                           \
-  D.nnzC = nnzC_;
+// get_solution's constraint values of the scaled point xs, before the division by con_scale, into ax
+void MPCSolver::cons_rows(const double* xs, double* ax) {
+  const unsigned nb = (unsigned)((m_ + NT / 64 - 1) / (NT / 64));
+  if (m_) k_cons<<<nb, NT, 0, stream_>>>(Jrp_, Jci_, Jv_, xs, cfix_, m_, nx_, ax);
+}
 
-// launch a GROUP_LOOP SpMV kernel with the problem's lane-group width
-#define SPMV_LAUNCH(kern, grid, strm, ...)                                        \
-  do {                                                                            \
-    switch (spmv_g_) {                                                            \
-      case 4: kern<4><<<(grid), NT, 0, (strm)>>>(__VA_ARGS__); break;             \
-      case 8: kern<8><<<(grid), NT, 0, (strm)>>>(__VA_ARGS__); break;             \
-      case 16: kern<16><<<(grid), NT, 0, (strm)>>>(__VA_ARGS__); break;           \
-      case 32: kern<32><<<(grid), NT, 0, (strm)>>>(__VA_ARGS__); break;           \
-      default: kern<64><<<(grid), NT, 0, (strm)>>>(__VA_ARGS__); break;           \
-    }                                                                             \
-  } while (0)
+// update_solution! of the iterate into device arrays (any may be null); ax: m_ doubles of scratch when cons is given
+void MPCSolver::unscale_point(const double* cscale, double* ax, double* x, double* y, double* zl, double* zu,
+                              double* cons) {
+  if (cons) cons_rows(x_, ax);
+  if (std::max(nx_, m_))
+    k_unscale<<<blocks(std::max(nx_, m_)), NT, 0, stream_>>>(nx_, m_, obj_scale_, x_, y_, zl_, zu_, ax, cscale, x, y,
+                                                              zl, zu, cons);
+}
+
+// The kernels' view of the member buffers (rebuilt per launch site; cheap, host-only)
+DV MPCSolver::view() const {
+  DV D;
+  D.n = n_, D.m = m_, D.nx = nx_, D.nlb = nlb_, D.nub = nub_;
+  D.x = x_, D.xl = xl_, D.xu = xu_, D.zl = zl_, D.zu = zu_, D.f = f_, D.jacl = jacl_, D.c = c_, D.y = y_, D.rhs = rhs_;
+  D.pr_diag = pr_diag_, D.l_diag = l_diag_, D.u_diag = u_diag_, D.l_lower = l_lower_, D.u_lower = u_lower_;
+  D.d = d_, D.p = p_, D.corr_lb = corr_lb_, D.corr_ub = corr_ub_;
+  D.Kx = Kx_, D.diag_pos = diag_pos_, D.Hdiag = Hdiag_, D.cs = cs_, D.gfix = gfix_, D.cfix = cfix_;
+  D.ind_lb = ind_lb_, D.ind_ub = ind_ub_, D.lbpos = lbpos_, D.ubpos = ubpos_, D.fixed = fixed_;
+  D.H = DCsr{Hrp_, Hci_, Hv_}, D.J = DCsr{Jrp_, Jci_, Jv_}, D.JT = DCsr{JTrp_, JTci_, JTv_};
+  D.part = part_, D.st = st_, D.kkt = kkt_;
+  D.sk = sk_, D.Krow = Krow_, D.Kcol = Kcol_, D.K0 = K0_, D.nnzK = nnzK_;
+  D.Dinv = Dinv_, D.bufm = bufm_, D.cpp = cpp_, D.cprod = reinterpret_cast<const int2*>(cprod_.p);
+  D.Cx = Cx_, D.nnzC = nnzC_;
+  return D;
+}
 
 // ---- warm start
 static void check_weight(double w) {
@@ -2526,8 +2212,6 @@ WarmStart& MPCSolver::warm_buffers() {
     w->rows.alloc(std::max(ns_, 1));
     w->ineq.alloc(std::max(ns_, 1));
     w->ineq.upload(H_->ind_ineq.data(), H_->ind_ineq.size(), stream_);
-    MADIPM_HIP(hipEventCreateWithFlags(&w->ev[0], hipEventDisableTiming));
-    MADIPM_HIP(hipEventCreateWithFlags(&w->ev[1], hipEventDisableTiming));
     device_con_scale();  // its one-off device copy (a solver without an update) now, not in initialize()
     MADIPM_HIP(hipStreamSynchronize(stream_));
     warm_ = std::move(w);
@@ -2543,10 +2227,7 @@ void MPCSolver::set_warm_start(const double* x, const double* y, const double* z
   WarmStart& w = warm_buffers();
   hipStream_t s = stream_;
   const auto kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  if (device) {  // the caller's arrays are read after the work already enqueued on its stream
-    MADIPM_HIP(hipEventRecord(w.ev[0], caller));
-    MADIPM_HIP(hipStreamWaitEvent(s, w.ev[0], 0));
-  }
+  if (device) w.sync.begin(caller, s);  // the caller's arrays are read after the work already enqueued on its stream
   const double* src[4] = {x, y, zl, zu};
   double* dst[4] = {w.x.p, w.y.p, w.zl.p, w.zu.p};
   const int64_t len[4] = {nx_, m_, nx_, nx_};
@@ -2554,12 +2235,10 @@ void MPCSolver::set_warm_start(const double* x, const double* y, const double* z
     w.has[k] = src[k] != nullptr;
     if (src[k] && len[k]) MADIPM_HIP(hipMemcpyAsync(dst[k], src[k], len[k] * sizeof(double), kind, s));
   }
-  if (device) {  // the caller's later work on its stream (overwriting the arrays) comes after the copies
-    MADIPM_HIP(hipEventRecord(w.ev[1], s));
-    MADIPM_HIP(hipStreamWaitEvent(caller, w.ev[1], 0));
-  } else {
+  if (device)
+    w.sync.end(s, caller);  // the caller's later work on its stream (overwriting the arrays) comes after the copies
+  else
     MADIPM_HIP(hipStreamSynchronize(s));  // host arrays are read during the call only
-  }
   w.weight = weight;
   w.active = true;
   initialized_ = false;
@@ -2569,10 +2248,7 @@ void MPCSolver::warm_start_last(double weight) {
   check_weight(weight);
   MADIPM_REQUIRE(solved_, "madipm_solver_warm_start_last: no solve has run on this solver yet");
   WarmStart& w = warm_buffers();
-  const double* cscale = device_con_scale();
-  if (std::max(nx_, m_))
-    k_unscale<<<blocks(std::max(nx_, m_)), NT, 0, stream_>>>(nx_, m_, obj_scale_, x_, y_, zl_, zu_, nullptr, cscale, w.x,
-                                                              w.y, w.zl, w.zu, nullptr);
+  unscale_point(device_con_scale(), nullptr, w.x, w.y, w.zl, w.zu, nullptr);
   MADIPM_HIP(hipGetLastError());
   for (bool& h : w.has) h = true;
   w.weight = weight;
@@ -2596,7 +2272,7 @@ void MPCSolver::warm_info(int32_t* active, double* weight, int64_t* n_warm_inits
 // point (the cold path leaves the initial point's f, c and objective in place; the first termination test of
 // a warm solve sees the blended point's residuals)
 void MPCSolver::warm_blend() {
-  DV_ARGS;
+  const DV D = view();
   hipStream_t s = stream_;
   WarmStart& w = *warm_;
   WarmArgs W{w.has[0] ? w.x.p : nullptr, w.has[1] ? w.y.p : nullptr, w.has[2] ? w.zl.p : nullptr,
@@ -2611,13 +2287,13 @@ void MPCSolver::warm_blend() {
 }
 
 void MPCSolver::kkt_diag(double dw, double dc) {
-  DV_ARGS;
+  const DV D = view();
   k_diag<<<blocks(n_ + m_), NT, 0, stream_>>>(D, dw, dc, fact_reset());
 }
 
 // set_aug_diagonal_reg! + build_kkt! of the chosen formulation (values consumed by the LDL^T)
 void MPCSolver::assemble_kkt(double dw, double dc, bool diag_done) {
-  DV_ARGS;
+  const DV D = view();
   if (!diag_done) kkt_diag(dw, dc);
   if (kkt_ == KKT_K25) k_k25_scale<<<blocks(nnzK_), NT, 0, stream_>>>(D);
   if (kkt_ == KKT_NORMAL) k_normal_asm<<<blocks(nnzC_), NT, 0, stream_>>>(D);
@@ -2649,7 +2325,7 @@ void MPCSolver::factor_enqueue(double dw, double dc) {
 
 // MadNLP.solve!(kkt, d) between reduce_rhs! (k_rhs) and finish_aug_solve! (k_residual)
 void MPCSolver::kkt_solve() {
-  DV_ARGS;
+  const DV D = view();
   if (kkt_ == KKT_NORMAL) {
     SPMV_LAUNCH(k_normal_rhs, spmv_blocks(m_), stream_, D);
     ldl_->solve_async(bufm_.p, stream_);
@@ -2661,7 +2337,7 @@ void MPCSolver::kkt_solve() {
 }
 
 void MPCSolver::launch_reduce_final(int kind, int nb, int amode, int nb_eval, LDLStatus* rs, bool publish) {
-  DV_ARGS;
+  const DV D = view();
   FinParams P{nb, 0, 0, 0, 0, 0, nb_eval, rs};
   if (publish) {
     P.host = hst_;
@@ -2693,7 +2369,7 @@ void MPCSolver::launch_reduce_final(int kind, int nb, int amode, int nb_eval, LD
 
 // solve_system! (linear_solver.jl:19-44): rhs (mode) -> LDL^T solve -> finish + residual
 void MPCSolver::solve_system(int mode, double mu, int reset, int amode, double atau, int mu_nb) {
-  DV_ARGS;
+  const DV D = view();
   const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
   DevState* host = nullptr;
   uint32_t seq = 0;
@@ -2720,7 +2396,7 @@ void MPCSolver::solve_system(int mode, double mu, int reset, int amode, double a
 
 // gondzio_correction_direction! (solver.jl:245-298): host-controlled loop, one read-back per solve
 void MPCSolver::gondzio() {
-  DV_ARGS;
+  const DV D = view();
   hipStream_t s = stream_;
   const double delta = 0.1, bmin = 0.1, bmax = 10.0, tau = 0.995;
   const int nbz = blocks(std::max(nlb_, nub_));
@@ -2781,7 +2457,7 @@ void MPCSolver::wait_state() {
 }
 
 void MPCSolver::init_starting_point() {
-  DV_ARGS;
+  const DV D = view();
   const int nb = blocks(n_ + m_), nbn = blocks(n_);
   hipStream_t s = stream_;
   k_init_kkt<<<nb, NT, 0, s>>>(D, del_w_, del_c_, fact_reset());
@@ -2823,7 +2499,7 @@ void MPCSolver::init_starting_point() {
 }
 
 void MPCSolver::initialize() {
-  DV_ARGS;
+  const DV D = view();
   hipStream_t s = stream_;
   {  // restart from the problem's initial point (solve! always restarts)
     const QPHost& P = *H_;
@@ -2890,7 +2566,7 @@ void MPCSolver::initialize_public() {
 
 // prediction_step! (solver.jl:230-237) + mehrotra_correction_direction! (solver.jl:239-243)
 void MPCSolver::directions(bool redo, bool fuse_step) {
-  DV_ARGS;
+  const DV D = view();
   hipStream_t s = stream_;
   const int nbz = blocks(std::max(nlb_, nub_));
   // the affine step test (get_alpha_max_primal/dual with tau = 1) is finalised with the residual
@@ -2916,7 +2592,7 @@ int MPCSolver::step_alpha_mode(double& tau) const {
 // update_step_size! (solver.jl:304-307)
 // fused: the corrector solve already ran the step test (directions(.., true))
 void MPCSolver::step_size(bool fused) {
-  DV_ARGS;
+  const DV D = view();
   hipStream_t s = stream_;
   const int nbz = blocks(std::max(nlb_, nub_));
   double tau = 1.0;
@@ -2933,7 +2609,7 @@ void MPCSolver::step_size(bool fused) {
 }
 
 int MPCSolver::solve(madipm_stats* stats) {
-  DV_ARGS;
+  const DV D = view();
   hipStream_t s = stream_;
   trace_.clear();
   point_ok_ = false;
@@ -3154,1261 +2830,13 @@ void MPCSolver::get_solution(double* x, double* y, double* zl, double* zu, doubl
   if (cons && m_) {  // A x = (J's columns < nx) x / con_scale + the fixed columns' part (cfix / con_scale)
     DBuf<double> ax;
     ax.alloc(m_);
-    k_cons<<<(unsigned)((m_ + NT / 64 - 1) / (NT / 64)), NT, 0, stream_>>>(Jrp_, Jci_, Jv_, x_, cfix_, m_, nx_, ax);
+    cons_rows(x_, ax);
     MADIPM_HIP(hipGetLastError());
     std::vector<double> h(m_);
     MADIPM_HIP(hipMemcpyAsync(h.data(), ax.p, sizeof(double) * m_, hipMemcpyDeviceToHost, stream_));
     MADIPM_HIP(hipStreamSynchronize(stream_));
     for (int j = 0; j < m_; ++j) cons[j] = h[j] / P.con_scale[j];
   }
-}
-
-}  // namespace madipm
-
-// ======================================================================= adjoint gradients
-// madipm_solver_adjoint / _adjoint_device: with gx = dl/dx* at the end point of a successful solve, one
-// solve with the K2 matrix of that point, K a~ = [gx on the free variables; 0; 0] in the solver's scaled
-// space, gives a = (ax, as, ay) = (obj_scale a~x, obj_scale a~s / con_scale, con_scale a~y) of the public
-// space, and every gradient is a product of entries of a with entries of the solution.  One thread (the
-// residual: one lane group) per output, every sum in a fixed order, no atomics: the same bits run to run.
-// madipm_solver_adjoint_full / _full_device: the loss also depends on y, zl, zu and A x.  The
-// same factor and refinement with the shifted right-hand side K a~' = g' (k_adj_shift, k_adj_rhs_full),
-// a~ = a~' - [q~; 0; 0] (k_adj_unshift), and the <true> instantiations of the gradient kernels.
-namespace madipm {
-
-struct AdjArgs {  // named in mpc.hpp (sens_solve)
-  int n, m, nx;
-  double os, sgn;                                  // obj_scale; +1 minimize, -1 maximize
-  const double *d, *x, *xl, *xu, *zl, *zu, *y;     // a~ = [a~x; a~s; a~y]; the iterate (scaled space)
-  const double* cscale;                            // con_scale
-  const int32_t *lbpos, *ubpos;
-  const uint8_t* fixed;
-};
-
-namespace {
-
-__device__ __forceinline__ double adj_ax(const AdjArgs& A, int i) { return A.fixed[i] ? 0.0 : A.os * A.d[i]; }
-__device__ __forceinline__ double adj_ay(const AdjArgs& A, int r) { return A.cscale[r] * A.d[A.n + r]; }
-// Sigma_l, Sigma_u of coordinate i of [x; s] in the scaled space (k_diag's terms of pr_diag); 0 without the bound
-__device__ __forceinline__ double adj_sig_l(const AdjArgs& A, int i) {
-  return A.lbpos[i] >= 0 ? A.zl[i] / (A.x[i] - A.xl[i]) : 0.0;
-}
-__device__ __forceinline__ double adj_sig_u(const AdjArgs& A, int i) {
-  return A.ubpos[i] >= 0 ? A.zu[i] / (A.xu[i] - A.x[i]) : 0.0;
-}
-
-// The loss of all five blocks: the cotangents besides gx (any may be null: 0), and a~'x, the
-// x part of the shifted system's solution, which the bound gradients of the free variables are formed from.
-struct AdjFull {
-  const double *gzl, *gzu, *gcons;
-  const double* apx;
-};
-// a bound the variable does not have makes its multiplier a constant: that cotangent is not read
-__device__ __forceinline__ double adj_gzl(const AdjArgs& A, const AdjFull& F, int i) {
-  return (F.gzl && A.lbpos[i] >= 0) ? F.gzl[i] : 0.0;
-}
-__device__ __forceinline__ double adj_gzu(const AdjArgs& A, const AdjFull& F, int i) {
-  return (F.gzu && A.ubpos[i] >= 0) ? F.gzu[i] : 0.0;
-}
-
-// v = [q~; 0; gcons / con_scale], the vector the shifted right-hand side applies K's blocks to:
-// q_i = (Sigma_l gzl - Sigma_u gzu)_i / (Sigma_l + Sigma_u)_i on a free variable with a bound, else 0 (the
-// scalings cancel in q), q~ = q / obj_scale.  The slack entries are written 0: their J~^T row is not empty.
-__global__ __launch_bounds__(NT) void k_adj_shift(AdjArgs A, AdjFull F, double* __restrict__ v, LDLStatus* t1) {
-#pragma clang fp contract(off)
-  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
-  GRID_LOOP(i, A.n + A.m) {
-    double o = 0.0;
-    if (i < A.nx) {
-      if (!A.fixed[i]) {
-        const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
-        if (sm > 0.0) o = ((sl * adj_gzl(A, F, (int)i) - su * adj_gzu(A, F, (int)i)) / sm) / A.os;
-      }
-    } else if (i >= A.n && F.gcons) {
-      o = F.gcons[i - A.n] / A.cscale[i - A.n];
-    }
-    v[i] = o;
-  }
-}
-
-// The shifted right-hand side into d (and p, which keeps it for the residual), k_adj_resid's access pattern
-// applied to v: gx + H~ q~ + J~^T (gcons / con_scale) on a free variable, 0 on a fixed one and on a slack,
-// con_scale_r gy_r / obj_scale + J~_r q~ on row r.  Every entry is of the cotangents' magnitude: the
-// Sigma terms of the plain form, 1e8 and more at an active bound, have cancelled in the algebra.
-template <int G>
-__global__ __launch_bounds__(NT) void k_adj_rhs_full(DV D, AdjArgs A, const double* __restrict__ gx,
-                                                     const double* __restrict__ gy, const double* __restrict__ v) {
-#pragma clang fp contract(off)
-  const int n = D.n, m = D.m;
-  const bool lead = (threadIdx.x & (G - 1)) == 0;
-  GROUP_LOOP(i, n + m, G) {
-    double g = 0.0;
-    if (i < n) {
-      if (i < D.nx && !D.fixed[i]) {
-        double hd, jd;
-        gdot2<G>(D.H, i, v, D.JT, i, v + n, hd, jd);
-        g = (gx ? gx[i] : 0.0) + (hd + jd);
-      }
-    } else {
-      const double jq = gdot<G>(D.J, i - n, v);
-      g = (gy ? A.cscale[i - n] * gy[i - n] / A.os : 0.0) + jq;
-    }
-    if (lead) {
-      D.d[i] = g;
-      D.p[i] = g;
-    }
-  }
-}
-
-// a~ = a~' - [q~; 0; 0], with a~'x kept for the bound gradients
-__global__ __launch_bounds__(NT) void k_adj_unshift(int nx, const double* __restrict__ v, double* __restrict__ sol,
-                                                    double* __restrict__ apx) {
-  GRID_LOOP(i, nx) {
-    const double ap = sol[i];
-    apx[i] = ap;
-    sol[i] = ap - v[i];
-  }
-}
-
-// gx into d's K2 layout (and into p, which keeps it for the residual): zero on fixed variables, slacks, rows
-// t1 != nullptr: the factorisation before this launch ended (LinSolver::lazy_inertia), as in k_rhs
-__global__ __launch_bounds__(NT) void k_adj_rhs(DV D, const double* __restrict__ gx, LDLStatus* t1) {
-  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
-  GRID_LOOP(i, D.n + D.m) {
-    const double v = (i < D.nx && !D.fixed[i]) ? gx[i] : 0.0;
-    D.d[i] = v;
-    D.p[i] = v;
-  }
-}
-
-// r = g - K v and |r| of every row, K the K2 matrix of the point WITHOUT the regularisation the factor carries:
-// H, J^T and Sigma_l + Sigma_u on a primal row, J on a dual row (k_residual's operator with the bound blocks
-// folded into Sigma).  v = the current a~; r (may be null) becomes the right-hand side of a refinement solve.
-template <int G>
-__global__ __launch_bounds__(NT) void k_adj_resid(DV D, AdjArgs A, const double* __restrict__ v, double* __restrict__ r,
-                                                  double* __restrict__ rowres) {
-  const int n = D.n, m = D.m;
-  const bool lead = (threadIdx.x & (G - 1)) == 0;
-  GROUP_LOOP(i, n + m, G) {
-    const double gi = D.p[i];
-    double kv;
-    if (i < n) {
-      double hd, jd;
-      gdot2<G>(D.H, i, v, D.JT, i, v + n, hd, jd);
-      kv = (hd + jd) + (adj_sig_l(A, (int)i) + adj_sig_u(A, (int)i)) * v[i];
-    } else {
-      kv = gdot<G>(D.J, i - n, v);
-    }
-    if (lead) {
-      const double ri = gi - kv;
-      if (r) r[i] = ri;
-      rowres[i] = fabs(ri);
-    }
-  }
-}
-
-// a~ = d (first) or a~ += d: the solve's result, then each refinement's correction
-__global__ __launch_bounds__(NT) void k_adj_acc(double* __restrict__ acc, const double* __restrict__ d, int64_t N,
-                                                int first) {
-  GRID_LOOP(i, N) acc[i] = first ? d[i] : acc[i] + d[i];
-}
-
-// out[0] = max_i rowres[i] / max(1, max_i |g_i|): one block, each thread a strided slice, then an LDS tree
-// (a maximum does not depend on the order; a NaN is kept)
-__global__ __launch_bounds__(NT) void k_adj_resmax(const double* __restrict__ rowres, const double* __restrict__ g,
-                                                   int64_t N, double* __restrict__ out) {
-  __shared__ double sw[NT], sg[NT];
-  const int t = threadIdx.x;
-  double w = 0.0, gm = 0.0;
-  for (int64_t i = t; i < N; i += NT) {
-    w = nmax(w, rowres[i]);
-    gm = nmax(gm, fabs(g[i]));
-  }
-  sw[t] = w;
-  sg[t] = gm;
-  __syncthreads();
-  for (int o = NT / 2; o > 0; o >>= 1) {
-    if (t < o) {
-      sw[t] = nmax(sw[t], sw[t + o]);
-      sg[t] = nmax(sg[t], sg[t + o]);
-    }
-    __syncthreads();
-  }
-  if (t == 0) out[0] = sw[0] / (sg[0] > 1.0 ? sg[0] : 1.0);
-}
-
-// The vector gradients (any output may be null).  Variable i: c_i = -sgn ax_i; a free one:
-// lvar_i = Sigma_l,i ax_i = Sigma~_l,i a~x_i and uvar_i likewise (the scalings cancel); a fixed one: uvar_i = 0
-// (lvar_i is k_adj_fix's).  Row i: an equality row lcon_i = ay_i, ucon_i = 0; a row with slack k:
-// lcon_i = Sigma_l,k as_k = con_scale_i Sigma~_l,k a~s_k and ucon_i likewise.
-// FULL (§13d; A.d is the un-shifted a~): a free variable's bounds in the shifted form,
-// lvar_i = Sigma~_l,i a~'x_i + h_i (gzl_i + gzu_i), uvar_i = Sigma~_u,i a~'x_i - h_i (gzl_i + gzu_i),
-// h_i = Sigma~_l Sigma~_u / (Sigma~_l + Sigma~_u) / obj_scale (0 where the sum is 0).
-template <bool FULL>
-__global__ __launch_bounds__(NT) void k_adj_vec(AdjArgs A, AdjFull F, const int32_t* __restrict__ rowslack,
-                                                double* __restrict__ gc, double* __restrict__ glv,
-                                                double* __restrict__ guv, double* __restrict__ glc,
-                                                double* __restrict__ guc) {
-#pragma clang fp contract(off)
-  GRID_LOOP(i, (A.nx > A.m ? A.nx : A.m)) {
-    if (i < A.nx) {
-      const bool fx = A.fixed[i];
-      const double at = fx ? 0.0 : A.d[i];
-      if (gc) gc[i] = -(A.sgn * (A.os * at));
-      if (!fx) {
-        if constexpr (FULL) {
-          const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
-          const double ap = F.apx[i];
-          const double hg = sm > 0.0 ? (sl * su / sm) / A.os * (adj_gzl(A, F, (int)i) + adj_gzu(A, F, (int)i)) : 0.0;
-          if (glv) glv[i] = sl * ap + hg;
-          if (guv) guv[i] = su * ap - hg;
-        } else {
-          if (glv) glv[i] = adj_sig_l(A, (int)i) * at;
-          if (guv) guv[i] = adj_sig_u(A, (int)i) * at;
-        }
-      } else if (guv) {
-        guv[i] = 0.0;
-      }
-    }
-    if (i < A.m && (glc || guc)) {
-      const int k = rowslack[i];
-      const double cs = A.cscale[i];
-      if (k < 0) {
-        if (glc) glc[i] = cs * A.d[A.n + i];
-        if (guc) guc[i] = 0.0;
-      } else {
-        const double as = A.d[k];
-        if (glc) glc[i] = cs * (adj_sig_l(A, k) * as);
-        if (guc) guc[i] = cs * (adj_sig_u(A, k) * as);
-      }
-    }
-  }
-}
-
-// Avals[k], entry (r, c): -(ax_c y_r + ay_r x_c), y the public multiplier (k_unscale's rounding)
-// FULL: + gcons_r x_c, the entry's own part of (A x)_r
-template <bool FULL>
-__global__ __launch_bounds__(NT) void k_adj_avals(AdjArgs A, AdjFull F, int64_t nnz, const int32_t* __restrict__ Ar,
-                                                  const int32_t* __restrict__ Ac, double* __restrict__ out) {
-#pragma clang fp contract(off)
-  GRID_LOOP(k, nnz) {
-    const int r = Ar[k], c = Ac[k];
-    const double yr = A.y[r] * A.cscale[r] / A.os;
-    const double v = -(adj_ax(A, c) * yr + adj_ay(A, r) * A.x[c]);
-    if constexpr (FULL)
-      out[k] = F.gcons ? v + F.gcons[r] * A.x[c] : v;
-    else
-      out[k] = v;
-  }
-}
-
-// Hvals[k], entry (r, c) of the lower triangle: -sgn ax_r x_r on the diagonal, -sgn (ax_r x_c + ax_c x_r) off it
-__global__ __launch_bounds__(NT) void k_adj_hvals(AdjArgs A, int64_t nnz, const int32_t* __restrict__ Hr,
-                                                  const int32_t* __restrict__ Hc, double* __restrict__ out) {
-#pragma clang fp contract(off)
-  GRID_LOOP(k, nnz) {
-    const int r = Hr[k], c = Hc[k];
-    const double ar = adj_ax(A, r);
-    const double v = r == c ? ar * A.x[r] : ar * A.x[c] + adj_ax(A, c) * A.x[r];
-    out[k] = -(A.sgn * v);
-  }
-}
-
-// lvar_f of fixed variable f = gx_f - sgn (H ax)_f - (A^T ay)_f, from the raw values: the entries of Hvals
-// between f and a free variable, then the entries of Avals in column f, each list in input order
-// FULL: gxe_f = gx_f + (A^T gcons)_f in the place of gx_f, over the same list of column f (J~^T has no row
-// of a fixed variable), and gx may be null
-template <bool FULL>
-__global__ __launch_bounds__(NT) void k_adj_fix(AdjArgs A, AdjFull F, int nfix, const int32_t* __restrict__ fix,
-                                                const int32_t* __restrict__ fhsp, const int2* __restrict__ fh,
-                                                const int32_t* __restrict__ fasp, const int2* __restrict__ fa,
-                                                const double* __restrict__ Hraw, const double* __restrict__ Araw,
-                                                const double* __restrict__ gx, double* __restrict__ glv) {
-#pragma clang fp contract(off)
-  GRID_LOOP(t, nfix) {
-    double hs = 0.0, as = 0.0;
-    for (int q = fhsp[t]; q < fhsp[t + 1]; ++q) {
-      const int2 e = fh[q];
-      hs = hs + Hraw[e.x] * (A.os * A.d[e.y]);
-    }
-    for (int q = fasp[t]; q < fasp[t + 1]; ++q) {
-      const int2 e = fa[q];
-      as = as + Araw[e.x] * adj_ay(A, e.y);
-    }
-    const int f = fix[t];
-    if constexpr (FULL) {
-      double gs = 0.0;
-      if (F.gcons)
-        for (int q = fasp[t]; q < fasp[t + 1]; ++q) {
-          const int2 e = fa[q];
-          gs = gs + Araw[e.x] * F.gcons[e.y];
-        }
-      glv[f] = ((gx ? gx[f] : 0.0) + gs) - A.sgn * hs - as;
-    } else {
-      glv[f] = gx[f] - A.sgn * hs - as;
-    }
-  }
-}
-
-}  // namespace
-
-// refinement solves per adjoint: 2, or MADIPM_ADJ_REFINE (0..8; A/B measurements of the refinement)
-static int adj_refine_steps() {
-  static const int k = [] {
-    const char* e = std::getenv("MADIPM_ADJ_REFINE");
-    const int v = e ? std::atoi(e) : 2;
-    return v < 0 ? 0 : (v > 8 ? 8 : v);
-  }();
-  return k;
-}
-
-// ---- what the adjoint and the tangent (§13e) share: the refusals, the scratch, the factor, the solves
-void MPCSolver::sens_refuse(const std::string& who) const {
-  MADIPM_REQUIRE(solved_, who + "no solve has run on this solver yet");
-  MADIPM_REQUIRE(point_ok_ && !initialized_ && solve_updates_ == n_updates_,
-                 who + "an update, update_device or initialize ran since the last solve, so the iterate no longer "
-                       "belongs to the problem data (solve first)");
-  MADIPM_REQUIRE(status_ == MADIPM_SOLVE_SUCCEEDED, who + "the last solve ended with status " +
-                                                        std::to_string(status_) + ", not SOLVE_SUCCEEDED");
-  MADIPM_REQUIRE(kkt_ == KKT_K2, who + "only kkt_system = SparseKKTSystem (K2) is supported; the K2.5 and "
-                                       "normal-equations formulations are left to a later release");
-  MADIPM_REQUIRE(!comm_, who + "a solver created with a communicator (madipm_solver_create_dist) is not supported");
-}
-
-Adjoint& MPCSolver::sens_state() {
-  if (!adj_) {
-    auto a = std::make_unique<Adjoint>();
-    a->rowres.alloc(std::max(n_ + m_, 1));
-    a->sol.alloc(std::max(n_ + m_, 1));
-    a->scal.alloc(2);
-    a->scal.zero(stream_);
-    MADIPM_HIP(hipEventCreateWithFlags(&a->ev[0], hipEventDisableTiming));
-    MADIPM_HIP(hipEventCreateWithFlags(&a->ev[1], hipEventDisableTiming));
-    adj_ = std::move(a);
-  }
-  return *adj_;
-}
-
-// the factor of the K2 matrix at the final iterate: once per solve
-void MPCSolver::sens_factor(Adjoint& a, const std::string& who) {
-  if (a.fact_solve == n_solves_) return;
-  a.fact_solve = -1;
-  if (pol_) pol_->fact_solve = -1;  // the polish's factor (§13f) is overwritten
-  double dw = 0.0, dc = 0.0;  // the options' regularisation; Adaptive: the current pair, not decayed
-  if (opt_.regularization == 1) {
-    dw = opt_.delta_p;
-    dc = opt_.delta_d;
-  } else if (opt_.regularization != 0) {
-    dw = adapt_dp_;
-    dc = adapt_dd_;
-  }
-  bool ok = false;
-  for (int trial = 0; trial < 3 && !ok; ++trial) {  // factorize_regularized_system!'s trials
-    if (trial) {
-      dw *= 100.0;
-      dc *= 100.0;
-    }
-    factor_enqueue(dw, dc);
-    ok = ldl_->status(stream_) == 0;
-  }
-  if (!ok) throw Error(who + "the factorisation of the KKT system at the solution failed in all three trials", -4);
-  a.fact_solve = n_solves_;
-  ++a.n_fact;
-}
-
-// With the right-hand side in d (and in p, which keeps it): a.sol = K^-1 p, refined; the residual ratio
-// into resid[0]
-void MPCSolver::sens_solve(Adjoint& a, const AdjArgs& A, double* resid) {
-  DV_ARGS;
-  hipStream_t s = stream_;
-  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
-  const int64_t N = (int64_t)n_ + m_;
-  kkt_solve();
-  k_adj_acc<<<nb, NT, 0, s>>>(a.sol.p, d_.p, N, 1);
-  // iterative refinement towards the system without the regularisation (the factor is the regularised
-  // matrix's: each step gains about -log10(delta |K^-1|) digits); a fixed count, so nothing is read back
-  for (int it = 0; it < adj_refine_steps(); ++it) {
-    SPMV_LAUNCH(k_adj_resid, nbs, s, D, A, a.sol.p, d_.p, a.rowres.p);
-    kkt_solve();
-    k_adj_acc<<<nb, NT, 0, s>>>(a.sol.p, d_.p, N, 0);
-  }
-  SPMV_LAUNCH(k_adj_resid, nbs, s, D, A, a.sol.p, (double*)nullptr, a.rowres.p);
-  k_adj_resmax<<<1, NT, 0, s>>>(a.rowres.p, p_.p, N, resid);
-}
-
-void MPCSolver::adjoint(const double* gx, const madipm_qp_gradients& g, bool device, hipStream_t caller) {
-  adjoint(madipm_qp_cotangents{gx, nullptr, nullptr, nullptr, nullptr}, g, device, caller, nullptr);
-}
-
-// name == nullptr: madipm_solver_adjoint / _adjoint_device (gx alone, which must be given).  full: a
-// cotangent other than gx is given, and the shifted system of §13d is solved; without one the kernels and
-// their order are those of the gx-only call whichever entry point was taken.
-void MPCSolver::adjoint(const madipm_qp_cotangents& ct, const madipm_qp_gradients& g, bool device,
-                        hipStream_t caller, const char* name) {
-  const std::string who =
-      name ? std::string(name) + ": " : (device ? "madipm_solver_adjoint_device: " : "madipm_solver_adjoint: ");
-  const double* const gx = ct.x;
-  const bool full = ct.y || ct.zl || ct.zu || ct.cons;
-  QPHost& P = *H_;
-  // ---- refusals, before anything is allocated or enqueued
-  sens_refuse(who);
-  if (name)
-    MADIPM_REQUIRE(gx || full, who + "all five cotangents are NULL");
-  else
-    MADIPM_REQUIRE(gx, who + "gx is NULL");
-  double* const user[7] = {g.c, g.Hvals, g.Avals, g.lcon, g.ucon, g.lvar, g.uvar};
-  MADIPM_REQUIRE(g.c || g.Hvals || g.Avals || g.lcon || g.ucon || g.lvar || g.uvar,
-                 who + "all seven outputs are NULL");
-  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
-  const bool needA = g.Avals && na > 0, needH = g.Hvals && nh > 0, needFix = g.lvar && P.anyfix;
-  MADIPM_REQUIRE(plan_ || !(needA || needH || needFix),
-                 who + "Avals, Hvals (and lvar on a problem with fixed variables) need "
-                       "madipm_solver_prepare_update first (it keeps the index arrays and the raw values)");
-  hipStream_t s = stream_;
-  // ---- allocations, each by the first call that needs it
-  Adjoint& a = sens_state();
-  const double* cscale = device_con_scale();
-  if (!device && gx && !a.gx.p) a.gx.alloc(std::max(nx_, 1));
-  const double* const cot[4] = {ct.y, ct.zl, ct.zu, ct.cons};
-  const int64_t clen[4] = {m_, nx_, nx_, m_};
-  if (full) {
-    if (!a.shift.p) {
-      a.shift.alloc(std::max(n_ + m_, 1));
-      a.apx.alloc(std::max(nx_, 1));
-    }
-    for (int j = 0; j < 4; ++j)
-      if (!device && cot[j] && !a.ct[j].p) a.ct[j].alloc(std::max<int64_t>(clen[j], 1));
-  }
-  if ((g.lcon || g.ucon) && !a.rowslack.p) {
-    a.rowslack.upload(adjoint_rowslack(P), s);
-    MADIPM_HIP(hipStreamSynchronize(s));
-  }
-  if (needA && !a.Ar.p) {
-    a.Ar.upload(plan_->Ar, s);
-    a.Ac.upload(plan_->Ac, s);
-  }
-  if (needH && !a.Hr.p) {
-    a.Hr.upload(P.Hr, s);
-    a.Hc.upload(P.Hc, s);
-  }
-  if (needFix && a.nfix < 0) {  // the fixed variables' entry lists, from the host COO copies
-    AdjointLists L = build_adjoint_lists(P);
-    L.fh.resize(std::max<size_t>(L.fh.size(), 1));  // the allocations are never empty
-    L.fa.resize(std::max<size_t>(L.fa.size(), 1));
-    a.fix.upload(L.fix, s);
-    a.fhsp.upload(L.fhsp, s);
-    a.fasp.upload(L.fasp, s);
-    a.fh.upload(as_int2(L.fh), L.fh.size(), s);
-    a.fa.upload(as_int2(L.fa), L.fa.size(), s);
-    MADIPM_HIP(hipStreamSynchronize(s));
-    a.nfix = (int)L.fix.size();
-  }
-  const int64_t len[7] = {nx_, nh, na, m_, m_, nx_, nx_};
-  double* out[7];
-  for (int j = 0; j < 7; ++j) {
-    out[j] = user[j];
-    if (!device && user[j]) {
-      if (!a.out[j].p) a.out[j].alloc(std::max<int64_t>(len[j], 1));
-      out[j] = a.out[j].p;
-    }
-  }
-  // ---- the factor of the K2 matrix at the final iterate: once per solve
-  DV_ARGS;
-  sens_factor(a, who);
-  // ---- right-hand side, solve, residual
-  const double* dgx = gx;
-  const double* dct[4] = {cot[0], cot[1], cot[2], cot[3]};  // gy, gzl, gzu, gcons on the device
-  if (device) {  // the cotangents are read after the work already enqueued on the caller's stream
-    MADIPM_HIP(hipEventRecord(a.ev[0], caller));
-    MADIPM_HIP(hipStreamWaitEvent(s, a.ev[0], 0));
-  } else {
-    if (gx) {
-      a.gx.upload(gx, nx_, s);
-      dgx = a.gx.p;
-    }
-    for (int j = 0; j < 4; ++j)
-      if (cot[j]) {
-        if (clen[j]) a.ct[j].upload(cot[j], clen[j], s);
-        dct[j] = a.ct[j].p;
-      }
-  }
-  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
-  const AdjArgs A{n_, m_, nx_, obj_scale_, P.sgn, a.sol.p, x_.p, xl_.p, xu_.p, zl_.p, zu_.p, y_.p,
-                  cscale, lbpos_.p, ubpos_.p, fixed_.p};
-  const AdjFull F{dct[1], dct[2], dct[3], a.apx.p};
-  if (full) {  // the shifted system K a~' = g' (§13d); p keeps g' for the residual
-    k_adj_shift<<<nb, NT, 0, s>>>(A, F, a.shift.p, take_fact_end());
-    SPMV_LAUNCH(k_adj_rhs_full, nbs, s, D, A, dgx, dct[0], (const double*)a.shift.p);
-  } else {
-    k_adj_rhs<<<nb, NT, 0, s>>>(D, dgx, take_fact_end());
-  }
-  sens_solve(a, A, a.scal.p);
-  if (full && nx_) k_adj_unshift<<<blocks(nx_), NT, 0, s>>>(nx_, a.shift.p, a.sol.p, a.apx.p);
-  // ---- gradients
-  const bool vec = (out[0] || out[3] || out[4] || out[5] || out[6]) && std::max(nx_, m_);
-  const bool fix = needFix && a.nfix > 0;
-  if (full) {
-    if (vec)
-      k_adj_vec<true><<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, F, a.rowslack.p, out[0], out[5], out[6], out[3],
-                                                                out[4]);
-    if (fix)
-      k_adj_fix<true><<<blocks(a.nfix), NT, 0, s>>>(A, F, a.nfix, a.fix.p, a.fhsp.p, a.fh.p, a.fasp.p, a.fa.p,
-                                                     plan_->Hraw.p, plan_->Araw.p, dgx, out[5]);
-    if (needA) k_adj_avals<true><<<blocks(na), NT, 0, s>>>(A, F, na, a.Ar.p, a.Ac.p, out[2]);
-  } else {
-    if (vec)
-      k_adj_vec<false><<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, F, a.rowslack.p, out[0], out[5], out[6], out[3],
-                                                                 out[4]);
-    if (fix)
-      k_adj_fix<false><<<blocks(a.nfix), NT, 0, s>>>(A, F, a.nfix, a.fix.p, a.fhsp.p, a.fh.p, a.fasp.p, a.fa.p,
-                                                      plan_->Hraw.p, plan_->Araw.p, dgx, out[5]);
-    if (needA) k_adj_avals<false><<<blocks(na), NT, 0, s>>>(A, F, na, a.Ar.p, a.Ac.p, out[2]);
-  }
-  if (needH) k_adj_hvals<<<blocks(nh), NT, 0, s>>>(A, nh, a.Hr.p, a.Hc.p, out[1]);
-  MADIPM_HIP(hipGetLastError());
-  if (device) {  // work enqueued on the caller's stream from now on sees the outputs
-    MADIPM_HIP(hipEventRecord(a.ev[1], s));
-    MADIPM_HIP(hipStreamWaitEvent(caller, a.ev[1], 0));
-  } else {
-    for (int j = 0; j < 7; ++j)
-      if (user[j] && len[j])
-        MADIPM_HIP(hipMemcpyAsync(user[j], out[j], len[j] * sizeof(double), hipMemcpyDeviceToHost, s));
-    MADIPM_HIP(hipStreamSynchronize(s));
-  }
-  ++a.n_adjoints;
-}
-
-void MPCSolver::adjoint_info(int64_t* n_adjoints, int64_t* n_adjoint_factorizations, double* last_residual) {
-  if (n_adjoints) *n_adjoints = adj_ ? adj_->n_adjoints : 0;
-  if (n_adjoint_factorizations) *n_adjoint_factorizations = adj_ ? adj_->n_fact : 0;
-  if (last_residual) {
-    *last_residual = 0.0;
-    if (adj_ && adj_->n_adjoints) {
-      MADIPM_HIP(hipMemcpyAsync(last_residual, adj_->scal.p, sizeof(double), hipMemcpyDeviceToHost, stream_));
-      MADIPM_HIP(hipStreamSynchronize(stream_));
-    }
-  }
-}
-
-}  // namespace madipm
-
-// ======================================================================= tangent
-// madipm_solver_tangent / _tangent_device: forward mode, the transpose of the adjoint.  A direction
-// (dc, dHvals, dAvals, dlcon, ducon, dlvar, duvar) of the data moves w = (x_F, s, y) by K dw = -(dF/dtheta) dtheta
-// with the K of §13c.  The system is solved in the shifted form, dx_F = dx' + p, ds = ds' + p_s, in which no
-// product of Sigma with a direction remains, with the adjoint's factor, refinement and residual.
-namespace madipm {
-namespace {
-
-struct TanDir {  // the direction blocks on the device (null: 0)
-  const double *c, *Hv, *Av, *lcon, *ucon, *lvar, *uvar;
-};
-// a direction entry of a bound the coordinate does not have is not read
-__device__ __forceinline__ double tan_dl(const AdjArgs& A, const TanDir& T, int i) {
-  return (T.lvar && A.lbpos[i] >= 0) ? T.lvar[i] : 0.0;
-}
-__device__ __forceinline__ double tan_du(const AdjArgs& A, const TanDir& T, int i) {
-  return (T.uvar && A.ubpos[i] >= 0) ? T.uvar[i] : 0.0;
-}
-
-// v = [p; p~_s; 0]: p_i = (Sigma_l dlvar + Sigma_u duvar)_i / (Sigma_l + Sigma_u)_i on a free variable with a
-// bound, else 0 (the scalings cancel in p); the slack k of row r: p~_s,k = con_scale_r (Sigma_l,k dlcon_r +
-// Sigma_u,k ducon_r) / (Sigma_l,k + Sigma_u,k).  One thread per variable and per row; a row's thread writes
-// its slack's entry.
-__global__ __launch_bounds__(NT) void k_tan_shift(AdjArgs A, TanDir T, const int32_t* __restrict__ rowslack,
-                                                  double* __restrict__ v, LDLStatus* t1) {
-#pragma clang fp contract(off)
-  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
-  GRID_LOOP(i, A.n + A.m) {
-    if (i < A.nx) {
-      double o = 0.0;
-      if (!A.fixed[i]) {
-        const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
-        if (sm > 0.0) o = (sl * tan_dl(A, T, (int)i) + su * tan_du(A, T, (int)i)) / sm;
-      }
-      v[i] = o;
-    } else if (i >= A.n) {
-      const int r = (int)(i - A.n), k = rowslack[r];
-      v[i] = 0.0;
-      if (k >= 0) {
-        const double sl = adj_sig_l(A, k), su = adj_sig_u(A, k), sm = sl + su;
-        const double dl = (T.lcon && A.lbpos[k] >= 0) ? T.lcon[r] : 0.0;
-        const double du = (T.ucon && A.ubpos[k] >= 0) ? T.ucon[r] : 0.0;
-        v[k] = sm > 0.0 ? A.cscale[r] * ((sl * dl + su * du) / sm) : 0.0;
-      }
-    }
-  }
-}
-
-// The data terms, one thread per destination, each list in ascending input index (build_tangent_lists).
-// A free variable i: base_i = -[ os sgn (dc_i + (dH x)_i + (H dxfix)_i) + os (dA^T y)_i ], y the public
-// multiplier, os y_r = con_scale_r y~_r; 0 on a fixed variable and a slack.  Row r (public space):
-// base_r = (dA x)_r + (A dxfix)_r.  dxfix = dlvar on the fixed variables.  Without lists (gsp == null) the
-// sums are empty: no Hvals / Avals direction and no fixed variable with an lvar direction.
-__global__ __launch_bounds__(NT) void k_tan_data(AdjArgs A, TanDir T, const int32_t* __restrict__ gsp,
-                                                 const int2* __restrict__ ge, const int32_t* __restrict__ csp,
-                                                 const int2* __restrict__ ce, const int32_t* __restrict__ asp,
-                                                 const int2* __restrict__ ae, const double* __restrict__ Hraw,
-                                                 const double* __restrict__ Araw, double* __restrict__ base) {
-#pragma clang fp contract(off)
-  GRID_LOOP(i, A.n + A.m) {
-    double o = 0.0;
-    if (i < A.nx) {
-      if (!A.fixed[i]) {
-        double hs = 0.0, as = 0.0;
-        if (gsp) {
-          for (int q = gsp[i]; q < gsp[i + 1]; ++q) {
-            const int2 e = ge[q];
-            if (T.Hv) hs = hs + T.Hv[e.x] * A.x[e.y];
-            if (T.lvar && A.fixed[e.y]) hs = hs + Hraw[e.x] * T.lvar[e.y];
-          }
-          if (T.Av)
-            for (int q = csp[i]; q < csp[i + 1]; ++q) {
-              const int2 e = ce[q];
-              as = as + T.Av[e.x] * (A.cscale[e.y] * A.y[e.y]);
-            }
-        }
-        const double dc = T.c ? T.c[i] : 0.0;
-        o = -((A.os * A.sgn) * (dc + hs) + as);
-      }
-    } else if (i >= A.n) {
-      const int r = (int)(i - A.n);
-      if (asp)
-        for (int q = asp[r]; q < asp[r + 1]; ++q) {
-          const int2 e = ae[q];
-          if (T.Av) o = o + T.Av[e.x] * A.x[e.y];
-          if (T.lvar && A.fixed[e.y]) o = o + Araw[e.x] * T.lvar[e.y];
-        }
-    }
-    base[i] = o;
-  }
-}
-
-// The shifted right-hand side into d (and p, which keeps it for the residual), k_adj_rhs_full's access
-// pattern applied to v: base_i - (H~ p)_i on a free variable (v's row part is 0: J~^T adds nothing), 0 on a
-// fixed one and on a slack, con_scale_r (db_r - base_r) - (J~ p - p~_s)_r on row r, db = dlcon on an equality
-// row.  Every entry is of the directions' magnitude.
-template <int G>
-__global__ __launch_bounds__(NT) void k_tan_rhs(DV D, AdjArgs A, TanDir T, const int32_t* __restrict__ rowslack,
-                                                const double* __restrict__ v, const double* __restrict__ base) {
-#pragma clang fp contract(off)
-  const int n = D.n, m = D.m;
-  const bool lead = (threadIdx.x & (G - 1)) == 0;
-  GROUP_LOOP(i, n + m, G) {
-    double g = 0.0;
-    if (i < n) {
-      if (i < D.nx && !D.fixed[i]) g = base[i] - gdot<G>(D.H, i, v);
-    } else {
-      const int r = (int)(i - n);
-      const double jq = gdot<G>(D.J, r, v);
-      const double db = (T.lcon && rowslack[r] < 0) ? T.lcon[r] : 0.0;
-      g = A.cscale[r] * (db - base[i]) - jq;
-    }
-    if (lead) {
-      D.d[i] = g;
-      D.p[i] = g;
-    }
-  }
-}
-
-// Un-shift and un-scale (A.d is the solution [dx'; ds~'; dy~] of the shifted system; any output may be null):
-// dx = dx' + p on a free variable, dlvar on a fixed one (also into dxs, with zeros on the slacks, for
-// k_tan_cons); dy = con_scale dy~ / obj_scale; dzl = -Sigma_l dx' + h (dlvar - duvar), dzu = Sigma_u dx' +
-// h (dlvar - duvar) with the public Sigma = Sigma~ / obj_scale and h = Sigma_l Sigma_u / (Sigma_l + Sigma_u);
-// 0 without that bound and on a fixed variable.
-__global__ __launch_bounds__(NT) void k_tan_out(AdjArgs A, TanDir T, const double* __restrict__ v,
-                                                double* __restrict__ dxs, double* __restrict__ ox,
-                                                double* __restrict__ oy, double* __restrict__ ozl,
-                                                double* __restrict__ ozu) {
-#pragma clang fp contract(off)
-  const int ns = A.n - A.nx;
-  const int top = A.nx > A.m ? A.nx : A.m;
-  GRID_LOOP(i, (top > ns ? top : ns)) {
-    if (i < A.nx) {
-      double dx, dzl = 0.0, dzu = 0.0;
-      if (A.fixed[i]) {
-        dx = T.lvar ? T.lvar[i] : 0.0;
-      } else {
-        const double dxp = A.d[i];
-        dx = dxp + v[i];
-        const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
-        const double hd = sm > 0.0 ? ((sl * su / sm) / A.os) * (tan_dl(A, T, (int)i) - tan_du(A, T, (int)i)) : 0.0;
-        if (A.lbpos[i] >= 0) dzl = hd - (sl / A.os) * dxp;
-        if (A.ubpos[i] >= 0) dzu = (su / A.os) * dxp + hd;
-      }
-      dxs[i] = dx;
-      if (ox) ox[i] = dx;
-      if (ozl) ozl[i] = dzl;
-      if (ozu) ozu[i] = dzu;
-    }
-    if (i < ns) dxs[A.nx + i] = 0.0;
-    if (i < A.m && oy) oy[i] = A.d[A.n + i] * A.cscale[i] / A.os;
-  }
-}
-
-// dcons_r = (A dx)_r + (dA x)_r: J~'s structural columns times dx / con_scale_r (J~ has no fixed column, and
-// dxs is 0 on the slacks), + base_r, which holds the fixed columns' part and dA x
-template <int G>
-__global__ __launch_bounds__(NT) void k_tan_cons(DV D, AdjArgs A, const double* __restrict__ dxs,
-                                                 const double* __restrict__ base, double* __restrict__ ocons) {
-#pragma clang fp contract(off)
-  const bool lead = (threadIdx.x & (G - 1)) == 0;
-  GROUP_LOOP(r, D.m, G) {
-    const double s = gdot<G>(D.J, r, dxs);
-    if (lead) ocons[r] = s / A.cscale[r] + base[D.n + r];
-  }
-}
-
-}  // namespace
-
-void MPCSolver::tangent(const madipm_qp_directions& dr, const madipm_qp_point_tangents& o, bool device,
-                        hipStream_t caller) {
-  const std::string who = device ? "madipm_solver_tangent_device: " : "madipm_solver_tangent: ";
-  QPHost& P = *H_;
-  // ---- refusals, before anything is allocated or enqueued
-  sens_refuse(who);
-  const double* const dir[7] = {dr.c, dr.Hvals, dr.Avals, dr.lcon, dr.ucon, dr.lvar, dr.uvar};
-  double* const user[5] = {o.x, o.y, o.zl, o.zu, o.cons};
-  MADIPM_REQUIRE(dr.c || dr.Hvals || dr.Avals || dr.lcon || dr.ucon || dr.lvar || dr.uvar,
-                 who + "all seven directions are NULL");
-  MADIPM_REQUIRE(o.x || o.y || o.zl || o.zu || o.cons, who + "all five outputs are NULL");
-  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
-  const bool needLists = (dr.Avals && na > 0) || (dr.Hvals && nh > 0) || (dr.lvar && P.anyfix);
-  MADIPM_REQUIRE(plan_ || !needLists,
-                 who + "Avals, Hvals (and lvar on a problem with fixed variables) need "
-                       "madipm_solver_prepare_update first (it keeps the index arrays and the raw values)");
-  hipStream_t s = stream_;
-  // ---- allocations, each by the first call that needs it
-  Adjoint& a = sens_state();
-  if (!tan_) {
-    auto t = std::make_unique<Tangent>();
-    t->base.alloc(std::max(n_ + m_, 1));
-    t->dx.alloc(std::max(n_, 1));
-    t->scal.alloc(1);
-    t->scal.zero(s);
-    tan_ = std::move(t);
-  }
-  Tangent& t = *tan_;
-  const double* cscale = device_con_scale();
-  if (!a.shift.p) {  // as the five-cotangent adjoint allocates them
-    a.shift.alloc(std::max(n_ + m_, 1));
-    a.apx.alloc(std::max(nx_, 1));
-  }
-  if (!a.rowslack.p) {
-    a.rowslack.upload(adjoint_rowslack(P), s);
-    MADIPM_HIP(hipStreamSynchronize(s));
-  }
-  if (needLists && !t.lists) {  // the entry lists, from the host COO copies
-    TangentLists L = build_tangent_lists(P);
-    L.ae.resize(std::max<size_t>(L.ae.size(), 1));  // the allocations are never empty
-    L.ce.resize(std::max<size_t>(L.ce.size(), 1));
-    L.ge.resize(std::max<size_t>(L.ge.size(), 1));
-    t.asp.upload(L.asp, s);
-    t.csp.upload(L.csp, s);
-    t.gsp.upload(L.gsp, s);
-    t.ae.upload(as_int2(L.ae), L.ae.size(), s);
-    t.ce.upload(as_int2(L.ce), L.ce.size(), s);
-    t.ge.upload(as_int2(L.ge), L.ge.size(), s);
-    MADIPM_HIP(hipStreamSynchronize(s));
-    t.lists = true;
-  }
-  const int64_t dlen[7] = {nx_, nh, na, m_, m_, nx_, nx_};
-  const int64_t olen[5] = {nx_, m_, nx_, nx_, m_};
-  const double* ddir[7];
-  double* out[5];
-  for (int j = 0; j < 7; ++j) {
-    ddir[j] = dir[j];
-    if (!device && dir[j]) {
-      if (!t.dir[j].p) t.dir[j].alloc(std::max<int64_t>(dlen[j], 1));
-      ddir[j] = t.dir[j].p;
-    }
-  }
-  for (int j = 0; j < 5; ++j) {
-    out[j] = user[j];
-    if (!device && user[j]) {
-      if (!t.out[j].p) t.out[j].alloc(std::max<int64_t>(olen[j], 1));
-      out[j] = t.out[j].p;
-    }
-  }
-  // ---- the factor of the K2 matrix at the final iterate: the adjoint's, once per solve
-  DV_ARGS;
-  sens_factor(a, who);
-  if (device) {  // the directions are read after the work already enqueued on the caller's stream
-    MADIPM_HIP(hipEventRecord(a.ev[0], caller));
-    MADIPM_HIP(hipStreamWaitEvent(s, a.ev[0], 0));
-  } else {
-    for (int j = 0; j < 7; ++j)
-      if (dir[j] && dlen[j]) t.dir[j].upload(dir[j], dlen[j], s);
-  }
-  // ---- right-hand side, solve, residual
-  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
-  const AdjArgs A{n_, m_, nx_, obj_scale_, P.sgn, a.sol.p, x_.p, xl_.p, xu_.p, zl_.p, zu_.p, y_.p,
-                  cscale, lbpos_.p, ubpos_.p, fixed_.p};
-  const TanDir T{ddir[0], ddir[1], ddir[2], ddir[3], ddir[4], ddir[5], ddir[6]};
-  const bool ls = needLists;  // lists built by an earlier call are not walked when this one has no use for them
-  k_tan_shift<<<nb, NT, 0, s>>>(A, T, a.rowslack.p, a.shift.p, take_fact_end());
-  k_tan_data<<<nb, NT, 0, s>>>(A, T, ls ? t.gsp.p : nullptr, t.ge.p, t.csp.p, t.ce.p, ls ? t.asp.p : nullptr, t.ae.p,
-                               plan_ ? plan_->Hraw.p : nullptr, plan_ ? plan_->Araw.p : nullptr, t.base.p);
-  SPMV_LAUNCH(k_tan_rhs, nbs, s, D, A, T, (const int32_t*)a.rowslack.p, (const double*)a.shift.p,
-              (const double*)t.base.p);
-  sens_solve(a, A, t.scal.p);
-  // ---- outputs
-  k_tan_out<<<blocks(std::max(std::max(nx_, m_), std::max(n_ - nx_, 1))), NT, 0, s>>>(
-      A, T, a.shift.p, t.dx.p, out[0], out[1], out[2], out[3]);
-  if (out[4] && m_)
-    SPMV_LAUNCH(k_tan_cons, spmv_blocks(m_), s, D, A, (const double*)t.dx.p, (const double*)t.base.p, out[4]);
-  MADIPM_HIP(hipGetLastError());
-  if (device) {  // work enqueued on the caller's stream from now on sees the outputs
-    MADIPM_HIP(hipEventRecord(a.ev[1], s));
-    MADIPM_HIP(hipStreamWaitEvent(caller, a.ev[1], 0));
-  } else {
-    for (int j = 0; j < 5; ++j)
-      if (user[j] && olen[j])
-        MADIPM_HIP(hipMemcpyAsync(user[j], out[j], olen[j] * sizeof(double), hipMemcpyDeviceToHost, s));
-    MADIPM_HIP(hipStreamSynchronize(s));
-  }
-  ++t.n_tangents;
-}
-
-void MPCSolver::tangent_info(int64_t* n_tangents, double* last_residual) {
-  if (n_tangents) *n_tangents = tan_ ? tan_->n_tangents : 0;
-  if (last_residual) {
-    *last_residual = 0.0;
-    if (tan_ && tan_->n_tangents) {
-      MADIPM_HIP(hipMemcpyAsync(last_residual, tan_->scal.p, sizeof(double), hipMemcpyDeviceToHost, stream_));
-      MADIPM_HIP(hipStreamSynchronize(stream_));
-    }
-  }
-}
-
-}  // namespace madipm
-
-// ======================================================================= polish
-// madipm_solver_polish / _polish_device: the active set the end point identifies (or the caller's), the active
-// coordinates of v = [x; s] at their bounds, and the equality-constrained QP of that face solved in delta form:
-// r = -[grad of the Lagrangian on the inactive coordinates; J v - b] at the scratch point w = [v; y], a solve
-// with the factor of the K2 pattern whose diagonal is H~_ii + delta_w (+ sigma on an active coordinate; no
-// Sigma), the correction masked on the active coordinates, a fixed number of times.  The factor is a
-// preconditioner: the residual is the exact masked operator's.  One thread (the residual: one lane group) per
-// output, every sum in a fixed order, no atomics but the integer maxima of the two flags.
-namespace madipm {
-namespace {
-
-struct PolArgs {
-  int n, m, nx;
-  double os;                                   // obj_scale
-  const double *x, *zl, *zu, *y;               // the iterate (scaled space); never written
-  const double* cscale;                        // con_scale
-  const int32_t *lbpos, *ubpos;
-  const uint8_t* fixed;
-  const double *lo, *hi;                       // raw bounds of [x; s], public space (lvar / lcon of the slack's row)
-  const int32_t *ineq, *rowslack;              // slack -> row; row -> slack coordinate or -1
-  int8_t* codes;                               // -1 lower-active, +1 upper-active, 0 inactive, per coordinate of [x; s]
-  const int8_t* codes_fact;                    // the codes the factor held was made with
-  double *w, *grad;                            // [v; y]; f + J~^T y on [x; s] at w
-  int32_t* flags;
-};
-
-// con_scale of coordinate i's row (1 on a variable), and its bounds in the scaled space
-__device__ __forceinline__ double pol_cs(const PolArgs& P, int i) { return i < P.nx ? 1.0 : P.cscale[P.ineq[i - P.nx]]; }
-// a multiplier of coordinate i, scaled space -> public (k_unscale's roundings: z / os, y cs / os)
-__device__ __forceinline__ double pol_mult(const PolArgs& P, int i, double z, double cs) {
-  return i < P.nx ? z / P.os : z * cs / P.os;
-}
-
-// The codes and the projected point.  av == null: the guess, on the values get_solution returns (multiplier
-// against gap, both un-scaled); else the supplied set, validated (flags[0]).  flags[1]: the codes differ from
-// those of the factor held.  Writes only scratch.  t1 as in k_adj_shift.
-__global__ __launch_bounds__(NT) void k_pol_classify(PolArgs P, const int8_t* __restrict__ av,
-                                                     const int8_t* __restrict__ ar, LDLStatus* t1) {
-#pragma clang fp contract(off)
-  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
-  const int top = P.n > P.m ? P.n : P.m;
-  GRID_LOOP(i, top) {
-    if (i < P.n) {
-      const bool fx = P.fixed[i], kl = P.lbpos[i] >= 0, ku = P.ubpos[i] >= 0;
-      const double cs = pol_cs(P, (int)i);
-      const double v = P.x[i];
-      const double ls = i < P.nx ? P.lo[i] : cs * P.lo[i], us = i < P.nx ? P.hi[i] : cs * P.hi[i];
-      int c = 0;
-      if (av) {
-        c = i < P.nx ? av[i] : ar[P.ineq[i - P.nx]];
-        if (c != 0 && (fx || (c != -1 && c != 1) || (c == -1 && !kl) || (c == 1 && !ku))) {
-          atomicMax(&P.flags[0], 1);
-          c = 0;
-        }
-      } else if (!fx) {
-        const double zl = kl ? pol_mult(P, (int)i, P.zl[i], cs) : 0.0, zu = ku ? pol_mult(P, (int)i, P.zu[i], cs) : 0.0;
-        const bool la = kl && zl > (v - ls) / cs, ua = ku && zu > (us - v) / cs;
-        c = (la && ua) ? (zu > zl ? 1 : -1) : (la ? -1 : (ua ? 1 : 0));
-      }
-      P.w[i] = c < 0 ? ls : (c > 0 ? us : v);
-      if (P.codes_fact[i] != c) atomicMax(&P.flags[1], 1);
-      P.codes[i] = (int8_t)c;
-    }
-    if (i < P.m) {
-      P.w[P.n + i] = P.y[i];
-      if (ar && P.rowslack[i] < 0 && ar[i] != 0) atomicMax(&P.flags[0], 1);
-    }
-  }
-}
-
-// The K2 diagonal of the polish factor: H~_ii + delta_w, + sigma on an active coordinate; delta_c on a row.
-// Only Kx's diagonal is written.  rs as in k_diag.
-__global__ __launch_bounds__(NT) void k_pol_diag(DV D, const int8_t* __restrict__ codes, double dw, double dc,
-                                                 double sigma, LDLStatus* rs) {
-#pragma clang fp contract(off)
-  if (rs && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_start(rs);
-  GRID_LOOP(i, D.n + D.m) {
-    if (i < D.n) {
-      const double h = D.Hdiag[i] + dw;
-      D.Kx[D.diag_pos[i]] = codes[i] ? h + sigma : h;
-    } else {
-      D.Kx[D.diag_pos[i]] = dc;
-    }
-  }
-}
-
-// The exact masked residual at w: on a coordinate of [x; s], t = (H~ v + c~ + gfix) + J~^T y (k_eval's f and
-// jacl), r = -t on an inactive free coordinate and 0 on an active or fixed one; on a row, r = -((J~ v - rhs) +
-// cfix).  r (may be null) becomes the right-hand side of the next solve; grad (may be null) keeps t.
-template <int G>
-__global__ __launch_bounds__(NT) void k_pol_resid(DV D, PolArgs P, double* __restrict__ r, double* __restrict__ rowres,
-                                                  double* __restrict__ grad, LDLStatus* t1) {
-#pragma clang fp contract(off)
-  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
-  const int n = D.n, m = D.m;
-  const bool lead = (threadIdx.x & (G - 1)) == 0;
-  const double* __restrict__ w = P.w;
-  GROUP_LOOP(i, n + m, G) {
-    double ri;
-    if (i < n) {
-      double hv, jy;
-      gdot2<G>(D.H, i, w, D.JT, i, w + n, hv, jy);
-      const double t = (hv + (D.cs[i] + D.gfix[i])) + jy;
-      ri = (P.codes[i] != 0 || D.fixed[i]) ? 0.0 : -t;
-      if (lead && grad) grad[i] = t;
-    } else {
-      const int64_t j = i - n;
-      const double jv = gdot<G>(D.J, j, w);
-      ri = -((jv - D.rhs[j]) + D.cfix[j]);
-    }
-    if (lead) {
-      if (r) r[i] = ri;
-      rowres[i] = fabs(ri);
-    }
-  }
-}
-
-// w += d, with the correction of an active or fixed coordinate dropped
-__global__ __launch_bounds__(NT) void k_pol_acc(PolArgs P, const double* __restrict__ d) {
-  GRID_LOOP(i, P.n + P.m) {
-    if (i < P.n && (P.codes[i] != 0 || P.fixed[i])) continue;
-    P.w[i] = P.w[i] + d[i];
-  }
-}
-
-// The checks as block partials (value-major, pidx): the smallest active multiplier, the largest |active
-// multiplier|, the smallest gap / max(1, |bound|) and the smallest gap over the inactive bounds, all in the
-// public space
-__global__ __launch_bounds__(NT) void k_pol_meas(PolArgs P, double* __restrict__ part) {
-#pragma clang fp contract(off)
-  double mn = INF, ma = 0.0, gp = INF, gr = INF;
-  GRID_LOOP(i, P.n) {
-    if (P.fixed[i]) continue;
-    const int c = P.codes[i];
-    const double cs = pol_cs(P, (int)i);
-    if (c != 0) {
-      const double t = pol_mult(P, (int)i, P.grad[i], cs);
-      const double z = c < 0 ? t : -t;
-      mn = fmin(mn, z);
-      ma = nmax(ma, fabs(z));
-    }
-    const double v = P.w[i];
-    if (P.lbpos[i] >= 0 && c != -1) {
-      const double b = P.lo[i], bs = i < P.nx ? b : cs * b;
-      const double g = (v - bs) / cs;
-      gr = fmin(gr, g);
-      gp = fmin(gp, g / fmax(1.0, fabs(b)));
-    }
-    if (P.ubpos[i] >= 0 && c != 1) {
-      const double b = P.hi[i], bs = i < P.nx ? b : cs * b;
-      const double g = (bs - v) / cs;
-      gr = fmin(gr, g);
-      gp = fmin(gp, g / fmax(1.0, fabs(b)));
-    }
-  }
-  double v[4] = {mn, ma, gp, gr};
-  const int ops[4] = {OP_MIN, OP_MAX, OP_MIN, OP_MIN};
-  block_partials<4>(v, ops, part);
-}
-
-// The verdict: one block, each thread a strided slice, then an LDS tree (k_adj_resmax's shape; maxima and
-// minima do not depend on the order, the count is an integer sum).  failed: all three factorisations failed.
-__global__ __launch_bounds__(NT) void k_pol_verdict(const double* __restrict__ rowres, int64_t N,
-                                                    const double* __restrict__ part, int nb,
-                                                    const int8_t* __restrict__ codes, int n, double tol_resid,
-                                                    double tol_sign, double tol_feas, int failed,
-                                                    PolMeasures* __restrict__ out) {
-  __shared__ double sr[NT], smn[NT], sma[NT], sgp[NT], sgr[NT];
-  __shared__ int sc[NT];
-  const int t = threadIdx.x;
-  double r = 0.0, mn = INF, ma = 0.0, gp = INF, gr = INF;
-  int cnt = 0;
-  for (int64_t i = t; i < N; i += NT) r = nmax(r, rowres[i]);
-  for (int b = t; b < nb; b += NT) {
-    mn = fmin(mn, part[pidx(b, 0)]);
-    ma = nmax(ma, part[pidx(b, 1)]);
-    gp = fmin(gp, part[pidx(b, 2)]);
-    gr = fmin(gr, part[pidx(b, 3)]);
-  }
-  for (int i = t; i < n; i += NT) cnt += codes[i] != 0;
-  sr[t] = r, smn[t] = mn, sma[t] = ma, sgp[t] = gp, sgr[t] = gr, sc[t] = cnt;
-  __syncthreads();
-  for (int o = NT / 2; o > 0; o >>= 1) {
-    if (t < o) {
-      sr[t] = nmax(sr[t], sr[t + o]);
-      smn[t] = fmin(smn[t], smn[t + o]);
-      sma[t] = nmax(sma[t], sma[t + o]);
-      sgp[t] = fmin(sgp[t], sgp[t + o]);
-      sgr[t] = fmin(sgr[t], sgr[t + o]);
-      sc[t] += sc[t + o];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    int v = MADIPM_POLISHED;
-    if (smn[0] < -tol_sign * (sma[0] > 1.0 ? sma[0] : 1.0) || sgp[0] < -tol_feas) v = MADIPM_POLISH_WRONG_SET;
-    if (!(sr[0] <= tol_resid)) v = MADIPM_POLISH_NO_CONVERGENCE;  // a NaN lands here
-    if (failed) v = MADIPM_POLISH_FACTORIZATION_FAILED;
-    out->verdict = v;
-    out->n_active = sc[0];
-    out->residual = sr[0];
-    out->min_multiplier = smn[0];
-    out->min_gap = sgr[0];
-  }
-}
-
-// The polished point, un-scaled (any output may be null): x = v; y = y~ cs / os; zl = t / os on a lower-active
-// variable, zu = -t / os on an upper-active one, 0 elsewhere; cons = (A x) / cs from k_cons' row values, the
-// bound itself on an active row
-__global__ __launch_bounds__(NT) void k_pol_out(PolArgs P, const double* __restrict__ ax, double* __restrict__ ox,
-                                                double* __restrict__ oy, double* __restrict__ ozl,
-                                                double* __restrict__ ozu, double* __restrict__ ocons) {
-#pragma clang fp contract(off)
-  GRID_LOOP(i, (P.nx > P.m ? P.nx : P.m)) {
-    if (i < P.nx) {
-      const int c = P.codes[i];
-      const double t = c != 0 ? P.grad[i] / P.os : 0.0;
-      if (ox) ox[i] = P.w[i];
-      if (ozl) ozl[i] = c < 0 ? t : 0.0;
-      if (ozu) ozu[i] = c > 0 ? -t : 0.0;
-    }
-    if (i < P.m) {
-      const double cs = P.cscale[i];
-      if (oy) oy[i] = P.w[P.n + i] * cs / P.os;
-      if (ocons) {
-        const int k = P.rowslack[i], c = k >= 0 ? P.codes[k] : 0;
-        ocons[i] = c < 0 ? P.lo[k] : (c > 0 ? P.hi[k] : ax[i] / cs);
-      }
-    }
-  }
-}
-
-// The codes as the caller sees them: one per variable, one per row (0 on an equality row)
-__global__ __launch_bounds__(NT) void k_pol_codes(PolArgs P, int8_t* __restrict__ ovar, int8_t* __restrict__ orow) {
-  GRID_LOOP(i, (P.nx > P.m ? P.nx : P.m)) {
-    if (i < P.nx && ovar) ovar[i] = P.codes[i];
-    if (i < P.m && orow) {
-      const int k = P.rowslack[i];
-      orow[i] = k >= 0 ? P.codes[k] : (int8_t)0;
-    }
-  }
-}
-
-}  // namespace
-
-void MPCSolver::polish(const madipm_polish_opts& o, const int8_t* av, const int8_t* ar, const madipm_polish_out& po,
-                       madipm_polish_info* info, bool device, hipStream_t caller) {
-  const std::string who = device ? "madipm_solver_polish_device: " : "madipm_solver_polish: ";
-  QPHost& P = *H_;
-  // ---- refusals, before anything is allocated or enqueued
-  sens_refuse(who);
-  MADIPM_REQUIRE((av == nullptr) == (ar == nullptr),
-                 who + "exactly one of active_var and active_row is given (pass both, or neither for the guess)");
-  double* const user[5] = {po.x, po.y, po.zl, po.zu, po.cons};
-  MADIPM_REQUIRE(po.x || po.y || po.zl || po.zu || po.cons || po.active_var || po.active_row,
-                 who + "all seven outputs are NULL");
-  auto tol_ok = [](double t) { return t >= 0.0 && std::isfinite(t); };
-  MADIPM_REQUIRE(o.sigma > 0.0 && std::isfinite(o.sigma), who + "sigma must be positive and finite");
-  MADIPM_REQUIRE(tol_ok(o.tol_resid) && tol_ok(o.tol_sign) && tol_ok(o.tol_feas),
-                 who + "tol_resid, tol_sign and tol_feas must be finite and not negative");
-  MADIPM_REQUIRE(o.refine_steps >= 0 && o.refine_steps <= 8,
-                 who + "refine_steps must be in 0..8, got " + std::to_string(o.refine_steps));
-  hipStream_t s = stream_;
-  // ---- allocations, by the first call
-  Adjoint& a = sens_state();
-  const double* cscale = device_con_scale();
-  if (!a.rowslack.p) {
-    a.rowslack.upload(adjoint_rowslack(P), s);
-    MADIPM_HIP(hipStreamSynchronize(s));
-  }
-  const int ns = n_ - nx_;
-  if (!pol_) {
-    auto p = std::make_unique<Polish>();
-    p->w.alloc(std::max(n_ + m_, 1));
-    p->grad.alloc(std::max(n_, 1));
-    p->lo.alloc(std::max(n_, 1));
-    p->hi.alloc(std::max(n_, 1));
-    p->part.alloc((size_t)4 * MAXB);
-    p->ax.alloc(std::max(m_, 1));
-    p->codes.alloc(std::max(n_, 1));
-    p->codes_fact.alloc(std::max(n_, 1));
-    p->codes_fact.zero(s);
-    p->ineq.alloc(std::max(ns, 1));
-    p->ineq.upload(P.ind_ineq.data(), P.ind_ineq.size(), s);
-    p->flags.alloc(2);
-    p->meas.alloc(1);
-    pol_ = std::move(p);
-  }
-  Polish& p = *pol_;
-  if (p.bounds_updates != n_updates_) {  // the raw bounds of [x; s], as the last update left them
-    refresh_host_mirrors();
-    std::vector<double> lo(std::max(n_, 1)), hi(std::max(n_, 1));
-    for (int i = 0; i < nx_; ++i) lo[i] = P.lvar[i], hi[i] = P.uvar[i];
-    for (int k = 0; k < ns; ++k) lo[nx_ + k] = P.lcon[P.ind_ineq[k]], hi[nx_ + k] = P.ucon[P.ind_ineq[k]];
-    p.lo.upload(lo, s);
-    p.hi.upload(hi, s);
-    MADIPM_HIP(hipStreamSynchronize(s));  // lo / hi are this scope's
-    p.bounds_updates = n_updates_;
-  }
-  const int64_t olen[5] = {nx_, m_, nx_, nx_, m_};
-  double* out[5];
-  for (int j = 0; j < 5; ++j) {
-    out[j] = user[j];
-    if (!device && user[j]) {
-      if (!p.out[j].p) p.out[j].alloc(std::max<int64_t>(olen[j], 1));
-      out[j] = p.out[j].p;
-    }
-  }
-  int8_t *ovar = po.active_var, *orow = po.active_row;
-  const int8_t *dav = av, *dar = ar;
-  if (!device) {
-    if (ovar && !p.out_var.p) p.out_var.alloc(std::max(nx_, 1));
-    if (orow && !p.out_row.p) p.out_row.alloc(std::max(m_, 1));
-    if (ovar) ovar = p.out_var.p;
-    if (orow) orow = p.out_row.p;
-    if (av) {
-      if (!p.in_var.p) {
-        p.in_var.alloc(std::max(nx_, 1));
-        p.in_row.alloc(std::max(m_, 1));
-      }
-      p.in_var.upload(av, nx_, s);
-      p.in_row.upload(ar, m_, s);
-      dav = p.in_var.p;
-      dar = p.in_row.p;
-    }
-  } else {  // the set is read, and the outputs written, after the work already enqueued on the caller's stream
-    MADIPM_HIP(hipEventRecord(a.ev[0], caller));
-    MADIPM_HIP(hipStreamWaitEvent(s, a.ev[0], 0));
-  }
-  // ---- the codes and the projected point
-  DV_ARGS;
-  const PolArgs A{n_, m_, nx_, obj_scale_, x_.p, zl_.p, zu_.p, y_.p, cscale, lbpos_.p, ubpos_.p, fixed_.p,
-                  p.lo.p, p.hi.p, p.ineq.p, a.rowslack.p, p.codes.p, p.codes_fact.p, p.w.p, p.grad.p, p.flags.p};
-  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_), nbn = blocks(std::max(n_, 1));
-  const int64_t N = (int64_t)n_ + m_;
-  p.flags.zero(s);
-  k_pol_classify<<<blocks(std::max(std::max(n_, m_), 1)), NT, 0, s>>>(A, dav, dar, take_fact_end());
-  MADIPM_HIP(hipGetLastError());
-  int32_t hflags[2] = {0, 0};
-  MADIPM_HIP(hipMemcpyAsync(hflags, p.flags.p, sizeof(hflags), hipMemcpyDeviceToHost, s));
-  MADIPM_HIP(hipStreamSynchronize(s));
-  MADIPM_REQUIRE(!hflags[0], who + "the supplied set has a code other than -1, 0, +1, or a code on a bound that does "
-                                   "not exist, on a fixed variable or on an equality row");
-  // ---- the factor: once per point, set and sigma
-  bool ok = true;
-  if (p.fact_solve != n_solves_ || p.fact_sigma != o.sigma || hflags[1]) {
-    p.fact_solve = -1;
-    a.fact_solve = -1;  // the adjoint's factor and KKT diagonal are overwritten
-    double dw = 0.0, dc = 0.0;  // sens_factor's regularisation and trials
-    if (opt_.regularization == 1) {
-      dw = opt_.delta_p;
-      dc = opt_.delta_d;
-    } else if (opt_.regularization != 0) {
-      dw = adapt_dp_;
-      dc = adapt_dd_;
-    }
-    ok = false;
-    for (int trial = 0; trial < 3 && !ok; ++trial) {
-      if (trial) {
-        dw *= 100.0;
-        dc *= 100.0;
-      }
-      k_pol_diag<<<nb, NT, 0, s>>>(D, p.codes.p, dw, dc, o.sigma, fact_reset());
-      timed_factorize();
-      ok = ldl_->status(s) == 0;
-    }
-    if (ok) {
-      if (n_) MADIPM_HIP(hipMemcpyAsync(p.codes_fact.p, p.codes.p, (size_t)n_, hipMemcpyDeviceToDevice, s));
-      p.fact_solve = n_solves_;
-      p.fact_sigma = o.sigma;
-      ++p.last.n_polish_factorizations;
-    }
-  }
-  // ---- 1 + refine_steps solves in delta form, the final residual, the verdict
-  if (ok)
-    for (int it = 0; it <= o.refine_steps; ++it) {
-      SPMV_LAUNCH(k_pol_resid, nbs, s, D, A, d_.p, a.rowres.p, (double*)nullptr, take_fact_end());
-      kkt_solve();
-      k_pol_acc<<<nb, NT, 0, s>>>(A, d_.p);
-    }
-  SPMV_LAUNCH(k_pol_resid, nbs, s, D, A, (double*)nullptr, a.rowres.p, p.grad.p, take_fact_end());
-  k_pol_meas<<<nbn, NT, 0, s>>>(A, p.part.p);
-  k_pol_verdict<<<1, NT, 0, s>>>(a.rowres.p, N, p.part.p, nbn, p.codes.p, n_, o.tol_resid, o.tol_sign, o.tol_feas,
-                                 ok ? 0 : 1, p.meas.p);
-  MADIPM_HIP(hipGetLastError());
-  PolMeasures hm{};
-  MADIPM_HIP(hipMemcpyAsync(&hm, p.meas.p, sizeof(hm), hipMemcpyDeviceToHost, s));
-  MADIPM_HIP(hipStreamSynchronize(s));
-  // ---- outputs: the polished point, or get_solution's bits
-  const bool any5 = out[0] || out[1] || out[2] || out[3] || out[4];
-  const unsigned nbc = (unsigned)((m_ + NT / 64 - 1) / (NT / 64));
-  if (any5 && std::max(nx_, m_)) {
-    if (hm.verdict == MADIPM_POLISHED) {
-      if (out[4] && m_) k_cons<<<nbc, NT, 0, s>>>(Jrp_, Jci_, Jv_, p.w.p, cfix_, m_, nx_, p.ax.p);
-      k_pol_out<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, p.ax.p, out[0], out[1], out[2], out[3], out[4]);
-    } else {
-      if (out[4] && m_) k_cons<<<nbc, NT, 0, s>>>(Jrp_, Jci_, Jv_, x_, cfix_, m_, nx_, p.ax.p);
-      k_unscale<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(nx_, m_, obj_scale_, x_, y_, zl_, zu_, p.ax.p, cscale, out[0],
-                                                          out[1], out[2], out[3], out[4]);
-    }
-  }
-  if ((ovar || orow) && std::max(nx_, m_)) k_pol_codes<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, ovar, orow);
-  MADIPM_HIP(hipGetLastError());
-  if (device) {  // work enqueued on the caller's stream from now on sees the outputs
-    MADIPM_HIP(hipEventRecord(a.ev[1], s));
-    MADIPM_HIP(hipStreamWaitEvent(caller, a.ev[1], 0));
-  } else {
-    for (int j = 0; j < 5; ++j)
-      if (user[j] && olen[j])
-        MADIPM_HIP(hipMemcpyAsync(user[j], out[j], olen[j] * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (po.active_var && nx_) MADIPM_HIP(hipMemcpyAsync(po.active_var, ovar, (size_t)nx_, hipMemcpyDeviceToHost, s));
-    if (po.active_row && m_) MADIPM_HIP(hipMemcpyAsync(po.active_row, orow, (size_t)m_, hipMemcpyDeviceToHost, s));
-    MADIPM_HIP(hipStreamSynchronize(s));
-  }
-  ++p.last.n_polishes;
-  p.last.verdict = hm.verdict;
-  p.last.n_active = hm.n_active;
-  p.last.residual = hm.residual;
-  p.last.min_multiplier = hm.min_multiplier;
-  p.last.min_gap = hm.min_gap;
-  if (info) *info = p.last;
-}
-
-void MPCSolver::polish_info(madipm_polish_info* info) const {
-  if (!info) return;
-  *info = pol_ ? pol_->last : madipm_polish_info{-1, 0, 0.0, 0.0, 0.0, 0, 0};
 }
 
 }  // namespace madipm

@@ -41,13 +41,14 @@ struct DevState {
 };
 
 struct QPHost;       // host copy of the problem (qp_model.hpp)
-struct UpdatePlan;   // index plans of the value refresh, built by prepare_update (mpc.hip)
+struct DV;           // the kernels' view of the device vectors (mpc_kernels.hpp)
+struct UpdatePlan;   // index plans of the value refresh, built by prepare_update (mpc_kernels.hpp)
 struct DevUpdate;    // staging, start vectors and sum-order lists of the device route (mpc.hip)
 struct WarmStart;    // the warm point and its scratch, on the device (mpc.hip)
-struct Adjoint;      // index copies, fixed-variable lists and scratch of the adjoint gradients (mpc.hip)
-struct AdjArgs;      // the adjoint kernels' view of the point and the solution (mpc.hip)
-struct Tangent;      // entry lists and scratch of the forward-mode sensitivities (mpc.hip)
-struct Polish;       // scratch, set codes and counters of the active-set polish (mpc.hip)
+struct PostSolve;    // everything adjoint, tangent and polish keep between calls (mpc_post.hip)
+struct PostSolveDelete {
+  void operator()(PostSolve* p) const;
+};
 
 class MPCSolver {
  public:
@@ -120,11 +121,20 @@ class MPCSolver {
   void warm_blend();
   void refresh_host_mirrors();
   const double* device_con_scale();
-  // shared by adjoint() and tangent(): the refusals, the scratch, the factor of the point, the refined solve
+  DV view() const;
+  // k_cons of a scaled point; k_cons (cons given) + k_unscale of the iterate: get_solution's values on the device
+  void cons_rows(const double* xs, double* ax);
+  void unscale_point(const double* cscale, double* ax, double* x, double* y, double* zl, double* zu, double* cons);
+  // shared by the post-solve calls (mpc_post.hip): the refusals, the state, the regularised factorisation
+  // trials (enqueue(dw, dc) writes the diagonal and enqueues one factorisation), the adjoint's and tangent's
+  // factor of the point and their refined solve
+  friend struct PostSolve;
   void sens_refuse(const std::string& who) const;
-  Adjoint& sens_state();
-  void sens_factor(Adjoint& a, const std::string& who);
-  void sens_solve(Adjoint& a, const AdjArgs& A, double* resid);
+  PostSolve& post_state();
+  template <class Enqueue>
+  bool factor_trials(Enqueue&& enqueue);
+  void sens_factor(const std::string& who);
+  void sens_solve(double* resid);
   std::unique_ptr<LinSolver> make_linsolver(int n, const int64_t* cp, const int32_t* ri, const SymbolicOptions& so);
   void initialize();
   void init_starting_point();
@@ -211,13 +221,11 @@ class MPCSolver {
   bool cscale_host_stale_ = false;     // QPHost::con_scale is older than the plan's device con_scale
   bool cscale_dev_ok_ = false;         // the plan's device con_scale has been written by an update
   DBuf<double> sol_ax_, sol_cs_;       // get_solution_device: constraint values; con_scale when no update wrote it
-  hipEvent_t sol_ev_[2] = {nullptr, nullptr};
+  StreamHandoff sol_sync_;
   std::unique_ptr<WarmStart> warm_;     // null until a warm point is set
   int64_t n_warm_inits_ = 0;           // initialize() calls that blended
   bool solved_ = false;                // a solve has run (warm_start_last needs its point)
-  std::unique_ptr<Adjoint> adj_;       // null until the first adjoint or tangent
-  std::unique_ptr<Tangent> tan_;       // null until the first tangent
-  std::unique_ptr<Polish> pol_;        // null until the first polish
+  std::unique_ptr<PostSolve, PostSolveDelete> post_;  // null until the first adjoint, tangent or polish
   bool point_ok_ = false;              // the iterate is the end point of a completed solve
   int64_t n_solves_ = 0;               // completed solves (the adjoint's factor belongs to one of them)
   int64_t solve_updates_ = 0;          // n_updates_ at the end of the last solve

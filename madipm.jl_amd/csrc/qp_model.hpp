@@ -3,8 +3,9 @@
 // Everything the solver derives on the host from the caller's QP before a byte is uploaded: the copy of
 // the problem and its index sets, the value-dependent vectors (numeric_host), the H / J / J^T CSR arrays,
 // the K2 and normal-equations patterns, the refresh plan of prepare_update, the sum-order lists of the
-// device route, the fixed-variable lists of the adjoint and the entry lists of the tangent.  mpc.hip builds
-// these, uploads them and synchronises; tools/model_check.cpp builds and checks them on a machine without a GPU.
+// device route, the fixed-variable lists of the adjoint and the entry lists of the tangent.  mpc.hip and
+// mpc_post.hip build these, upload them and synchronise; tools/model_check.cpp builds and checks them on a
+// machine without a GPU.
 #pragma once
 
 #include <cstdint>
@@ -17,7 +18,7 @@ namespace madipm {
 
 struct PhaseClock;  // common.hpp (MADIPM_SYMBOLIC_TIMING); the builders take one or null
 
-struct I2 {  // the device code's int2 (mpc.hip asserts the layout)
+struct I2 {  // the device code's int2 (mpc_kernels.hpp asserts the layout)
   int32_t x, y;
 };
 

@@ -550,6 +550,26 @@ def load_options(**kw) -> Options:
     return o
 
 
+def _is_code(name: str) -> bool:
+    return name.startswith("active")   # the polish's set: int8 codes; every other block is float64
+
+
+def _host_outputs(struct, size: dict, names) -> dict:
+    """Host route of adjoint / tangent / polish: one numpy buffer per wanted output (an empty output still has
+    a non-null address), its address in the C struct's field of the same name."""
+    buf = {k: np.empty(max(size[k], 1), np.int8 if _is_code(k) else np.float64) for k in names}
+    for k in names:
+        setattr(struct, k, L.ptr(buf[k], C.c_int8 if _is_code(k) else C.c_double))
+    return buf
+
+
+def _host_inputs(given: dict) -> dict:
+    """Addresses of the given host blocks.  An empty block (ncon = 0, nnzh = 0) has nothing to read: any
+    non-null address says "given"."""
+    return {k: L.ptr(a if a.size else np.zeros(1, a.dtype), C.c_int8 if a.dtype == np.int8 else C.c_double)
+            for k, a in given.items()}
+
+
 class MPCSolver:
     """`MPCSolver(nlp; kwargs...)` (src/structure.jl:79-178) on the GPU."""
 
@@ -859,6 +879,30 @@ class MPCSolver:
         L.check(L.lib.madipm_solver_warm_info(self.h, C.byref(a), C.byref(w), C.byref(k)), "warm_info")
         return {"active": bool(a.value), "weight": float(w.value), "n_warm_inits": int(k.value)}
 
+    # ------------------------------------------------------------ what the post-solve device calls share
+    def _device_call(self, who, stream, recheck, struct, size, names, given):
+        """`stream` validated; the device resolved (a solver that had none yet: recheck() repeats the argument
+        check against it); on the stream, one tensor per wanted output (an empty output still has a non-null
+        address), its address in the C struct's field of the same name, and every given block kept alive, an
+        empty one as one element.  Returns the stream, the outputs, the given blocks' addresses and the blocks
+        themselves, which the caller holds until the library call has returned."""
+        import torch
+        if stream is not None and not isinstance(stream, torch.cuda.Stream):
+            raise TypeError(f"{who}: stream must be a torch.cuda.Stream, not {type(stream).__name__}")
+        if self._device is None:
+            self._device = torch.device("cuda", torch.cuda.current_device())
+            recheck()
+        st = stream if stream is not None else torch.cuda.current_stream(self._device)
+        with torch.cuda.stream(st):
+            buf = {k: torch.empty(max(size[k], 1), dtype=torch.int8 if _is_code(k) else torch.float64,
+                                  device=self._device) for k in names}
+            keep = {k: a if a.numel() else torch.zeros(1, dtype=a.dtype, device=self._device)
+                    for k, a in given.items()}
+        for k in names:
+            setattr(struct, k, C.cast(buf[k].data_ptr(), L.i8p if _is_code(k) else L.f64p))
+        p = {k: C.cast(a.data_ptr(), L.i8p if a.dtype == torch.int8 else L.f64p) for k, a in keep.items()}
+        return st, buf, p, keep
+
     # ------------------------------------------------------------ adjoint gradients (DESIGN §13c)
     def _adjoint_sizes(self) -> dict:
         qp = self.qp
@@ -889,13 +933,10 @@ class MPCSolver:
         names = check_adjoint_want(want)
         given = check_adjoint_cotangents(self.qp.nvar, self.qp.ncon, gx, gy, gzl, gzu, gcons)
         size = self._adjoint_sizes()
-        buf = {k: np.empty(max(size[k], 1)) for k in names}  # an empty output still has a non-null address
         g = L.QPGrad()
-        for k in names:
-            setattr(g, k, L.ptr(buf[k], C.c_double))
+        buf = _host_outputs(g, size, names)
         self._adjoint_prepare(names)
-        # an empty block (ncon = 0) has nothing to read: any non-null address says "given"
-        p = {k: L.ptr(a if a.size else np.zeros(1), C.c_double) for k, a in given.items()}
+        p = _host_inputs(given)
         if list(given) == ["x"]:
             L.check(L.lib.madipm_solver_adjoint(self.h, p["x"], C.byref(g)), "adjoint")
         else:
@@ -913,24 +954,13 @@ class MPCSolver:
         nvar, ncon = self.qp.nvar, self.qp.ncon
         given = check_adjoint_cotangents(nvar, ncon, gx, gy, gzl, gzu, gcons, on_device=True, device=self._device,
                                          who="adjoint_device")
-        import torch
-        if stream is not None and not isinstance(stream, torch.cuda.Stream):
-            raise TypeError(f"adjoint_device: stream must be a torch.cuda.Stream, not {type(stream).__name__}")
-        if self._device is None:
-            self._device = torch.device("cuda", torch.cuda.current_device())
-            check_adjoint_cotangents(nvar, ncon, gx, gy, gzl, gzu, gcons, on_device=True, device=self._device,
-                                     who="adjoint_device")
-        st = stream if stream is not None else torch.cuda.current_stream(self._device)
         size = self._adjoint_sizes()
-        with torch.cuda.stream(st):
-            buf = {k: torch.empty(max(size[k], 1), dtype=torch.float64, device=self._device) for k in names}
-            keep = {k: a if a.numel() else torch.zeros(1, dtype=torch.float64, device=self._device)
-                    for k, a in given.items()}
         g = L.QPGrad()
-        for k in names:
-            setattr(g, k, C.cast(buf[k].data_ptr(), L.f64p))
+        st, buf, p, _alive = self._device_call(
+            "adjoint_device", stream, lambda: check_adjoint_cotangents(
+                nvar, ncon, gx, gy, gzl, gzu, gcons, on_device=True, device=self._device, who="adjoint_device"),
+            g, size, names, given)
         self._adjoint_prepare(names)
-        p = {k: C.cast(a.data_ptr(), L.f64p) for k, a in keep.items()}
         if list(given) == ["x"]:
             L.check(L.lib.madipm_solver_adjoint_device(self.h, p["x"], C.byref(g), L.vp(st.cuda_stream)),
                     "adjoint_device")
@@ -964,13 +994,10 @@ class MPCSolver:
         given = check_tangent_directions(size, dict(c=c, Hvals=Hvals, Avals=Avals, lcon=lcon, ucon=ucon, lvar=lvar,
                                                     uvar=uvar))
         osize = self._tangent_sizes()
-        buf = {k: np.empty(max(osize[k], 1)) for k in names}  # an empty output still has a non-null address
         o = L.QPTan()
-        for k in names:
-            setattr(o, k, L.ptr(buf[k], C.c_double))
+        buf = _host_outputs(o, osize, names)
         self._adjoint_prepare(given)
-        # an empty block (nnzh = 0) has nothing to read: any non-null address says "given"
-        d = L.QPDir(**{k: L.ptr(a if a.size else np.zeros(1), C.c_double) for k, a in given.items()})
+        d = L.QPDir(**_host_inputs(given))
         L.check(L.lib.madipm_solver_tangent(self.h, C.byref(d), C.byref(o)), "tangent")
         return {k: buf[k][:osize[k]] for k in names}
 
@@ -989,23 +1016,14 @@ class MPCSolver:
         size = self._adjoint_sizes()
         dirs = dict(c=c, Hvals=Hvals, Avals=Avals, lcon=lcon, ucon=ucon, lvar=lvar, uvar=uvar)
         given = check_tangent_directions(size, dirs, on_device=True, device=self._device, who="tangent_device")
-        import torch
-        if stream is not None and not isinstance(stream, torch.cuda.Stream):
-            raise TypeError(f"tangent_device: stream must be a torch.cuda.Stream, not {type(stream).__name__}")
-        if self._device is None:
-            self._device = torch.device("cuda", torch.cuda.current_device())
-            check_tangent_directions(size, dirs, on_device=True, device=self._device, who="tangent_device")
-        st = stream if stream is not None else torch.cuda.current_stream(self._device)
         osize = self._tangent_sizes()
-        with torch.cuda.stream(st):
-            buf = {k: torch.empty(max(osize[k], 1), dtype=torch.float64, device=self._device) for k in names}
-            keep = {k: a if a.numel() else torch.zeros(1, dtype=torch.float64, device=self._device)
-                    for k, a in given.items()}
         o = L.QPTan()
-        for k in names:
-            setattr(o, k, C.cast(buf[k].data_ptr(), L.f64p))
+        st, buf, p, _alive = self._device_call(
+            "tangent_device", stream, lambda: check_tangent_directions(
+                size, dirs, on_device=True, device=self._device, who="tangent_device"),
+            o, osize, names, given)
         self._adjoint_prepare(given)
-        d = L.QPDir(**{k: C.cast(a.data_ptr(), L.f64p) for k, a in keep.items()})
+        d = L.QPDir(**p)
         L.check(L.lib.madipm_solver_tangent_device(self.h, C.byref(d), C.byref(o), L.vp(st.cuda_stream)),
                 "tangent_device")
         return {k: buf[k][:osize[k]] for k in names}
@@ -1038,15 +1056,13 @@ class MPCSolver:
         opts = check_polish_opts(sigma, tol_resid, tol_sign, tol_feas, refine_steps)
         size = self._polish_sizes()
         sets = check_polish_set(size["active_var"], size["active_row"], active_var, active_row)
-        buf = {k: np.empty(max(size[k], 1), np.int8 if k.startswith("active") else np.float64) for k in names}
         o = L.PolishOut()
-        for k in names:
-            setattr(o, k, L.ptr(buf[k], C.c_int8 if k.startswith("active") else C.c_double))
+        buf = _host_outputs(o, size, names)
         po = L.PolishOpts(*opts)
         info = L.PolishInfo()
-        # an empty block (ncon = 0) has nothing to read: any non-null address says "given"
-        p = [L.ptr(a if a.size else np.zeros(1, np.int8), C.c_int8) for a in sets] if sets else [None, None]
-        L.check(L.lib.madipm_solver_polish(self.h, C.byref(po), p[0], p[1], C.byref(o), C.byref(info)), "polish")
+        p = _host_inputs(dict(zip(("active_var", "active_row"), sets)))
+        L.check(L.lib.madipm_solver_polish(self.h, C.byref(po), p.get("active_var"), p.get("active_row"), C.byref(o),
+                                           C.byref(info)), "polish")
         res = {k: buf[k][:size[k]] for k in names}
         res["info"] = _polish_info_dict(info)
         return res
@@ -1063,26 +1079,15 @@ class MPCSolver:
         size = self._polish_sizes()
         sets = check_polish_set(size["active_var"], size["active_row"], active_var, active_row, on_device=True,
                                 device=self._device)
-        import torch
-        if stream is not None and not isinstance(stream, torch.cuda.Stream):
-            raise TypeError(f"polish_device: stream must be a torch.cuda.Stream, not {type(stream).__name__}")
-        if self._device is None:
-            self._device = torch.device("cuda", torch.cuda.current_device())
-            check_polish_set(size["active_var"], size["active_row"], active_var, active_row, on_device=True,
-                             device=self._device)
-        st = stream if stream is not None else torch.cuda.current_stream(self._device)
-        with torch.cuda.stream(st):
-            buf = {k: torch.empty(max(size[k], 1), dtype=torch.int8 if k.startswith("active") else torch.float64,
-                                  device=self._device) for k in names}
-            keep = [a if a.numel() else torch.zeros(1, dtype=torch.int8, device=self._device) for a in sets]
         o = L.PolishOut()
-        for k in names:
-            setattr(o, k, C.cast(buf[k].data_ptr(), L.i8p if k.startswith("active") else L.f64p))
+        st, buf, p, _alive = self._device_call(
+            "polish_device", stream, lambda: check_polish_set(
+                size["active_var"], size["active_row"], active_var, active_row, on_device=True, device=self._device),
+            o, size, names, dict(zip(("active_var", "active_row"), sets)))
         po = L.PolishOpts(*opts)
         info = L.PolishInfo()
-        p = [C.cast(a.data_ptr(), L.i8p) for a in keep] if keep else [None, None]
-        L.check(L.lib.madipm_solver_polish_device(self.h, C.byref(po), p[0], p[1], C.byref(o), C.byref(info),
-                                                  L.vp(st.cuda_stream)), "polish_device")
+        L.check(L.lib.madipm_solver_polish_device(self.h, C.byref(po), p.get("active_var"), p.get("active_row"),
+                                                  C.byref(o), C.byref(info), L.vp(st.cuda_stream)), "polish_device")
         res = {k: buf[k][:size[k]] for k in names}
         res["info"] = _polish_info_dict(info)
         return res

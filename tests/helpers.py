@@ -749,8 +749,9 @@ def signed_diagonal(n=20001, seed=7):
 # ---------------------------------------------------------------- MPC reduction regimes
 # (test_step_gpu.py, test_mpc_regimes_gpu.py; pinned on the sources and the oracle in
 # test_regime_helpers_cpu.py)
-# The launch constants of csrc/mpc.hip and csrc/mpc.hpp that decide which path a reduction takes: the
-# regime tests derive every boundary from these and test_regime_helpers_cpu.py fails when a source changes.
+# The launch constants of csrc/mpc_kernels.hpp (NT, MAXB), csrc/mpc.hip (FT1, FG, FT) and csrc/mpc.hpp (maxb_)
+# that decide which path a reduction takes: the regime tests derive every boundary from these and
+# test_regime_helpers_cpu.py fails when a source changes.
 MPC_CONSTANTS = {"NT": 256, "FT1": 1024, "MAXB": 2048, "FG": 16, "FT": 128, "maxb_": 2048}
 MPC_NT, MPC_FT1, MPC_MAXB = MPC_CONSTANTS["NT"], MPC_CONSTANTS["FT1"], MPC_CONSTANTS["maxb_"]
 

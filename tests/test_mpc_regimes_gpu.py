@@ -4,10 +4,10 @@ vectors in max-norm and objective, dual_objective, inf_pr, inf_du, inf_compl, mu
 same max_iter = k with FixedRegularization(1e-4, -1e-4), within max(1e-9, 30 s), s the oracle's own
 SuperLU-vs-LDL^T spread, <= 3e-9 required) on the sized separable family helpers.regime_problem.
 
-Every scalar the loop steers by is a multi-block reduction of csrc/mpc.hip: producers write one partial per
-block, k_final combines them.  Up to FT1 = 1024 partial blocks one workgroup combines them; past that, FG
-workgroups, level-2 partials and a ticket.  Producers launch at most MAXB = 2048 blocks and stride past
-that.  The constants are helpers.MPC_CONSTANTS, pinned on the sources by test_regime_helpers_cpu.py, which
+Every scalar the loop steers by is a multi-block reduction of csrc/mpc.hip (block_partials is in
+csrc/mpc_kernels.hpp): producers write one partial per block, k_final combines them.  Up to FT1 = 1024
+partial blocks one workgroup combines them; past that, FG workgroups, level-2 partials and a ticket.
+Producers launch at most MAXB = 2048 blocks and stride past that.  The constants are helpers.MPC_CONSTANTS, pinned on the sources by test_regime_helpers_cpu.py, which
 also pins the family's row counts, its planted extremes and every case's oracle spread on the CPU.  Every
 test first asserts (assert_regime) that its launches lie on the side of 1024 and 2048 it is named for.
 

@@ -1,7 +1,7 @@
 """What the reduction-regime GPU tests (test_step_gpu.py::test_step_regimes and companions,
 test_mpc_regimes_gpu.py) rest on, pinned without a GPU:
 
-  * the launch constants of csrc/mpc.hip and csrc/mpc.hpp are helpers.MPC_CONSTANTS, from which those tests
+  * the launch constants of csrc/mpc_kernels.hpp, csrc/mpc.hip and csrc/mpc.hpp are helpers.MPC_CONSTANTS, from which those tests
     derive every boundary: a changed source fails here by name;
   * every size of the tables reaches the regime it is listed for (blocks, finaliser path, stride);
   * regime_problem has n_ + m_ = 3 m + n_ineq rows on the oracle, and its planted row and coordinate are
@@ -34,12 +34,17 @@ WHO = ("the reduction-regime tests (tests/test_step_gpu.py::test_step_regimes, t
 
 
 def test_source_constants():
-    hip = open(os.path.join(CSRC, "mpc.hip")).read()
-    hpp = open(os.path.join(CSRC, "mpc.hpp")).read()
-    for name in ("NT", "FT1", "MAXB", "FG", "FT"):
-        found = re.findall(r"constexpr int (?:\w+ = \d+, )*%s = (\d+)" % name, hip)
-        assert found == [str(MPC_CONSTANTS[name])], f"csrc/mpc.hip: {name} = {found}, pinned {MPC_CONSTANTS[name]}; {WHO}"
-    found = re.findall(r"\bint maxb_ = (\d+);", hpp)
+    """Each launch constant is defined once, in the file named here: once among the MPC driver's sources
+    (csrc/mpc*.hip, csrc/mpc*.hpp) and, but for NT, once in all of csrc/*.hip and csrc/*.hpp (the LDL^T and
+    the KKT units have an NT of their own, ldl_plan.hpp and kkt.hip, which the MPC kernels never see)."""
+    home = {"NT": "mpc_kernels.hpp", "MAXB": "mpc_kernels.hpp", "FT1": "mpc.hip", "FG": "mpc.hip", "FT": "mpc.hip"}
+    src = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp"))}
+    for name, where in home.items():
+        found = {f: re.findall(r"constexpr int (?:\w+ = \d+, )*%s = (\d+)" % name, text) for f, text in src.items()}
+        found = {f: v for f, v in found.items() if v and (f.startswith("mpc") or name != "NT")}
+        assert found == {where: [str(MPC_CONSTANTS[name])]}, (
+            f"csrc: {name} = {found}, pinned {MPC_CONSTANTS[name]} in {where}; {WHO}")
+    found = re.findall(r"\bint maxb_ = (\d+);", src["mpc.hpp"])
     assert found == [str(MPC_CONSTANTS["maxb_"])], f"csrc/mpc.hpp: maxb_ = {found}; {WHO}"
     assert MPC_CONSTANTS["MAXB"] == MPC_CONSTANTS["FG"] * MPC_CONSTANTS["FT"] >= MPC_CONSTANTS["maxb_"]
 
