@@ -680,6 +680,37 @@ int madipm_solver_polish_device(madipm_solver_t s, const madipm_polish_opts* opt
 /* The last polish's info (zeros and verdict -1 before the first); no device access. */
 int madipm_solver_polish_info(madipm_solver_t s, madipm_polish_info* info);
 
+/* ------------------------------------------------------------------ sensitivities at the polished point  [ABI 0.2.11, additive]
+ * madipm_solver_tangent / _adjoint differentiate the central-path point.  These differentiate the point the last
+ * madipm_solver_polish left: the exact derivatives of the equality-constrained QP of the face its active set
+ * defines.  Structs, conventions (what is not read, where a fixed variable's and an equality
+ * row's derivative goes), routes and the stream contract are those of madipm_solver_tangent /
+ * madipm_solver_adjoint_full.  What differs: the tangent of an active variable IS the direction of its bound
+ * and dcons of an active row the direction of the row's bound (copies); dzl / dzu of an inactive, absent or
+ * fixed bound are exactly 0; the gradient of an inactive or absent bound is exactly 0; cons of an inequality
+ * row is the row's slack and of an equality row lcon itself.  (Five symbols, no struct; madipm_version()
+ * still returns 203; nothing above changed.)
+ * Both solve one system with the polish's operator and factor, 1 + refine_steps (the polish's) times; when an
+ * adjoint or tangent took the LDL^T since the polish, the polish's factor is rebuilt from the kept set and
+ * sigma (counted in n_factorizations), and a later adjoint / tangent factorises again.
+ * Refused as madipm_solver_tangent / _adjoint_full refuse, and: no polish has run on the point of the last
+ * solve; the last polish's verdict was not POLISHED (the message names it).
+ * Memory, allocated by the first call: 8 B x (3 n + 2 ncon) of its own (n = nvar + inequality rows), the
+ * tangent's data terms and entry lists or the adjoint's index lists as those calls allocate them; on the host
+ * route 8 B per entry of each block given or asked for. */
+int madipm_solver_tangent_polished(madipm_solver_t s, const madipm_qp_directions* d,
+                                   const madipm_qp_point_tangents* out);
+int madipm_solver_tangent_polished_device(madipm_solver_t s, const madipm_qp_directions* d_d,
+                                          const madipm_qp_point_tangents* d_out, madipm_stream_t stream);
+int madipm_solver_adjoint_polished(madipm_solver_t s, const madipm_qp_cotangents* g, const madipm_qp_gradients* out);
+int madipm_solver_adjoint_polished_device(madipm_solver_t s, const madipm_qp_cotangents* d_g,
+                                          const madipm_qp_gradients* d_out, madipm_stream_t stream);
+/* Successful polished tangent / adjoint calls; factorisations they ran to restore the polish's factor;
+ * last_residual: the max-norm of the last call's final masked residual, scaled space (0 before the first;
+ * synchronises the solver's stream).  Any pointer may be NULL. */
+int madipm_solver_polished_sens_info(madipm_solver_t s, int64_t* n_tangents, int64_t* n_adjoints,
+                                     int64_t* n_factorizations, double* last_residual);
+
 #ifdef __cplusplus
 }
 #endif

@@ -861,6 +861,58 @@ int madipm_solver_polish_info(madipm_solver_t s, madipm_polish_info* info) {
   MADIPM_API_END
 }
 
+int madipm_solver_tangent_polished(madipm_solver_t s, const madipm_qp_directions* d,
+                                   const madipm_qp_point_tangents* out) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(d, "madipm_solver_tangent_polished: null direction struct");
+  MADIPM_REQUIRE(out, "madipm_solver_tangent_polished: null output struct");
+  s->s->tangent_polished(*d, *out, false, nullptr);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_tangent_polished_device(madipm_solver_t s, const madipm_qp_directions* d_d,
+                                          const madipm_qp_point_tangents* d_out, madipm_stream_t stream) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(d_d, "madipm_solver_tangent_polished_device: null direction struct");
+  MADIPM_REQUIRE(d_out, "madipm_solver_tangent_polished_device: null output struct");
+  s->s->tangent_polished(*d_d, *d_out, true, (hipStream_t)stream);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_adjoint_polished(madipm_solver_t s, const madipm_qp_cotangents* g, const madipm_qp_gradients* out) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(g, "madipm_solver_adjoint_polished: null cotangent struct");
+  MADIPM_REQUIRE(out, "madipm_solver_adjoint_polished: null output struct");
+  s->s->adjoint_polished(*g, *out, false, nullptr);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_adjoint_polished_device(madipm_solver_t s, const madipm_qp_cotangents* d_g,
+                                          const madipm_qp_gradients* d_out, madipm_stream_t stream) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(d_g, "madipm_solver_adjoint_polished_device: null cotangent struct");
+  MADIPM_REQUIRE(d_out, "madipm_solver_adjoint_polished_device: null output struct");
+  s->s->adjoint_polished(*d_g, *d_out, true, (hipStream_t)stream);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_polished_sens_info(madipm_solver_t s, int64_t* n_tangents, int64_t* n_adjoints,
+                                     int64_t* n_factorizations, double* last_residual) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->polished_sens_info(n_tangents, n_adjoints, n_factorizations, last_residual);
+  return 0;
+  MADIPM_API_END
+}
+
 int madipm_update_step(int32_t rule, double tau, double mu, int32_t nlb, int32_t nub, const double* d_x_lr,
                        const double* d_xl_r, const double* d_zl_r, const double* d_dx_lr, const double* d_dzl,
                        const double* d_x_ur, const double* d_xu_r, const double* d_zu_r, const double* d_dx_ur,

@@ -110,6 +110,15 @@ class MPCSolver {
   void polish(const madipm_polish_opts& o, const int8_t* av, const int8_t* ar, const madipm_polish_out& out,
               madipm_polish_info* info, bool device, hipStream_t caller);
   void polish_info(madipm_polish_info* info) const;
+  // tangent() and adjoint() at the polished point (madipm_solver_tangent_polished / _adjoint_polished / _device /
+  // _polished_sens_info): the exact derivatives of the face the last polish() of this solved point
+  // ended POLISHED on.  They solve with the polish's factor (restored from the kept set when an adjoint or a
+  // tangent took the LDL^T since) and read the polish's scratch point; arguments and `caller` as there.
+  void tangent_polished(const madipm_qp_directions& d, const madipm_qp_point_tangents& out, bool device,
+                        hipStream_t caller);
+  void adjoint_polished(const madipm_qp_cotangents& g, const madipm_qp_gradients& out, bool device,
+                        hipStream_t caller);
+  void polished_sens_info(int64_t* n_tangents, int64_t* n_adjoints, int64_t* n_factorizations, double* last_residual);
   int64_t n_analyses() const { return n_analyses_; }
   int64_t n_updates() const { return n_updates_; }
   double last_update_s() const { return last_update_s_; }
@@ -135,6 +144,10 @@ class MPCSolver {
   bool factor_trials(Enqueue&& enqueue);
   void sens_factor(const std::string& who);
   void sens_solve(double* resid);
+  // the polished sensitivities': the refusals, the polish's factor, the masked solves
+  void polished_refuse(const std::string& who) const;
+  void polished_factor(const std::string& who);
+  void polished_solve();
   std::unique_ptr<LinSolver> make_linsolver(int n, const int64_t* cp, const int32_t* ri, const SymbolicOptions& so);
   void initialize();
   void init_starting_point();

@@ -98,18 +98,37 @@ struct Polish {
   int64_t bounds_updates = -1;            // n_updates_ of the bounds in lo / hi
   int64_t fact_solve = -1;                // n_solves_ of the point the LDL^T holds the polish factor of
   double fact_sigma = 0.0;
+  int64_t point_solve = -1;               // n_solves_ of the point w / codes / grad belong to (-1: none, or a polish threw)
+  int refine_steps = 0;                   // of that polish
   madipm_polish_info last{-1, 0, 0.0, 0.0, 0.0, 0, 0};
 };
 
-// What the three calls keep between them, created by the first of them; the tangent and the polish allocate
-// their own parts in their first call.
+// The sensitivities at the polished point (madipm_solver_tangent_polished* / _adjoint_polished*)
+// read the polish's scratch point, codes and factor and share the tangent's data terms and lists, the adjoint's
+// index lists and residual rows.  Their own, allocated by the first call: the solution u and the right-hand
+// side (8 B x 2 (n + m)), K0 u - rhs on the active coordinates (8 B x n), the residual scalar; the host route's
+// staging of the blocks given and wanted.
+struct PolSens {
+  DBuf<double> u, rhs, keep, scal;
+  Staged<double, 7> dir, grad;            // host route: c, Hvals, Avals, lcon, ucon, lvar, uvar
+  Staged<double, 5> out, ct;              // host route: x, y, zl, zu, cons
+  int64_t n_tangents = 0, n_adjoints = 0, n_fact = 0;
+};
+
+// What the calls keep between them, created by the first of them; the tangent, the polish and the polished
+// sensitivities allocate their own parts in their first call.
 struct AdjArgs;
 struct PostSolve {
   Adjoint adj;
   Tangent tan;
   Polish pol;
-  StreamHandoff sync;  // the device routes of all three
+  PolSens sens;
+  StreamHandoff sync;  // the device routes of all of them
   AdjArgs args(MPCSolver& S);
+  // the adjoint's COO indices and fixed-variable lists, the tangent's data terms and entry lists: each by the
+  // first call that needs it
+  void adjoint_lists(MPCSolver& S, bool needA, bool needH, bool needFix);
+  void tangent_scratch(MPCSolver& S, bool needLists);
   // row -> slack; the shift vector and a~'x: by the first call that needs them
   const int32_t* rowslack(const QPHost& P, hipStream_t s) {
     if (!adj.rowslack.p) {
@@ -277,7 +296,7 @@ __global__ __launch_bounds__(NT) void k_adj_acc(double* __restrict__ acc, const 
 }
 
 // out[0] = max_i rowres[i] / max(1, max_i |g_i|): one block, each thread a strided slice, then an LDS tree
-// (a maximum does not depend on the order; a NaN is kept)
+// (a maximum does not depend on the order; a NaN is kept).  g == null: the plain maximum.
 __global__ __launch_bounds__(NT) void k_adj_resmax(const double* __restrict__ rowres, const double* __restrict__ g,
                                                    int64_t N, double* __restrict__ out) {
   __shared__ double sw[NT], sg[NT];
@@ -285,7 +304,7 @@ __global__ __launch_bounds__(NT) void k_adj_resmax(const double* __restrict__ ro
   double w = 0.0, gm = 0.0;
   for (int64_t i = t; i < N; i += NT) {
     w = nmax(w, rowres[i]);
-    gm = nmax(gm, fabs(g[i]));
+    if (g) gm = nmax(gm, fabs(g[i]));
   }
   sw[t] = w;
   sg[t] = gm;
@@ -457,6 +476,57 @@ AdjArgs PostSolve::args(MPCSolver& S) {
                  S.zl_.p, S.zu_.p, S.y_.p,  S.device_con_scale(), S.lbpos_.p, S.ubpos_.p, S.fixed_.p};
 }
 
+void PostSolve::adjoint_lists(MPCSolver& S, bool needA, bool needH, bool needFix) {
+  Adjoint& a = adj;
+  QPHost& P = *S.H_;
+  hipStream_t s = S.stream_;
+  if (needA && !a.Ar.p) {
+    a.Ar.upload(S.plan_->Ar, s);
+    a.Ac.upload(S.plan_->Ac, s);
+  }
+  if (needH && !a.Hr.p) {
+    a.Hr.upload(P.Hr, s);
+    a.Hc.upload(P.Hc, s);
+  }
+  if (needFix && a.nfix < 0) {  // the fixed variables' entry lists, from the host COO copies
+    AdjointLists L = build_adjoint_lists(P);
+    L.fh.resize(std::max<size_t>(L.fh.size(), 1));  // the allocations are never empty
+    L.fa.resize(std::max<size_t>(L.fa.size(), 1));
+    a.fix.upload(L.fix, s);
+    a.fhsp.upload(L.fhsp, s);
+    a.fasp.upload(L.fasp, s);
+    a.fh.upload(as_int2(L.fh), L.fh.size(), s);
+    a.fa.upload(as_int2(L.fa), L.fa.size(), s);
+    MADIPM_HIP(hipStreamSynchronize(s));
+    a.nfix = (int)L.fix.size();
+  }
+}
+
+void PostSolve::tangent_scratch(MPCSolver& S, bool needLists) {
+  Tangent& t = tan;
+  hipStream_t s = S.stream_;
+  if (!t.base.p) {
+    t.base.alloc(std::max(S.n_ + S.m_, 1));
+    t.dx.alloc(std::max(S.n_, 1));
+    t.scal.alloc(1);
+    t.scal.zero(s);
+  }
+  if (needLists && !t.lists) {  // the entry lists, from the host COO copies
+    TangentLists L = build_tangent_lists(*S.H_);
+    L.ae.resize(std::max<size_t>(L.ae.size(), 1));  // the allocations are never empty
+    L.ce.resize(std::max<size_t>(L.ce.size(), 1));
+    L.ge.resize(std::max<size_t>(L.ge.size(), 1));
+    t.asp.upload(L.asp, s);
+    t.csp.upload(L.csp, s);
+    t.gsp.upload(L.gsp, s);
+    t.ae.upload(as_int2(L.ae), L.ae.size(), s);
+    t.ce.upload(as_int2(L.ce), L.ce.size(), s);
+    t.ge.upload(as_int2(L.ge), L.ge.size(), s);
+    MADIPM_HIP(hipStreamSynchronize(s));
+    t.lists = true;
+  }
+}
+
 // factorize_regularized_system!'s trials at the end point: the options' regularisation (Adaptive: the current
 // pair, not decayed), x 100 after each failure.  enqueue(dw, dc) writes the KKT diagonal and enqueues one
 // factorisation.  false: all three failed.
@@ -554,26 +624,7 @@ void MPCSolver::adjoint(const madipm_qp_cotangents& ct, const madipm_qp_gradient
   a.ct.bind(cot, clen, device, dct);
   if (full) ps.need_shift(n_ + m_, nx_);
   if (g.lcon || g.ucon) ps.rowslack(P, s);
-  if (needA && !a.Ar.p) {
-    a.Ar.upload(plan_->Ar, s);
-    a.Ac.upload(plan_->Ac, s);
-  }
-  if (needH && !a.Hr.p) {
-    a.Hr.upload(P.Hr, s);
-    a.Hc.upload(P.Hc, s);
-  }
-  if (needFix && a.nfix < 0) {  // the fixed variables' entry lists, from the host COO copies
-    AdjointLists L = build_adjoint_lists(P);
-    L.fh.resize(std::max<size_t>(L.fh.size(), 1));  // the allocations are never empty
-    L.fa.resize(std::max<size_t>(L.fa.size(), 1));
-    a.fix.upload(L.fix, s);
-    a.fhsp.upload(L.fhsp, s);
-    a.fasp.upload(L.fasp, s);
-    a.fh.upload(as_int2(L.fh), L.fh.size(), s);
-    a.fa.upload(as_int2(L.fa), L.fa.size(), s);
-    MADIPM_HIP(hipStreamSynchronize(s));
-    a.nfix = (int)L.fix.size();
-  }
+  ps.adjoint_lists(*this, needA, needH, needFix);
   const int64_t len[7] = {nx_, nh, na, m_, m_, nx_, nx_};
   double* out[7];
   a.out.bind(user, len, device, out);
@@ -830,29 +881,10 @@ void MPCSolver::tangent(const madipm_qp_directions& dr, const madipm_qp_point_ta
   PostSolve& ps = post_state();
   Adjoint& a = ps.adj;
   Tangent& t = ps.tan;
-  if (!t.base.p) {
-    t.base.alloc(std::max(n_ + m_, 1));
-    t.dx.alloc(std::max(n_, 1));
-    t.scal.alloc(1);
-    t.scal.zero(s);
-  }
   const AdjArgs A = ps.args(*this);
   ps.need_shift(n_ + m_, nx_);  // as the five-cotangent adjoint allocates them
   ps.rowslack(P, s);
-  if (needLists && !t.lists) {  // the entry lists, from the host COO copies
-    TangentLists L = build_tangent_lists(P);
-    L.ae.resize(std::max<size_t>(L.ae.size(), 1));  // the allocations are never empty
-    L.ce.resize(std::max<size_t>(L.ce.size(), 1));
-    L.ge.resize(std::max<size_t>(L.ge.size(), 1));
-    t.asp.upload(L.asp, s);
-    t.csp.upload(L.csp, s);
-    t.gsp.upload(L.gsp, s);
-    t.ae.upload(as_int2(L.ae), L.ae.size(), s);
-    t.ce.upload(as_int2(L.ce), L.ce.size(), s);
-    t.ge.upload(as_int2(L.ge), L.ge.size(), s);
-    MADIPM_HIP(hipStreamSynchronize(s));
-    t.lists = true;
-  }
+  ps.tangent_scratch(*this, needLists);
   const int64_t dlen[7] = {nx_, nh, na, m_, m_, nx_, nx_};
   const int64_t olen[5] = {nx_, m_, nx_, nx_, m_};
   const double* ddir[7];
@@ -1212,6 +1244,7 @@ void MPCSolver::polish(const madipm_polish_opts& o, const int8_t* av, const int8
                   p.lo.p, p.hi.p, p.ineq.p, a.rowslack.p, p.codes.p, p.codes_fact.p, p.w.p, p.grad.p, p.flags.p};
   const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_), nbn = blocks(std::max(n_, 1));
   const int64_t N = (int64_t)n_ + m_;
+  p.point_solve = -1;  // w, codes and grad are overwritten from here on
   p.flags.zero(s);
   k_pol_classify<<<blocks(std::max(std::max(n_, m_), 1)), NT, 0, s>>>(A, dset[0], dset[1], take_fact_end());
   MADIPM_HIP(hipGetLastError());
@@ -1270,6 +1303,8 @@ void MPCSolver::polish(const madipm_polish_opts& o, const int8_t* av, const int8
     p.out.download(user, olen, s, false);
     p.set_out.download(uset, slen, s);
   }
+  p.point_solve = n_solves_;
+  p.refine_steps = o.refine_steps;
   ++p.last.n_polishes;
   p.last.verdict = hm.verdict;
   p.last.n_active = hm.n_active;
@@ -1282,6 +1317,426 @@ void MPCSolver::polish(const madipm_polish_opts& o, const int8_t* av, const int8
 void MPCSolver::polish_info(madipm_polish_info* info) const {
   if (!info) return;
   *info = post_ ? post_->pol.last : madipm_polish_info{-1, 0, 0.0, 0.0, 0.0, 0, 0};
+}
+
+}  // namespace madipm
+
+// ======================================================================= sensitivities at the polished point
+// madipm_solver_tangent_polished / _adjoint_polished (and _device): the derivatives of the face's
+// equality-constrained QP at the point the last polish() left in its scratch.  With K0 the K2 operator without
+// Sigma and without regularisation (H~, J~^T on a primal row, J~ on a dual row), A the active coordinates of
+// [x; s] and N the others, both calls solve one masked system
+//     (K0 u)_i = rhs_i on N and on the rows,   u_A given,
+// in delta form, exactly as the polish solves its own: r = rhs - K0 u with the rows of A and of the fixed
+// variables written 0, a solve with the polish's factor (a preconditioner), the correction masked on A,
+// 1 + refine_steps times; the last residual keeps K0 u - rhs on A.
+//   tangent: u_A = the direction of the active bound (x cs on a slack), rhs = the data terms (k_tan_data at the
+//     polished point); dw = u, and K0 u - rhs on A is the tangent of t = grad of the Lagrangian, so of zl / zu.
+//   adjoint: u_A = -taubar~ (taubar = gzl on a lower-active variable, -gzu on an upper-active one), rhs = the
+//     cotangents' image ghat~ on [x; s; y]; then u = a~ - taubar~ is -e of the derivation, the place §13c's a~
+//     has in the gradient kernels, and rhs - K0 u on A is beta, the gradient of the active bound.
+// No product with Sigma occurs.  One thread (the residual, dcons: one lane group) per output, fixed summation
+// orders, no atomics: the same bits run to run.
+namespace madipm {
+namespace {
+
+// u and rhs of the tangent; base: k_tan_data's terms at the polished point (0 on fixed variables and slacks)
+__global__ __launch_bounds__(NT) void k_pst_rhs(AdjArgs A, TanDir T, const int8_t* __restrict__ codes,
+                                                const int32_t* __restrict__ ineq, const int32_t* __restrict__ rowslack,
+                                                const double* __restrict__ base, double* __restrict__ u,
+                                                double* __restrict__ rhs, LDLStatus* t1) {
+#pragma clang fp contract(off)
+  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  GRID_LOOP(i, A.n + A.m) {
+    double ui = 0.0, ri;
+    if (i < A.n) {
+      const int c = codes[i];
+      if (c != 0) {
+        if (i < A.nx) {
+          const double* b = c < 0 ? T.lvar : T.uvar;
+          ui = b ? b[i] : 0.0;
+        } else {
+          const int r = ineq[i - A.nx];
+          const double* b = c < 0 ? T.lcon : T.ucon;
+          ui = b ? A.cscale[r] * b[r] : 0.0;
+        }
+      }
+      ri = base[i];
+    } else {
+      const int r = (int)(i - A.n);
+      const double db = (T.lcon && rowslack[r] < 0) ? T.lcon[r] : 0.0;
+      ri = A.cscale[r] * (db - base[i]);
+    }
+    u[i] = ui;
+    rhs[i] = ri;
+  }
+}
+
+// u and rhs of the adjoint (any cotangent may be null: 0): gx on a free variable, gcons_r / cs_r on the slack
+// of row r (cons_r = s_r on the face), cs_r gy_r / os on row r; -taubar / os on an active variable
+__global__ __launch_bounds__(NT) void k_psa_rhs(AdjArgs A, const double* __restrict__ gx, const double* __restrict__ gy,
+                                                const double* __restrict__ gzl, const double* __restrict__ gzu,
+                                                const double* __restrict__ gcons, const int8_t* __restrict__ codes,
+                                                const int32_t* __restrict__ ineq, double* __restrict__ u,
+                                                double* __restrict__ rhs, LDLStatus* t1) {
+#pragma clang fp contract(off)
+  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  GRID_LOOP(i, A.n + A.m) {
+    double ui = 0.0, ri = 0.0;
+    if (i < A.nx) {
+      if (!A.fixed[i]) {
+        const int c = codes[i];
+        if (c < 0 && gzl) ui = -(gzl[i] / A.os);
+        if (c > 0 && gzu) ui = gzu[i] / A.os;
+        if (gx) ri = gx[i];
+      }
+    } else if (i < A.n) {
+      const int r = ineq[i - A.nx];
+      if (gcons) ri = gcons[r] / A.cscale[r];
+    } else if (gy) {
+      const int r = (int)(i - A.n);
+      ri = A.cscale[r] * gy[r] / A.os;
+    }
+    u[i] = ui;
+    rhs[i] = ri;
+  }
+}
+
+// r = rhs - K0 u and |r| of every row, k_pol_resid's access pattern on an arbitrary u: the rows of active and
+// fixed coordinates write 0.  r (may be null) becomes the right-hand side of the next solve; keep (may be null)
+// gets K0 u - rhs on the active coordinates and 0 on the others.  t1 as in k_pol_resid.
+template <int G>
+__global__ __launch_bounds__(NT) void k_ps_resid(DV D, const int8_t* __restrict__ codes, const double* __restrict__ u,
+                                                 const double* __restrict__ rhs, double* __restrict__ r,
+                                                 double* __restrict__ rowres, double* __restrict__ keep,
+                                                 LDLStatus* t1) {
+#pragma clang fp contract(off)
+  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  const int n = D.n, m = D.m;
+  const bool lead = (threadIdx.x & (G - 1)) == 0;
+  GROUP_LOOP(i, n + m, G) {
+    double ku;
+    bool act = false, masked = false;
+    if (i < n) {
+      double hv, jy;
+      gdot2<G>(D.H, i, u, D.JT, i, u + n, hv, jy);
+      ku = hv + jy;
+      act = codes[i] != 0;
+      masked = act || D.fixed[i];
+    } else {
+      ku = gdot<G>(D.J, i - n, u);
+    }
+    if (lead) {
+      const double ri = masked ? 0.0 : rhs[i] - ku;
+      if (r) r[i] = ri;
+      rowres[i] = fabs(ri);
+      if (keep && i < n) keep[i] = act ? ku - rhs[i] : 0.0;
+    }
+  }
+}
+
+// Un-scale the tangent (A.d is u; any output may be null): dx = the bound's direction on an active variable,
+// dlvar on a fixed one (copies), u elsewhere (also into dxs, zeros on the slacks, for k_pst_cons);
+// dy = con_scale dy~ / obj_scale; dzl = keep / obj_scale on a lower-active variable, dzu = -keep / obj_scale
+// on an upper-active one, the constant 0 everywhere else.
+__global__ __launch_bounds__(NT) void k_pst_out(AdjArgs A, TanDir T, const int8_t* __restrict__ codes,
+                                                const double* __restrict__ keep, double* __restrict__ dxs,
+                                                double* __restrict__ ox, double* __restrict__ oy,
+                                                double* __restrict__ ozl, double* __restrict__ ozu) {
+#pragma clang fp contract(off)
+  const int ns = A.n - A.nx;
+  const int top = A.nx > A.m ? A.nx : A.m;
+  GRID_LOOP(i, (top > ns ? top : ns)) {
+    if (i < A.nx) {
+      const int c = A.fixed[i] ? -1 : codes[i];
+      double dx, dzl = 0.0, dzu = 0.0;
+      if (c != 0) {
+        const double* b = c < 0 ? T.lvar : T.uvar;
+        dx = b ? b[i] : 0.0;
+        if (!A.fixed[i]) {
+          const double dt = keep[i] / A.os;
+          if (c < 0) dzl = dt;
+          else dzu = -dt;
+        }
+      } else {
+        dx = A.d[i];
+      }
+      dxs[i] = dx;
+      if (ox) ox[i] = dx;
+      if (ozl) ozl[i] = dzl;
+      if (ozu) ozu[i] = dzu;
+    }
+    if (i < ns) dxs[A.nx + i] = 0.0;
+    if (i < A.m && oy) oy[i] = A.d[A.n + i] * A.cscale[i] / A.os;
+  }
+}
+
+// dcons_r: the bound's direction itself on an active row (a copy), else k_tan_cons' (A dx)_r + (dA x)_r
+template <int G>
+__global__ __launch_bounds__(NT) void k_pst_cons(DV D, AdjArgs A, TanDir T, const int8_t* __restrict__ codes,
+                                                 const int32_t* __restrict__ rowslack, const double* __restrict__ dxs,
+                                                 const double* __restrict__ base, double* __restrict__ ocons) {
+#pragma clang fp contract(off)
+  const bool lead = (threadIdx.x & (G - 1)) == 0;
+  GROUP_LOOP(r, D.m, G) {
+    const double s = gdot<G>(D.J, r, dxs);
+    if (lead) {
+      const int k = rowslack[r], c = k >= 0 ? codes[k] : 0;
+      if (c != 0) {
+        const double* b = c < 0 ? T.lcon : T.ucon;
+        ocons[r] = b ? b[r] : 0.0;
+      } else {
+        ocons[r] = s / A.cscale[r] + base[D.n + r];
+      }
+    }
+  }
+}
+
+// The vector gradients (A.d is u = a~ - taubar~; any output may be null).  Variable i: c_i = -sgn os u_i (0 on a
+// fixed one, whose lvar is k_adj_fix's and whose uvar is 0); the bound of an active variable gets beta_i =
+// -keep_i, every other bound the constant 0.  Row r: an equality row lcon_r = cs_r u_y,r + gcons_r (cons_r is
+// lcon_r there), ucon_r = 0; a row with slack k: cs_r beta_k on the active side, 0 elsewhere.
+__global__ __launch_bounds__(NT) void k_psa_vec(AdjArgs A, const int8_t* __restrict__ codes,
+                                                const double* __restrict__ keep, const int32_t* __restrict__ rowslack,
+                                                const double* __restrict__ gcons, double* __restrict__ gc,
+                                                double* __restrict__ glv, double* __restrict__ guv,
+                                                double* __restrict__ glc, double* __restrict__ guc) {
+#pragma clang fp contract(off)
+  GRID_LOOP(i, (A.nx > A.m ? A.nx : A.m)) {
+    if (i < A.nx) {
+      const bool fx = A.fixed[i];
+      const double at = fx ? 0.0 : A.d[i];
+      if (gc) gc[i] = -(A.sgn * (A.os * at));
+      if (!fx) {
+        const int c = codes[i];
+        const double b = c != 0 ? -keep[i] : 0.0;
+        if (glv) glv[i] = c < 0 ? b : 0.0;
+        if (guv) guv[i] = c > 0 ? b : 0.0;
+      } else if (guv) {
+        guv[i] = 0.0;
+      }
+    }
+    if (i < A.m && (glc || guc)) {
+      const int k = rowslack[i];
+      const double cs = A.cscale[i];
+      if (k < 0) {
+        const double ay = cs * A.d[A.n + i];
+        if (glc) glc[i] = gcons ? ay + gcons[i] : ay;
+        if (guc) guc[i] = 0.0;
+      } else {
+        const int c = codes[k];
+        const double b = c != 0 ? cs * -keep[k] : 0.0;
+        if (glc) glc[i] = c < 0 ? b : 0.0;
+        if (guc) guc[i] = c > 0 ? b : 0.0;
+      }
+    }
+  }
+}
+
+const char* polish_verdict_name(int v) {
+  switch (v) {
+    case MADIPM_POLISHED: return "POLISHED";
+    case MADIPM_POLISH_WRONG_SET: return "WRONG_SET";
+    case MADIPM_POLISH_NO_CONVERGENCE: return "NO_CONVERGENCE";
+    case MADIPM_POLISH_FACTORIZATION_FAILED: return "FACTORIZATION_FAILED";
+  }
+  return "unknown";
+}
+
+}  // namespace
+
+// sens_refuse's refusals, then: the last polish belongs to this solved point and ended POLISHED
+void MPCSolver::polished_refuse(const std::string& who) const {
+  sens_refuse(who);
+  MADIPM_REQUIRE(post_ && post_->pol.point_solve == n_solves_,
+                 who + "no polish has run on the point of the last solve (madipm_solver_polish first)");
+  const int v = post_->pol.last.verdict;
+  MADIPM_REQUIRE(v == MADIPM_POLISHED, who + "the last polish ended with verdict " + polish_verdict_name(v) +
+                                           ", not POLISHED: the face has no polished point to differentiate");
+}
+
+// The polish's factor back into the LDL^T when an adjoint / tangent overwrote it: the kept codes and sigma
+void MPCSolver::polished_factor(const std::string& who) {
+  Polish& p = post_->pol;
+  if (p.fact_solve == n_solves_) return;
+  p.fact_solve = -1;
+  post_->adj.fact_solve = -1;  // the adjoint's factor and KKT diagonal are overwritten
+  const DV D = view();
+  const int nb = blocks(n_ + m_);
+  if (!factor_trials([&](double dw, double dc) {
+        k_pol_diag<<<nb, NT, 0, stream_>>>(D, p.codes.p, dw, dc, p.fact_sigma, fact_reset());
+        timed_factorize();
+      }))
+    throw Error(who + "the factorisation of the polish's KKT system failed in all three trials", -4);
+  if (n_) MADIPM_HIP(hipMemcpyAsync(p.codes_fact.p, p.codes.p, (size_t)n_, hipMemcpyDeviceToDevice, stream_));
+  p.fact_solve = n_solves_;
+  ++post_->sens.n_fact;
+}
+
+// With sens.u and sens.rhs set: the masked solves in delta form, K0 u - rhs on the active coordinates into
+// sens.keep, the max-norm of the final masked residual into sens.scal
+void MPCSolver::polished_solve() {
+  PostSolve& ps = *post_;
+  Polish& p = ps.pol;
+  PolSens& q = ps.sens;
+  const DV D = view();
+  hipStream_t s = stream_;
+  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
+  PolArgs M{};  // k_pol_acc's masking on u: it reads the sizes, the codes, the fixed flags and w
+  M.n = n_, M.m = m_, M.nx = nx_, M.fixed = fixed_.p, M.codes = p.codes.p, M.w = q.u.p;
+  const int8_t* codes = p.codes.p;
+  for (int it = 0; it <= p.refine_steps; ++it) {
+    SPMV_LAUNCH(k_ps_resid, nbs, s, D, codes, (const double*)q.u.p, (const double*)q.rhs.p, d_.p, ps.adj.rowres.p,
+                (double*)nullptr, take_fact_end());
+    kkt_solve();
+    k_pol_acc<<<nb, NT, 0, s>>>(M, d_.p);
+  }
+  SPMV_LAUNCH(k_ps_resid, nbs, s, D, codes, (const double*)q.u.p, (const double*)q.rhs.p, (double*)nullptr,
+              ps.adj.rowres.p, q.keep.p, take_fact_end());
+  k_adj_resmax<<<1, NT, 0, s>>>(ps.adj.rowres.p, (const double*)nullptr, (int64_t)n_ + m_, q.scal.p);
+}
+
+static void polished_scratch(PolSens& q, int n, int m, hipStream_t s) {
+  if (q.u.p) return;
+  q.u.alloc(std::max(n + m, 1));
+  q.rhs.alloc(std::max(n + m, 1));
+  q.keep.alloc(std::max(n, 1));
+  q.scal.alloc(1);
+  q.scal.zero(s);
+}
+
+void MPCSolver::tangent_polished(const madipm_qp_directions& dr, const madipm_qp_point_tangents& o, bool device,
+                                 hipStream_t caller) {
+  const std::string who = device ? "madipm_solver_tangent_polished_device: " : "madipm_solver_tangent_polished: ";
+  QPHost& P = *H_;
+  // ---- refusals, before anything is allocated or enqueued
+  polished_refuse(who);
+  const double* const dir[7] = {dr.c, dr.Hvals, dr.Avals, dr.lcon, dr.ucon, dr.lvar, dr.uvar};
+  double* const user[5] = {o.x, o.y, o.zl, o.zu, o.cons};
+  MADIPM_REQUIRE(dr.c || dr.Hvals || dr.Avals || dr.lcon || dr.ucon || dr.lvar || dr.uvar,
+                 who + "all seven directions are NULL");
+  MADIPM_REQUIRE(o.x || o.y || o.zl || o.zu || o.cons, who + "all five outputs are NULL");
+  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
+  const bool needLists = (dr.Avals && na > 0) || (dr.Hvals && nh > 0) || (dr.lvar && P.anyfix);
+  MADIPM_REQUIRE(plan_ || !needLists,
+                 who + "Avals, Hvals (and lvar on a problem with fixed variables) need "
+                       "madipm_solver_prepare_update first (it keeps the index arrays and the raw values)");
+  hipStream_t s = stream_;
+  // ---- allocations, each by the first call that needs it
+  PostSolve& ps = *post_;
+  Tangent& t = ps.tan;
+  Polish& p = ps.pol;
+  PolSens& q = ps.sens;
+  polished_scratch(q, n_, m_, s);
+  ps.tangent_scratch(*this, needLists);
+  AdjArgs A = ps.args(*this);  // the polished point in the iterate's place, u in a~'s
+  A.d = q.u.p, A.x = p.w.p, A.y = p.w.p + n_;
+  const int64_t dlen[7] = {nx_, nh, na, m_, m_, nx_, nx_};
+  const int64_t olen[5] = {nx_, m_, nx_, nx_, m_};
+  const double* ddir[7];
+  double* out[5];
+  q.dir.bind(dir, dlen, device, ddir);
+  q.out.bind(user, olen, device, out);
+  // ---- the polish's factor, if an adjoint / tangent took the LDL^T since
+  const DV D = view();
+  polished_factor(who);
+  if (device)
+    ps.sync.begin(caller, s);  // the directions are read after the work already enqueued on the caller's stream
+  else
+    q.dir.upload(dir, dlen, s);
+  // ---- right-hand side, solves, residual
+  const int nb = blocks(n_ + m_);
+  const TanDir T{ddir[0], ddir[1], ddir[2], ddir[3], ddir[4], ddir[5], ddir[6]};
+  const bool ls = needLists;
+  k_tan_data<<<nb, NT, 0, s>>>(A, T, ls ? t.gsp.p : nullptr, t.ge.p, t.csp.p, t.ce.p, ls ? t.asp.p : nullptr, t.ae.p,
+                               plan_ ? plan_->Hraw.p : nullptr, plan_ ? plan_->Araw.p : nullptr, t.base.p);
+  k_pst_rhs<<<nb, NT, 0, s>>>(A, T, (const int8_t*)p.codes.p, (const int32_t*)p.ineq.p,
+                              (const int32_t*)ps.adj.rowslack.p, (const double*)t.base.p, q.u.p, q.rhs.p,
+                              take_fact_end());
+  polished_solve();
+  // ---- outputs
+  k_pst_out<<<blocks(std::max(std::max(nx_, m_), std::max(n_ - nx_, 1))), NT, 0, s>>>(
+      A, T, (const int8_t*)p.codes.p, (const double*)q.keep.p, t.dx.p, out[0], out[1], out[2], out[3]);
+  if (out[4] && m_)
+    SPMV_LAUNCH(k_pst_cons, spmv_blocks(m_), s, D, A, T, (const int8_t*)p.codes.p, (const int32_t*)ps.adj.rowslack.p,
+                (const double*)t.dx.p, (const double*)t.base.p, out[4]);
+  MADIPM_HIP(hipGetLastError());
+  if (device)
+    ps.sync.end(s, caller);  // work enqueued on the caller's stream from now on sees the outputs
+  else
+    q.out.download(user, olen, s);
+  ++q.n_tangents;
+}
+
+void MPCSolver::adjoint_polished(const madipm_qp_cotangents& ct, const madipm_qp_gradients& g, bool device,
+                                 hipStream_t caller) {
+  const std::string who = device ? "madipm_solver_adjoint_polished_device: " : "madipm_solver_adjoint_polished: ";
+  QPHost& P = *H_;
+  // ---- refusals, before anything is allocated or enqueued
+  polished_refuse(who);
+  MADIPM_REQUIRE(ct.x || ct.y || ct.zl || ct.zu || ct.cons, who + "all five cotangents are NULL");
+  double* const user[7] = {g.c, g.Hvals, g.Avals, g.lcon, g.ucon, g.lvar, g.uvar};
+  MADIPM_REQUIRE(g.c || g.Hvals || g.Avals || g.lcon || g.ucon || g.lvar || g.uvar,
+                 who + "all seven outputs are NULL");
+  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
+  const bool needA = g.Avals && na > 0, needH = g.Hvals && nh > 0, needFix = g.lvar && P.anyfix;
+  MADIPM_REQUIRE(plan_ || !(needA || needH || needFix),
+                 who + "Avals, Hvals (and lvar on a problem with fixed variables) need "
+                       "madipm_solver_prepare_update first (it keeps the index arrays and the raw values)");
+  hipStream_t s = stream_;
+  // ---- allocations, each by the first call that needs it
+  PostSolve& ps = *post_;
+  Adjoint& a = ps.adj;
+  Polish& p = ps.pol;
+  PolSens& q = ps.sens;
+  polished_scratch(q, n_, m_, s);
+  ps.adjoint_lists(*this, needA, needH, needFix);
+  AdjArgs A = ps.args(*this);  // the polished point in the iterate's place, u in a~'s
+  A.d = q.u.p, A.x = p.w.p, A.y = p.w.p + n_;
+  const double* const cot[5] = {ct.x, ct.y, ct.zl, ct.zu, ct.cons};
+  const int64_t clen[5] = {nx_, m_, nx_, nx_, m_};
+  const double* dct[5];  // gx, gy, gzl, gzu, gcons on the device
+  q.ct.bind(cot, clen, device, dct);
+  const int64_t len[7] = {nx_, nh, na, m_, m_, nx_, nx_};
+  double* out[7];
+  q.grad.bind(user, len, device, out);
+  // ---- the polish's factor, if an adjoint / tangent took the LDL^T since
+  polished_factor(who);
+  if (device)
+    ps.sync.begin(caller, s);  // the cotangents are read after the work already enqueued on the caller's stream
+  else
+    q.ct.upload(cot, clen, s);
+  // ---- right-hand side, solves, residual
+  k_psa_rhs<<<blocks(n_ + m_), NT, 0, s>>>(A, dct[0], dct[1], dct[2], dct[3], dct[4], (const int8_t*)p.codes.p,
+                                           (const int32_t*)p.ineq.p, q.u.p, q.rhs.p, take_fact_end());
+  polished_solve();
+  // ---- gradients: §13c's kernels with u in a~'s place and the polished point in the iterate's
+  const AdjFull F{nullptr, nullptr, nullptr, nullptr};
+  if ((out[0] || out[3] || out[4] || out[5] || out[6]) && std::max(nx_, m_))
+    k_psa_vec<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, (const int8_t*)p.codes.p, (const double*)q.keep.p,
+                                                       (const int32_t*)a.rowslack.p, dct[4], out[0], out[5], out[6],
+                                                       out[3], out[4]);
+  if (needFix && a.nfix > 0)  // <true> with no gcons: gx may be null, and cons reaches a fixed column through u_y
+    k_adj_fix<true><<<blocks(a.nfix), NT, 0, s>>>(A, F, a.nfix, a.fix.p, a.fhsp.p, a.fh.p, a.fasp.p, a.fa.p,
+                                                  plan_->Hraw.p, plan_->Araw.p, dct[0], out[5]);
+  if (needA) k_adj_avals<false><<<blocks(na), NT, 0, s>>>(A, F, na, a.Ar.p, a.Ac.p, out[2]);
+  if (needH) k_adj_hvals<<<blocks(nh), NT, 0, s>>>(A, nh, a.Hr.p, a.Hc.p, out[1]);
+  MADIPM_HIP(hipGetLastError());
+  if (device)
+    ps.sync.end(s, caller);  // work enqueued on the caller's stream from now on sees the outputs
+  else
+    q.grad.download(user, len, s);
+  ++q.n_adjoints;
+}
+
+void MPCSolver::polished_sens_info(int64_t* n_tangents, int64_t* n_adjoints, int64_t* n_factorizations,
+                                   double* last_residual) {
+  const PolSens* q = post_ ? &post_->sens : nullptr;
+  if (n_tangents) *n_tangents = q ? q->n_tangents : 0;
+  if (n_adjoints) *n_adjoints = q ? q->n_adjoints : 0;
+  if (n_factorizations) *n_factorizations = q ? q->n_fact : 0;
+  const int64_t calls = q ? q->n_tangents + q->n_adjoints : 0;
+  read_residual(last_residual, calls, calls ? q->scal.p : nullptr, stream_);
 }
 
 }  // namespace madipm

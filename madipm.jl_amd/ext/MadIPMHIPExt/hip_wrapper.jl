@@ -485,3 +485,82 @@ function solver_polish_info(h::Ptr{Cvoid})
           "madipm_solver_polish_info")
     return info[]
 end
+
+# ---- sensitivities at the polished point (ABI 0.2.11): the exact derivatives of the face the last solver_polish
+# of this solved point ended polished on (verdict 0; refused otherwise, and before any polish).  The tangent's
+# structs have the layouts of the adjoint's: madipm_qp_directions is seven pointers (c, Hvals, Avals, lcon, ucon,
+# lvar, uvar), madipm_qp_point_tangents five (x, y, zl, zu, cons); a null one = 0 / not wanted.  The tangent of
+# an active variable is its bound's direction, zl / zu of an inactive bound move by exactly 0, the gradient of
+# an inactive bound is exactly 0.
+const MadipmQPDirections = MadipmQPGradients
+const MadipmQPPointTangents = MadipmQPCotangents
+
+# HOST vectors (or nothing): directions dc ... duvar in, dx ... dcons out
+function solver_tangent_polished(h::Ptr{Cvoid}; dc=nothing, dHvals=nothing, dAvals=nothing, dlcon=nothing,
+                                 ducon=nothing, dlvar=nothing, duvar=nothing, x=nothing, y=nothing, zl=nothing,
+                                 zu=nothing, cons=nothing)
+    GC.@preserve dc dHvals dAvals dlcon ducon dlvar duvar x y zl zu cons begin
+        d = Ref(MadipmQPDirections(_ptr_or_null(dc), _ptr_or_null(dHvals), _ptr_or_null(dAvals), _ptr_or_null(dlcon),
+                                   _ptr_or_null(ducon), _ptr_or_null(dlvar), _ptr_or_null(duvar)))
+        o = Ref(MadipmQPPointTangents(_ptr_or_null(x), _ptr_or_null(y), _ptr_or_null(zl), _ptr_or_null(zu),
+                                      _ptr_or_null(cons)))
+        check(ccall((:madipm_solver_tangent_polished, libmadipm), Cint,
+                    (Ptr{Cvoid}, Ref{MadipmQPDirections}, Ref{MadipmQPPointTangents}), h, d, o),
+              "madipm_solver_tangent_polished")
+    end
+    return
+end
+
+# DEVICE arrays (Ptr{Float64} into device memory, or nothing), with solver_adjoint_device's stream contract
+function solver_tangent_polished_device(h::Ptr{Cvoid}; dc=nothing, dHvals=nothing, dAvals=nothing, dlcon=nothing,
+                                        ducon=nothing, dlvar=nothing, duvar=nothing, x=nothing, y=nothing,
+                                        zl=nothing, zu=nothing, cons=nothing, stream::Ptr{Cvoid}=C_NULL)
+    d = Ref(MadipmQPDirections(_dptr_or_null(dc), _dptr_or_null(dHvals), _dptr_or_null(dAvals), _dptr_or_null(dlcon),
+                               _dptr_or_null(ducon), _dptr_or_null(dlvar), _dptr_or_null(duvar)))
+    o = Ref(MadipmQPPointTangents(_dptr_or_null(x), _dptr_or_null(y), _dptr_or_null(zl), _dptr_or_null(zu),
+                                  _dptr_or_null(cons)))
+    check(ccall((:madipm_solver_tangent_polished_device, libmadipm), Cint,
+                (Ptr{Cvoid}, Ref{MadipmQPDirections}, Ref{MadipmQPPointTangents}, Ptr{Cvoid}), h, d, o, stream),
+          "madipm_solver_tangent_polished_device")
+    return
+end
+
+# HOST vectors (or nothing): the arguments of solver_adjoint_full
+function solver_adjoint_polished(h::Ptr{Cvoid}; gx=nothing, gy=nothing, gzl=nothing, gzu=nothing, gcons=nothing,
+                                 c=nothing, Hvals=nothing, Avals=nothing, lcon=nothing, ucon=nothing, lvar=nothing,
+                                 uvar=nothing)
+    GC.@preserve gx gy gzl gzu gcons c Hvals Avals lcon ucon lvar uvar begin
+        ct = Ref(MadipmQPCotangents(_ptr_or_null(gx), _ptr_or_null(gy), _ptr_or_null(gzl), _ptr_or_null(gzu),
+                                    _ptr_or_null(gcons)))
+        g = Ref(MadipmQPGradients(_ptr_or_null(c), _ptr_or_null(Hvals), _ptr_or_null(Avals), _ptr_or_null(lcon),
+                                  _ptr_or_null(ucon), _ptr_or_null(lvar), _ptr_or_null(uvar)))
+        check(ccall((:madipm_solver_adjoint_polished, libmadipm), Cint,
+                    (Ptr{Cvoid}, Ref{MadipmQPCotangents}, Ref{MadipmQPGradients}), h, ct, g),
+              "madipm_solver_adjoint_polished")
+    end
+    return
+end
+
+# DEVICE arrays (Ptr{Float64} into device memory, or nothing), with solver_adjoint_device's stream contract
+function solver_adjoint_polished_device(h::Ptr{Cvoid}; gx=nothing, gy=nothing, gzl=nothing, gzu=nothing,
+                                        gcons=nothing, c=nothing, Hvals=nothing, Avals=nothing, lcon=nothing,
+                                        ucon=nothing, lvar=nothing, uvar=nothing, stream::Ptr{Cvoid}=C_NULL)
+    ct = Ref(MadipmQPCotangents(_dptr_or_null(gx), _dptr_or_null(gy), _dptr_or_null(gzl), _dptr_or_null(gzu),
+                                _dptr_or_null(gcons)))
+    g = Ref(MadipmQPGradients(_dptr_or_null(c), _dptr_or_null(Hvals), _dptr_or_null(Avals), _dptr_or_null(lcon),
+                              _dptr_or_null(ucon), _dptr_or_null(lvar), _dptr_or_null(uvar)))
+    check(ccall((:madipm_solver_adjoint_polished_device, libmadipm), Cint,
+                (Ptr{Cvoid}, Ref{MadipmQPCotangents}, Ref{MadipmQPGradients}, Ptr{Cvoid}), h, ct, g, stream),
+          "madipm_solver_adjoint_polished_device")
+    return
+end
+
+# (n_tangents, n_adjoints, n_factorizations, last_residual): successful polished calls, the factorisations that
+# restored the polish's factor, the max-norm of the last call's final masked residual
+function solver_polished_sens_info(h::Ptr{Cvoid})
+    nt, na, nf, r = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Float64}(0.0)
+    check(ccall((:madipm_solver_polished_sens_info, libmadipm), Cint,
+                (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Float64}), h, nt, na, nf, r),
+          "madipm_solver_polished_sens_info")
+    return (n_tangents = nt[], n_adjoints = na[], n_factorizations = nf[], last_residual = r[])
+end

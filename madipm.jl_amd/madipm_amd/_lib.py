@@ -183,6 +183,13 @@ _sig("madipm_solver_polish_device", C.c_int, [vp, C.POINTER(PolishOpts), i8p, i8
                                               C.POINTER(PolishInfo), vp])
 _sig("madipm_solver_polish_info", C.c_int, [vp, C.POINTER(PolishInfo)])
 
+# sensitivities at the polished point (ABI 0.2.11): the tangent's and the adjoint's structs
+_sig("madipm_solver_tangent_polished", C.c_int, [vp, C.POINTER(QPDir), C.POINTER(QPTan)])
+_sig("madipm_solver_tangent_polished_device", C.c_int, [vp, C.POINTER(QPDir), C.POINTER(QPTan), vp])
+_sig("madipm_solver_adjoint_polished", C.c_int, [vp, C.POINTER(QPCot), C.POINTER(QPGrad)])
+_sig("madipm_solver_adjoint_polished_device", C.c_int, [vp, C.POINTER(QPCot), C.POINTER(QPGrad), vp])
+_sig("madipm_solver_polished_sens_info", C.c_int, [vp, i64p, i64p, i64p, f64p])
+
 
 class MadIPMError(RuntimeError):
     pass

@@ -11,13 +11,20 @@ Forward and backward stay on the device (MPCSolver.update_device / solution_devi
 gradients are those of MPCSolver.adjoint, K2 formulation.  Forward-mode autograd
 (torch.autograd.forward_ad) goes through MPCSolver.tangent_device; the torch.func transforms
 ask a Function for the setup_context form of forward, which QPFunction does not have.
+
+    layer = QPLayer(solver, outputs=("x", "zl"), polish=True)
+    x, zl = layer(c=c)               # ... -> solve -> polish_device: the exact point of the active face
+
+With polish=True forward returns the polished point and backward / jvp differentiate it exactly
+(adjoint_device / tangent_device with polished=True): what an active-set QP layer gives.
 `import torch` comes before this package in the process, as for every device-route call.
 """
 from __future__ import annotations
 
 import torch
 
-from .solver import ADJOINT_NAMES, SOLVE_SUCCEEDED, STATUS_NAMES, MadIPMError, check_layer_outputs
+from .solver import (ADJOINT_NAMES, SOLVE_SUCCEEDED, STATUS_NAMES, MadIPMError, PolishVerdict,
+                     check_layer_outputs)
 
 # output name -> (key of MPCSolver.solution_device(), cotangent keyword of MPCSolver.adjoint_device())
 _OUTPUTS = {"x": ("solution", "gx"), "y": ("multipliers", "gy"), "zl": ("multipliers_L", "gzl"),
@@ -32,11 +39,15 @@ class QPFunction(torch.autograd.Function):
     returns that tuple of tensors, and backward passes on the cotangents of those the loss used.
     jvp hands tangent_device the tangents of the data tensors that carry one and returns the tangents of the
     selected outputs; like backward it must run before the solver is updated or solved again,
-    which forward-mode autograd does by calling it right after forward."""
+    which forward-mode autograd does by calling it right after forward.
+    True as a tenth argument (the ninth may be None) polishes: forward returns polish_device's blocks and raises
+    MadIPMError unless the verdict is POLISHED, backward and jvp pass polished=True."""
 
     @staticmethod
     def forward(ctx, solver, *data):
-        outputs = None
+        outputs, polish = None, False
+        if len(data) > len(ADJOINT_NAMES) + 1:
+            polish = bool(data[len(ADJOINT_NAMES) + 1])
         if len(data) > len(ADJOINT_NAMES):
             data, outputs = data[:len(ADJOINT_NAMES)], data[len(ADJOINT_NAMES)]
         given = {k: t.detach() for k, t in zip(ADJOINT_NAMES, data) if t is not None}
@@ -49,6 +60,17 @@ class QPFunction(torch.autograd.Function):
         ctx.solver = solver
         ctx.names = ADJOINT_NAMES
         ctx.outputs = outputs
+        ctx.sens = {"polished": True} if polish else {}   # no keyword at all without the polish: today's calls
+        if polish:
+            pol = solver.polish_device(want=("x",) if outputs is None else outputs)
+            verdict = pol["info"]["verdict"]
+            if verdict != PolishVerdict.POLISHED:
+                raise MadIPMError(f"QPLayer: the polish ended with verdict {PolishVerdict(verdict).name}, not "
+                                  "POLISHED: the face has no unique derivative")
+            if outputs is None:
+                return pol["x"]
+            ctx.set_materialize_grads(False)
+            return tuple(pol[k] for k in outputs)
         if outputs is None:
             return solver.solution_device()["solution"]
         ctx.set_materialize_grads(False)   # an output the loss did not use arrives as None and stays absent
@@ -63,12 +85,12 @@ class QPFunction(torch.autograd.Function):
         if not want:
             return (None,) * nin
         if ctx.outputs is None:
-            g = ctx.solver.adjoint_device(grads[0].contiguous(), want=want)
+            g = ctx.solver.adjoint_device(grads[0].contiguous(), want=want, **ctx.sens)
         else:
             cot = {_OUTPUTS[k][1]: t.contiguous() for k, t in zip(ctx.outputs, grads) if t is not None}
             if not cot:
                 return (None,) * nin
-            g = ctx.solver.adjoint_device(cot.pop("gx", None), want=want, **cot)
+            g = ctx.solver.adjoint_device(cot.pop("gx", None), want=want, **cot, **ctx.sens)
         return ((None,) + tuple(g.get(k) for k in ctx.names) + (None,) * nin)[:nin]
 
     @staticmethod
@@ -79,7 +101,7 @@ class QPFunction(torch.autograd.Function):
         keys = ("x",) if ctx.outputs is None else ctx.outputs
         if not d:
             return None if ctx.outputs is None else (None,) * len(keys)
-        t = ctx.solver.tangent_device(want=keys, **d)
+        t = ctx.solver.tangent_device(want=keys, **d, **ctx.sens)
         return t["x"] if ctx.outputs is None else tuple(t[k] for k in keys)
 
 
@@ -94,14 +116,23 @@ class QPLayer(torch.nn.Module):
     "zl", "zu", "cons") returns that tuple of MPCSolver.solution_device()'s solution, multipliers,
     multipliers_L, multipliers_U and constraints, all differentiable; backward hands the solver the
     cotangents of the outputs the loss used and no others.  zl / zu of a variable without that bound, and of
-    a fixed variable, are constants (0)."""
+    a fixed variable, are constants (0).
 
-    def __init__(self, solver, outputs=("x",)):
+    polish=True: forward runs update_device -> solve -> polish_device and returns the polished blocks (active
+    bounds attained bitwise, inactive multipliers exactly 0); backward and forward-mode autograd differentiate
+    that point exactly.  Raises MadIPMError, naming the verdict, when the polish does not end
+    POLISHED: a degenerate face has no unique derivative.  The default is the layer without it, bit for bit."""
+
+    def __init__(self, solver, outputs=("x",), polish=False):
         super().__init__()
         self.solver = solver
         self.outputs = check_layer_outputs(outputs)
+        self.polish = bool(polish)
 
     def forward(self, c=None, Hvals=None, Avals=None, lcon=None, ucon=None, lvar=None, uvar=None):
+        if self.polish:
+            outputs = None if self.outputs == ("x",) else self.outputs
+            return QPFunction.apply(self.solver, c, Hvals, Avals, lcon, ucon, lvar, uvar, outputs, True)
         if self.outputs == ("x",):
             return QPFunction.apply(self.solver, c, Hvals, Avals, lcon, ucon, lvar, uvar)
         return QPFunction.apply(self.solver, c, Hvals, Avals, lcon, ucon, lvar, uvar, self.outputs)

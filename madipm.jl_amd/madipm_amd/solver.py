@@ -915,7 +915,7 @@ class MPCSolver:
         if "Avals" in names or "Hvals" in names or ("lvar" in names and np.any(self.qp.lvar == self.qp.uvar)):
             self._prepare_update()
 
-    def adjoint(self, gx=None, want=None, *, gy=None, gzl=None, gzu=None, gcons=None) -> dict:
+    def adjoint(self, gx=None, want=None, *, gy=None, gzl=None, gzu=None, gcons=None, polished=False) -> dict:
         """Gradients of a loss l(x*) with respect to the problem data, given gx = dl/dx* (length nvar) at the
         optimum the last solve() returned: a dict of numpy arrays over `want`, a subset of ADJOINT_NAMES
         (None: all seven), Hvals / Avals in the creation-time COO order.  An infinite bound gets 0; a fixed
@@ -929,7 +929,12 @@ class MPCSolver:
         its derivatives with respect to multipliers, multipliers_L, multipliers_U and constraints (= A x),
         lengths ncon, nvar, nvar, ncon; any of the five may be None (0), not all.  Constants, whose
         cotangents are ignored: zl_i / zu_i of a variable without that bound and zl, zu of a fixed variable
-        (solve() returns 0 there).  With gx alone the call is the one above, bit for bit."""
+        (solve() returns 0 there).  With gx alone the call is the one above, bit for bit.
+
+        polished=True: the gradients at the point the last polish() returned, which must have
+        ended POLISHED on this solved point: the exact derivatives of the face's equality-constrained QP.  The
+        gradient of an inactive bound is exactly 0 and that of an active one is the whole sensitivity; zl / zu
+        of an inactive bound are constants there.  Arguments and checks are the same."""
         names = check_adjoint_want(want)
         given = check_adjoint_cotangents(self.qp.nvar, self.qp.ncon, gx, gy, gzl, gzu, gcons)
         size = self._adjoint_sizes()
@@ -937,19 +942,23 @@ class MPCSolver:
         buf = _host_outputs(g, size, names)
         self._adjoint_prepare(names)
         p = _host_inputs(given)
-        if list(given) == ["x"]:
+        if polished:
+            ct = L.QPCot(**p)
+            L.check(L.lib.madipm_solver_adjoint_polished(self.h, C.byref(ct), C.byref(g)), "adjoint")
+        elif list(given) == ["x"]:
             L.check(L.lib.madipm_solver_adjoint(self.h, p["x"], C.byref(g)), "adjoint")
         else:
             ct = L.QPCot(**p)
             L.check(L.lib.madipm_solver_adjoint_full(self.h, C.byref(ct), C.byref(g)), "adjoint")
         return {k: buf[k][:size[k]] for k in names}
 
-    def adjoint_device(self, gx=None, want=None, stream=None, *, gy=None, gzl=None, gzu=None, gcons=None) -> dict:
+    def adjoint_device(self, gx=None, want=None, stream=None, *, gy=None, gzl=None, gzu=None, gcons=None,
+                       polished=False) -> dict:
         """adjoint() from and into torch tensors on the solver's GPU (every cotangent: float64, contiguous, the
         shape adjoint() expects), without a copy through the host.  `stream` is the torch.cuda.Stream the
         cotangents were produced on (None: the current stream): they are read after the work enqueued on it,
         and work enqueued on it after the call sees the returned tensors.  The arguments are checked before
-        any library call."""
+        any library call.  polished as in adjoint()."""
         names = check_adjoint_want(want)
         nvar, ncon = self.qp.nvar, self.qp.ncon
         given = check_adjoint_cotangents(nvar, ncon, gx, gy, gzl, gzu, gcons, on_device=True, device=self._device,
@@ -961,7 +970,11 @@ class MPCSolver:
                 nvar, ncon, gx, gy, gzl, gzu, gcons, on_device=True, device=self._device, who="adjoint_device"),
             g, size, names, given)
         self._adjoint_prepare(names)
-        if list(given) == ["x"]:
+        if polished:
+            ct = L.QPCot(**p)
+            L.check(L.lib.madipm_solver_adjoint_polished_device(self.h, C.byref(ct), C.byref(g),
+                                                                L.vp(st.cuda_stream)), "adjoint_device")
+        elif list(given) == ["x"]:
             L.check(L.lib.madipm_solver_adjoint_device(self.h, p["x"], C.byref(g), L.vp(st.cuda_stream)),
                     "adjoint_device")
         else:
@@ -980,7 +993,7 @@ class MPCSolver:
 
     # ------------------------------------------------------------ forward-mode sensitivities
     def tangent(self, want=None, *, c=None, Hvals=None, Avals=None, lcon=None, ucon=None, lvar=None,
-                uvar=None) -> dict:
+                uvar=None, polished=False) -> dict:
         """The directional derivative of the solution the last solve() returned along a direction of the
         problem data: a dict of numpy arrays over `want`, a subset of TANGENT_NAMES (None: all five: x, y,
         zl, zu and cons = A x).  The direction blocks have the data's shapes (Hvals / Avals in the
@@ -988,7 +1001,12 @@ class MPCSolver:
         fixed variable moves by lvar's entry and an equality row by lcon's (uvar's / ucon's is not read), so
         one array passed as both bounds stays right.  x* + tangent is the first-order prediction of the
         optimum after the data moved by the direction.  The call shares adjoint()'s factor of the point (one
-        factorisation serves both) and leaves the solver's state untouched.  MadIPMError as adjoint()."""
+        factorisation serves both) and leaves the solver's state untouched.  MadIPMError as adjoint().
+
+        polished=True: the derivative of the point the last polish() returned, which must have
+        ended POLISHED on this solved point: an active variable moves with its bound and an active row's cons
+        with the row's bound (copies of the direction), zl / zu of an inactive bound stay exactly 0, and the
+        directions of inactive bounds are not read.  Arguments and checks are the same."""
         names = check_tangent_want(want)
         size = self._adjoint_sizes()
         given = check_tangent_directions(size, dict(c=c, Hvals=Hvals, Avals=Avals, lcon=lcon, ucon=ucon, lvar=lvar,
@@ -998,7 +1016,8 @@ class MPCSolver:
         buf = _host_outputs(o, osize, names)
         self._adjoint_prepare(given)
         d = L.QPDir(**_host_inputs(given))
-        L.check(L.lib.madipm_solver_tangent(self.h, C.byref(d), C.byref(o)), "tangent")
+        fn = L.lib.madipm_solver_tangent_polished if polished else L.lib.madipm_solver_tangent
+        L.check(fn(self.h, C.byref(d), C.byref(o)), "tangent")
         return {k: buf[k][:osize[k]] for k in names}
 
     def _tangent_sizes(self) -> dict:
@@ -1006,12 +1025,12 @@ class MPCSolver:
         return {"x": qp.nvar, "y": qp.ncon, "zl": qp.nvar, "zu": qp.nvar, "cons": qp.ncon}
 
     def tangent_device(self, want=None, stream=None, *, c=None, Hvals=None, Avals=None, lcon=None, ucon=None,
-                       lvar=None, uvar=None) -> dict:
+                       lvar=None, uvar=None, polished=False) -> dict:
         """tangent() from and into torch tensors on the solver's GPU (every direction: float64, contiguous, the
         shape tangent() expects), without a copy through the host.  `stream` is the torch.cuda.Stream the
         directions were produced on (None: the current stream): they are read after the work enqueued on it,
         and work enqueued on it after the call sees the returned tensors.  The arguments are checked before
-        any library call."""
+        any library call.  polished as in tangent()."""
         names = check_tangent_want(want)
         size = self._adjoint_sizes()
         dirs = dict(c=c, Hvals=Hvals, Avals=Avals, lcon=lcon, ucon=ucon, lvar=lvar, uvar=uvar)
@@ -1024,8 +1043,8 @@ class MPCSolver:
             o, osize, names, given)
         self._adjoint_prepare(given)
         d = L.QPDir(**p)
-        L.check(L.lib.madipm_solver_tangent_device(self.h, C.byref(d), C.byref(o), L.vp(st.cuda_stream)),
-                "tangent_device")
+        fn = L.lib.madipm_solver_tangent_polished_device if polished else L.lib.madipm_solver_tangent_device
+        L.check(fn(self.h, C.byref(d), C.byref(o), L.vp(st.cuda_stream)), "tangent_device")
         return {k: buf[k][:osize[k]] for k in names}
 
     def tangent_info(self) -> dict:
@@ -1097,6 +1116,16 @@ class MPCSolver:
         info = L.PolishInfo()
         L.check(L.lib.madipm_solver_polish_info(self.h, C.byref(info)), "polish_info")
         return _polish_info_dict(info)
+
+    def polished_sens_info(self) -> dict:
+        """n_tangents / n_adjoints: successful calls with polished=True; n_factorizations: those that rebuilt the
+        polish's factor (an adjoint or a tangent had taken it); last_residual: the max-norm of the last call's
+        final masked residual (scaled space)."""
+        nt, na, nf, r = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+        L.check(L.lib.madipm_solver_polished_sens_info(self.h, C.byref(nt), C.byref(na), C.byref(nf), C.byref(r)),
+                "polished_sens_info")
+        return {"n_tangents": int(nt.value), "n_adjoints": int(na.value), "n_factorizations": int(nf.value),
+                "last_residual": float(r.value)}
 
     def counters(self) -> dict:
         """n_analyses: linear-solver analyses run for this solver (stays 1); n_updates: successful update()

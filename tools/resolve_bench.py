@@ -46,7 +46,16 @@ tangent_warm_iters_last and tangent_warm_iters_predicted.
 update_device + solve, polish_device for all seven blocks, stream synchronised: polish_s (the first call on a
 point: classification, factorisation, three solves, the verdict's read-back) beside polish_solve_s (the solve
 before it) and polish_again_s (a second call with the returned set supplied: no factorisation), polish_verdicts
-(how often each verdict came back), polish_residual (the largest) and the counters."""
+(how often each verdict came back), polish_residual (the largest) and the counters.
+
+--polished-sens adds the sensitivities at the polished point: after each update_device + solve +
+polish_device, one tangent_device(polished=True) of a seeded direction in all seven data blocks for all five
+outputs and one adjoint_device(polished=True) of seeded cotangents of all five blocks for all seven gradients,
+each with the stream synchronised: polished_tangent_s, polished_adjoint_s (medians), polished_sens_residual (the
+largest), polished_sens_verdicts and polished_sens_refused (the points whose polish did not end POLISHED: the
+calls are refused there, by design: the LP stand-ins are degenerate).  The instance name sparse_qp is the
+strictly complementary 1000 x 600 sparse QP of the tests (tests/adjoint_oracle.py), on which every point is
+polished."""
 import dataclasses
 import json
 import os
@@ -76,8 +85,16 @@ def perturb(qp, rng):
                 lvar=qp.lvar * fv, uvar=qp.uvar * fv, lcon=qp.lcon * fc, ucon=qp.ucon * fc)
 
 
-def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polish=False):
-    qp, desc = bench.build_problem(name)
+def build_problem(name):
+    if name == "sparse_qp":
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import adjoint_oracle
+        return adjoint_oracle.sparse_fixture()[0], "strictly complementary sparse QP of the tests, 1000 x 600"
+    return bench.build_problem(name)
+
+
+def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polish=False, polished_sens=False):
+    qp, desc = build_problem(name)
     opts = bench.solver_opts()
     MPCSolver(qp, **opts)                      # the first construction of a process pays one-off set-up
     t = time.perf_counter()
@@ -309,6 +326,47 @@ def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polis
                      "polish_n_active": info["n_active"], "n_polishes": info["n_polishes"],
                      "n_polish_factorizations": info["n_polish_factorizations"]})
         c = s.counters()
+    if polished_sens:   # the same data again: one polished tangent and one polished adjoint per polished point
+        from madipm_amd import MadIPMError, PolishVerdict
+        rng = np.random.default_rng(0)
+        perturb(qp, rng)
+        drng = np.random.default_rng(3)
+        size = dict(c=qp.nvar, Hvals=qp.nnzh, Avals=qp.nnzj, lcon=qp.ncon, ucon=qp.ncon, lvar=qp.nvar, uvar=qp.nvar)
+        csize = dict(gx=qp.nvar, gy=qp.ncon, gzl=qp.nvar, gzu=qp.nvar, gcons=qp.ncon)
+        draw = lambda sz: {k: torch.as_tensor(drng.standard_normal(n), device="cuda") for k, n in sz.items()}  # noqa: E731
+        qtan, qadj, qverd, qres, refused = [], [], {}, 0.0, 0
+        for rep in range(WARMUP + REPS):
+            s.update_device(**{k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()})
+            if s.solve(fetch_solution=False).status != 1:
+                continue
+            verdict = s.polish_device()["info"]["verdict"]
+            qverd[verdict.name] = qverd.get(verdict.name, 0) + 1
+            d, cot = draw(size), draw(csize)
+            torch.cuda.synchronize()
+            if verdict != PolishVerdict.POLISHED:
+                try:
+                    s.tangent_device(polished=True, **d)
+                except MadIPMError:
+                    refused += 1
+                continue
+            t = time.perf_counter()
+            s.tangent_device(polished=True, **d)
+            torch.cuda.current_stream().synchronize()
+            t_tan = time.perf_counter() - t
+            qres = max(qres, s.polished_sens_info()["last_residual"])
+            t = time.perf_counter()
+            s.adjoint_device(cot.pop("gx"), polished=True, **cot)
+            torch.cuda.current_stream().synchronize()
+            t_adj = time.perf_counter() - t
+            qres = max(qres, s.polished_sens_info()["last_residual"])
+            if rep >= WARMUP:
+                qtan.append(t_tan)
+                qadj.append(t_adj)
+        med = lambda v: statistics.median(v) if v else float("nan")  # noqa: E731
+        wres.update({"polished_tangent_s": med(qtan), "polished_adjoint_s": med(qadj), "polished_sens_residual": qres,
+                     "polished_sens_verdicts": qverd, "polished_sens_refused": refused,
+                     **{"polished_" + k: v for k, v in s.polished_sens_info().items() if k != "last_residual"}})
+        c = s.counters()
     update_s, solve_s = statistics.median(upd), statistics.median(sol)
     return {**wres, "instance": name, "description": desc, "nvar": qp.nvar, "ncon": qp.ncon, "nnzj": qp.nnzj, "nnzh": qp.nnzh,
             "construct_s": construct_s, "prepare_update_s": prepare_update_s, "update_s": update_s,
@@ -350,8 +408,11 @@ def main():
     polish = "--polish" in args
     if polish:
         args.remove("--polish")
+    polished_sens = "--polished-sens" in args
+    if polished_sens:
+        args.remove("--polished-sens")
     for name in args or ["ex10", "supportcase10"]:
-        r = run(name, warm, adjoint, adjoint_full, tangent, polish)
+        r = run(name, warm, adjoint, adjoint_full, tangent, polish, polished_sens)
         print(f"{name}: construct_s {r['construct_s']:.4f}  prepare_update_s {r['prepare_update_s']:.4f}  "
               f"update_s {r['update_s']:.5f}  solve_s {r['solve_s']:.4f}  ->  update + solve "
               f"{r['update_plus_solve_s']:.4f} s against construct + solve {r['construct_plus_solve_s']:.4f} s "
@@ -386,6 +447,12 @@ def main():
                   f"again with the returned set supplied {r['polish_again_s']:.4f} s; verdicts {r['polish_verdicts']}, "
                   f"residual <= {r['polish_residual']:.1e}, {r['polish_n_active']} active in the last set, "
                   f"{r['n_polish_factorizations']} factorisations in {r['n_polishes']} calls", flush=True)
+        if polished_sens:
+            print(f"{name}: at the polished point: tangent (seven direction blocks, five outputs) "
+                  f"{r['polished_tangent_s']:.4f} s, adjoint (five cotangents, seven gradients) "
+                  f"{r['polished_adjoint_s']:.4f} s; verdicts {r['polished_sens_verdicts']}, refused "
+                  f"{r['polished_sens_refused']}, residual <= {r['polished_sens_residual']:.1e}, "
+                  f"{r['polished_n_factorizations']} factorisations of their own", flush=True)
         out.append(r)
     print(json.dumps({"resolve_bench": out, "warmup": WARMUP, "reps": REPS, "rel_noise": REL}))
 
