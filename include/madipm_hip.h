@@ -711,6 +711,58 @@ int madipm_solver_adjoint_polished_device(madipm_solver_t s, const madipm_qp_cot
 int madipm_solver_polished_sens_info(madipm_solver_t s, int64_t* n_tangents, int64_t* n_adjoints,
                                      int64_t* n_factorizations, double* last_residual);
 
+/* ------------------------------------------------------------------ active-set solve of the held data  [ABI 0.2.12, additive]
+ * After madipm_solver_update / _update_device everything an active-set solve of the new problem needs is on the
+ * device, and in a sequence of problems the optimal active set is often the previous one or a few bounds away
+ * from it.  This call solves the problem the solver holds from a starting set, without an interior-point solve
+ * and without reading the iterate.  Set encoding, outputs, routes and the stream contract are
+ * madipm_solver_polish's.  (Four symbols and two structs; madipm_version() still returns 203; nothing above
+ * changed.)
+ * Round k = 1 .. max_rounds: the start (an active coordinate of v = [x_free; s] at its raw bound, an inactive
+ * one at 0, y = 0, a fixed variable at its value), then the polish's factor, 1 + refine_steps delta-form solves,
+ * residual, measures and verdict.  POLISHED, NO_CONVERGENCE and FACTORIZATION_FAILED end the call; so does
+ * WRONG_SET in the last round; WRONG_SET before it gives the next set from exactly the violations found, with
+ * M = max(1, max |active multiplier|): an active coordinate with multiplier < -tol_sign M becomes inactive, an
+ * inactive one with gap < -tol_feas max(1, |bound|) to a bound it has becomes active there (the lower bound
+ * when both are violated).  Every round starts the same way, so the result depends on the data, the final set
+ * and the options only.  POLISHED is an optimality certificate of the convex QP.
+ * The starting set: active_var / active_row, or with both NULL the kept set: the codes of the last
+ * madipm_solver_polish or active-set solve on this solver that ended POLISHED.
+ * Outputs: on POLISHED the five blocks exactly as madipm_solver_polish writes a polished point; on any other
+ * verdict they are NOT written.  active_var / active_row always receive the last set tried.
+ * info: verdict (the MADIPM_POLISH* values), rounds, n_active, n_changed (codes of the last set that differ from
+ * the starting set), residual / min_multiplier / min_gap of the last round, the cumulative counters.
+ * It needs K2, no communicator, valid codes, an output, max_rounds in 1..16 and the polish's option ranges; with
+ * both sets NULL, a kept set.  It needs NO solve, status or initialize: it runs on a fresh solver, after an
+ * update, or after a solve.  A round's factor is the polish factor already held when data (update count), codes
+ * and sigma are its own: such a call does not factorise.
+ * State: a POLISHED call makes its point the current polished point of madipm_solver_tangent_polished /
+ * _adjoint_polished until the next update, initialize, solve, polish or active-set solve; any other verdict
+ * leaves none.  madipm_solver_adjoint / _tangent / _polish / _warm_start_last, madipm_solver_get_solution and
+ * madipm_solver_polish_info are unchanged, and nothing a later madipm_solver_initialize / _solve reads is
+ * changed: update; active-set solve; solve gives the bits of update; solve.
+ * Memory: the polish's scratch, allocated by the first call of either, + 2 n bytes for the kept and the starting
+ * set. */
+typedef struct madipm_active_set_opts { madipm_polish_opts polish; int32_t max_rounds; } madipm_active_set_opts;
+typedef struct madipm_active_set_info {
+  int32_t verdict, rounds, n_active, n_changed;
+  double residual, min_multiplier, min_gap;
+  int64_t n_calls, n_factorizations;
+} madipm_active_set_info;
+void madipm_active_set_default_opts(madipm_active_set_opts* o); /* the polish defaults, max_rounds 4 */
+/* HOST pointers.  opts NULL: the defaults; active_var and active_row both NULL: the kept set; info may be NULL. */
+int madipm_solver_active_set_solve(madipm_solver_t s, const madipm_active_set_opts* opts, const int8_t* active_var,
+                                   const int8_t* active_row, const madipm_polish_out* out,
+                                   madipm_active_set_info* info);
+/* DEVICE pointers for the sets and `out`, with madipm_solver_polish_device's contract; the call waits, on the
+ * host, for the set's validation and each round's verdict. */
+int madipm_solver_active_set_solve_device(madipm_solver_t s, const madipm_active_set_opts* opts,
+                                          const int8_t* d_active_var, const int8_t* d_active_row,
+                                          const madipm_polish_out* d_out, madipm_active_set_info* info,
+                                          madipm_stream_t stream);
+/* The last active-set solve's info (zeros and verdict -1 before the first); no device access. */
+int madipm_solver_active_set_info(madipm_solver_t s, madipm_active_set_info* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -861,6 +861,49 @@ int madipm_solver_polish_info(madipm_solver_t s, madipm_polish_info* info) {
   MADIPM_API_END
 }
 
+void madipm_active_set_default_opts(madipm_active_set_opts* o) {
+  if (!o) return;
+  madipm_polish_default_opts(&o->polish);
+  o->max_rounds = 4;
+}
+
+static madipm_active_set_opts active_set_opts(const madipm_active_set_opts* o) {
+  madipm_active_set_opts d;
+  madipm_active_set_default_opts(&d);
+  return o ? *o : d;
+}
+
+int madipm_solver_active_set_solve(madipm_solver_t s, const madipm_active_set_opts* opts, const int8_t* active_var,
+                                   const int8_t* active_row, const madipm_polish_out* out,
+                                   madipm_active_set_info* info) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(out, "madipm_solver_active_set_solve: null output struct");
+  s->s->active_set_solve(active_set_opts(opts), active_var, active_row, *out, info, false, nullptr);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_active_set_solve_device(madipm_solver_t s, const madipm_active_set_opts* opts,
+                                          const int8_t* d_active_var, const int8_t* d_active_row,
+                                          const madipm_polish_out* d_out, madipm_active_set_info* info,
+                                          madipm_stream_t stream) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(d_out, "madipm_solver_active_set_solve_device: null output struct");
+  s->s->active_set_solve(active_set_opts(opts), d_active_var, d_active_row, *d_out, info, true, (hipStream_t)stream);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_active_set_info(madipm_solver_t s, madipm_active_set_info* info) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->active_set_info(info);
+  return 0;
+  MADIPM_API_END
+}
+
 int madipm_solver_tangent_polished(madipm_solver_t s, const madipm_qp_directions* d,
                                    const madipm_qp_point_tangents* out) {
   MADIPM_API_BEGIN

@@ -1956,6 +1956,14 @@ void MPCSolver::refresh_host_mirrors() {
   host_stale_ = 0;
 }
 
+// lvar, uvar, lcon, ucon of the device route's staging, when they are what the solver holds (no host update
+// ran since they were written)
+bool MPCSolver::device_raw_bounds(const double* (&raw)[4]) const {
+  if (!dev_ || dev_raw_stale_) return false;
+  raw[0] = dev_->lvar.p, raw[1] = dev_->uvar.p, raw[2] = dev_->lcon.p, raw[3] = dev_->ucon.p;
+  return true;
+}
+
 void MPCSolver::get_data(double* c, double* c0, double* Hvals, double* Avals, double* lcon, double* ucon,
                          double* lvar, double* uvar, double* x0, double* y0) {
   QPHost& P = *H_;
@@ -2305,6 +2313,7 @@ const double* MPCSolver::kvals() const { return kkt_ == KKT_NORMAL ? Cx_.p : Kx_
 // the pool grows only when a solve needs more pairs than any earlier one did
 void MPCSolver::timed_factorize() {
   ldl_->factorize_async(kvals(), stream_);
+  ++n_factor_calls_;
   // the next k_rhs stamps the factorisation's end (an asynchronous tail stamps its own)
   fact_end_pending_ = ldl_->lazy_inertia && !ldl_->tail_async();
 }
@@ -2501,6 +2510,7 @@ void MPCSolver::init_starting_point() {
 void MPCSolver::initialize() {
   const DV D = view();
   hipStream_t s = stream_;
+  ++n_inits_;
   {  // restart from the problem's initial point (solve! always restarts)
     const QPHost& P = *H_;
     if (start_on_device_) {  // the last update was a device update: its start vectors never left the device

@@ -110,6 +110,13 @@ class MPCSolver {
   void polish(const madipm_polish_opts& o, const int8_t* av, const int8_t* ar, const madipm_polish_out& out,
               madipm_polish_info* info, bool device, hipStream_t caller);
   void polish_info(madipm_polish_info* info) const;
+  // The active-set solve of the data the solver holds, without an interior-point end point
+  // (madipm_solver_active_set_solve / _device / _active_set_info): rounds of the polish's
+  // factor, solves and verdict from a start that reads nothing of the iterate, the set repaired between
+  // them.  av / ar: the starting set (both null: the kept set); device and `caller` as in polish().
+  void active_set_solve(const madipm_active_set_opts& o, const int8_t* av, const int8_t* ar,
+                        const madipm_polish_out& out, madipm_active_set_info* info, bool device, hipStream_t caller);
+  void active_set_info(madipm_active_set_info* info) const;
   // tangent() and adjoint() at the polished point (madipm_solver_tangent_polished / _adjoint_polished / _device /
   // _polished_sens_info): the exact derivatives of the face the last polish() of this solved point
   // ended POLISHED on.  They solve with the polish's factor (restored from the kept set when an adjoint or a
@@ -148,6 +155,13 @@ class MPCSolver {
   void polished_refuse(const std::string& who) const;
   void polished_factor(const std::string& who);
   void polished_solve();
+  // the polish's and the active-set solve's buffers and raw bounds (device_bounds: gathered from the device
+  // route's staging, no host copy); the tag of the polish factor the LDL^T holds
+  void polish_buffers(bool device_bounds);
+  bool device_raw_bounds(const double* (&raw)[4]) const;  // false: the host's copies are the newer ones
+  bool polish_factor_held() const;
+  void polish_factor_tag(double sigma);
+  bool active_set_point() const;
   std::unique_ptr<LinSolver> make_linsolver(int n, const int64_t* cp, const int32_t* ri, const SymbolicOptions& so);
   void initialize();
   void init_starting_point();
@@ -243,6 +257,7 @@ class MPCSolver {
   int64_t n_solves_ = 0;               // completed solves (the adjoint's factor belongs to one of them)
   int64_t solve_updates_ = 0;          // n_updates_ at the end of the last solve
   int64_t n_analyses_ = 0, n_updates_ = 0;
+  int64_t n_inits_ = 0, n_factor_calls_ = 0;  // initialize() calls; factorisations enqueued (the post-solve factors' tags)
   double last_update_s_ = 0;
 };
 

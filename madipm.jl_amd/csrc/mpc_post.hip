@@ -1,7 +1,9 @@
 // The post-solve calls of the MPC driver: adjoint gradients, forward-mode tangents and the active-set polish
-// (DESIGN §13c-§13f).  Each reads the end point of a finished solve, factorises once per point and leaves
+// (DESIGN §13c-§13g).  Each reads the end point of a finished solve, factorises once per point and leaves
 // alone everything a later initialize / solve / warm_start_last reads; the interior-point loop (mpc.hip)
-// knows nothing of the state kept here.  Kernels and what they share with the loop's: mpc_kernels.hpp.
+// knows nothing of the state kept here.  The active-set solve (§13h) runs the polish's kernels on the data the
+// solver holds, from a start that reads no end point, and so needs no solve at all.  Kernels and what they
+// share with the loop's: mpc_kernels.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -87,6 +89,7 @@ struct Tangent {
 struct PolMeasures {  // k_pol_verdict's result, read back with one copy
   int32_t verdict, n_active;
   double residual, min_multiplier, min_gap;
+  double max_multiplier;                  // the largest |active multiplier|: the active-set solve's M (§13h)
 };
 struct Polish {
   DBuf<double> w, grad, lo, hi, part, ax;
@@ -101,6 +104,17 @@ struct Polish {
   int64_t point_solve = -1;               // n_solves_ of the point w / codes / grad belong to (-1: none, or a polish threw)
   int refine_steps = 0;                   // of that polish
   madipm_polish_info last{-1, 0, 0.0, 0.0, 0.0, 0, 0};
+  // the rest of the factor's tag: the data (n_updates_) it was made of, and its place among the factorisations
+  // enqueued (n_factor_calls_: nothing has taken the LDL^T since)
+  int64_t fact_updates = -1, fact_calls = -1;
+  // The active-set solve (madipm_solver_active_set_solve*), allocated with the rest: the kept set
+  // (the codes of the last polish or active-set solve that ended POLISHED) and the starting set of the call
+  // (2 n B), the count of changed codes.  as_*: the data and the state the current active-set point belongs to.
+  DBuf<int8_t> codes_kept, codes0;
+  DBuf<int32_t> changed;
+  bool kept = false, as_point = false;
+  int64_t as_updates = -1, as_solves = -1, as_inits = -1;
+  madipm_active_set_info as_last{-1, 0, 0, 0, 0.0, 0.0, 0.0, 0, 0};
 };
 
 // The sensitivities at the polished point (madipm_solver_tangent_polished* / _adjoint_polished*)
@@ -533,8 +547,8 @@ void PostSolve::tangent_scratch(MPCSolver& S, bool needLists) {
 template <class Enqueue>
 bool MPCSolver::factor_trials(Enqueue&& enqueue) {
   double dw = 0.0, dc = 0.0;
-  if (opt_.regularization == 1) {
-    dw = opt_.delta_p;
+  if (opt_.regularization == 1 || (opt_.regularization != 0 && n_inits_ == 0)) {
+    dw = opt_.delta_p;  // Adaptive before the first initialize (an active-set solve on a fresh solver): its first pair
     dc = opt_.delta_d;
   } else if (opt_.regularization != 0) {
     dw = adapt_dp_;
@@ -1132,6 +1146,7 @@ __global__ __launch_bounds__(NT) void k_pol_verdict(const double* __restrict__ r
     out->residual = sr[0];
     out->min_multiplier = smn[0];
     out->min_gap = sgr[0];
+    out->max_multiplier = sma[0];
   }
 }
 
@@ -1172,12 +1187,188 @@ __global__ __launch_bounds__(NT) void k_pol_codes(PolArgs P, int8_t* __restrict_
   }
 }
 
+// ---- the active-set solve's own kernels; everything else it launches is the polish's
+// The raw bounds of [x; s] from the device route's staging: lvar / uvar, lcon / ucon of the slack's row
+__global__ __launch_bounds__(NT) void k_as_bounds(int nx, int n, const double* __restrict__ lvar,
+                                                  const double* __restrict__ uvar, const double* __restrict__ lcon,
+                                                  const double* __restrict__ ucon, const int32_t* __restrict__ ineq,
+                                                  double* __restrict__ lo, double* __restrict__ hi) {
+  GRID_LOOP(i, n) {
+    if (i < nx) {
+      lo[i] = lvar[i], hi[i] = uvar[i];
+    } else {
+      const int r = ineq[i - nx];
+      lo[i] = lcon[r], hi[i] = ucon[r];
+    }
+  }
+}
+
+// The start of a round.  The codes: the supplied set, validated as k_pol_classify validates it (flags[0]); or
+// `from` (the kept set); or, with neither, those k_as_next left in P.codes.  Then v = the raw bound on an active
+// coordinate and 0 on an inactive one, a fixed variable at its value, y = 0: the iterate is not read, so the
+// round's result depends on the data, the set and the options only.  flags[1] and t1 as in k_pol_classify;
+// codes0 (may be null) keeps the set the call started from.
+__global__ __launch_bounds__(NT) void k_as_start(PolArgs P, const int8_t* __restrict__ av,
+                                                 const int8_t* __restrict__ ar, const int8_t* __restrict__ from,
+                                                 int8_t* __restrict__ codes0, LDLStatus* t1) {
+#pragma clang fp contract(off)
+  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  const int top = P.n > P.m ? P.n : P.m;
+  GRID_LOOP(i, top) {
+    if (i < P.n) {
+      const bool fx = P.fixed[i], kl = P.lbpos[i] >= 0, ku = P.ubpos[i] >= 0;
+      int c;
+      if (av) {
+        c = i < P.nx ? av[i] : ar[P.ineq[i - P.nx]];
+        if (c != 0 && (fx || (c != -1 && c != 1) || (c == -1 && !kl) || (c == 1 && !ku))) {
+          atomicMax(&P.flags[0], 1);
+          c = 0;
+        }
+      } else {
+        c = from ? from[i] : P.codes[i];
+      }
+      double v = 0.0;
+      if (fx) {
+        v = P.lo[i];
+      } else if (c != 0) {
+        const double b = c < 0 ? P.lo[i] : P.hi[i];
+        v = i < P.nx ? b : pol_cs(P, (int)i) * b;
+      }
+      P.w[i] = v;
+      if (P.codes_fact[i] != c) atomicMax(&P.flags[1], 1);
+      P.codes[i] = (int8_t)c;
+      if (codes0) codes0[i] = (int8_t)c;
+    }
+    if (i < P.m) {
+      P.w[P.n + i] = 0.0;
+      if (ar && P.rowslack[i] < 0 && ar[i] != 0) atomicMax(&P.flags[0], 1);
+    }
+  }
+}
+
+// The next set after a round that ended WRONG_SET, from exactly the violations k_pol_verdict found (k_pol_meas'
+// expressions, the verdict's thresholds, M = max(1, max |active multiplier|) of this round): an active
+// coordinate whose multiplier is < -tol_sign M becomes inactive; an inactive one whose gap to a bound it has is
+// < -tol_feas max(1, |bound|) becomes active there, the lower bound when both are violated.  One thread per
+// coordinate, so a coordinate dropped here is not added again.
+__global__ __launch_bounds__(NT) void k_as_next(PolArgs P, const PolMeasures* __restrict__ meas, double tol_sign,
+                                                double tol_feas) {
+#pragma clang fp contract(off)
+  const double ma = meas->max_multiplier;
+  const double M = ma > 1.0 ? ma : 1.0;
+  GRID_LOOP(i, P.n) {
+    if (P.fixed[i]) continue;
+    const int c = P.codes[i];
+    const double cs = pol_cs(P, (int)i);
+    if (c != 0) {
+      const double t = pol_mult(P, (int)i, P.grad[i], cs);
+      const double z = c < 0 ? t : -t;
+      if (z < -tol_sign * M) P.codes[i] = 0;
+      continue;
+    }
+    const double v = P.w[i];
+    int nc = 0;
+    if (P.ubpos[i] >= 0) {
+      const double b = P.hi[i], bs = i < P.nx ? b : cs * b;
+      if ((bs - v) / cs / fmax(1.0, fabs(b)) < -tol_feas) nc = 1;
+    }
+    if (P.lbpos[i] >= 0) {
+      const double b = P.lo[i], bs = i < P.nx ? b : cs * b;
+      if ((v - bs) / cs / fmax(1.0, fabs(b)) < -tol_feas) nc = -1;
+    }
+    if (nc) P.codes[i] = (int8_t)nc;
+  }
+}
+
+// The codes that differ between two sets: an integer sum per block (an LDS tree), one integer atomic per block
+__global__ __launch_bounds__(NT) void k_as_changed(int n, const int8_t* __restrict__ a, const int8_t* __restrict__ b,
+                                                   int32_t* __restrict__ count) {
+  __shared__ int sc[NT];
+  int cnt = 0;
+  GRID_LOOP(i, n) cnt += a[i] != b[i];
+  sc[threadIdx.x] = cnt;
+  __syncthreads();
+  for (int o = NT / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sc[threadIdx.x] += sc[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && sc[0]) atomicAdd(count, sc[0]);
+}
+
 }  // namespace
+
+// The polish's and the active-set solve's scratch, by the first call of either, and the raw bounds of [x; s] as
+// the last update left them.  device_bounds: the device route's staging holds them (k_as_bounds, no host copy).
+void MPCSolver::polish_buffers(bool device_bounds) {
+  QPHost& P = *H_;
+  hipStream_t s = stream_;
+  PostSolve& ps = post_state();
+  Polish& p = ps.pol;
+  ps.rowslack(P, s);
+  const int ns = n_ - nx_;
+  if (!p.w.p) {
+    p.w.alloc(std::max(n_ + m_, 1));
+    p.grad.alloc(std::max(n_, 1));
+    p.lo.alloc(std::max(n_, 1));
+    p.hi.alloc(std::max(n_, 1));
+    p.part.alloc((size_t)4 * MAXB);
+    p.ax.alloc(std::max(m_, 1));
+    p.codes.alloc(std::max(n_, 1));
+    p.codes_fact.alloc(std::max(n_, 1));
+    p.codes_fact.zero(s);
+    p.codes_kept.alloc(std::max(n_, 1));
+    p.codes0.alloc(std::max(n_, 1));
+    p.changed.alloc(1);
+    p.ineq.alloc(std::max(ns, 1));
+    p.ineq.upload(P.ind_ineq.data(), P.ind_ineq.size(), s);
+    p.flags.alloc(2);
+    p.meas.alloc(1);
+  }
+  if (p.bounds_updates == n_updates_) return;
+  const double* raw[4];  // lvar, uvar, lcon, ucon of the device route's staging
+  if (device_bounds && device_raw_bounds(raw)) {
+    if (n_)
+      k_as_bounds<<<blocks(n_), NT, 0, s>>>(nx_, n_, raw[0], raw[1], raw[2], raw[3], p.ineq.p, p.lo.p, p.hi.p);
+    MADIPM_HIP(hipGetLastError());
+  } else {
+    refresh_host_mirrors();
+    std::vector<double> lo(std::max(n_, 1)), hi(std::max(n_, 1));
+    for (int i = 0; i < nx_; ++i) lo[i] = P.lvar[i], hi[i] = P.uvar[i];
+    for (int k = 0; k < ns; ++k) lo[nx_ + k] = P.lcon[P.ind_ineq[k]], hi[nx_ + k] = P.ucon[P.ind_ineq[k]];
+    p.lo.upload(lo, s);
+    p.hi.upload(hi, s);
+    MADIPM_HIP(hipStreamSynchronize(s));  // lo / hi are this scope's
+  }
+  p.bounds_updates = n_updates_;
+}
+
+// The LDL^T holds the polish factor of the current data: made at this solve and update count, and nothing has
+// factorised since.  (Its codes and sigma are compared by the caller.)
+bool MPCSolver::polish_factor_held() const {
+  const Polish& p = post_->pol;
+  return p.fact_solve == n_solves_ && p.fact_updates == n_updates_ && p.fact_calls == n_factor_calls_;
+}
+
+void MPCSolver::polish_factor_tag(double sigma) {
+  Polish& p = post_->pol;
+  if (n_) MADIPM_HIP(hipMemcpyAsync(p.codes_fact.p, p.codes.p, (size_t)n_, hipMemcpyDeviceToDevice, stream_));
+  p.fact_solve = n_solves_;
+  p.fact_updates = n_updates_;
+  p.fact_calls = n_factor_calls_;
+  p.fact_sigma = sigma;
+}
+
+// The current polished point is an active-set solve's: it ended POLISHED, and no update, initialize, solve,
+// polish or active-set solve ran since
+bool MPCSolver::active_set_point() const {
+  if (!post_) return false;
+  const Polish& p = post_->pol;
+  return p.as_point && p.as_updates == n_updates_ && p.as_solves == n_solves_ && p.as_inits == n_inits_;
+}
 
 void MPCSolver::polish(const madipm_polish_opts& o, const int8_t* av, const int8_t* ar, const madipm_polish_out& po,
                        madipm_polish_info* info, bool device, hipStream_t caller) {
   const std::string who = device ? "madipm_solver_polish_device: " : "madipm_solver_polish: ";
-  QPHost& P = *H_;
   // ---- refusals, before anything is allocated or enqueued
   sens_refuse(who);
   MADIPM_REQUIRE((av == nullptr) == (ar == nullptr),
@@ -1193,37 +1384,11 @@ void MPCSolver::polish(const madipm_polish_opts& o, const int8_t* av, const int8
                  who + "refine_steps must be in 0..8, got " + std::to_string(o.refine_steps));
   hipStream_t s = stream_;
   // ---- allocations, by the first call
-  PostSolve& ps = post_state();
+  polish_buffers(false);
+  PostSolve& ps = *post_;
   Adjoint& a = ps.adj;
   Polish& p = ps.pol;
   const double* cscale = device_con_scale();
-  ps.rowslack(P, s);
-  const int ns = n_ - nx_;
-  if (!p.w.p) {
-    p.w.alloc(std::max(n_ + m_, 1));
-    p.grad.alloc(std::max(n_, 1));
-    p.lo.alloc(std::max(n_, 1));
-    p.hi.alloc(std::max(n_, 1));
-    p.part.alloc((size_t)4 * MAXB);
-    p.ax.alloc(std::max(m_, 1));
-    p.codes.alloc(std::max(n_, 1));
-    p.codes_fact.alloc(std::max(n_, 1));
-    p.codes_fact.zero(s);
-    p.ineq.alloc(std::max(ns, 1));
-    p.ineq.upload(P.ind_ineq.data(), P.ind_ineq.size(), s);
-    p.flags.alloc(2);
-    p.meas.alloc(1);
-  }
-  if (p.bounds_updates != n_updates_) {  // the raw bounds of [x; s], as the last update left them
-    refresh_host_mirrors();
-    std::vector<double> lo(std::max(n_, 1)), hi(std::max(n_, 1));
-    for (int i = 0; i < nx_; ++i) lo[i] = P.lvar[i], hi[i] = P.uvar[i];
-    for (int k = 0; k < ns; ++k) lo[nx_ + k] = P.lcon[P.ind_ineq[k]], hi[nx_ + k] = P.ucon[P.ind_ineq[k]];
-    p.lo.upload(lo, s);
-    p.hi.upload(hi, s);
-    MADIPM_HIP(hipStreamSynchronize(s));  // lo / hi are this scope's
-    p.bounds_updates = n_updates_;
-  }
   const int64_t olen[5] = {nx_, m_, nx_, nx_, m_};
   double* out[5];
   p.out.bind(user, olen, device, out);
@@ -1245,6 +1410,7 @@ void MPCSolver::polish(const madipm_polish_opts& o, const int8_t* av, const int8
   const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_), nbn = blocks(std::max(n_, 1));
   const int64_t N = (int64_t)n_ + m_;
   p.point_solve = -1;  // w, codes and grad are overwritten from here on
+  p.as_point = false;
   p.flags.zero(s);
   k_pol_classify<<<blocks(std::max(std::max(n_, m_), 1)), NT, 0, s>>>(A, dset[0], dset[1], take_fact_end());
   MADIPM_HIP(hipGetLastError());
@@ -1255,7 +1421,7 @@ void MPCSolver::polish(const madipm_polish_opts& o, const int8_t* av, const int8
                                    "not exist, on a fixed variable or on an equality row");
   // ---- the factor: once per point, set and sigma
   bool ok = true;
-  if (p.fact_solve != n_solves_ || p.fact_sigma != o.sigma || hflags[1]) {
+  if (!polish_factor_held() || p.fact_sigma != o.sigma || hflags[1]) {
     p.fact_solve = -1;
     a.fact_solve = -1;  // the adjoint's factor and KKT diagonal are overwritten
     ok = factor_trials([&](double dw, double dc) {
@@ -1263,9 +1429,7 @@ void MPCSolver::polish(const madipm_polish_opts& o, const int8_t* av, const int8
       timed_factorize();
     });
     if (ok) {
-      if (n_) MADIPM_HIP(hipMemcpyAsync(p.codes_fact.p, p.codes.p, (size_t)n_, hipMemcpyDeviceToDevice, s));
-      p.fact_solve = n_solves_;
-      p.fact_sigma = o.sigma;
+      polish_factor_tag(o.sigma);
       ++p.last.n_polish_factorizations;
     }
   }
@@ -1305,6 +1469,10 @@ void MPCSolver::polish(const madipm_polish_opts& o, const int8_t* av, const int8
   }
   p.point_solve = n_solves_;
   p.refine_steps = o.refine_steps;
+  if (hm.verdict == MADIPM_POLISHED) {  // the kept set of the active-set solve (§13h)
+    if (n_) MADIPM_HIP(hipMemcpyAsync(p.codes_kept.p, p.codes.p, (size_t)n_, hipMemcpyDeviceToDevice, s));
+    p.kept = true;
+  }
   ++p.last.n_polishes;
   p.last.verdict = hm.verdict;
   p.last.n_active = hm.n_active;
@@ -1317,6 +1485,171 @@ void MPCSolver::polish(const madipm_polish_opts& o, const int8_t* av, const int8
 void MPCSolver::polish_info(madipm_polish_info* info) const {
   if (!info) return;
   *info = post_ ? post_->pol.last : madipm_polish_info{-1, 0, 0.0, 0.0, 0.0, 0, 0};
+}
+
+// madipm_solver_active_set_solve / _device: up to max_rounds rounds of start (k_as_start), the
+// polish's factor, 1 + refine_steps delta-form solves, final residual, measures and verdict; WRONG_SET before
+// the last round repairs the set (k_as_next) and goes on, every other verdict ends the call.  It needs no
+// solve: everything it reads is what the constructor or the last update left on the device.
+void MPCSolver::active_set_solve(const madipm_active_set_opts& ao, const int8_t* av, const int8_t* ar,
+                                 const madipm_polish_out& po, madipm_active_set_info* info, bool device,
+                                 hipStream_t caller) {
+  const std::string who = device ? "madipm_solver_active_set_solve_device: " : "madipm_solver_active_set_solve: ";
+  const madipm_polish_opts& o = ao.polish;
+  // ---- refusals, before anything is allocated or enqueued
+  MADIPM_REQUIRE(kkt_ == KKT_K2, who + "only kkt_system = SparseKKTSystem (K2) is supported; the K2.5 and "
+                                       "normal-equations formulations are left to a later release");
+  MADIPM_REQUIRE(!comm_, who + "a solver created with a communicator (madipm_solver_create_dist) is not supported");
+  MADIPM_REQUIRE((av == nullptr) == (ar == nullptr),
+                 who + "exactly one of active_var and active_row is given (pass both, or neither for the kept set)");
+  double* const user[5] = {po.x, po.y, po.zl, po.zu, po.cons};
+  MADIPM_REQUIRE(po.x || po.y || po.zl || po.zu || po.cons || po.active_var || po.active_row,
+                 who + "all seven outputs are NULL");
+  auto tol_ok = [](double t) { return t >= 0.0 && std::isfinite(t); };
+  MADIPM_REQUIRE(o.sigma > 0.0 && std::isfinite(o.sigma), who + "sigma must be positive and finite");
+  MADIPM_REQUIRE(tol_ok(o.tol_resid) && tol_ok(o.tol_sign) && tol_ok(o.tol_feas),
+                 who + "tol_resid, tol_sign and tol_feas must be finite and not negative");
+  MADIPM_REQUIRE(o.refine_steps >= 0 && o.refine_steps <= 8,
+                 who + "refine_steps must be in 0..8, got " + std::to_string(o.refine_steps));
+  MADIPM_REQUIRE(ao.max_rounds >= 1 && ao.max_rounds <= 16,
+                 who + "max_rounds must be in 1..16, got " + std::to_string(ao.max_rounds));
+  MADIPM_REQUIRE(av || (post_ && post_->pol.kept),
+                 who + "no set is given and none is kept: no polish or active-set solve on this solver has ended "
+                       "POLISHED yet (pass active_var and active_row)");
+  hipStream_t s = stream_;
+  // ---- allocations, by the first call; the raw bounds of this data
+  polish_buffers(true);
+  PostSolve& ps = *post_;
+  Adjoint& a = ps.adj;
+  Polish& p = ps.pol;
+  const double* cscale = device_con_scale();
+  const int64_t olen[5] = {nx_, m_, nx_, nx_, m_};
+  double* out[5];
+  p.out.bind(user, olen, device, out);
+  const int8_t* const set[2] = {av, ar};
+  int8_t* const uset[2] = {po.active_var, po.active_row};
+  const int64_t slen[2] = {nx_, m_};
+  const int8_t* dset[2];
+  int8_t* oset[2];
+  p.set_in.bind(set, slen, device, dset);
+  p.set_out.bind(uset, slen, device, oset);
+  if (device)  // the set is read, and the outputs written, after the work already enqueued on the caller's stream
+    ps.sync.begin(caller, s);
+  else
+    p.set_in.upload(set, slen, s);
+  const DV D = view();
+  // the iterate's place stays empty: no kernel launched here may read it
+  const PolArgs A{n_, m_, nx_, obj_scale_, nullptr, nullptr, nullptr, nullptr, cscale, lbpos_.p, ubpos_.p, fixed_.p,
+                  p.lo.p, p.hi.p, p.ineq.p, a.rowslack.p, p.codes.p, p.codes_fact.p, p.w.p, p.grad.p, p.flags.p};
+  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_), nbn = blocks(std::max(n_, 1));
+  const int nbt = blocks(std::max(std::max(n_, m_), 1));
+  const int64_t N = (int64_t)n_ + m_;
+  p.point_solve = -1;  // w, codes and grad are overwritten from here on: no current polished point
+  p.as_point = false;
+  PolMeasures hm{};
+  int rounds = 0;
+  for (int k = 1; k <= ao.max_rounds; ++k) {
+    rounds = k;
+    // ---- the start; the first round's set is validated and kept for n_changed
+    p.flags.zero(s);
+    if (k == 1)
+      k_as_start<<<nbt, NT, 0, s>>>(A, dset[0], dset[1], dset[0] ? nullptr : (const int8_t*)p.codes_kept.p,
+                                    p.codes0.p, take_fact_end());
+    else
+      k_as_start<<<nbt, NT, 0, s>>>(A, nullptr, nullptr, nullptr, nullptr, take_fact_end());
+    MADIPM_HIP(hipGetLastError());
+    bool held = false;
+    if (k == 1) {
+      int32_t hflags[2] = {0, 0};
+      MADIPM_HIP(hipMemcpyAsync(hflags, p.flags.p, sizeof(hflags), hipMemcpyDeviceToHost, s));
+      MADIPM_HIP(hipStreamSynchronize(s));
+      if (hflags[0] && device) ps.sync.end(s, caller);
+      MADIPM_REQUIRE(!hflags[0], who + "the supplied set has a code other than -1, 0, +1, or a code on a bound that "
+                                       "does not exist, on a fixed variable or on an equality row");
+      held = polish_factor_held() && p.fact_sigma == o.sigma && !hflags[1];
+    }
+    // ---- the factor: the one held when data, set and sigma are its own; a repaired set is a new one
+    bool ok = true;
+    if (!held) {
+      p.fact_solve = -1;
+      a.fact_solve = -1;  // the adjoint's factor and KKT diagonal are overwritten
+      ok = factor_trials([&](double dw, double dc) {
+        k_pol_diag<<<nb, NT, 0, s>>>(D, p.codes.p, dw, dc, o.sigma, fact_reset());
+        timed_factorize();
+      });
+      if (ok) {
+        polish_factor_tag(o.sigma);
+        ++p.as_last.n_factorizations;
+      }
+    }
+    // ---- 1 + refine_steps solves in delta form, the final residual, the verdict
+    if (ok)
+      for (int it = 0; it <= o.refine_steps; ++it) {
+        SPMV_LAUNCH(k_pol_resid, nbs, s, D, A, d_.p, a.rowres.p, (double*)nullptr, take_fact_end());
+        kkt_solve();
+        k_pol_acc<<<nb, NT, 0, s>>>(A, d_.p);
+      }
+    SPMV_LAUNCH(k_pol_resid, nbs, s, D, A, (double*)nullptr, a.rowres.p, p.grad.p, take_fact_end());
+    k_pol_meas<<<nbn, NT, 0, s>>>(A, p.part.p);
+    k_pol_verdict<<<1, NT, 0, s>>>(a.rowres.p, N, p.part.p, nbn, p.codes.p, n_, o.tol_resid, o.tol_sign, o.tol_feas,
+                                   ok ? 0 : 1, p.meas.p);
+    MADIPM_HIP(hipGetLastError());
+    MADIPM_HIP(hipMemcpyAsync(&hm, p.meas.p, sizeof(hm), hipMemcpyDeviceToHost, s));
+    MADIPM_HIP(hipStreamSynchronize(s));
+    if (hm.verdict != MADIPM_POLISH_WRONG_SET || k == ao.max_rounds) break;
+    // ---- the next set, from this round's violations
+    k_as_next<<<nbn, NT, 0, s>>>(A, p.meas.p, o.tol_sign, o.tol_feas);
+  }
+  // ---- the codes of the last set that differ from the starting set
+  int32_t changed = 0;
+  if (rounds > 1) {
+    p.changed.zero(s);
+    k_as_changed<<<nbn, NT, 0, s>>>(n_, p.codes.p, p.codes0.p, p.changed.p);
+    MADIPM_HIP(hipMemcpyAsync(&changed, p.changed.p, sizeof(changed), hipMemcpyDeviceToHost, s));
+    MADIPM_HIP(hipStreamSynchronize(s));
+  }
+  // ---- outputs: the polished point, or nothing but the last set tried
+  const bool polished = hm.verdict == MADIPM_POLISHED;
+  const bool any5 = out[0] || out[1] || out[2] || out[3] || out[4];
+  if (polished && any5 && std::max(nx_, m_)) {
+    if (out[4]) cons_rows(p.w.p, p.ax.p);
+    k_pol_out<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, p.ax.p, out[0], out[1], out[2], out[3], out[4]);
+  }
+  if ((oset[0] || oset[1]) && std::max(nx_, m_))
+    k_pol_codes<<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, oset[0], oset[1]);
+  if (polished) {  // the kept set of the next call
+    if (n_) MADIPM_HIP(hipMemcpyAsync(p.codes_kept.p, p.codes.p, (size_t)n_, hipMemcpyDeviceToDevice, s));
+    p.kept = true;
+  }
+  MADIPM_HIP(hipGetLastError());
+  if (device) {  // work enqueued on the caller's stream from now on sees the outputs
+    ps.sync.end(s, caller);
+  } else {
+    if (polished) p.out.download(user, olen, s, false);
+    p.set_out.download(uset, slen, s);
+  }
+  if (polished) {  // the current polished point: tangent_polished / adjoint_polished differentiate it
+    p.as_point = true;
+    p.as_updates = n_updates_;
+    p.as_solves = n_solves_;
+    p.as_inits = n_inits_;
+    p.refine_steps = o.refine_steps;
+  }
+  madipm_active_set_info& L = p.as_last;
+  ++L.n_calls;
+  L.verdict = hm.verdict;
+  L.rounds = rounds;
+  L.n_active = hm.n_active;
+  L.n_changed = changed;
+  L.residual = hm.residual;
+  L.min_multiplier = hm.min_multiplier;
+  L.min_gap = hm.min_gap;
+  if (info) *info = L;
+}
+
+void MPCSolver::active_set_info(madipm_active_set_info* info) const {
+  if (!info) return;
+  *info = post_ ? post_->pol.as_last : madipm_active_set_info{-1, 0, 0, 0, 0.0, 0.0, 0.0, 0, 0};
 }
 
 }  // namespace madipm
@@ -1547,6 +1880,7 @@ const char* polish_verdict_name(int v) {
 
 // sens_refuse's refusals, then: the last polish belongs to this solved point and ended POLISHED
 void MPCSolver::polished_refuse(const std::string& who) const {
+  if (active_set_point()) return;  // an active-set solve's point (§13h): it checked K2 and the communicator itself
   sens_refuse(who);
   MADIPM_REQUIRE(post_ && post_->pol.point_solve == n_solves_,
                  who + "no polish has run on the point of the last solve (madipm_solver_polish first)");
@@ -1558,7 +1892,7 @@ void MPCSolver::polished_refuse(const std::string& who) const {
 // The polish's factor back into the LDL^T when an adjoint / tangent overwrote it: the kept codes and sigma
 void MPCSolver::polished_factor(const std::string& who) {
   Polish& p = post_->pol;
-  if (p.fact_solve == n_solves_) return;
+  if (polish_factor_held()) return;
   p.fact_solve = -1;
   post_->adj.fact_solve = -1;  // the adjoint's factor and KKT diagonal are overwritten
   const DV D = view();
@@ -1568,8 +1902,7 @@ void MPCSolver::polished_factor(const std::string& who) {
         timed_factorize();
       }))
     throw Error(who + "the factorisation of the polish's KKT system failed in all three trials", -4);
-  if (n_) MADIPM_HIP(hipMemcpyAsync(p.codes_fact.p, p.codes.p, (size_t)n_, hipMemcpyDeviceToDevice, stream_));
-  p.fact_solve = n_solves_;
+  polish_factor_tag(p.fact_sigma);
   ++post_->sens.n_fact;
 }
 

@@ -564,3 +564,72 @@ function solver_polished_sens_info(h::Ptr{Cvoid})
           "madipm_solver_polished_sens_info")
     return (n_tangents = nt[], n_adjoints = na[], n_factorizations = nf[], last_residual = r[])
 end
+
+# ---- active-set solve of the data the solver holds, without the interior-point method (ABI 0.2.12).  From a
+# starting set (active_var / active_row as in solver_polish; both nothing: the kept set, the codes of the last
+# solver_polish or active-set solve that ended polished) up to max_rounds rounds of the polish's factor, solves and
+# verdict, the set repaired between them.  It needs no solve: it runs on a fresh solver, after an update, or after
+# a solve.  The five blocks are written on verdict 0 only; out_active_var / out_active_row always receive the last
+# set tried.  A polished call's point is the one solver_tangent_polished / solver_adjoint_polished differentiate.
+struct MadipmActiveSetOpts
+    polish::MadipmPolishOpts
+    max_rounds::Int32
+end
+struct MadipmActiveSetInfo
+    verdict::Int32
+    rounds::Int32
+    n_active::Int32
+    n_changed::Int32
+    residual::Float64
+    min_multiplier::Float64
+    min_gap::Float64
+    n_calls::Int64
+    n_factorizations::Int64
+end
+MadipmActiveSetInfo() = MadipmActiveSetInfo(-1, 0, 0, 0, 0.0, 0.0, 0.0, 0, 0)
+
+function active_set_default_opts()
+    o = Ref(MadipmActiveSetOpts(MadipmPolishOpts(0.0, 0.0, 0.0, 0.0, 0), 0))
+    ccall((:madipm_active_set_default_opts, libmadipm), Cvoid, (Ref{MadipmActiveSetOpts},), o)
+    return o[]
+end
+
+# host arrays, as solver_polish
+function solver_active_set_solve(h::Ptr{Cvoid}; opts::MadipmActiveSetOpts=active_set_default_opts(),
+                                 active_var=nothing, active_row=nothing, x=nothing, y=nothing, zl=nothing,
+                                 zu=nothing, cons=nothing, out_active_var=nothing, out_active_row=nothing)
+    info = Ref(MadipmActiveSetInfo())
+    GC.@preserve active_var active_row x y zl zu cons out_active_var out_active_row begin
+        o = Ref(MadipmPolishOut(_ptr_or_null(x), _ptr_or_null(y), _ptr_or_null(zl), _ptr_or_null(zu),
+                                _ptr_or_null(cons), _i8ptr_or_null(out_active_var), _i8ptr_or_null(out_active_row)))
+        check(ccall((:madipm_solver_active_set_solve, libmadipm), Cint,
+                    (Ptr{Cvoid}, Ref{MadipmActiveSetOpts}, Ptr{Int8}, Ptr{Int8}, Ref{MadipmPolishOut},
+                     Ref{MadipmActiveSetInfo}),
+                    h, Ref(opts), _i8ptr_or_null(active_var), _i8ptr_or_null(active_row), o, info),
+              "madipm_solver_active_set_solve")
+    end
+    return info[]
+end
+
+# device arrays and the stream contract of solver_polish_device; the info comes back on the host
+function solver_active_set_solve_device(h::Ptr{Cvoid}; opts::MadipmActiveSetOpts=active_set_default_opts(),
+                                        active_var=nothing, active_row=nothing, x=nothing, y=nothing, zl=nothing,
+                                        zu=nothing, cons=nothing, out_active_var=nothing, out_active_row=nothing,
+                                        stream::Ptr{Cvoid}=C_NULL)
+    info = Ref(MadipmActiveSetInfo())
+    o = Ref(MadipmPolishOut(_dptr_or_null(x), _dptr_or_null(y), _dptr_or_null(zl), _dptr_or_null(zu),
+                            _dptr_or_null(cons), _i8ptr_or_null(out_active_var), _i8ptr_or_null(out_active_row)))
+    check(ccall((:madipm_solver_active_set_solve_device, libmadipm), Cint,
+                (Ptr{Cvoid}, Ref{MadipmActiveSetOpts}, Ptr{Int8}, Ptr{Int8}, Ref{MadipmPolishOut},
+                 Ref{MadipmActiveSetInfo}, Ptr{Cvoid}),
+                h, Ref(opts), _i8ptr_or_null(active_var), _i8ptr_or_null(active_row), o, info, stream),
+          "madipm_solver_active_set_solve_device")
+    return info[]
+end
+
+function solver_active_set_info(h::Ptr{Cvoid})
+    info = Ref(MadipmActiveSetInfo())
+    check(ccall((:madipm_solver_active_set_info, libmadipm), Cint, (Ptr{Cvoid}, Ref{MadipmActiveSetInfo}), h, info),
+          "madipm_solver_active_set_info")
+    return info[]
+end

@@ -191,6 +191,27 @@ _sig("madipm_solver_adjoint_polished_device", C.c_int, [vp, C.POINTER(QPCot), C.
 _sig("madipm_solver_polished_sens_info", C.c_int, [vp, i64p, i64p, i64p, f64p])
 
 
+# active-set solve of the data the solver holds, without the interior-point method (ABI 0.2.12)
+class ActiveSetOpts(C.Structure):
+    """madipm_active_set_opts."""
+    _fields_ = [("polish", PolishOpts), ("max_rounds", C.c_int32)]
+
+
+class ActiveSetInfo(C.Structure):
+    """madipm_active_set_info."""
+    _fields_ = [("verdict", C.c_int32), ("rounds", C.c_int32), ("n_active", C.c_int32), ("n_changed", C.c_int32),
+                ("residual", C.c_double), ("min_multiplier", C.c_double), ("min_gap", C.c_double),
+                ("n_calls", C.c_int64), ("n_factorizations", C.c_int64)]
+
+
+_sig("madipm_active_set_default_opts", None, [C.POINTER(ActiveSetOpts)])
+_sig("madipm_solver_active_set_solve", C.c_int, [vp, C.POINTER(ActiveSetOpts), i8p, i8p, C.POINTER(PolishOut),
+                                                 C.POINTER(ActiveSetInfo)])
+_sig("madipm_solver_active_set_solve_device", C.c_int, [vp, C.POINTER(ActiveSetOpts), i8p, i8p, C.POINTER(PolishOut),
+                                                        C.POINTER(ActiveSetInfo), vp])
+_sig("madipm_solver_active_set_info", C.c_int, [vp, C.POINTER(ActiveSetInfo)])
+
+
 class MadIPMError(RuntimeError):
     pass
 

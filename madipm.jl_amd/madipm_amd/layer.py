@@ -17,6 +17,11 @@ ask a Function for the setup_context form of forward, which QPFunction does not 
 
 With polish=True forward returns the polished point and backward / jvp differentiate it exactly
 (adjoint_device / tangent_device with polished=True): what an active-set QP layer gives.
+
+    layer = QPLayer(solver, outputs=("x", "zl"), polish=True, active_set=True)
+    x, zl = layer(c=c)               # update_device -> active_set_solve_device from the kept set; the
+    layer.last_route                 # interior-point path above when that does not end POLISHED ("active_set" / "ipm")
+
 `import torch` comes before this package in the process, as for every device-route call.
 """
 from __future__ import annotations
@@ -41,11 +46,16 @@ class QPFunction(torch.autograd.Function):
     selected outputs; like backward it must run before the solver is updated or solved again,
     which forward-mode autograd does by calling it right after forward.
     True as a tenth argument (the ninth may be None) polishes: forward returns polish_device's blocks and raises
-    MadIPMError unless the verdict is POLISHED, backward and jvp pass polished=True."""
+    MadIPMError unless the verdict is POLISHED, backward and jvp pass polished=True.
+    A QPLayer as an eleventh argument (with the polish) tries the active-set solve first: after
+    update_device, when the solver keeps a set, active_set_solve_device from it; POLISHED returns its blocks,
+    anything else goes on with the solve and the polish as without it.  The layer's last_route says which."""
 
     @staticmethod
     def forward(ctx, solver, *data):
-        outputs, polish = None, False
+        outputs, polish, layer = None, False, None
+        if len(data) > len(ADJOINT_NAMES) + 2:
+            layer = data[len(ADJOINT_NAMES) + 2]
         if len(data) > len(ADJOINT_NAMES) + 1:
             polish = bool(data[len(ADJOINT_NAMES) + 1])
         if len(data) > len(ADJOINT_NAMES):
@@ -53,6 +63,20 @@ class QPFunction(torch.autograd.Function):
         given = {k: t.detach() for k, t in zip(ADJOINT_NAMES, data) if t is not None}
         if given:
             solver.update_device(**given)
+        if layer is not None:
+            layer.last_route = "ipm"
+            if polish and solver.has_kept_set():
+                res = solver.active_set_solve_device(want=("x",) if outputs is None else outputs)
+                if res["info"]["verdict"] == PolishVerdict.POLISHED:
+                    layer.last_route = "active_set"
+                    ctx.solver = solver
+                    ctx.names = ADJOINT_NAMES
+                    ctx.outputs = outputs
+                    ctx.sens = {"polished": True}
+                    if outputs is None:
+                        return res["x"]
+                    ctx.set_materialize_grads(False)
+                    return tuple(res[k] for k in outputs)
         st = solver.solve(fetch_solution=False)
         if st.status != SOLVE_SUCCEEDED:
             raise MadIPMError(f"QPLayer: the solve ended with status {STATUS_NAMES.get(st.status, st.status)}, "
@@ -121,17 +145,29 @@ class QPLayer(torch.nn.Module):
     polish=True: forward runs update_device -> solve -> polish_device and returns the polished blocks (active
     bounds attained bitwise, inactive multipliers exactly 0); backward and forward-mode autograd differentiate
     that point exactly.  Raises MadIPMError, naming the verdict, when the polish does not end
-    POLISHED: a degenerate face has no unique derivative.  The default is the layer without it, bit for bit."""
+    POLISHED: a degenerate face has no unique derivative.  The default is the layer without it, bit for bit.
 
-    def __init__(self, solver, outputs=("x",), polish=False):
+    active_set=True (needs polish=True): after update_device, when the solver keeps the set of an earlier
+    POLISHED polish or active-set solve, forward first runs active_set_solve_device from it and
+    returns its blocks when it ends POLISHED: no interior-point solve.  Otherwise the path above runs
+    unchanged.  last_route is "active_set" or "ipm" after each forward (None before the first); backward and
+    jvp are the polished ones either way."""
+
+    def __init__(self, solver, outputs=("x",), polish=False, active_set=False):
         super().__init__()
         self.solver = solver
         self.outputs = check_layer_outputs(outputs)
         self.polish = bool(polish)
+        self.active_set = bool(active_set)
+        if self.active_set and not self.polish:
+            raise ValueError("QPLayer: active_set=True requires polish=True")
+        self.last_route = None
 
     def forward(self, c=None, Hvals=None, Avals=None, lcon=None, ucon=None, lvar=None, uvar=None):
         if self.polish:
             outputs = None if self.outputs == ("x",) else self.outputs
+            if self.active_set:
+                return QPFunction.apply(self.solver, c, Hvals, Avals, lcon, ucon, lvar, uvar, outputs, True, self)
             return QPFunction.apply(self.solver, c, Hvals, Avals, lcon, ucon, lvar, uvar, outputs, True)
         if self.outputs == ("x",):
             return QPFunction.apply(self.solver, c, Hvals, Avals, lcon, ucon, lvar, uvar)

@@ -378,6 +378,40 @@ def _polish_info_dict(info) -> dict:
             "n_polish_factorizations": int(info.n_polish_factorizations)}
 
 
+def check_active_set_opts(max_rounds=None, sigma=None, tol_resid=None, tol_sign=None, tol_feas=None,
+                          refine_steps=None) -> tuple:
+    """The options of MPCSolver.active_set_solve / active_set_solve_device, before any library call: the
+    polish's (check_polish_opts) and max_rounds, an integer in 1..16 (None: madipm_active_set_default_opts'
+    4).  Returns (the five polish values, max_rounds)."""
+    opts = check_polish_opts(sigma, tol_resid, tol_sign, tol_feas, refine_steps)
+    if max_rounds is None:
+        d = L.ActiveSetOpts()
+        L.lib.madipm_active_set_default_opts(C.byref(d))
+        max_rounds = d.max_rounds
+    if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)):
+        raise TypeError(f"active_set_solve: max_rounds must be an integer, not {type(max_rounds).__name__}")
+    if not 1 <= int(max_rounds) <= 16:
+        raise ValueError(f"active_set_solve: max_rounds must be in 1..16, got {int(max_rounds)}")
+    return opts, int(max_rounds)
+
+
+def _active_set_info_dict(info) -> dict:
+    v = int(info.verdict)
+    return {"verdict": PolishVerdict(v) if v >= 0 else None, "rounds": int(info.rounds),
+            "n_active": int(info.n_active), "n_changed": int(info.n_changed), "residual": float(info.residual),
+            "min_multiplier": float(info.min_multiplier), "min_gap": float(info.min_gap),
+            "n_calls": int(info.n_calls), "n_factorizations": int(info.n_factorizations)}
+
+
+def _active_set_result(buf: dict, size: dict, names, info) -> dict:
+    """The blocks of an active-set solve: the five point blocks are None unless the verdict is POLISHED (the
+    library did not write them); the set is the last one tried."""
+    ok = int(info.verdict) == PolishVerdict.POLISHED
+    res = {k: (buf[k][:size[k]] if ok or _is_code(k) else None) for k in names}
+    res["info"] = _active_set_info_dict(info)
+    return res
+
+
 def check_layer_outputs(outputs) -> tuple:
     """The `outputs` argument of QPLayer: an ordered selection out of COTANGENT_NAMES without repeats.
     Returns it as a tuple; TypeError for a bare string, ValueError for an unknown or repeated name or an
@@ -581,6 +615,7 @@ class MPCSolver:
         self._update_ready = False  # madipm_solver_prepare_update has run (update() calls it on first use)
         self.qp_current = True      # self.qp's value arrays are the solver's (False after update_device)
         self._device = None         # the solver's torch device, looked up by the first device-route call
+        self._kept_set = False      # a polish or an active-set solve ended POLISHED: the library keeps its set
         q = QPStruct()
         q.nvar, q.ncon = qp.nvar, qp.ncon
         q.nnzh, q.nnzj = qp.nnzh, qp.nnzj
@@ -1084,6 +1119,7 @@ class MPCSolver:
                                            C.byref(info)), "polish")
         res = {k: buf[k][:size[k]] for k in names}
         res["info"] = _polish_info_dict(info)
+        self._kept_set |= info.verdict == PolishVerdict.POLISHED
         return res
 
     def polish_device(self, want=None, stream=None, *, active_var=None, active_row=None, sigma=None, tol_resid=None,
@@ -1109,7 +1145,69 @@ class MPCSolver:
                                                   C.byref(o), C.byref(info), L.vp(st.cuda_stream)), "polish_device")
         res = {k: buf[k][:size[k]] for k in names}
         res["info"] = _polish_info_dict(info)
+        self._kept_set |= info.verdict == PolishVerdict.POLISHED
         return res
+
+    # ------------------------------------------------------------ active-set solve
+    def active_set_solve(self, want=None, *, active_var=None, active_row=None, max_rounds=None, sigma=None,
+                         tol_resid=None, tol_sign=None, tol_feas=None, refine_steps=None) -> dict:
+        """The exact solution of the problem the solver holds (after update(), or on a fresh solver) from a
+        starting active set, without the interior-point method: up to max_rounds (None: 4) rounds of the
+        polish's factor, solves and verdict from a start that reads nothing of the iterate, the set repaired
+        between them from the violations found.  active_var / active_row (both or neither) are the starting
+        set; neither: the kept set, the codes of the last polish() or active-set solve on this solver that
+        ended POLISHED.  Returns a dict over `want` as polish() does; with a verdict other than POLISHED the
+        five point blocks are None and active_var / active_row the last set tried.  "info": verdict (a
+        PolishVerdict), rounds, n_active, n_changed, residual, min_multiplier, min_gap, n_calls,
+        n_factorizations.  A POLISHED call makes its point the one adjoint(polished=True) and
+        tangent(polished=True) differentiate; solve() is untouched.  The arguments are checked before any
+        library call."""
+        names = check_polish_want(want)
+        opts, rounds = check_active_set_opts(max_rounds, sigma, tol_resid, tol_sign, tol_feas, refine_steps)
+        size = self._polish_sizes()
+        sets = check_polish_set(size["active_var"], size["active_row"], active_var, active_row)
+        o = L.PolishOut()
+        buf = _host_outputs(o, size, names)
+        ao = L.ActiveSetOpts(L.PolishOpts(*opts), rounds)
+        info = L.ActiveSetInfo()
+        p = _host_inputs(dict(zip(("active_var", "active_row"), sets)))
+        L.check(L.lib.madipm_solver_active_set_solve(self.h, C.byref(ao), p.get("active_var"), p.get("active_row"),
+                                                     C.byref(o), C.byref(info)), "active_set_solve")
+        self._kept_set |= info.verdict == PolishVerdict.POLISHED
+        return _active_set_result(buf, size, names, info)
+
+    def active_set_solve_device(self, want=None, stream=None, *, active_var=None, active_row=None, max_rounds=None,
+                                sigma=None, tol_resid=None, tol_sign=None, tol_feas=None, refine_steps=None) -> dict:
+        """active_set_solve() into torch tensors on the solver's GPU, with polish_device()'s arguments and
+        stream contract; "info" is a host dict.  The arguments are checked before any library call."""
+        names = check_polish_want(want)
+        opts, rounds = check_active_set_opts(max_rounds, sigma, tol_resid, tol_sign, tol_feas, refine_steps)
+        size = self._polish_sizes()
+        sets = check_polish_set(size["active_var"], size["active_row"], active_var, active_row, on_device=True,
+                                device=self._device)
+        o = L.PolishOut()
+        st, buf, p, _alive = self._device_call(
+            "active_set_solve_device", stream, lambda: check_polish_set(
+                size["active_var"], size["active_row"], active_var, active_row, on_device=True, device=self._device),
+            o, size, names, dict(zip(("active_var", "active_row"), sets)))
+        ao = L.ActiveSetOpts(L.PolishOpts(*opts), rounds)
+        info = L.ActiveSetInfo()
+        L.check(L.lib.madipm_solver_active_set_solve_device(
+            self.h, C.byref(ao), p.get("active_var"), p.get("active_row"), C.byref(o), C.byref(info),
+            L.vp(st.cuda_stream)), "active_set_solve_device")
+        self._kept_set |= info.verdict == PolishVerdict.POLISHED
+        return _active_set_result(buf, size, names, info)
+
+    def has_kept_set(self) -> bool:
+        """A polish() or an active-set solve on this solver has ended POLISHED, so active_set_solve() can start
+        from the set the library kept."""
+        return bool(self._kept_set)
+
+    def active_set_info(self) -> dict:
+        """The last active-set solve's info (verdict None before the first); no device access."""
+        info = L.ActiveSetInfo()
+        L.check(L.lib.madipm_solver_active_set_info(self.h, C.byref(info)), "active_set_info")
+        return _active_set_info_dict(info)
 
     def polish_info(self) -> dict:
         """The last polish()'s info (verdict None before the first); no device access."""

@@ -55,7 +55,17 @@ each with the stream synchronised: polished_tangent_s, polished_adjoint_s (media
 largest), polished_sens_verdicts and polished_sens_refused (the points whose polish did not end POLISHED: the
 calls are refused there, by design: the LP stand-ins are degenerate).  The instance name sparse_qp is the
 strictly complementary 1000 x 600 sparse QP of the tests (tests/adjoint_oracle.py), on which every point is
-polished."""
+polished.
+
+--active-set adds the active-set re-solve: after one update_device + solve + polish_device (which
+leaves a kept set when it ends POLISHED), per updated problem of the same sequence update_device +
+active_set_solve_device from the kept set, stream synchronised (active_set_loop_s; active_set_s without the
+update), beside update_device + solve + polish_device on the same data (active_set_ipm_loop_s): the verdicts, the
+rounds, active_set_share (the part of the problems the active-set route solved: POLISHED) and the counters.  A
+problem whose attempt does not end POLISHED is solved by the interior-point route, whose polish renews the kept set
+when it can; active_set_failed_s is the cost of such an attempt.  While the solver keeps no set (no polish has ended
+POLISHED: the degenerate LP stand-ins) the attempt starts from the set the last polish guessed, supplied.  --rel REL sets the relative noise of every
+sequence (default 1e-3).  The instance name random_qp:N is instances.random_qp with N variables, N / 4 rows and about 8 entries per row."""
 import dataclasses
 import json
 import os
@@ -90,10 +100,16 @@ def build_problem(name):
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import adjoint_oracle
         return adjoint_oracle.sparse_fixture()[0], "strictly complementary sparse QP of the tests, 1000 x 600"
+    if name.startswith("random_qp:"):
+        from madipm_amd import instances
+        n = int(name.split(":")[1])
+        return (instances.random_qp(n // 4, n, density=8.0 / n, seed=0),
+                f"instances.random_qp, {n} box-bounded variables, {n // 4} equality rows, about 8 entries per row")
     return bench.build_problem(name)
 
 
-def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polish=False, polished_sens=False):
+def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polish=False, polished_sens=False,
+        active_set=False):
     qp, desc = build_problem(name)
     opts = bench.solver_opts()
     MPCSolver(qp, **opts)                      # the first construction of a process pays one-off set-up
@@ -367,6 +383,57 @@ def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polis
                      "polished_sens_verdicts": qverd, "polished_sens_refused": refused,
                      **{"polished_" + k: v for k, v in s.polished_sens_info().items() if k != "last_residual"}})
         c = s.counters()
+    if active_set:   # the same data again: the active-set re-solve from the kept set against solve + polish
+        from madipm_amd import PolishVerdict
+        rng = np.random.default_rng(0)
+        s.update_device(**{k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()})
+        first, last_set = "not solved", None   # last_set: the set the last polish tried, whatever its verdict
+        if s.solve(fetch_solution=False).status == 1:
+            pol = s.polish_device()
+            first, last_set = pol["info"]["verdict"].name, (pol["active_var"], pol["active_row"])
+        aloop, acall, afail, iloop, averd, arounds, share = [], [], [], [], {}, [], 0
+        for rep in range(WARMUP + REPS):
+            dnew = {k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()}
+            torch.cuda.synchronize()
+            verdict = None
+            t_loop = t_call = float("nan")
+            if s.has_kept_set() or last_set is not None:
+                # no kept set (no polish has ended POLISHED yet: the degenerate LP stand-ins): the last polish's guess
+                start = {} if s.has_kept_set() else dict(active_var=last_set[0], active_row=last_set[1])
+                t = time.perf_counter()
+                s.update_device(**dnew)
+                t1 = time.perf_counter()
+                res = s.active_set_solve_device(**start)
+                torch.cuda.current_stream().synchronize()
+                t_loop, t_call = time.perf_counter() - t, time.perf_counter() - t1
+                verdict = res["info"]["verdict"]
+            t = time.perf_counter()
+            s.update_device(**dnew)
+            ist = s.solve(fetch_solution=False)
+            if ist.status == 1:
+                pol = s.polish_device()
+                last_set = (pol["active_var"], pol["active_row"])
+            torch.cuda.current_stream().synchronize()
+            t_ipm = time.perf_counter() - t
+            if rep >= WARMUP:
+                v = verdict.name if verdict is not None else "no kept set"
+                averd[v] = averd.get(v, 0) + 1
+                iloop.append(t_ipm)
+                if verdict == PolishVerdict.POLISHED:
+                    share += 1
+                    aloop.append(t_loop)
+                    acall.append(t_call)
+                    arounds.append(res["info"]["rounds"])
+                elif verdict is not None:
+                    afail.append(t_call)
+                    arounds.append(res["info"]["rounds"])
+        med = lambda v: statistics.median(v) if v else float("nan")  # noqa: E731
+        wres.update({"active_set_first_polish": first, "active_set_loop_s": med(aloop), "active_set_s": med(acall),
+                     "active_set_failed_s": med(afail), "active_set_ipm_loop_s": med(iloop),
+                     "active_set_verdicts": averd, "active_set_rounds": arounds, "active_set_share": share / REPS,
+                     **{"active_set_" + k: v for k, v in s.active_set_info().items()
+                        if k in ("n_calls", "n_factorizations")}})
+        c = s.counters()
     update_s, solve_s = statistics.median(upd), statistics.median(sol)
     return {**wres, "instance": name, "description": desc, "nvar": qp.nvar, "ncon": qp.ncon, "nnzj": qp.nnzj, "nnzh": qp.nnzh,
             "construct_s": construct_s, "prepare_update_s": prepare_update_s, "update_s": update_s,
@@ -411,8 +478,16 @@ def main():
     polished_sens = "--polished-sens" in args
     if polished_sens:
         args.remove("--polished-sens")
+    active_set = "--active-set" in args
+    if active_set:
+        args.remove("--active-set")
+    if "--rel" in args:
+        global REL
+        k = args.index("--rel")
+        REL = float(args[k + 1])
+        del args[k:k + 2]
     for name in args or ["ex10", "supportcase10"]:
-        r = run(name, warm, adjoint, adjoint_full, tangent, polish, polished_sens)
+        r = run(name, warm, adjoint, adjoint_full, tangent, polish, polished_sens, active_set)
         print(f"{name}: construct_s {r['construct_s']:.4f}  prepare_update_s {r['prepare_update_s']:.4f}  "
               f"update_s {r['update_s']:.5f}  solve_s {r['solve_s']:.4f}  ->  update + solve "
               f"{r['update_plus_solve_s']:.4f} s against construct + solve {r['construct_plus_solve_s']:.4f} s "
@@ -453,6 +528,13 @@ def main():
                   f"{r['polished_adjoint_s']:.4f} s; verdicts {r['polished_sens_verdicts']}, refused "
                   f"{r['polished_sens_refused']}, residual <= {r['polished_sens_residual']:.1e}, "
                   f"{r['polished_n_factorizations']} factorisations of their own", flush=True)
+        if active_set:
+            print(f"{name}: active-set re-solve: update_device + active_set_solve_device {r['active_set_loop_s']:.4f} s "
+                  f"(the call alone {r['active_set_s']:.4f} s) against update_device + solve + polish_device "
+                  f"{r['active_set_ipm_loop_s']:.4f} s; verdicts {r['active_set_verdicts']}, rounds "
+                  f"{r['active_set_rounds']}, share {r['active_set_share']:.2f}; a failed attempt "
+                  f"{r['active_set_failed_s']:.4f} s; first polish {r['active_set_first_polish']}; "
+                  f"{r['active_set_n_factorizations']} factorisations in {r['active_set_n_calls']} calls", flush=True)
         out.append(r)
     print(json.dumps({"resolve_bench": out, "warmup": WARMUP, "reps": REPS, "rel_noise": REL}))
 
