@@ -763,6 +763,48 @@ int madipm_solver_active_set_solve_device(madipm_solver_t s, const madipm_active
 /* The last active-set solve's info (zeros and verdict -1 before the first); no device access. */
 int madipm_solver_active_set_info(madipm_solver_t s, madipm_active_set_info* info);
 
+/* ------------------------------------------------------------------ batched sensitivities  [ABI 0.2.13, additive]
+ * k tangents or k adjoints of ONE point per call: the columns of a Jacobian, a Gauss-Newton step, several
+ * losses on one solve.  The structs are those of madipm_solver_tangent / _adjoint_full, and every
+ * non-NULL block holds k vectors back to back: vector j of a block of length len starts at j * len.  A NULL
+ * direction / cotangent block is 0 in every column, a NULL output is not wanted; k >= 1.  Column j of every
+ * output is, bit for bit, what the single call returns for column j of the inputs (with gx alone:
+ * madipm_solver_adjoint's bits; with any other cotangent block given: madipm_solver_adjoint_full's for every
+ * column).  (Six symbols, no struct; madipm_version() still returns 203; nothing above changed.)
+ * polished = 0, the central-path point: the columns are processed in chunks of at most W =
+ * madipm_sens_batch_cols().  Per chunk the right-hand sides, the refinement residuals (the KKT operator's
+ * entries and column indices are read once and applied to every column of the chunk) and the outputs are one
+ * launch each instead of one per column; the solves are the single call's, one column after the other, with
+ * the factor the single calls use (one factorisation per solved point, however many batches and single calls
+ * follow).  madipm_solver_tangent_info / _adjoint_info count k more calls and report as last_residual the
+ * largest of the columns' ratios (a NaN is kept).
+ * polished != 0, the point of the last madipm_solver_polish (or POLISHED active-set solve): the columns run one
+ * after another through madipm_solver_tangent_polished / _adjoint_polished with offset pointers: the same bits
+ * by construction, no batched kernels and no saving per column; madipm_solver_polished_sens_info counts k more
+ * calls and reports the last column's residual.
+ * Refused, before anything is allocated or enqueued: k < 1; whatever madipm_solver_tangent / _adjoint_full
+ * (polished: _tangent_polished / _adjoint_polished) refuse, including all blocks or all outputs NULL and the
+ * madipm_solver_prepare_update requirement of Hvals, Avals and lvar.
+ * Memory (polished = 0), allocated by the first batched call that needs it: W columns of what the single call
+ * allocates, 8 B x W x (7 n + 6 ncon + nvar + 1) with all of it in use (n = nvar + inequality rows); on the host
+ * route 8 B x W per entry of each block given or asked for (the chunks are staged one at a time).  A solver
+ * that never batches pays nothing.  The single-column calls are unchanged and share no kernel with these. */
+int madipm_sens_batch_cols(void); /* the chunk width W, a compile-time constant (8) */
+/* HOST pointers, read / written during the call. */
+int madipm_solver_tangent_batch(madipm_solver_t s, int32_t k, const madipm_qp_directions* d,
+                                const madipm_qp_point_tangents* out, int32_t polished);
+int madipm_solver_adjoint_batch(madipm_solver_t s, int32_t k, const madipm_qp_cotangents* g,
+                                const madipm_qp_gradients* out, int32_t polished);
+/* DEVICE pointers, with the stream contract of madipm_solver_tangent_device / _adjoint_device. */
+int madipm_solver_tangent_batch_device(madipm_solver_t s, int32_t k, const madipm_qp_directions* d_d,
+                                       const madipm_qp_point_tangents* d_out, int32_t polished,
+                                       madipm_stream_t stream);
+int madipm_solver_adjoint_batch_device(madipm_solver_t s, int32_t k, const madipm_qp_cotangents* d_g,
+                                       const madipm_qp_gradients* d_out, int32_t polished, madipm_stream_t stream);
+/* Successful batched calls, the columns they held, and the chunks of at most W columns the polished = 0 calls
+ * ran (ceil(k / W) each; a polished batch adds none); no device access.  Any pointer may be NULL. */
+int madipm_solver_sens_batch_info(madipm_solver_t s, int64_t* n_batches, int64_t* n_columns, int64_t* n_chunks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -956,6 +956,61 @@ int madipm_solver_polished_sens_info(madipm_solver_t s, int64_t* n_tangents, int
   MADIPM_API_END
 }
 
+int madipm_sens_batch_cols(void) { return MPCSolver::sens_batch_cols(); }
+
+int madipm_solver_tangent_batch(madipm_solver_t s, int32_t k, const madipm_qp_directions* d,
+                                const madipm_qp_point_tangents* out, int32_t polished) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(d, "madipm_solver_tangent_batch: null direction struct");
+  MADIPM_REQUIRE(out, "madipm_solver_tangent_batch: null output struct");
+  s->s->tangent_batch(k, *d, *out, polished != 0, false, nullptr);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_tangent_batch_device(madipm_solver_t s, int32_t k, const madipm_qp_directions* d_d,
+                                       const madipm_qp_point_tangents* d_out, int32_t polished,
+                                       madipm_stream_t stream) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(d_d, "madipm_solver_tangent_batch_device: null direction struct");
+  MADIPM_REQUIRE(d_out, "madipm_solver_tangent_batch_device: null output struct");
+  s->s->tangent_batch(k, *d_d, *d_out, polished != 0, true, (hipStream_t)stream);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_adjoint_batch(madipm_solver_t s, int32_t k, const madipm_qp_cotangents* g,
+                                const madipm_qp_gradients* out, int32_t polished) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(g, "madipm_solver_adjoint_batch: null cotangent struct");
+  MADIPM_REQUIRE(out, "madipm_solver_adjoint_batch: null output struct");
+  s->s->adjoint_batch(k, *g, *out, polished != 0, false, nullptr);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_adjoint_batch_device(madipm_solver_t s, int32_t k, const madipm_qp_cotangents* d_g,
+                                       const madipm_qp_gradients* d_out, int32_t polished, madipm_stream_t stream) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  MADIPM_REQUIRE(d_g, "madipm_solver_adjoint_batch_device: null cotangent struct");
+  MADIPM_REQUIRE(d_out, "madipm_solver_adjoint_batch_device: null output struct");
+  s->s->adjoint_batch(k, *d_g, *d_out, polished != 0, true, (hipStream_t)stream);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_sens_batch_info(madipm_solver_t s, int64_t* n_batches, int64_t* n_columns, int64_t* n_chunks) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->sens_batch_info(n_batches, n_columns, n_chunks);
+  return 0;
+  MADIPM_API_END
+}
+
 int madipm_update_step(int32_t rule, double tau, double mu, int32_t nlb, int32_t nub, const double* d_x_lr,
                        const double* d_xl_r, const double* d_zl_r, const double* d_dx_lr, const double* d_dzl,
                        const double* d_x_ur, const double* d_xu_r, const double* d_zu_r, const double* d_dx_ur,

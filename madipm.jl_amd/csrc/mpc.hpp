@@ -126,6 +126,16 @@ class MPCSolver {
   void adjoint_polished(const madipm_qp_cotangents& g, const madipm_qp_gradients& out, bool device,
                         hipStream_t caller);
   void polished_sens_info(int64_t* n_tangents, int64_t* n_adjoints, int64_t* n_factorizations, double* last_residual);
+  // k tangents / adjoints of one point per call (madipm_solver_tangent_batch / _adjoint_batch / _device /
+  // _sens_batch_info): every non-null block holds k vectors back to back.  At the end point the
+  // columns run in chunks of sens_batch_cols() through kernels of their own that give each column the single
+  // call's bits; polished: one tangent_polished / adjoint_polished per column.
+  static int sens_batch_cols();
+  void tangent_batch(int32_t k, const madipm_qp_directions& d, const madipm_qp_point_tangents& out, bool polished,
+                     bool device, hipStream_t caller);
+  void adjoint_batch(int32_t k, const madipm_qp_cotangents& g, const madipm_qp_gradients& out, bool polished,
+                     bool device, hipStream_t caller);
+  void sens_batch_info(int64_t* n_batches, int64_t* n_columns, int64_t* n_chunks) const;
   int64_t n_analyses() const { return n_analyses_; }
   int64_t n_updates() const { return n_updates_; }
   double last_update_s() const { return last_update_s_; }
@@ -151,6 +161,8 @@ class MPCSolver {
   bool factor_trials(Enqueue&& enqueue);
   void sens_factor(const std::string& who);
   void sens_solve(double* resid);
+  // the same for the kc columns of a chunk in the batch scratch (§13i); resid[0]: the largest ratio of the call so far
+  void sens_solve_batch(int kc, double* resid, bool first_chunk);
   // the polished sensitivities': the refusals, the polish's factor, the masked solves
   void polished_refuse(const std::string& who) const;
   void polished_factor(const std::string& who);

@@ -2,7 +2,8 @@
 // (DESIGN §13c-§13g).  Each reads the end point of a finished solve, factorises once per point and leaves
 // alone everything a later initialize / solve / warm_start_last reads; the interior-point loop (mpc.hip)
 // knows nothing of the state kept here.  The active-set solve (§13h) runs the polish's kernels on the data the
-// solver holds, from a start that reads no end point, and so needs no solve at all.  Kernels and what they
+// solver holds, from a start that reads no end point, and so needs no solve at all.  The batched sensitivities
+// (§13i) run k columns of one point through kernels of their own, at the end of the file.  Kernels and what they
 // share with the loop's: mpc_kernels.hpp.
 #include <algorithm>
 #include <cmath>
@@ -129,6 +130,40 @@ struct PolSens {
   int64_t n_tangents = 0, n_adjoints = 0, n_fact = 0;
 };
 
+// The batched sensitivities (madipm_solver_tangent_batch / _adjoint_batch) keep SENS_W columns of
+// the single calls' scratch, column-contiguous (column j of a buffer of vectors of length len starts at j len), so
+// that the LDL^T solves one column in place.  Each part by the first batched call that needs it: the solve's
+// vector, the kept right-hand side, the solution, the residual rows and the columns' ratios (8 B x W x (4 (n + m)
+// + 1)); the shift vector and a~'x with the tangent or a cotangent other than gx (8 B x W x (n + m + nvar)); the
+// data terms and the full dx with the tangent (8 B x W x (2 n + m)); the host route's staging of one chunk.
+constexpr int SENS_W = 8;
+struct SensBatch {
+  DBuf<double> d, p, sol, rowres, scal;
+  DBuf<double> shift, apx, base, dx;
+  Staged<double, 7> dir, grad;            // host route: c, Hvals, Avals, lcon, ucon, lvar, uvar
+  Staged<double, 5> out, ct;              // host route: x, y, zl, zu, cons
+  int64_t n_batches = 0, n_columns = 0, n_chunks = 0;
+  // N = n + m.  shifted: the tangent, or a cotangent other than gx; tangent: its data terms and dx
+  void need(int64_t N, int nx, int n, bool shifted, bool tangent) {
+    const auto cols = [](int64_t len) { return std::max<int64_t>(SENS_W * len, 1); };
+    if (!d.p) {
+      d.alloc(cols(N));
+      p.alloc(cols(N));
+      sol.alloc(cols(N));
+      rowres.alloc(cols(N));
+      scal.alloc(SENS_W);
+    }
+    if (shifted && !shift.p) {
+      shift.alloc(cols(N));
+      apx.alloc(cols(nx));
+    }
+    if (tangent && !base.p) {
+      base.alloc(cols(N));
+      dx.alloc(cols(n));
+    }
+  }
+};
+
 // What the calls keep between them, created by the first of them; the tangent, the polish and the polished
 // sensitivities allocate their own parts in their first call.
 struct AdjArgs;
@@ -137,6 +172,7 @@ struct PostSolve {
   Tangent tan;
   Polish pol;
   PolSens sens;
+  SensBatch bat;
   StreamHandoff sync;  // the device routes of all of them
   AdjArgs args(MPCSolver& S);
   // the adjoint's COO indices and fixed-variable lists, the tangent's data terms and entry lists: each by the
@@ -2070,6 +2106,842 @@ void MPCSolver::polished_sens_info(int64_t* n_tangents, int64_t* n_adjoints, int
   if (n_factorizations) *n_factorizations = q ? q->n_fact : 0;
   const int64_t calls = q ? q->n_tangents + q->n_adjoints : 0;
   read_residual(last_residual, calls, calls ? q->scal.p : nullptr, stream_);
+}
+
+}  // namespace madipm
+
+// ======================================================================= batched sensitivities
+// madipm_solver_tangent_batch / _adjoint_batch / _device: k columns of one point per call.  At the end point
+// the columns run in chunks of kc <= SENS_W through the kernels below: the single calls' kernels with the column
+// in blockIdx.y (every expression, and so every bit, is the single kernel's), and the residual k_adj_resid_b,
+// whose lane groups load a row's entries and column indices once and gather from each column's vector.  The
+// solves are ldl_->solve_async on one column after the other.  The single calls launch none of these.
+namespace madipm {
+namespace {
+
+struct BLen {  // entries of Hvals / Avals: the column strides the kernels cannot read from AdjArgs
+  int64_t nh, na;
+};
+// column j of a block of vectors of length len (null stays null)
+__device__ __forceinline__ const double* bcol(const double* p, int j, int64_t len) { return p ? p + j * len : nullptr; }
+__device__ __forceinline__ double* bcol(double* p, int j, int64_t len) { return p ? p + j * len : nullptr; }
+__device__ __forceinline__ AdjArgs adj_col(AdjArgs A, int j) {  // a~ of column j
+  A.d = A.d + j * ((int64_t)A.n + A.m);
+  return A;
+}
+__device__ __forceinline__ TanDir tan_col(const TanDir& T, const AdjArgs& A, const BLen& L, int j) {
+  return TanDir{bcol(T.c, j, A.nx),   bcol(T.Hv, j, L.nh),  bcol(T.Av, j, L.na),  bcol(T.lcon, j, A.m),
+                bcol(T.ucon, j, A.m), bcol(T.lvar, j, A.nx), bcol(T.uvar, j, A.nx)};
+}
+__device__ __forceinline__ AdjFull full_col(const AdjFull& F, const AdjArgs& A, int j) {
+  return AdjFull{bcol(F.gzl, j, A.nx), bcol(F.gzu, j, A.nx), bcol(F.gcons, j, A.m), bcol(F.apx, j, A.nx)};
+}
+
+// ---- the tangent's kernels, column blockIdx.y (bodies: k_tan_shift, k_tan_data, k_tan_rhs, k_tan_out, k_tan_cons)
+__global__ __launch_bounds__(NT) void k_tan_shift_b(AdjArgs A, TanDir T0, BLen L, const int32_t* __restrict__ rowslack,
+                                                    double* __restrict__ vb, LDLStatus* t1) {
+#pragma clang fp contract(off)
+  if (t1 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  const int col = blockIdx.y;
+  const TanDir T = tan_col(T0, A, L, col);
+  double* __restrict__ v = vb + col * ((int64_t)A.n + A.m);
+  GRID_LOOP(i, A.n + A.m) {
+    if (i < A.nx) {
+      double o = 0.0;
+      if (!A.fixed[i]) {
+        const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
+        if (sm > 0.0) o = (sl * tan_dl(A, T, (int)i) + su * tan_du(A, T, (int)i)) / sm;
+      }
+      v[i] = o;
+    } else if (i >= A.n) {
+      const int r = (int)(i - A.n), k = rowslack[r];
+      v[i] = 0.0;
+      if (k >= 0) {
+        const double sl = adj_sig_l(A, k), su = adj_sig_u(A, k), sm = sl + su;
+        const double dl = (T.lcon && A.lbpos[k] >= 0) ? T.lcon[r] : 0.0;
+        const double du = (T.ucon && A.ubpos[k] >= 0) ? T.ucon[r] : 0.0;
+        v[k] = sm > 0.0 ? A.cscale[r] * ((sl * dl + su * du) / sm) : 0.0;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_tan_data_b(AdjArgs A, TanDir T0, BLen L, const int32_t* __restrict__ gsp,
+                                                   const int2* __restrict__ ge, const int32_t* __restrict__ csp,
+                                                   const int2* __restrict__ ce, const int32_t* __restrict__ asp,
+                                                   const int2* __restrict__ ae, const double* __restrict__ Hraw,
+                                                   const double* __restrict__ Araw, double* __restrict__ baseb) {
+#pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const TanDir T = tan_col(T0, A, L, col);
+  double* __restrict__ base = baseb + col * ((int64_t)A.n + A.m);
+  GRID_LOOP(i, A.n + A.m) {
+    double o = 0.0;
+    if (i < A.nx) {
+      if (!A.fixed[i]) {
+        double hs = 0.0, as = 0.0;
+        if (gsp) {
+          for (int q = gsp[i]; q < gsp[i + 1]; ++q) {
+            const int2 e = ge[q];
+            if (T.Hv) hs = hs + T.Hv[e.x] * A.x[e.y];
+            if (T.lvar && A.fixed[e.y]) hs = hs + Hraw[e.x] * T.lvar[e.y];
+          }
+          if (T.Av)
+            for (int q = csp[i]; q < csp[i + 1]; ++q) {
+              const int2 e = ce[q];
+              as = as + T.Av[e.x] * (A.cscale[e.y] * A.y[e.y]);
+            }
+        }
+        const double dc = T.c ? T.c[i] : 0.0;
+        o = -((A.os * A.sgn) * (dc + hs) + as);
+      }
+    } else if (i >= A.n) {
+      const int r = (int)(i - A.n);
+      if (asp)
+        for (int q = asp[r]; q < asp[r + 1]; ++q) {
+          const int2 e = ae[q];
+          if (T.Av) o = o + T.Av[e.x] * A.x[e.y];
+          if (T.lvar && A.fixed[e.y]) o = o + Araw[e.x] * T.lvar[e.y];
+        }
+    }
+    base[i] = o;
+  }
+}
+
+// bd: the solves' vectors, bp: the right-hand sides kept for the residual (DV's d and p of the single call)
+template <int G>
+__global__ __launch_bounds__(NT) void k_tan_rhs_b(DV D, AdjArgs A, TanDir T0, BLen L,
+                                                  const int32_t* __restrict__ rowslack, const double* __restrict__ vb,
+                                                  const double* __restrict__ baseb, double* __restrict__ bd,
+                                                  double* __restrict__ bp) {
+#pragma clang fp contract(off)
+  const int n = D.n, m = D.m;
+  const int col = blockIdx.y;
+  const int64_t off = col * ((int64_t)n + m);
+  const TanDir T = tan_col(T0, A, L, col);
+  const double* __restrict__ v = vb + off;
+  const double* __restrict__ base = baseb + off;
+  const bool lead = (threadIdx.x & (G - 1)) == 0;
+  GROUP_LOOP(i, n + m, G) {
+    double g = 0.0;
+    if (i < n) {
+      if (i < D.nx && !D.fixed[i]) g = base[i] - gdot<G>(D.H, i, v);
+    } else {
+      const int r = (int)(i - n);
+      const double jq = gdot<G>(D.J, r, v);
+      const double db = (T.lcon && rowslack[r] < 0) ? T.lcon[r] : 0.0;
+      g = A.cscale[r] * (db - base[i]) - jq;
+    }
+    if (lead) {
+      bd[off + i] = g;
+      bp[off + i] = g;
+    }
+  }
+}
+
+// A0.d: the solutions' columns; ox .. ozu: the output blocks' first column of the chunk (null: not wanted)
+__global__ __launch_bounds__(NT) void k_tan_out_b(AdjArgs A0, TanDir T0, BLen L, const double* __restrict__ vb,
+                                                  double* __restrict__ dxsb, double* __restrict__ oxb,
+                                                  double* __restrict__ oyb, double* __restrict__ ozlb,
+                                                  double* __restrict__ ozub) {
+#pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const AdjArgs A = adj_col(A0, col);
+  const TanDir T = tan_col(T0, A, L, col);
+  const double* __restrict__ v = vb + col * ((int64_t)A.n + A.m);
+  double* __restrict__ dxs = dxsb + col * (int64_t)A.n;
+  double* __restrict__ ox = bcol(oxb, col, A.nx);
+  double* __restrict__ oy = bcol(oyb, col, A.m);
+  double* __restrict__ ozl = bcol(ozlb, col, A.nx);
+  double* __restrict__ ozu = bcol(ozub, col, A.nx);
+  const int ns = A.n - A.nx;
+  const int top = A.nx > A.m ? A.nx : A.m;
+  GRID_LOOP(i, (top > ns ? top : ns)) {
+    if (i < A.nx) {
+      double dx, dzl = 0.0, dzu = 0.0;
+      if (A.fixed[i]) {
+        dx = T.lvar ? T.lvar[i] : 0.0;
+      } else {
+        const double dxp = A.d[i];
+        dx = dxp + v[i];
+        const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
+        const double hd = sm > 0.0 ? ((sl * su / sm) / A.os) * (tan_dl(A, T, (int)i) - tan_du(A, T, (int)i)) : 0.0;
+        if (A.lbpos[i] >= 0) dzl = hd - (sl / A.os) * dxp;
+        if (A.ubpos[i] >= 0) dzu = (su / A.os) * dxp + hd;
+      }
+      dxs[i] = dx;
+      if (ox) ox[i] = dx;
+      if (ozl) ozl[i] = dzl;
+      if (ozu) ozu[i] = dzu;
+    }
+    if (i < ns) dxs[A.nx + i] = 0.0;
+    if (i < A.m && oy) oy[i] = A.d[A.n + i] * A.cscale[i] / A.os;
+  }
+}
+
+template <int G>
+__global__ __launch_bounds__(NT) void k_tan_cons_b(DV D, AdjArgs A, const double* __restrict__ dxsb,
+                                                   const double* __restrict__ baseb, double* __restrict__ oconsb) {
+#pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const double* __restrict__ dxs = dxsb + col * (int64_t)D.n;
+  const double* __restrict__ base = baseb + col * ((int64_t)D.n + D.m);
+  double* __restrict__ ocons = oconsb + col * (int64_t)D.m;
+  const bool lead = (threadIdx.x & (G - 1)) == 0;
+  GROUP_LOOP(r, D.m, G) {
+    const double s = gdot<G>(D.J, r, dxs);
+    if (lead) ocons[r] = s / A.cscale[r] + base[D.n + r];
+  }
+}
+
+// ---- the adjoint's kernels, column blockIdx.y (bodies: k_adj_shift, k_adj_rhs_full, k_adj_rhs, k_adj_unshift,
+// k_adj_vec, k_adj_avals, k_adj_hvals, k_adj_fix)
+__global__ __launch_bounds__(NT) void k_adj_shift_b(AdjArgs A, AdjFull F0, double* __restrict__ vb, LDLStatus* t1) {
+#pragma clang fp contract(off)
+  if (t1 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  const int col = blockIdx.y;
+  const AdjFull F = full_col(F0, A, col);
+  double* __restrict__ v = vb + col * ((int64_t)A.n + A.m);
+  GRID_LOOP(i, A.n + A.m) {
+    double o = 0.0;
+    if (i < A.nx) {
+      if (!A.fixed[i]) {
+        const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
+        if (sm > 0.0) o = ((sl * adj_gzl(A, F, (int)i) - su * adj_gzu(A, F, (int)i)) / sm) / A.os;
+      }
+    } else if (i >= A.n && F.gcons) {
+      o = F.gcons[i - A.n] / A.cscale[i - A.n];
+    }
+    v[i] = o;
+  }
+}
+
+template <int G>
+__global__ __launch_bounds__(NT) void k_adj_rhs_full_b(DV D, AdjArgs A, const double* __restrict__ gxb,
+                                                       const double* __restrict__ gyb, const double* __restrict__ vb,
+                                                       double* __restrict__ bd, double* __restrict__ bp) {
+#pragma clang fp contract(off)
+  const int n = D.n, m = D.m;
+  const int col = blockIdx.y;
+  const int64_t off = col * ((int64_t)n + m);
+  const double* __restrict__ gx = bcol(gxb, col, D.nx);
+  const double* __restrict__ gy = bcol(gyb, col, m);
+  const double* __restrict__ v = vb + off;
+  const bool lead = (threadIdx.x & (G - 1)) == 0;
+  GROUP_LOOP(i, n + m, G) {
+    double g = 0.0;
+    if (i < n) {
+      if (i < D.nx && !D.fixed[i]) {
+        double hd, jd;
+        gdot2<G>(D.H, i, v, D.JT, i, v + n, hd, jd);
+        g = (gx ? gx[i] : 0.0) + (hd + jd);
+      }
+    } else {
+      const double jq = gdot<G>(D.J, i - n, v);
+      g = (gy ? A.cscale[i - n] * gy[i - n] / A.os : 0.0) + jq;
+    }
+    if (lead) {
+      bd[off + i] = g;
+      bp[off + i] = g;
+    }
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_adj_rhs_b(DV D, const double* __restrict__ gxb, double* __restrict__ bd,
+                                                  double* __restrict__ bp, LDLStatus* t1) {
+  if (t1 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  const int col = blockIdx.y;
+  const int64_t off = col * ((int64_t)D.n + D.m);
+  const double* __restrict__ gx = gxb + col * (int64_t)D.nx;
+  GRID_LOOP(i, D.n + D.m) {
+    const double v = (i < D.nx && !D.fixed[i]) ? gx[i] : 0.0;
+    bd[off + i] = v;
+    bp[off + i] = v;
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_adj_unshift_b(int nx, int64_t N, const double* __restrict__ vb,
+                                                      double* __restrict__ solb, double* __restrict__ apxb) {
+  const int col = blockIdx.y;
+  const double* __restrict__ v = vb + col * N;
+  double* __restrict__ sol = solb + col * N;
+  double* __restrict__ apx = apxb + col * (int64_t)nx;
+  GRID_LOOP(i, nx) {
+    const double ap = sol[i];
+    apx[i] = ap;
+    sol[i] = ap - v[i];
+  }
+}
+
+// The refinement residual of the chunk's kc columns (k_adj_resid for each): a lane group per K2 row loads its
+// entries of H~ and J~^T (or J~) and their column indices once per trip, two entries a trip as gdot / gdot2 issue
+// them, and gathers from each column's vector; one fma chain per column in gdot's order, each with gdot's
+// butterfly; Sigma_l + Sigma_u once per row.  g: the kept right-hand sides; v: the current a~; r (may be null):
+// the next solves' right-hand sides.
+template <int G>
+__device__ __forceinline__ void gdot_b(const DCsr& A, int64_t row, const double* __restrict__ x, int64_t ld, int kc,
+                                       double (&s)[SENS_W]) {
+  const int gl = threadIdx.x & (G - 1);
+#pragma unroll
+  for (int j = 0; j < SENS_W; ++j) s[j] = 0.0;
+  const int64_t q1 = A.rp[row + 1];
+  for (int64_t q = A.rp[row] + gl; q < q1; q += 2 * G) {
+    const int64_t qb = min(q + G, q1 - 1);
+    const double va = A.v[q], vb = A.v[qb];
+    const int64_t ca = A.ci[q], cb = A.ci[qb];
+    const double vb0 = (q + G < q1) ? vb : 0.0;
+    double xa[SENS_W], xb[SENS_W];
+#pragma unroll
+    for (int j = 0; j < SENS_W; ++j)
+      if (j < kc) {
+        xa[j] = x[ca + j * ld];
+        xb[j] = x[cb + j * ld];
+      }
+#pragma unroll
+    for (int j = 0; j < SENS_W; ++j)
+      if (j < kc) {
+        s[j] = fma(va, xa[j], s[j]);
+        s[j] = fma(vb0, xb[j], s[j]);
+      }
+  }
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) {
+#pragma unroll
+    for (int j = 0; j < SENS_W; ++j)
+      if (j < kc) s[j] += __shfl_xor(s[j], o, G);
+  }
+}
+
+template <int G>
+__device__ __forceinline__ void gdot2_b(const DCsr& A, int64_t ra, const double* __restrict__ xa, const DCsr& B,
+                                        int64_t rb, const double* __restrict__ xb, int64_t ld, int kc,
+                                        double (&sa)[SENS_W], double (&sb)[SENS_W]) {
+  const int gl = threadIdx.x & (G - 1);
+  const int64_t a1 = A.rp[ra + 1], b1 = B.rp[rb + 1];
+  int64_t qa = A.rp[ra] + gl, qb = B.rp[rb] + gl;
+#pragma unroll
+  for (int j = 0; j < SENS_W; ++j) {
+    sa[j] = 0.0;
+    sb[j] = 0.0;
+  }
+  while (qa < a1 || qb < b1) {
+    const bool ta = qa < a1, tb = qb < b1;
+    double va = 0.0, va2 = 0.0, vb = 0.0, vb2 = 0.0;
+    int64_t ia = 0, ia2 = 0, ib = 0, ib2 = 0;
+    if (ta) {
+      const int64_t q2 = min(qa + G, a1 - 1);
+      va = A.v[qa];
+      va2 = (qa + G < a1) ? A.v[q2] : 0.0;
+      ia = A.ci[qa];
+      ia2 = A.ci[q2];
+    }
+    if (tb) {
+      const int64_t q2 = min(qb + G, b1 - 1);
+      vb = B.v[qb];
+      vb2 = (qb + G < b1) ? B.v[q2] : 0.0;
+      ib = B.ci[qb];
+      ib2 = B.ci[q2];
+    }
+    double ya[SENS_W], ya2[SENS_W], yb[SENS_W], yb2[SENS_W];
+#pragma unroll
+    for (int j = 0; j < SENS_W; ++j)
+      if (j < kc) {
+        if (ta) {
+          ya[j] = xa[ia + j * ld];
+          ya2[j] = xa[ia2 + j * ld];
+        }
+        if (tb) {
+          yb[j] = xb[ib + j * ld];
+          yb2[j] = xb[ib2 + j * ld];
+        }
+      }
+#pragma unroll
+    for (int j = 0; j < SENS_W; ++j)
+      if (j < kc) {
+        if (ta) {
+          sa[j] = fma(va, ya[j], sa[j]);
+          sa[j] = fma(va2, ya2[j], sa[j]);
+        }
+        if (tb) {
+          sb[j] = fma(vb, yb[j], sb[j]);
+          sb[j] = fma(vb2, yb2[j], sb[j]);
+        }
+      }
+    if (ta) qa += 2 * G;
+    if (tb) qb += 2 * G;
+  }
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) {
+#pragma unroll
+    for (int j = 0; j < SENS_W; ++j)
+      if (j < kc) {
+        sa[j] += __shfl_xor(sa[j], o, G);
+        sb[j] += __shfl_xor(sb[j], o, G);
+      }
+  }
+}
+
+template <int G>
+__global__ __launch_bounds__(NT) void k_adj_resid_b(DV D, AdjArgs A, int kc, const double* __restrict__ g,
+                                                    const double* __restrict__ v, double* __restrict__ r,
+                                                    double* __restrict__ rowres) {
+  const int n = D.n, m = D.m;
+  const int64_t N = (int64_t)n + m;
+  const bool lead = (threadIdx.x & (G - 1)) == 0;
+  GROUP_LOOP(i, n + m, G) {
+    double kv[SENS_W];
+    if (i < n) {
+      double hd[SENS_W], jd[SENS_W];
+      gdot2_b<G>(D.H, i, v, D.JT, i, v + n, N, kc, hd, jd);
+      const double sig = adj_sig_l(A, (int)i) + adj_sig_u(A, (int)i);
+#pragma unroll
+      for (int j = 0; j < SENS_W; ++j)
+        if (j < kc) kv[j] = (hd[j] + jd[j]) + sig * v[i + j * N];
+    } else {
+      gdot_b<G>(D.J, i - n, v, N, kc, kv);
+    }
+    if (lead) {
+#pragma unroll
+      for (int j = 0; j < SENS_W; ++j)
+        if (j < kc) {
+          const double ri = g[i + j * N] - kv[j];
+          if (r) r[i + j * N] = ri;
+          rowres[i + j * N] = fabs(ri);
+        }
+    }
+  }
+}
+
+// k_adj_resmax of column blockIdx.x: out[column] = max_i rowres[i] / max(1, max_i |g_i|)
+__global__ __launch_bounds__(NT) void k_adj_resmax_b(const double* __restrict__ rowresb, const double* __restrict__ gb,
+                                                     int64_t N, double* __restrict__ out) {
+  __shared__ double sw[NT], sg[NT];
+  const int t = threadIdx.x;
+  const double* __restrict__ rowres = rowresb + blockIdx.x * N;
+  const double* __restrict__ g = gb + blockIdx.x * N;
+  double w = 0.0, gm = 0.0;
+  for (int64_t i = t; i < N; i += NT) {
+    w = nmax(w, rowres[i]);
+    gm = nmax(gm, fabs(g[i]));
+  }
+  sw[t] = w;
+  sg[t] = gm;
+  __syncthreads();
+  for (int o = NT / 2; o > 0; o >>= 1) {
+    if (t < o) {
+      sw[t] = nmax(sw[t], sw[t + o]);
+      sg[t] = nmax(sg[t], sg[t + o]);
+    }
+    __syncthreads();
+  }
+  if (t == 0) out[blockIdx.x] = sw[0] / (sg[0] > 1.0 ? sg[0] : 1.0);
+}
+
+// out[0] = the largest of the chunk's ratios and, after the call's first chunk, of out[0] (a NaN is kept)
+__global__ void k_sens_fold(const double* __restrict__ col, int kc, int first, double* __restrict__ out) {
+  if (blockIdx.x || threadIdx.x) return;
+  double w = first ? col[0] : out[0];
+  for (int j = first ? 1 : 0; j < kc; ++j) w = nmax(w, col[j]);
+  out[0] = w;
+}
+
+template <bool FULL>
+__global__ __launch_bounds__(NT) void k_adj_vec_b(AdjArgs A0, AdjFull F0, const int32_t* __restrict__ rowslack,
+                                                  double* __restrict__ gcb, double* __restrict__ glvb,
+                                                  double* __restrict__ guvb, double* __restrict__ glcb,
+                                                  double* __restrict__ gucb) {
+#pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const AdjArgs A = adj_col(A0, col);
+  const AdjFull F = full_col(F0, A, col);
+  double* __restrict__ gc = bcol(gcb, col, A.nx);
+  double* __restrict__ glv = bcol(glvb, col, A.nx);
+  double* __restrict__ guv = bcol(guvb, col, A.nx);
+  double* __restrict__ glc = bcol(glcb, col, A.m);
+  double* __restrict__ guc = bcol(gucb, col, A.m);
+  GRID_LOOP(i, (A.nx > A.m ? A.nx : A.m)) {
+    if (i < A.nx) {
+      const bool fx = A.fixed[i];
+      const double at = fx ? 0.0 : A.d[i];
+      if (gc) gc[i] = -(A.sgn * (A.os * at));
+      if (!fx) {
+        if constexpr (FULL) {
+          const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
+          const double ap = F.apx[i];
+          const double hg = sm > 0.0 ? (sl * su / sm) / A.os * (adj_gzl(A, F, (int)i) + adj_gzu(A, F, (int)i)) : 0.0;
+          if (glv) glv[i] = sl * ap + hg;
+          if (guv) guv[i] = su * ap - hg;
+        } else {
+          if (glv) glv[i] = adj_sig_l(A, (int)i) * at;
+          if (guv) guv[i] = adj_sig_u(A, (int)i) * at;
+        }
+      } else if (guv) {
+        guv[i] = 0.0;
+      }
+    }
+    if (i < A.m && (glc || guc)) {
+      const int k = rowslack[i];
+      const double cs = A.cscale[i];
+      if (k < 0) {
+        if (glc) glc[i] = cs * A.d[A.n + i];
+        if (guc) guc[i] = 0.0;
+      } else {
+        const double as = A.d[k];
+        if (glc) glc[i] = cs * (adj_sig_l(A, k) * as);
+        if (guc) guc[i] = cs * (adj_sig_u(A, k) * as);
+      }
+    }
+  }
+}
+
+template <bool FULL>
+__global__ __launch_bounds__(NT) void k_adj_avals_b(AdjArgs A0, AdjFull F0, int64_t nnz,
+                                                    const int32_t* __restrict__ Ar, const int32_t* __restrict__ Ac,
+                                                    double* __restrict__ outb) {
+#pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const AdjArgs A = adj_col(A0, col);
+  const AdjFull F = full_col(F0, A, col);
+  double* __restrict__ out = outb + col * nnz;
+  GRID_LOOP(k, nnz) {
+    const int r = Ar[k], c = Ac[k];
+    const double yr = A.y[r] * A.cscale[r] / A.os;
+    const double v = -(adj_ax(A, c) * yr + adj_ay(A, r) * A.x[c]);
+    if constexpr (FULL)
+      out[k] = F.gcons ? v + F.gcons[r] * A.x[c] : v;
+    else
+      out[k] = v;
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_adj_hvals_b(AdjArgs A0, int64_t nnz, const int32_t* __restrict__ Hr,
+                                                    const int32_t* __restrict__ Hc, double* __restrict__ outb) {
+#pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const AdjArgs A = adj_col(A0, col);
+  double* __restrict__ out = outb + col * nnz;
+  GRID_LOOP(k, nnz) {
+    const int r = Hr[k], c = Hc[k];
+    const double ar = adj_ax(A, r);
+    const double v = r == c ? ar * A.x[r] : ar * A.x[c] + adj_ax(A, c) * A.x[r];
+    out[k] = -(A.sgn * v);
+  }
+}
+
+template <bool FULL>
+__global__ __launch_bounds__(NT) void k_adj_fix_b(AdjArgs A0, AdjFull F0, int nfix, const int32_t* __restrict__ fix,
+                                                  const int32_t* __restrict__ fhsp, const int2* __restrict__ fh,
+                                                  const int32_t* __restrict__ fasp, const int2* __restrict__ fa,
+                                                  const double* __restrict__ Hraw, const double* __restrict__ Araw,
+                                                  const double* __restrict__ gxb, double* __restrict__ glvb) {
+#pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const AdjArgs A = adj_col(A0, col);
+  const AdjFull F = full_col(F0, A, col);
+  const double* __restrict__ gx = bcol(gxb, col, A.nx);
+  double* __restrict__ glv = glvb + col * (int64_t)A.nx;
+  GRID_LOOP(t, nfix) {
+    double hs = 0.0, as = 0.0;
+    for (int q = fhsp[t]; q < fhsp[t + 1]; ++q) {
+      const int2 e = fh[q];
+      hs = hs + Hraw[e.x] * (A.os * A.d[e.y]);
+    }
+    for (int q = fasp[t]; q < fasp[t + 1]; ++q) {
+      const int2 e = fa[q];
+      as = as + Araw[e.x] * adj_ay(A, e.y);
+    }
+    const int f = fix[t];
+    if constexpr (FULL) {
+      double gs = 0.0;
+      if (F.gcons)
+        for (int q = fasp[t]; q < fasp[t + 1]; ++q) {
+          const int2 e = fa[q];
+          gs = gs + Araw[e.x] * F.gcons[e.y];
+        }
+      glv[f] = ((gx ? gx[f] : 0.0) + gs) - A.sgn * hs - as;
+    } else {
+      glv[f] = gx[f] - A.sgn * hs - as;
+    }
+  }
+}
+
+// column c0 of a block of the caller's (null stays null)
+template <class T>
+T* at_col(T* p, int64_t c0, int64_t len) {
+  return p ? p + c0 * len : nullptr;
+}
+
+// launch a GROUP_LOOP SpMV kernel over the chunk's columns (grid.y) with the problem's lane-group width
+#define SPMV_LAUNCH_B(kern, grid, kc, strm, ...)                                             \
+  do {                                                                                       \
+    switch (spmv_g_) {                                                                       \
+      case 4: kern<4><<<dim3((grid), (kc)), NT, 0, (strm)>>>(__VA_ARGS__); break;            \
+      case 8: kern<8><<<dim3((grid), (kc)), NT, 0, (strm)>>>(__VA_ARGS__); break;            \
+      case 16: kern<16><<<dim3((grid), (kc)), NT, 0, (strm)>>>(__VA_ARGS__); break;          \
+      case 32: kern<32><<<dim3((grid), (kc)), NT, 0, (strm)>>>(__VA_ARGS__); break;          \
+      default: kern<64><<<dim3((grid), (kc)), NT, 0, (strm)>>>(__VA_ARGS__); break;          \
+    }                                                                                        \
+  } while (0)
+
+}  // namespace
+
+int MPCSolver::sens_batch_cols() { return SENS_W; }
+
+// With the chunk's right-hand sides in bat.d (and in bat.p, which keeps them): bat.sol = K^-1 bat.p column by
+// column, refined as sens_solve refines; the largest residual ratio into resid[0]
+void MPCSolver::sens_solve_batch(int kc, double* resid, bool first_chunk) {
+  SensBatch& b = post_->bat;
+  AdjArgs A = post_->args(*this);
+  A.d = b.sol.p;
+  const DV D = view();
+  hipStream_t s = stream_;
+  const int64_t N = (int64_t)n_ + m_;
+  const int nb = blocks(kc * N), nbs = spmv_blocks(n_ + m_);
+  auto solves = [&] {
+    for (int j = 0; j < kc; ++j) ldl_->solve_async(b.d.p + j * N, s);
+  };
+  solves();
+  k_adj_acc<<<nb, NT, 0, s>>>(b.sol.p, b.d.p, kc * N, 1);  // the columns are contiguous: one flat pass
+  for (int it = 0; it < adj_refine_steps(); ++it) {
+    SPMV_LAUNCH(k_adj_resid_b, nbs, s, D, A, kc, (const double*)b.p.p, (const double*)b.sol.p, b.d.p, b.rowres.p);
+    solves();
+    k_adj_acc<<<nb, NT, 0, s>>>(b.sol.p, b.d.p, kc * N, 0);
+  }
+  SPMV_LAUNCH(k_adj_resid_b, nbs, s, D, A, kc, (const double*)b.p.p, (const double*)b.sol.p, (double*)nullptr,
+              b.rowres.p);
+  k_adj_resmax_b<<<kc, NT, 0, s>>>(b.rowres.p, b.p.p, N, b.scal.p);
+  k_sens_fold<<<1, 1, 0, s>>>(b.scal.p, kc, first_chunk ? 1 : 0, resid);
+}
+
+void MPCSolver::tangent_batch(int32_t k, const madipm_qp_directions& dr, const madipm_qp_point_tangents& o,
+                              bool polished, bool device, hipStream_t caller) {
+  const std::string who = device ? "madipm_solver_tangent_batch_device: " : "madipm_solver_tangent_batch: ";
+  QPHost& P = *H_;
+  // ---- refusals, before anything is allocated or enqueued
+  MADIPM_REQUIRE(k >= 1, who + "k = " + std::to_string(k) + ", a batch holds at least one column");
+  if (polished)
+    polished_refuse(who);
+  else
+    sens_refuse(who);
+  const double* const dir[7] = {dr.c, dr.Hvals, dr.Avals, dr.lcon, dr.ucon, dr.lvar, dr.uvar};
+  double* const user[5] = {o.x, o.y, o.zl, o.zu, o.cons};
+  MADIPM_REQUIRE(dr.c || dr.Hvals || dr.Avals || dr.lcon || dr.ucon || dr.lvar || dr.uvar,
+                 who + "all seven directions are NULL");
+  MADIPM_REQUIRE(o.x || o.y || o.zl || o.zu || o.cons, who + "all five outputs are NULL");
+  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
+  const bool needLists = (dr.Avals && na > 0) || (dr.Hvals && nh > 0) || (dr.lvar && P.anyfix);
+  MADIPM_REQUIRE(plan_ || !needLists,
+                 who + "Avals, Hvals (and lvar on a problem with fixed variables) need "
+                       "madipm_solver_prepare_update first (it keeps the index arrays and the raw values)");
+  const int64_t dlen[7] = {nx_, nh, na, m_, m_, nx_, nx_};
+  const int64_t olen[5] = {nx_, m_, nx_, nx_, m_};
+  if (polished) {  // the single polished call per column, with offset pointers: its bits by construction
+    for (int64_t j = 0; j < k; ++j) {
+      const madipm_qp_directions dj{at_col(dir[0], j, dlen[0]), at_col(dir[1], j, dlen[1]), at_col(dir[2], j, dlen[2]),
+                                    at_col(dir[3], j, dlen[3]), at_col(dir[4], j, dlen[4]), at_col(dir[5], j, dlen[5]),
+                                    at_col(dir[6], j, dlen[6])};
+      const madipm_qp_point_tangents oj{at_col(user[0], j, olen[0]), at_col(user[1], j, olen[1]),
+                                        at_col(user[2], j, olen[2]), at_col(user[3], j, olen[3]),
+                                        at_col(user[4], j, olen[4])};
+      tangent_polished(dj, oj, device, caller);
+    }
+    SensBatch& b = post_->bat;
+    ++b.n_batches;
+    b.n_columns += k;
+    return;
+  }
+  hipStream_t s = stream_;
+  // ---- allocations, each by the first call that needs it
+  PostSolve& ps = post_state();
+  Adjoint& a = ps.adj;
+  Tangent& t = ps.tan;
+  SensBatch& b = ps.bat;
+  const int64_t N = (int64_t)n_ + m_;
+  constexpr int W = SENS_W;
+  ps.rowslack(P, s);
+  ps.tangent_scratch(*this, needLists);
+  b.need(N, nx_, n_, true, true);
+  int64_t dcap[7], ocap[5];  // a chunk's staging
+  for (int q = 0; q < 7; ++q) dcap[q] = W * dlen[q];
+  for (int q = 0; q < 5; ++q) ocap[q] = W * olen[q];
+  const double* ddir[7];
+  double* out[5];
+  b.dir.bind(dir, dcap, device, ddir);
+  b.out.bind(user, ocap, device, out);
+  AdjArgs A = ps.args(*this);
+  A.d = b.sol.p;
+  const BLen L{nh, na};
+  // ---- the factor of the K2 matrix at the final iterate: the single calls', once per solve
+  const DV D = view();
+  sens_factor(who);
+  if (device) ps.sync.begin(caller, s);  // the directions are read after the work already enqueued on the caller's stream
+  const bool ls = needLists;
+  const int nbv = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
+  for (int64_t c0 = 0; c0 < k; c0 += W) {
+    const int kc = (int)std::min<int64_t>(W, k - c0);
+    const int64_t co = device ? c0 : 0;  // the host route stages the chunk's columns from 0
+    if (!device) {
+      const double* uc[7];
+      int64_t ul[7];
+      for (int q = 0; q < 7; ++q) uc[q] = at_col(dir[q], c0, dlen[q]), ul[q] = kc * dlen[q];
+      b.dir.upload(uc, ul, s);
+    }
+    // ---- right-hand sides, solves, residuals
+    const TanDir T{at_col(ddir[0], co, dlen[0]), at_col(ddir[1], co, dlen[1]), at_col(ddir[2], co, dlen[2]),
+                   at_col(ddir[3], co, dlen[3]), at_col(ddir[4], co, dlen[4]), at_col(ddir[5], co, dlen[5]),
+                   at_col(ddir[6], co, dlen[6])};
+    k_tan_shift_b<<<dim3(nbv, kc), NT, 0, s>>>(A, T, L, a.rowslack.p, b.shift.p, take_fact_end());
+    k_tan_data_b<<<dim3(nbv, kc), NT, 0, s>>>(A, T, L, ls ? t.gsp.p : nullptr, t.ge.p, t.csp.p, t.ce.p,
+                                             ls ? t.asp.p : nullptr, t.ae.p, plan_ ? plan_->Hraw.p : nullptr,
+                                             plan_ ? plan_->Araw.p : nullptr, b.base.p);
+    SPMV_LAUNCH_B(k_tan_rhs_b, nbs, kc, s, D, A, T, L, (const int32_t*)a.rowslack.p, (const double*)b.shift.p,
+                  (const double*)b.base.p, b.d.p, b.p.p);
+    sens_solve_batch(kc, t.scal.p, c0 == 0);
+    // ---- outputs
+    k_tan_out_b<<<dim3(blocks(std::max(std::max(nx_, m_), std::max(n_ - nx_, 1))), kc), NT, 0, s>>>(
+        A, T, L, b.shift.p, b.dx.p, at_col(out[0], co, olen[0]), at_col(out[1], co, olen[1]),
+        at_col(out[2], co, olen[2]), at_col(out[3], co, olen[3]));
+    if (out[4] && m_)
+      SPMV_LAUNCH_B(k_tan_cons_b, spmv_blocks(m_), kc, s, D, A, (const double*)b.dx.p, (const double*)b.base.p,
+                    at_col(out[4], co, olen[4]));
+    MADIPM_HIP(hipGetLastError());
+    if (!device) {
+      double* uc[5];
+      int64_t ul[5];
+      for (int q = 0; q < 5; ++q) uc[q] = at_col(user[q], c0, olen[q]), ul[q] = kc * olen[q];
+      b.out.download(uc, ul, s);  // synchronises: the next chunk reuses the staging
+    }
+    ++b.n_chunks;
+  }
+  if (device) ps.sync.end(s, caller);  // work enqueued on the caller's stream from now on sees the outputs
+  t.n_tangents += k;
+  ++b.n_batches;
+  b.n_columns += k;
+}
+
+void MPCSolver::adjoint_batch(int32_t k, const madipm_qp_cotangents& ct, const madipm_qp_gradients& g, bool polished,
+                              bool device, hipStream_t caller) {
+  const std::string who = device ? "madipm_solver_adjoint_batch_device: " : "madipm_solver_adjoint_batch: ";
+  QPHost& P = *H_;
+  // ---- refusals, before anything is allocated or enqueued
+  MADIPM_REQUIRE(k >= 1, who + "k = " + std::to_string(k) + ", a batch holds at least one column");
+  if (polished)
+    polished_refuse(who);
+  else
+    sens_refuse(who);
+  // full: a cotangent block other than gx is given, and every column solves the shifted system of §13d
+  const bool full = ct.y || ct.zl || ct.zu || ct.cons;
+  MADIPM_REQUIRE(ct.x || full, who + "all five cotangents are NULL");
+  double* const user[7] = {g.c, g.Hvals, g.Avals, g.lcon, g.ucon, g.lvar, g.uvar};
+  MADIPM_REQUIRE(g.c || g.Hvals || g.Avals || g.lcon || g.ucon || g.lvar || g.uvar,
+                 who + "all seven outputs are NULL");
+  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
+  const bool needA = g.Avals && na > 0, needH = g.Hvals && nh > 0, needFix = g.lvar && P.anyfix;
+  MADIPM_REQUIRE(plan_ || !(needA || needH || needFix),
+                 who + "Avals, Hvals (and lvar on a problem with fixed variables) need "
+                       "madipm_solver_prepare_update first (it keeps the index arrays and the raw values)");
+  const double* const cot[5] = {ct.x, ct.y, ct.zl, ct.zu, ct.cons};
+  const int64_t clen[5] = {nx_, m_, nx_, nx_, m_};
+  const int64_t len[7] = {nx_, nh, na, m_, m_, nx_, nx_};
+  if (polished) {  // the single polished call per column, with offset pointers: its bits by construction
+    for (int64_t j = 0; j < k; ++j) {
+      const madipm_qp_cotangents cj{at_col(cot[0], j, clen[0]), at_col(cot[1], j, clen[1]), at_col(cot[2], j, clen[2]),
+                                    at_col(cot[3], j, clen[3]), at_col(cot[4], j, clen[4])};
+      const madipm_qp_gradients gj{at_col(user[0], j, len[0]), at_col(user[1], j, len[1]), at_col(user[2], j, len[2]),
+                                   at_col(user[3], j, len[3]), at_col(user[4], j, len[4]), at_col(user[5], j, len[5]),
+                                   at_col(user[6], j, len[6])};
+      adjoint_polished(cj, gj, device, caller);
+    }
+    SensBatch& b = post_->bat;
+    ++b.n_batches;
+    b.n_columns += k;
+    return;
+  }
+  hipStream_t s = stream_;
+  // ---- allocations, each by the first call that needs it
+  PostSolve& ps = post_state();
+  Adjoint& a = ps.adj;
+  SensBatch& b = ps.bat;
+  const int64_t N = (int64_t)n_ + m_;
+  constexpr int W = SENS_W;
+  b.need(N, nx_, n_, full, false);
+  if (g.lcon || g.ucon) ps.rowslack(P, s);
+  ps.adjoint_lists(*this, needA, needH, needFix);
+  int64_t ccap[5], gcap[7];  // a chunk's staging
+  for (int q = 0; q < 5; ++q) ccap[q] = W * clen[q];
+  for (int q = 0; q < 7; ++q) gcap[q] = W * len[q];
+  const double* dct[5];  // gx, gy, gzl, gzu, gcons on the device
+  double* out[7];
+  b.ct.bind(cot, ccap, device, dct);
+  b.grad.bind(user, gcap, device, out);
+  AdjArgs A = ps.args(*this);
+  A.d = b.sol.p;
+  // ---- the factor of the K2 matrix at the final iterate: the single calls', once per solve
+  const DV D = view();
+  sens_factor(who);
+  if (device) ps.sync.begin(caller, s);  // the cotangents are read after the work already enqueued on the caller's stream
+  const int nbv = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
+  const bool vec = (out[0] || out[3] || out[4] || out[5] || out[6]) && std::max(nx_, m_);
+  const bool fix = needFix && a.nfix > 0;
+  for (int64_t c0 = 0; c0 < k; c0 += W) {
+    const int kc = (int)std::min<int64_t>(W, k - c0);
+    const int64_t co = device ? c0 : 0;  // the host route stages the chunk's columns from 0
+    if (!device) {
+      const double* uc[5];
+      int64_t ul[5];
+      for (int q = 0; q < 5; ++q) uc[q] = at_col(cot[q], c0, clen[q]), ul[q] = kc * clen[q];
+      b.ct.upload(uc, ul, s);
+    }
+    const double* const gx = at_col(dct[0], co, clen[0]);
+    const double* const gy = at_col(dct[1], co, clen[1]);
+    const AdjFull F{at_col(dct[2], co, clen[2]), at_col(dct[3], co, clen[3]), at_col(dct[4], co, clen[4]), b.apx.p};
+    double* oc[7];
+    for (int q = 0; q < 7; ++q) oc[q] = at_col(out[q], co, len[q]);
+    // ---- right-hand sides, solves, residuals
+    if (full) {
+      k_adj_shift_b<<<dim3(nbv, kc), NT, 0, s>>>(A, F, b.shift.p, take_fact_end());
+      SPMV_LAUNCH_B(k_adj_rhs_full_b, nbs, kc, s, D, A, gx, gy, (const double*)b.shift.p, b.d.p, b.p.p);
+    } else {
+      k_adj_rhs_b<<<dim3(nbv, kc), NT, 0, s>>>(D, gx, b.d.p, b.p.p, take_fact_end());
+    }
+    sens_solve_batch(kc, a.scal.p, c0 == 0);
+    if (full && nx_) k_adj_unshift_b<<<dim3(blocks(nx_), kc), NT, 0, s>>>(nx_, N, b.shift.p, b.sol.p, b.apx.p);
+    // ---- gradients
+    auto gradients = [&](auto is_full) {  // the <true> instantiations read F (§13d)
+      constexpr bool FULL = decltype(is_full)::value;
+      if (vec)
+        k_adj_vec_b<FULL><<<dim3(blocks(std::max(nx_, m_)), kc), NT, 0, s>>>(A, F, a.rowslack.p, oc[0], oc[5], oc[6],
+                                                                            oc[3], oc[4]);
+      if (fix)
+        k_adj_fix_b<FULL><<<dim3(blocks(a.nfix), kc), NT, 0, s>>>(A, F, a.nfix, a.fix.p, a.fhsp.p, a.fh.p, a.fasp.p,
+                                                                 a.fa.p, plan_->Hraw.p, plan_->Araw.p, gx, oc[5]);
+      if (needA) k_adj_avals_b<FULL><<<dim3(blocks(na), kc), NT, 0, s>>>(A, F, na, a.Ar.p, a.Ac.p, oc[2]);
+    };
+    if (full)
+      gradients(std::true_type{});
+    else
+      gradients(std::false_type{});
+    if (needH) k_adj_hvals_b<<<dim3(blocks(nh), kc), NT, 0, s>>>(A, nh, a.Hr.p, a.Hc.p, oc[1]);
+    MADIPM_HIP(hipGetLastError());
+    if (!device) {
+      double* uc[7];
+      int64_t ul[7];
+      for (int q = 0; q < 7; ++q) uc[q] = at_col(user[q], c0, len[q]), ul[q] = kc * len[q];
+      b.grad.download(uc, ul, s);  // synchronises: the next chunk reuses the staging
+    }
+    ++b.n_chunks;
+  }
+  if (device) ps.sync.end(s, caller);  // work enqueued on the caller's stream from now on sees the outputs
+  a.n_adjoints += k;
+  ++b.n_batches;
+  b.n_columns += k;
+}
+
+void MPCSolver::sens_batch_info(int64_t* n_batches, int64_t* n_columns, int64_t* n_chunks) const {
+  const SensBatch* b = post_ ? &post_->bat : nullptr;
+  if (n_batches) *n_batches = b ? b->n_batches : 0;
+  if (n_columns) *n_columns = b ? b->n_columns : 0;
+  if (n_chunks) *n_chunks = b ? b->n_chunks : 0;
 }
 
 }  // namespace madipm

@@ -633,3 +633,78 @@ function solver_active_set_info(h::Ptr{Cvoid})
           "madipm_solver_active_set_info")
     return info[]
 end
+
+# ---- batched sensitivities (ABI 0.2.13): k tangents or adjoints of one point per call.  Every array holds k
+# vectors back to back (a k-column Matrix{Float64} in Julia's column-major layout is exactly that); nothing is 0 in
+# every column (inputs) or not wanted (outputs).  Column j of every output has the bits of the single call on
+# column j.  polished = true differentiates the polished point, one single polished call per column inside the
+# library.
+sens_batch_cols() = Int(ccall((:madipm_sens_batch_cols, libmadipm), Cint, ()))
+_ptr_or_null(a::Matrix{Float64}) = pointer(a)   # len x k: column j is vector j
+
+function solver_tangent_batch(h::Ptr{Cvoid}, k::Integer; dc=nothing, dHvals=nothing, dAvals=nothing, dlcon=nothing,
+                              ducon=nothing, dlvar=nothing, duvar=nothing, x=nothing, y=nothing, zl=nothing,
+                              zu=nothing, cons=nothing, polished::Bool=false)
+    GC.@preserve dc dHvals dAvals dlcon ducon dlvar duvar x y zl zu cons begin
+        d = Ref(MadipmQPDirections(_ptr_or_null(dc), _ptr_or_null(dHvals), _ptr_or_null(dAvals), _ptr_or_null(dlcon),
+                                   _ptr_or_null(ducon), _ptr_or_null(dlvar), _ptr_or_null(duvar)))
+        o = Ref(MadipmQPPointTangents(_ptr_or_null(x), _ptr_or_null(y), _ptr_or_null(zl), _ptr_or_null(zu),
+                                      _ptr_or_null(cons)))
+        check(ccall((:madipm_solver_tangent_batch, libmadipm), Cint,
+                    (Ptr{Cvoid}, Int32, Ref{MadipmQPDirections}, Ref{MadipmQPPointTangents}, Int32),
+                    h, k, d, o, polished ? 1 : 0), "madipm_solver_tangent_batch")
+    end
+    return
+end
+
+# DEVICE arrays (Ptr{Float64} into device memory, or nothing), with solver_adjoint_device's stream contract
+function solver_tangent_batch_device(h::Ptr{Cvoid}, k::Integer; dc=nothing, dHvals=nothing, dAvals=nothing,
+                                     dlcon=nothing, ducon=nothing, dlvar=nothing, duvar=nothing, x=nothing,
+                                     y=nothing, zl=nothing, zu=nothing, cons=nothing, polished::Bool=false,
+                                     stream::Ptr{Cvoid}=C_NULL)
+    d = Ref(MadipmQPDirections(_dptr_or_null(dc), _dptr_or_null(dHvals), _dptr_or_null(dAvals), _dptr_or_null(dlcon),
+                               _dptr_or_null(ducon), _dptr_or_null(dlvar), _dptr_or_null(duvar)))
+    o = Ref(MadipmQPPointTangents(_dptr_or_null(x), _dptr_or_null(y), _dptr_or_null(zl), _dptr_or_null(zu),
+                                  _dptr_or_null(cons)))
+    check(ccall((:madipm_solver_tangent_batch_device, libmadipm), Cint,
+                (Ptr{Cvoid}, Int32, Ref{MadipmQPDirections}, Ref{MadipmQPPointTangents}, Int32, Ptr{Cvoid}),
+                h, k, d, o, polished ? 1 : 0, stream), "madipm_solver_tangent_batch_device")
+    return
+end
+
+function solver_adjoint_batch(h::Ptr{Cvoid}, k::Integer; gx=nothing, gy=nothing, gzl=nothing, gzu=nothing,
+                              gcons=nothing, c=nothing, Hvals=nothing, Avals=nothing, lcon=nothing, ucon=nothing,
+                              lvar=nothing, uvar=nothing, polished::Bool=false)
+    GC.@preserve gx gy gzl gzu gcons c Hvals Avals lcon ucon lvar uvar begin
+        ct = Ref(MadipmQPCotangents(_ptr_or_null(gx), _ptr_or_null(gy), _ptr_or_null(gzl), _ptr_or_null(gzu),
+                                    _ptr_or_null(gcons)))
+        g = Ref(MadipmQPGradients(_ptr_or_null(c), _ptr_or_null(Hvals), _ptr_or_null(Avals), _ptr_or_null(lcon),
+                                  _ptr_or_null(ucon), _ptr_or_null(lvar), _ptr_or_null(uvar)))
+        check(ccall((:madipm_solver_adjoint_batch, libmadipm), Cint,
+                    (Ptr{Cvoid}, Int32, Ref{MadipmQPCotangents}, Ref{MadipmQPGradients}, Int32),
+                    h, k, ct, g, polished ? 1 : 0), "madipm_solver_adjoint_batch")
+    end
+    return
+end
+
+function solver_adjoint_batch_device(h::Ptr{Cvoid}, k::Integer; gx=nothing, gy=nothing, gzl=nothing, gzu=nothing,
+                                     gcons=nothing, c=nothing, Hvals=nothing, Avals=nothing, lcon=nothing,
+                                     ucon=nothing, lvar=nothing, uvar=nothing, polished::Bool=false,
+                                     stream::Ptr{Cvoid}=C_NULL)
+    ct = Ref(MadipmQPCotangents(_dptr_or_null(gx), _dptr_or_null(gy), _dptr_or_null(gzl), _dptr_or_null(gzu),
+                                _dptr_or_null(gcons)))
+    g = Ref(MadipmQPGradients(_dptr_or_null(c), _dptr_or_null(Hvals), _dptr_or_null(Avals), _dptr_or_null(lcon),
+                              _dptr_or_null(ucon), _dptr_or_null(lvar), _dptr_or_null(uvar)))
+    check(ccall((:madipm_solver_adjoint_batch_device, libmadipm), Cint,
+                (Ptr{Cvoid}, Int32, Ref{MadipmQPCotangents}, Ref{MadipmQPGradients}, Int32, Ptr{Cvoid}),
+                h, k, ct, g, polished ? 1 : 0, stream), "madipm_solver_adjoint_batch_device")
+    return
+end
+
+# (n_batches, n_columns, n_chunks): successful batched calls, their columns, the chunks of sens_batch_cols() columns
+function solver_sens_batch_info(h::Ptr{Cvoid})
+    nb, nc, nk = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:madipm_solver_sens_batch_info, libmadipm), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                h, nb, nc, nk), "madipm_solver_sens_batch_info")
+    return (n_batches = nb[], n_columns = nc[], n_chunks = nk[])
+end

@@ -22,6 +22,7 @@ def __getattr__(name):
                 "ADJOINT_NAMES", "COTANGENT_NAMES",  # MPCSolver.adjoint's gradients; its cotangents' blocks
                 "TANGENT_NAMES",  # MPCSolver.tangent's output blocks (its directions' blocks are ADJOINT_NAMES)
                 "POLISH_NAMES", "PolishVerdict",  # MPCSolver.polish's blocks; its verdict
+                "check_batch_blocks",  # the argument check of MPCSolver.tangent_batch / adjoint_batch
                 "MadIPMError"):  # MadIPMError: what MPCSolver.update raises on a change of classification
         from . import solver
         return getattr(solver, name)

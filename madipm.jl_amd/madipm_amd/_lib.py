@@ -211,6 +211,15 @@ _sig("madipm_solver_active_set_solve_device", C.c_int, [vp, C.POINTER(ActiveSetO
                                                         C.POINTER(ActiveSetInfo), vp])
 _sig("madipm_solver_active_set_info", C.c_int, [vp, C.POINTER(ActiveSetInfo)])
 
+# batched sensitivities (ABI 0.2.13): k columns per call in the tangent's and the adjoint's structs
+_sig("madipm_sens_batch_cols", C.c_int, [])
+_sig("madipm_solver_tangent_batch", C.c_int, [vp, C.c_int32, C.POINTER(QPDir), C.POINTER(QPTan), C.c_int32])
+_sig("madipm_solver_tangent_batch_device", C.c_int, [vp, C.c_int32, C.POINTER(QPDir), C.POINTER(QPTan), C.c_int32, vp])
+_sig("madipm_solver_adjoint_batch", C.c_int, [vp, C.c_int32, C.POINTER(QPCot), C.POINTER(QPGrad), C.c_int32])
+_sig("madipm_solver_adjoint_batch_device", C.c_int, [vp, C.c_int32, C.POINTER(QPCot), C.POINTER(QPGrad), C.c_int32,
+                                                     vp])
+_sig("madipm_solver_sens_batch_info", C.c_int, [vp, i64p, i64p, i64p])
+
 
 class MadIPMError(RuntimeError):
     pass

@@ -22,6 +22,9 @@ With polish=True forward returns the polished point and backward / jvp different
     x, zl = layer(c=c)               # update_device -> active_set_solve_device from the kept set; the
     layer.last_route                 # interior-point path above when that does not end POLISHED ("active_set" / "ipm")
 
+    J = layer.jacobian(("c", "lcon"))  # {(out, par): tensor} at the last forward's point, from batched
+                                       # tangents or adjoints, whichever needs fewer columns
+
 `import torch` comes before this package in the process, as for every device-route call.
 """
 from __future__ import annotations
@@ -172,3 +175,11 @@ class QPLayer(torch.nn.Module):
         if self.outputs == ("x",):
             return QPFunction.apply(self.solver, c, Hvals, Avals, lcon, ucon, lvar, uvar)
         return QPFunction.apply(self.solver, c, Hvals, Avals, lcon, ucon, lvar, uvar, self.outputs)
+
+    def jacobian(self, wrt, outputs=None, mode=None):
+        """The Jacobian of the layer's outputs (or of `outputs`) with respect to the data blocks `wrt` at the
+        point of the last forward: MPCSolver.jacobian_device's dict {(out, par): tensor}, of the polished point
+        with polish=True.  Like backward it must run before the solver is updated or solved
+        again."""
+        return self.solver.jacobian_device(outputs=self.outputs if outputs is None else outputs, wrt=wrt, mode=mode,
+                                           polished=self.polish)

@@ -276,6 +276,91 @@ def check_tangent_directions(sizes: dict, directions: dict, *, on_device: bool =
     return given
 
 
+def check_batch_blocks(sizes: dict, blocks: dict, *, labels: dict | None = None, on_device: bool = False,
+                       device=None, who: str = "tangent_batch") -> tuple:
+    """The direction / cotangent arguments of MPCSolver.tangent_batch / adjoint_batch (and the device routes),
+    before any library call: `blocks` maps the names in `sizes` to arrays of shape (k, sizes[name]) (None: 0 in
+    every column), not all None, all with the same k >= 1.  Host route: each is converted to a C-contiguous
+    float64 array.  Device route (on_device): each must be a contiguous float64 tensor on the GPU, checked by
+    check_device_array (its TypeErrors and its ValueError for a non-contiguous tensor).  ValueError for a block
+    that is not 2-D, a wrong second dimension, k == 0 and blocks whose k disagree.  `labels` maps a name to the
+    keyword the messages use (the cotangents: x -> gx, ...).  Returns (k, {name: array} of those given, in the
+    order of `sizes`)."""
+    labels = labels or {}
+    given, k, first = {}, None, None
+    for name, length in sizes.items():
+        a = blocks.get(name)
+        if a is None:
+            continue
+        label = labels.get(name, name)
+        if on_device:
+            import torch
+            flat = a.reshape(-1) if isinstance(a, torch.Tensor) and a.is_contiguous() else a
+            check_device_array(label, flat, flat.numel() if isinstance(flat, torch.Tensor) else 0, device, who=who)
+        else:
+            a = np.array(a, dtype=np.float64, order="C")
+        if a.ndim != 2:
+            raise ValueError(f"{who}: {label} has shape {tuple(a.shape)}, expected (k, {int(length)}): one row per "
+                             "column of the batch")
+        if a.shape[1] != int(length):
+            raise ValueError(f"{who}: {label} has shape {tuple(a.shape)}, expected (k, {int(length)})")
+        if a.shape[0] == 0:
+            raise ValueError(f"{who}: {label} holds k = 0 columns; a batch holds at least one")
+        if k is None:
+            k, first = int(a.shape[0]), label
+        elif int(a.shape[0]) != k:
+            raise ValueError(f"{who}: {label} holds k = {int(a.shape[0])} columns, {first} holds {k}")
+        given[name] = a
+    if not given:
+        raise ValueError(f"{who}: no block given; pass at least one of "
+                         f"{', '.join(labels.get(n, n) for n in sizes)}")
+    return k, given
+
+
+JACOBIAN_BATCHES = 8   # Jacobian columns per library call, in units of sens_batch_cols(): bounds the unit blocks
+
+
+def check_jacobian_selection(sel, sizes: dict, what: str, who: str = "jacobian") -> dict:
+    """The `outputs` / `wrt` argument of MPCSolver.jacobian: an iterable of names out of `sizes`, or a dict
+    name -> index array (None: every coordinate).  Returns {name: int64 index array} in the order given.
+    TypeError for a bare string, ValueError for an unknown name, an empty selection, an index array that is not
+    1-D or an index out of range."""
+    if isinstance(sel, str):
+        raise TypeError(f"{who}: {what} must be a collection of names or a dict name -> indices, not the string "
+                        f"{sel!r}")
+    items = list(sel.items()) if isinstance(sel, dict) else [(k, None) for k in sel]
+    if not items:
+        raise ValueError(f"{who}: {what} is empty")
+    out = {}
+    for name, idx in items:
+        if name not in sizes:
+            raise ValueError(f"{who}: unknown name {name!r} in {what}; the blocks are {list(sizes)}")
+        if name in out:
+            raise ValueError(f"{who}: {name!r} appears twice in {what}")
+        n = int(sizes[name])
+        if idx is None:
+            idx = np.arange(n, dtype=np.int64)
+        else:
+            idx = np.array(idx.cpu() if hasattr(idx, "cpu") else idx)
+            if idx.ndim != 1 or (idx.size and not np.issubdtype(idx.dtype, np.integer)):
+                raise ValueError(f"{who}: the indices of {name!r} in {what} must be a 1-D integer array")
+            idx = idx.astype(np.int64)
+            if idx.size and (idx.min() < 0 or idx.max() >= n):
+                raise ValueError(f"{who}: an index of {name!r} in {what} is outside [0, {n})")
+        out[name] = idx
+    return out
+
+
+def jacobian_mode(mode, n_parameters: int, n_outputs: int, who: str = "jacobian") -> str:
+    """"forward" (one tangent column per selected parameter) or "reverse" (one adjoint column per selected
+    output coordinate); None picks the one with fewer columns, forward on a tie."""
+    if mode is None:
+        return "forward" if n_parameters <= n_outputs else "reverse"
+    if mode not in ("forward", "reverse"):
+        raise ValueError(f"{who}: mode must be None, 'forward' or 'reverse', not {mode!r}")
+    return mode
+
+
 POLISH_NAMES = ("x", "y", "zl", "zu", "cons", "active_var", "active_row")   # madipm_polish_out's fields
 
 
@@ -1088,6 +1173,166 @@ class MPCSolver:
         nt, r = C.c_int64(), C.c_double()
         L.check(L.lib.madipm_solver_tangent_info(self.h, C.byref(nt), C.byref(r)), "tangent_info")
         return {"n_tangents": int(nt.value), "last_residual": float(r.value)}
+
+    # ------------------------------------------------------------ batched sensitivities
+    _COT_LABELS = {"x": "gx", "y": "gy", "zl": "gzl", "zu": "gzu", "cons": "gcons"}
+
+    @staticmethod
+    def sens_batch_cols() -> int:
+        """W: the columns one chunk of a batched call runs together (a compile-time constant of the library)."""
+        return int(L.lib.madipm_sens_batch_cols())
+
+    def sens_batch_info(self) -> dict:
+        """n_batches: successful batched calls; n_columns: the columns they held; n_chunks: the chunks of at most
+        sens_batch_cols() columns the calls at the interior point ran (a polished batch adds none)."""
+        nb, nc, nk = C.c_int64(), C.c_int64(), C.c_int64()
+        L.check(L.lib.madipm_solver_sens_batch_info(self.h, C.byref(nb), C.byref(nc), C.byref(nk)),
+                "sens_batch_info")
+        return {"n_batches": int(nb.value), "n_columns": int(nc.value), "n_chunks": int(nk.value)}
+
+    def tangent_batch(self, want=None, *, polished=False, c=None, Hvals=None, Avals=None, lcon=None, ucon=None,
+                      lvar=None, uvar=None) -> dict:
+        """k tangent() calls on one point in one library call: every direction block has shape (k, len) (row j
+        is column j's block; None is 0 in every column), and the result is a dict of (k, len) arrays over
+        `want`.  Row j of every block is, bit for bit, what tangent() returns for row j of the directions.  The
+        columns run in chunks of sens_batch_cols() that share the passes over the KKT operator and the launches
+        of everything but the solves; polished=True runs tangent(polished=True) per column inside the library.
+        tangent_info() counts k more calls and reports the largest residual of the columns.  ValueError /
+        TypeError as check_batch_blocks raises them, before any library call; MadIPMError as tangent()."""
+        names = check_tangent_want(want)
+        size = self._adjoint_sizes()
+        k, given = check_batch_blocks(size, dict(c=c, Hvals=Hvals, Avals=Avals, lcon=lcon, ucon=ucon, lvar=lvar,
+                                                 uvar=uvar), who="tangent_batch")
+        osize = self._tangent_sizes()
+        o = L.QPTan()
+        buf = _host_outputs(o, {n: k * osize[n] for n in names}, names)
+        self._adjoint_prepare(given)
+        d = L.QPDir(**_host_inputs(given))
+        L.check(L.lib.madipm_solver_tangent_batch(self.h, k, C.byref(d), C.byref(o), int(bool(polished))),
+                "tangent_batch")
+        return {n: buf[n][:k * osize[n]].reshape(k, osize[n]) for n in names}
+
+    def tangent_batch_device(self, want=None, stream=None, *, polished=False, c=None, Hvals=None, Avals=None,
+                             lcon=None, ucon=None, lvar=None, uvar=None) -> dict:
+        """tangent_batch() from and into torch tensors on the solver's GPU (every direction block: float64,
+        contiguous, shape (k, len)), with tangent_device()'s stream contract."""
+        names = check_tangent_want(want)
+        size = self._adjoint_sizes()
+        dirs = dict(c=c, Hvals=Hvals, Avals=Avals, lcon=lcon, ucon=ucon, lvar=lvar, uvar=uvar)
+        k, given = check_batch_blocks(size, dirs, on_device=True, device=self._device, who="tangent_batch_device")
+        osize = self._tangent_sizes()
+        o = L.QPTan()
+        st, buf, p, _alive = self._device_call(
+            "tangent_batch_device", stream, lambda: check_batch_blocks(
+                size, dirs, on_device=True, device=self._device, who="tangent_batch_device"),
+            o, {n: k * osize[n] for n in names}, names, given)
+        self._adjoint_prepare(given)
+        d = L.QPDir(**p)
+        L.check(L.lib.madipm_solver_tangent_batch_device(self.h, k, C.byref(d), C.byref(o), int(bool(polished)),
+                                                         L.vp(st.cuda_stream)), "tangent_batch_device")
+        return {n: buf[n][:k * osize[n]].view(k, osize[n]) for n in names}
+
+    def adjoint_batch(self, gx=None, want=None, *, gy=None, gzl=None, gzu=None, gcons=None, polished=False) -> dict:
+        """k adjoint() calls on one point in one library call: every cotangent block has shape (k, len) (None is
+        0 in every column), and the result is a dict of (k, len) arrays over `want`.  Row j of every gradient
+        is, bit for bit, what adjoint() returns for row j of the cotangents: with gx alone the gx-only call's
+        bits, with any other block given those of the five-cotangent call for every column.  Chunks, polished,
+        counters (adjoint_info()) and errors as tangent_batch()."""
+        names = check_adjoint_want(want)
+        k, given = check_batch_blocks(self._tangent_sizes(), dict(x=gx, y=gy, zl=gzl, zu=gzu, cons=gcons),
+                                      labels=self._COT_LABELS, who="adjoint_batch")
+        size = self._adjoint_sizes()
+        g = L.QPGrad()
+        buf = _host_outputs(g, {n: k * size[n] for n in names}, names)
+        self._adjoint_prepare(names)
+        ct = L.QPCot(**_host_inputs(given))
+        L.check(L.lib.madipm_solver_adjoint_batch(self.h, k, C.byref(ct), C.byref(g), int(bool(polished))),
+                "adjoint_batch")
+        return {n: buf[n][:k * size[n]].reshape(k, size[n]) for n in names}
+
+    def adjoint_batch_device(self, gx=None, want=None, stream=None, *, gy=None, gzl=None, gzu=None, gcons=None,
+                             polished=False) -> dict:
+        """adjoint_batch() from and into torch tensors on the solver's GPU (every cotangent block: float64,
+        contiguous, shape (k, len)), with adjoint_device()'s stream contract."""
+        names = check_adjoint_want(want)
+        cots = dict(x=gx, y=gy, zl=gzl, zu=gzu, cons=gcons)
+        csize = self._tangent_sizes()
+        k, given = check_batch_blocks(csize, cots, labels=self._COT_LABELS, on_device=True, device=self._device,
+                                      who="adjoint_batch_device")
+        size = self._adjoint_sizes()
+        g = L.QPGrad()
+        st, buf, p, _alive = self._device_call(
+            "adjoint_batch_device", stream, lambda: check_batch_blocks(
+                csize, cots, labels=self._COT_LABELS, on_device=True, device=self._device,
+                who="adjoint_batch_device"),
+            g, {n: k * size[n] for n in names}, names, given)
+        self._adjoint_prepare(names)
+        ct = L.QPCot(**p)
+        L.check(L.lib.madipm_solver_adjoint_batch_device(self.h, k, C.byref(ct), C.byref(g), int(bool(polished)),
+                                                         L.vp(st.cuda_stream)), "adjoint_batch_device")
+        return {n: buf[n][:k * size[n]].view(k, size[n]) for n in names}
+
+    def _jacobian(self, outputs, wrt, mode, polished, device, stream, who):
+        # one batched call per JACOBIAN_BATCHES * W unit columns of one block: forward mode seeds the parameters,
+        # reverse mode the output coordinates; the other side's selection is gathered from the returned blocks
+        out_sel = check_jacobian_selection(outputs, self._tangent_sizes(), "outputs", who)
+        par_sel = check_jacobian_selection(wrt, self._adjoint_sizes(), "wrt", who)
+        n_par = sum(len(i) for i in par_sel.values())
+        n_out = sum(len(i) for i in out_sel.values())
+        mode = jacobian_mode(mode, n_par, n_out, who)
+        seeds, reads = (par_sel, out_sel) if mode == "forward" else (out_sel, par_sel)
+        seed_size = self._adjoint_sizes() if mode == "forward" else self._tangent_sizes()
+        step = JACOBIAN_BATCHES * self.sens_batch_cols()
+        if device:
+            import torch
+            if stream is not None and not isinstance(stream, torch.cuda.Stream):
+                raise TypeError(f"{who}: stream must be a torch.cuda.Stream, not {type(stream).__name__}")
+            if self._device is None:
+                self._device = torch.device("cuda", torch.cuda.current_device())
+            dev = self._device
+            zeros = lambda r, c: torch.zeros((r, c), dtype=torch.float64, device=dev)   # noqa: E731
+            index = lambda i: torch.as_tensor(i, device=dev)                            # noqa: E731
+            if stream is not None:     # the unit blocks and the gathers are enqueued where the calls read and write
+                with torch.cuda.stream(stream):
+                    return self._jacobian(outputs, wrt, mode, polished, True, None, who)
+        else:
+            zeros = lambda r, c: np.zeros((r, c))   # noqa: E731
+            index = lambda i: i                     # noqa: E731
+        read_idx = {name: index(i) for name, i in reads.items()}
+        J = {(o, p): zeros(len(oi), len(pi)) for o, oi in out_sel.items() for p, pi in par_sel.items()}
+        for seed, idx in seeds.items():
+            for lo in range(0, len(idx), step):
+                part = idx[lo:lo + step]
+                E = zeros(len(part), seed_size[seed])
+                E[index(np.arange(len(part))), index(part)] = 1.0
+                if mode == "forward":
+                    call = self.tangent_batch_device if device else self.tangent_batch
+                    res = call(want=tuple(reads), polished=polished, **{seed: E})
+                    for o in reads:      # row j: d out / d parameter part[j]
+                        J[(o, seed)][:, lo:lo + len(part)] = res[o][:, read_idx[o]].T
+                else:
+                    call = self.adjoint_batch_device if device else self.adjoint_batch
+                    res = call(want=tuple(reads), polished=polished, **{self._COT_LABELS[seed]: E})
+                    for p in reads:      # row j: d output coordinate part[j] / d parameters
+                        J[(seed, p)][lo:lo + len(part), :] = res[p][:, read_idx[p]]
+        return J
+
+    def jacobian(self, outputs=("x",), wrt=("c",), *, mode=None, polished=False) -> dict:
+        """The Jacobian of solution blocks with respect to data blocks at the point of the last solve():
+        {(out, par): array of shape (selected coordinates of out, selected entries of par)}.  `outputs` (names
+        out of TANGENT_NAMES) and `wrt` (names out of ADJOINT_NAMES) are tuples of block names, or dicts
+        name -> index array that select coordinates (None: all).  mode="forward" feeds unit directions through
+        tangent_batch(), one column per selected parameter; mode="reverse" feeds unit cotangents through
+        adjoint_batch(), one column per selected output coordinate; None picks the side with fewer columns,
+        forward on a tie.  Either way at most 8 sens_batch_cols() columns go into one library call, which
+        bounds the memory of the unit blocks.  A forward-mode column is tangent(par=e_i) and a reverse-mode row
+        adjoint() of the unit cotangent, bit for bit.  polished and the errors as tangent() / adjoint()."""
+        return self._jacobian(outputs, wrt, mode, polished, False, None, "jacobian")
+
+    def jacobian_device(self, outputs=("x",), wrt=("c",), *, mode=None, polished=False, stream=None) -> dict:
+        """jacobian() with the unit blocks built and the Jacobian blocks returned as torch tensors on the
+        solver's GPU; `stream` as in tangent_device()."""
+        return self._jacobian(outputs, wrt, mode, polished, True, stream, "jacobian_device")
 
     # ------------------------------------------------------------ polish (DESIGN §13f)
     def _polish_sizes(self) -> dict:

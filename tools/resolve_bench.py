@@ -65,7 +65,14 @@ rounds, active_set_share (the part of the problems the active-set route solved: 
 problem whose attempt does not end POLISHED is solved by the interior-point route, whose polish renews the kept set
 when it can; active_set_failed_s is the cost of such an attempt.  While the solver keeps no set (no polish has ended
 POLISHED: the degenerate LP stand-ins) the attempt starts from the set the last polish guessed, supplied.  --rel REL sets the relative noise of every
-sequence (default 1e-3).  The instance name random_qp:N is instances.random_qp with N variables, N / 4 rows and about 8 entries per row."""
+sequence (default 1e-3).
+
+--sens-batch K adds the batched sensitivities: after each update_device + solve, and after one single
+tangent_device that factorises the point, one tangent_batch_device and one adjoint_batch_device of K seeded
+columns (all seven direction blocks / all five cotangents given, all outputs), each against K single tangent_device /
+adjoint_device calls of the same columns on the same point, stream synchronised, medians of 10:
+sens_batch_tangent_s / sens_loop_tangent_s, sens_batch_adjoint_s / sens_loop_adjoint_s, and sens_batch_same_bits (every
+row of the batches is the single call's).  The instance name random_qp:N is instances.random_qp with N variables, N / 4 rows and about 8 entries per row."""
 import dataclasses
 import json
 import os
@@ -109,7 +116,7 @@ def build_problem(name):
 
 
 def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polish=False, polished_sens=False,
-        active_set=False):
+        active_set=False, sens_batch=None):
     qp, desc = build_problem(name)
     opts = bench.solver_opts()
     MPCSolver(qp, **opts)                      # the first construction of a process pays one-off set-up
@@ -434,6 +441,53 @@ def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polis
                      **{"active_set_" + k: v for k, v in s.active_set_info().items()
                         if k in ("n_calls", "n_factorizations")}})
         c = s.counters()
+    if sens_batch:   # the same data again: K columns in one batched call against K single calls on the same point
+        K = int(sens_batch)
+        rng = np.random.default_rng(0)
+        perturb(qp, rng)
+        drng = np.random.default_rng(4)
+        size = dict(c=qp.nvar, Hvals=qp.nnzh, Avals=qp.nnzj, lcon=qp.ncon, ucon=qp.ncon, lvar=qp.nvar, uvar=qp.nvar)
+        csize = dict(gx=qp.nvar, gy=qp.ncon, gzl=qp.nvar, gzu=qp.nvar, gcons=qp.ncon)
+        draw = lambda sz: {k: torch.as_tensor(drng.standard_normal((K, n)), device="cuda") for k, n in sz.items()}  # noqa: E731
+        sync = lambda: torch.cuda.current_stream().synchronize()  # noqa: E731
+        bt, lt, ba, la, same, bstat = [], [], [], [], True, set()
+        for rep in range(WARMUP + REPS):
+            s.update_device(**{k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()})
+            st_ = s.solve(fetch_solution=False).status
+            bstat.add(st_)
+            if st_ != 1:
+                continue
+            d, cot = draw(size), draw(csize)
+            s.tangent_device(**{k: v[0] for k, v in d.items()})      # the point's factorisation
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            tb = s.tangent_batch_device(**d)
+            sync()
+            t_bt = time.perf_counter() - t
+            t = time.perf_counter()
+            ts = [s.tangent_device(**{k: v[j] for k, v in d.items()}) for j in range(K)]
+            sync()
+            t_lt = time.perf_counter() - t
+            t = time.perf_counter()
+            gb = s.adjoint_batch_device(**cot)
+            sync()
+            t_ba = time.perf_counter() - t
+            t = time.perf_counter()
+            gs = [s.adjoint_device(**{k: v[j] for k, v in cot.items()}) for j in range(K)]
+            sync()
+            t_la = time.perf_counter() - t
+            same = same and all(torch.equal(tb[k][j], ts[j][k]) for j in range(K) for k in tb) \
+                and all(torch.equal(gb[k][j], gs[j][k]) for j in range(K) for k in gb)
+            if rep >= WARMUP:
+                bt.append(t_bt)
+                lt.append(t_lt)
+                ba.append(t_ba)
+                la.append(t_la)
+        med = lambda v: statistics.median(v) if v else float("nan")  # noqa: E731
+        wres.update({"sens_batch_k": K, "sens_batch_cols": s.sens_batch_cols(), "sens_batch_tangent_s": med(bt),
+                     "sens_loop_tangent_s": med(lt), "sens_batch_adjoint_s": med(ba), "sens_loop_adjoint_s": med(la),
+                     "sens_batch_same_bits": bool(same), "sens_batch_status": sorted(bstat), **s.sens_batch_info()})
+        c = s.counters()
     update_s, solve_s = statistics.median(upd), statistics.median(sol)
     return {**wres, "instance": name, "description": desc, "nvar": qp.nvar, "ncon": qp.ncon, "nnzj": qp.nnzj, "nnzh": qp.nnzh,
             "construct_s": construct_s, "prepare_update_s": prepare_update_s, "update_s": update_s,
@@ -481,13 +535,18 @@ def main():
     active_set = "--active-set" in args
     if active_set:
         args.remove("--active-set")
+    sens_batch = None
+    if "--sens-batch" in args:
+        k = args.index("--sens-batch")
+        sens_batch = int(args[k + 1])
+        del args[k:k + 2]
     if "--rel" in args:
         global REL
         k = args.index("--rel")
         REL = float(args[k + 1])
         del args[k:k + 2]
     for name in args or ["ex10", "supportcase10"]:
-        r = run(name, warm, adjoint, adjoint_full, tangent, polish, polished_sens, active_set)
+        r = run(name, warm, adjoint, adjoint_full, tangent, polish, polished_sens, active_set, sens_batch)
         print(f"{name}: construct_s {r['construct_s']:.4f}  prepare_update_s {r['prepare_update_s']:.4f}  "
               f"update_s {r['update_s']:.5f}  solve_s {r['solve_s']:.4f}  ->  update + solve "
               f"{r['update_plus_solve_s']:.4f} s against construct + solve {r['construct_plus_solve_s']:.4f} s "
@@ -535,6 +594,14 @@ def main():
                   f"{r['active_set_rounds']}, share {r['active_set_share']:.2f}; a failed attempt "
                   f"{r['active_set_failed_s']:.4f} s; first polish {r['active_set_first_polish']}; "
                   f"{r['active_set_n_factorizations']} factorisations in {r['active_set_n_calls']} calls", flush=True)
+        if sens_batch:
+            K = r["sens_batch_k"]
+            print(f"{name}: {K} columns (chunks of {r['sens_batch_cols']}): tangent_batch_device "
+                  f"{r['sens_batch_tangent_s'] * 1e3:.3f} ms against {K} tangent_device calls "
+                  f"{r['sens_loop_tangent_s'] * 1e3:.3f} ms (x{r['sens_loop_tangent_s'] / r['sens_batch_tangent_s']:.2f}); "
+                  f"adjoint_batch_device {r['sens_batch_adjoint_s'] * 1e3:.3f} ms against {K} adjoint_device calls "
+                  f"{r['sens_loop_adjoint_s'] * 1e3:.3f} ms (x{r['sens_loop_adjoint_s'] / r['sens_batch_adjoint_s']:.2f}); "
+                  f"same bits {r['sens_batch_same_bits']}, status {r['sens_batch_status']}", flush=True)
         out.append(r)
     print(json.dumps({"resolve_bench": out, "warmup": WARMUP, "reps": REPS, "rel_noise": REL}))
 
