@@ -46,6 +46,7 @@ struct UpdatePlan;   // index plans of the value refresh, built by prepare_updat
 struct DevUpdate;    // staging, start vectors and sum-order lists of the device route (mpc.hip)
 struct WarmStart;    // the warm point and its scratch, on the device (mpc.hip)
 struct PostSolve;    // everything adjoint, tangent and polish keep between calls (mpc_post.hip)
+struct SensView;     // the scratch one tangent / adjoint call runs on: the single calls' or the batch's (mpc_post.hip)
 struct PostSolveDelete {
   void operator()(PostSolve* p) const;
 };
@@ -128,8 +129,8 @@ class MPCSolver {
   void polished_sens_info(int64_t* n_tangents, int64_t* n_adjoints, int64_t* n_factorizations, double* last_residual);
   // k tangents / adjoints of one point per call (madipm_solver_tangent_batch / _adjoint_batch / _device /
   // _sens_batch_info): every non-null block holds k vectors back to back.  At the end point the
-  // columns run in chunks of sens_batch_cols() through kernels of their own that give each column the single
-  // call's bits; polished: one tangent_polished / adjoint_polished per column.
+  // columns run in chunks of sens_batch_cols() through the single calls' kernels and host path, so each column
+  // has the single call's bits; polished: one tangent_polished / adjoint_polished per column.
   static int sens_batch_cols();
   void tangent_batch(int32_t k, const madipm_qp_directions& d, const madipm_qp_point_tangents& out, bool polished,
                      bool device, hipStream_t caller);
@@ -160,9 +161,13 @@ class MPCSolver {
   template <class Enqueue>
   bool factor_trials(Enqueue&& enqueue);
   void sens_factor(const std::string& who);
-  void sens_solve(double* resid);
-  // the same for the kc columns of a chunk in the batch scratch (§13i); resid[0]: the largest ratio of the call so far
-  void sens_solve_batch(int kc, double* resid, bool first_chunk);
+  // (of the kc columns of a chunk on the scratch V names, §13i; resid[0]: the largest ratio of the call so far),
+  // and the one implementation of tangent / tangent_batch and of adjoint / adjoint_batch: k columns in chunks
+  void sens_solve(const SensView& V, int kc, double* resid, bool first_chunk);
+  int64_t tangent_cols(const std::string& who, int64_t k, bool batch, bool polished, const madipm_qp_directions& d,
+                       const madipm_qp_point_tangents& out, bool device, hipStream_t caller);
+  int64_t adjoint_cols(const std::string& who, int64_t k, bool batch, bool polished, bool need_gx,
+                       const madipm_qp_cotangents& g, const madipm_qp_gradients& out, bool device, hipStream_t caller);
   // the polished sensitivities': the refusals, the polish's factor, the masked solves
   void polished_refuse(const std::string& who) const;
   void polished_factor(const std::string& who);

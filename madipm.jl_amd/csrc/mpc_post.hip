@@ -2,9 +2,10 @@
 // (DESIGN §13c-§13g).  Each reads the end point of a finished solve, factorises once per point and leaves
 // alone everything a later initialize / solve / warm_start_last reads; the interior-point loop (mpc.hip)
 // knows nothing of the state kept here.  The active-set solve (§13h) runs the polish's kernels on the data the
-// solver holds, from a start that reads no end point, and so needs no solve at all.  The batched sensitivities
-// (§13i) run k columns of one point through kernels of their own, at the end of the file.  Kernels and what they
-// share with the loop's: mpc_kernels.hpp.
+// solver holds, from a start that reads no end point, and so needs no solve at all.  The adjoint's and the
+// tangent's kernels take a column from blockIdx.y: a single call is one column, a batched call (§13i) up to
+// SENS_W of them, and both run the one host path at the end of the file.  Kernels and what they share with the
+// loop's: mpc_kernels.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -51,7 +52,7 @@ struct Staged {
 // list start) with lvar on a problem that has fixed variables; the host route's output staging (8 B per
 // output entry) with each output it is asked for.
 struct Adjoint {
-  DBuf<double> sol, rowres, scal;         // a~ (refined); |g - K a~| per row; [residual ratio, unused]
+  DBuf<double> sol, rowres, scal;         // a~ (refined); |g - K a~| per row; [residual ratio, the single view's scal]
   DBuf<int32_t> rowslack;                 // row -> its slack (index into [nx, n)) or -1 (equality row)
   DBuf<int32_t> Ar, Ac, Hr, Hc;           // COO indices, creation-time entry order
   DBuf<int32_t> fix, fhsp, fasp;          // fixed variables; their list starts into fh / fa
@@ -131,7 +132,7 @@ struct PolSens {
 };
 
 // The batched sensitivities (madipm_solver_tangent_batch / _adjoint_batch) keep SENS_W columns of
-// the single calls' scratch, column-contiguous (column j of a buffer of vectors of length len starts at j len), so
+// the single calls' scratch (SensView names which buffer stands for which), column-contiguous (column j of a buffer of vectors of length len starts at j len), so
 // that the LDL^T solves one column in place.  Each part by the first batched call that needs it: the solve's
 // vector, the kept right-hand side, the solution, the residual rows and the columns' ratios (8 B x W x (4 (n + m)
 // + 1)); the shift vector and a~'x with the tangent or a cotangent other than gx (8 B x W x (n + m + nvar)); the
@@ -143,6 +144,7 @@ struct SensBatch {
   Staged<double, 7> dir, grad;            // host route: c, Hvals, Avals, lcon, ucon, lvar, uvar
   Staged<double, 5> out, ct;              // host route: x, y, zl, zu, cons
   int64_t n_batches = 0, n_columns = 0, n_chunks = 0;
+  void count(int64_t k, int64_t chunks) { ++n_batches, n_columns += k, n_chunks += chunks; }
   // N = n + m.  shifted: the tangent, or a cotangent other than gx; tangent: its data terms and dx
   void need(int64_t N, int nx, int n, bool shifted, bool tangent) {
     const auto cols = [](int64_t len) { return std::max<int64_t>(SENS_W * len, 1); };
@@ -162,6 +164,18 @@ struct SensBatch {
       dx.alloc(cols(n));
     }
   }
+};
+
+// The scratch one tangent or adjoint call runs on: W columns of each vector, column j of a vector of length len
+// at j len, and the host route's staging of a chunk.  A single call's view (W = 1) is over the solver's own d / p
+// and the Adjoint's and Tangent's buffers, so it writes exactly the vectors it always wrote; a batched call's is
+// over SensBatch.  scal: the columns' residual ratios of a chunk that is folded (never the single call's).
+struct SensView {
+  int W;
+  double *d, *p, *sol, *rowres, *scal;    // the solves' vectors; the kept right-hand sides; a~; |g - K a~|; ratios
+  double *shift, *apx, *base, *dx;        // null where the call has no use for them
+  Staged<double, 7>*dir, *grad;           // the tangent's directions, the adjoint's gradients
+  Staged<double, 5>*out, *ct;             // the tangent's outputs, the adjoint's cotangents
 };
 
 // What the calls keep between them, created by the first of them; the tangent, the polish and the polished
@@ -192,6 +206,9 @@ struct PostSolve {
     adj.shift.alloc(std::max(N, 1));
     adj.apx.alloc(std::max(nx, 1));
   }
+  // shifted: the tangent, or a cotangent other than gx; tangent: after tangent_scratch.  Allocates what the
+  // view lacks: the shift vector and a~'x of a single call, the parts of SensBatch of a batched one.
+  SensView sens_view(MPCSolver& S, bool batch, bool shifted, bool tangent);
 };
 void PostSolveDelete::operator()(PostSolve* p) const { delete p; }
 
@@ -243,12 +260,32 @@ __device__ __forceinline__ double adj_gzu(const AdjArgs& A, const AdjFull& F, in
   return (F.gzu && A.ubpos[i] >= 0) ? F.gzu[i] : 0.0;
 }
 
+// The kernels below and the tangent's (§13e) work on column blockIdx.y of a call's blocks and scratch (§13i): a
+// single call launches them with gridDim.y == 1, a batched one with a chunk's columns.  Arguments named ...b and
+// the structs named ...0 hold the first column; column j of a block of vectors of length len starts at j len.
+struct BLen {  // entries of Hvals / Avals: the column strides the kernels cannot read from AdjArgs
+  int64_t nh, na;
+};
+// column j of a block of vectors of length len (null stays null)
+__device__ __forceinline__ const double* bcol(const double* p, int j, int64_t len) { return p ? p + j * len : nullptr; }
+__device__ __forceinline__ double* bcol(double* p, int j, int64_t len) { return p ? p + j * len : nullptr; }
+__device__ __forceinline__ AdjArgs adj_col(AdjArgs A, int j) {  // a~ of column j
+  A.d = A.d + j * ((int64_t)A.n + A.m);
+  return A;
+}
+__device__ __forceinline__ AdjFull full_col(const AdjFull& F, const AdjArgs& A, int j) {
+  return AdjFull{bcol(F.gzl, j, A.nx), bcol(F.gzu, j, A.nx), bcol(F.gcons, j, A.m), bcol(F.apx, j, A.nx)};
+}
+
 // v = [q~; 0; gcons / con_scale], the vector the shifted right-hand side applies K's blocks to:
 // q_i = (Sigma_l gzl - Sigma_u gzu)_i / (Sigma_l + Sigma_u)_i on a free variable with a bound, else 0 (the
 // scalings cancel in q), q~ = q / obj_scale.  The slack entries are written 0: their J~^T row is not empty.
-__global__ __launch_bounds__(NT) void k_adj_shift(AdjArgs A, AdjFull F, double* __restrict__ v, LDLStatus* t1) {
+__global__ __launch_bounds__(NT) void k_adj_shift(AdjArgs A, AdjFull F0, double* __restrict__ vb, LDLStatus* t1) {
 #pragma clang fp contract(off)
-  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  if (t1 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  const int col = blockIdx.y;
+  const AdjFull F = full_col(F0, A, col);
+  double* __restrict__ v = vb + col * ((int64_t)A.n + A.m);
   GRID_LOOP(i, A.n + A.m) {
     double o = 0.0;
     if (i < A.nx) {
@@ -263,15 +300,22 @@ __global__ __launch_bounds__(NT) void k_adj_shift(AdjArgs A, AdjFull F, double* 
   }
 }
 
-// The shifted right-hand side into d (and p, which keeps it for the residual), k_adj_resid's access pattern
-// applied to v: gx + H~ q~ + J~^T (gcons / con_scale) on a free variable, 0 on a fixed one and on a slack,
-// con_scale_r gy_r / obj_scale + J~_r q~ on row r.  Every entry is of the cotangents' magnitude: the
-// Sigma terms of the plain form, 1e8 and more at an active bound, have cancelled in the algebra.
+// The shifted right-hand side into bd (the solve's vector: the solver's d in a single call) and bp (which keeps
+// it for the residual: the solver's p), k_adj_resid's access pattern applied to v: gx + H~ q~ +
+// J~^T (gcons / con_scale) on a free variable, 0 on a fixed one and on a slack, con_scale_r gy_r / obj_scale +
+// J~_r q~ on row r.  Every entry is of the cotangents' magnitude: the Sigma terms of the plain form, 1e8 and more
+// at an active bound, have cancelled in the algebra.
 template <int G>
-__global__ __launch_bounds__(NT) void k_adj_rhs_full(DV D, AdjArgs A, const double* __restrict__ gx,
-                                                     const double* __restrict__ gy, const double* __restrict__ v) {
+__global__ __launch_bounds__(NT) void k_adj_rhs_full(DV D, AdjArgs A, const double* __restrict__ gxb,
+                                                     const double* __restrict__ gyb, const double* __restrict__ vb,
+                                                     double* __restrict__ bd, double* __restrict__ bp) {
 #pragma clang fp contract(off)
   const int n = D.n, m = D.m;
+  const int col = blockIdx.y;
+  const int64_t off = col * ((int64_t)n + m);
+  const double* __restrict__ gx = bcol(gxb, col, D.nx);
+  const double* __restrict__ gy = bcol(gyb, col, m);
+  const double* __restrict__ v = vb + off;
   const bool lead = (threadIdx.x & (G - 1)) == 0;
   GROUP_LOOP(i, n + m, G) {
     double g = 0.0;
@@ -286,15 +330,19 @@ __global__ __launch_bounds__(NT) void k_adj_rhs_full(DV D, AdjArgs A, const doub
       g = (gy ? A.cscale[i - n] * gy[i - n] / A.os : 0.0) + jq;
     }
     if (lead) {
-      D.d[i] = g;
-      D.p[i] = g;
+      bd[off + i] = g;
+      bp[off + i] = g;
     }
   }
 }
 
 // a~ = a~' - [q~; 0; 0], with a~'x kept for the bound gradients
-__global__ __launch_bounds__(NT) void k_adj_unshift(int nx, const double* __restrict__ v, double* __restrict__ sol,
-                                                    double* __restrict__ apx) {
+__global__ __launch_bounds__(NT) void k_adj_unshift(int nx, int64_t N, const double* __restrict__ vb,
+                                                    double* __restrict__ solb, double* __restrict__ apxb) {
+  const int col = blockIdx.y;
+  const double* __restrict__ v = vb + col * N;
+  double* __restrict__ sol = solb + col * N;
+  double* __restrict__ apx = apxb + col * (int64_t)nx;
   GRID_LOOP(i, nx) {
     const double ap = sol[i];
     apx[i] = ap;
@@ -302,27 +350,33 @@ __global__ __launch_bounds__(NT) void k_adj_unshift(int nx, const double* __rest
   }
 }
 
-// gx into d's K2 layout (and into p, which keeps it for the residual): zero on fixed variables, slacks, rows
+// gx into bd's K2 layout (and into bp, which keeps it for the residual): zero on fixed variables, slacks, rows
 // t1 != nullptr: the factorisation before this launch ended (LinSolver::lazy_inertia), as in k_rhs
-__global__ __launch_bounds__(NT) void k_adj_rhs(DV D, const double* __restrict__ gx, LDLStatus* t1) {
-  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
+__global__ __launch_bounds__(NT) void k_adj_rhs(DV D, const double* __restrict__ gxb, double* __restrict__ bd,
+                                                double* __restrict__ bp, LDLStatus* t1) {
+  if (t1 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  const int col = blockIdx.y;
+  const int64_t off = col * ((int64_t)D.n + D.m);
+  const double* __restrict__ gx = gxb + col * (int64_t)D.nx;
   GRID_LOOP(i, D.n + D.m) {
     const double v = (i < D.nx && !D.fixed[i]) ? gx[i] : 0.0;
-    D.d[i] = v;
-    D.p[i] = v;
+    bd[off + i] = v;
+    bp[off + i] = v;
   }
 }
 
 // r = g - K v and |r| of every row, K the K2 matrix of the point WITHOUT the regularisation the factor carries:
 // H, J^T and Sigma_l + Sigma_u on a primal row, J on a dual row (k_residual's operator with the bound blocks
-// folded into Sigma).  v = the current a~; r (may be null) becomes the right-hand side of a refinement solve.
+// folded into Sigma).  g = the kept right-hand side; v = the current a~; r (may be null) becomes the right-hand
+// side of a refinement solve.  One column: a chunk of more runs k_adj_resid_b (§13i, at the end of the file).
 template <int G>
-__global__ __launch_bounds__(NT) void k_adj_resid(DV D, AdjArgs A, const double* __restrict__ v, double* __restrict__ r,
+__global__ __launch_bounds__(NT) void k_adj_resid(DV D, AdjArgs A, const double* __restrict__ g,
+                                                  const double* __restrict__ v, double* __restrict__ r,
                                                   double* __restrict__ rowres) {
   const int n = D.n, m = D.m;
   const bool lead = (threadIdx.x & (G - 1)) == 0;
   GROUP_LOOP(i, n + m, G) {
-    const double gi = D.p[i];
+    const double gi = g[i];
     double kv;
     if (i < n) {
       double hd, jd;
@@ -345,16 +399,22 @@ __global__ __launch_bounds__(NT) void k_adj_acc(double* __restrict__ acc, const 
   GRID_LOOP(i, N) acc[i] = first ? d[i] : acc[i] + d[i];
 }
 
-// out[0] = max_i rowres[i] / max(1, max_i |g_i|): one block, each thread a strided slice, then an LDS tree
-// (a maximum does not depend on the order; a NaN is kept).  g == null: the plain maximum.
-__global__ __launch_bounds__(NT) void k_adj_resmax(const double* __restrict__ rowres, const double* __restrict__ g,
+// Column blockIdx.x: out[column] = max_i rowres[i] / max(1, max_i |g_i|): one block, each thread a strided slice,
+// then an LDS tree (a maximum does not depend on the order; a NaN is kept).  gb == null: the plain maximum.
+__global__ __launch_bounds__(NT) void k_adj_resmax(const double* __restrict__ rowresb, const double* __restrict__ gb,
                                                    int64_t N, double* __restrict__ out) {
   __shared__ double sw[NT], sg[NT];
   const int t = threadIdx.x;
+  const double* __restrict__ rowres = rowresb + blockIdx.x * N;
+  const double* __restrict__ g = bcol(gb, blockIdx.x, N);
   double w = 0.0, gm = 0.0;
-  for (int64_t i = t; i < N; i += NT) {
-    w = nmax(w, rowres[i]);
-    if (g) gm = nmax(gm, fabs(g[i]));
+  if (g) {  // tested outside the loop, which is a third of a call's time on a large problem (one block, N trips / NT)
+    for (int64_t i = t; i < N; i += NT) {
+      w = nmax(w, rowres[i]);
+      gm = nmax(gm, fabs(g[i]));
+    }
+  } else {
+    for (int64_t i = t; i < N; i += NT) w = nmax(w, rowres[i]);
   }
   sw[t] = w;
   sg[t] = gm;
@@ -366,7 +426,7 @@ __global__ __launch_bounds__(NT) void k_adj_resmax(const double* __restrict__ ro
     }
     __syncthreads();
   }
-  if (t == 0) out[0] = sw[0] / (sg[0] > 1.0 ? sg[0] : 1.0);
+  if (t == 0) out[blockIdx.x] = sw[0] / (sg[0] > 1.0 ? sg[0] : 1.0);
 }
 
 // The vector gradients (any output may be null).  Variable i: c_i = -sgn ax_i; a free one:
@@ -377,11 +437,19 @@ __global__ __launch_bounds__(NT) void k_adj_resmax(const double* __restrict__ ro
 // lvar_i = Sigma~_l,i a~'x_i + h_i (gzl_i + gzu_i), uvar_i = Sigma~_u,i a~'x_i - h_i (gzl_i + gzu_i),
 // h_i = Sigma~_l Sigma~_u / (Sigma~_l + Sigma~_u) / obj_scale (0 where the sum is 0).
 template <bool FULL>
-__global__ __launch_bounds__(NT) void k_adj_vec(AdjArgs A, AdjFull F, const int32_t* __restrict__ rowslack,
-                                                double* __restrict__ gc, double* __restrict__ glv,
-                                                double* __restrict__ guv, double* __restrict__ glc,
-                                                double* __restrict__ guc) {
+__global__ __launch_bounds__(NT) void k_adj_vec(AdjArgs A0, AdjFull F0, const int32_t* __restrict__ rowslack,
+                                                double* __restrict__ gcb, double* __restrict__ glvb,
+                                                double* __restrict__ guvb, double* __restrict__ glcb,
+                                                double* __restrict__ gucb) {
 #pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const AdjArgs A = adj_col(A0, col);
+  const AdjFull F = full_col(F0, A, col);
+  double* __restrict__ gc = bcol(gcb, col, A.nx);
+  double* __restrict__ glv = bcol(glvb, col, A.nx);
+  double* __restrict__ guv = bcol(guvb, col, A.nx);
+  double* __restrict__ glc = bcol(glcb, col, A.m);
+  double* __restrict__ guc = bcol(gucb, col, A.m);
   GRID_LOOP(i, (A.nx > A.m ? A.nx : A.m)) {
     if (i < A.nx) {
       const bool fx = A.fixed[i];
@@ -420,9 +488,13 @@ __global__ __launch_bounds__(NT) void k_adj_vec(AdjArgs A, AdjFull F, const int3
 // Avals[k], entry (r, c): -(ax_c y_r + ay_r x_c), y the public multiplier (k_unscale's rounding)
 // FULL: + gcons_r x_c, the entry's own part of (A x)_r
 template <bool FULL>
-__global__ __launch_bounds__(NT) void k_adj_avals(AdjArgs A, AdjFull F, int64_t nnz, const int32_t* __restrict__ Ar,
-                                                  const int32_t* __restrict__ Ac, double* __restrict__ out) {
+__global__ __launch_bounds__(NT) void k_adj_avals(AdjArgs A0, AdjFull F0, int64_t nnz, const int32_t* __restrict__ Ar,
+                                                  const int32_t* __restrict__ Ac, double* __restrict__ outb) {
 #pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const AdjArgs A = adj_col(A0, col);
+  const AdjFull F = full_col(F0, A, col);
+  double* __restrict__ out = outb + col * nnz;
   GRID_LOOP(k, nnz) {
     const int r = Ar[k], c = Ac[k];
     const double yr = A.y[r] * A.cscale[r] / A.os;
@@ -435,9 +507,12 @@ __global__ __launch_bounds__(NT) void k_adj_avals(AdjArgs A, AdjFull F, int64_t 
 }
 
 // Hvals[k], entry (r, c) of the lower triangle: -sgn ax_r x_r on the diagonal, -sgn (ax_r x_c + ax_c x_r) off it
-__global__ __launch_bounds__(NT) void k_adj_hvals(AdjArgs A, int64_t nnz, const int32_t* __restrict__ Hr,
-                                                  const int32_t* __restrict__ Hc, double* __restrict__ out) {
+__global__ __launch_bounds__(NT) void k_adj_hvals(AdjArgs A0, int64_t nnz, const int32_t* __restrict__ Hr,
+                                                  const int32_t* __restrict__ Hc, double* __restrict__ outb) {
 #pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const AdjArgs A = adj_col(A0, col);
+  double* __restrict__ out = outb + col * nnz;
   GRID_LOOP(k, nnz) {
     const int r = Hr[k], c = Hc[k];
     const double ar = adj_ax(A, r);
@@ -451,12 +526,17 @@ __global__ __launch_bounds__(NT) void k_adj_hvals(AdjArgs A, int64_t nnz, const 
 // FULL: gxe_f = gx_f + (A^T gcons)_f in the place of gx_f, over the same list of column f (J~^T has no row
 // of a fixed variable), and gx may be null
 template <bool FULL>
-__global__ __launch_bounds__(NT) void k_adj_fix(AdjArgs A, AdjFull F, int nfix, const int32_t* __restrict__ fix,
+__global__ __launch_bounds__(NT) void k_adj_fix(AdjArgs A0, AdjFull F0, int nfix, const int32_t* __restrict__ fix,
                                                 const int32_t* __restrict__ fhsp, const int2* __restrict__ fh,
                                                 const int32_t* __restrict__ fasp, const int2* __restrict__ fa,
                                                 const double* __restrict__ Hraw, const double* __restrict__ Araw,
-                                                const double* __restrict__ gx, double* __restrict__ glv) {
+                                                const double* __restrict__ gxb, double* __restrict__ glvb) {
 #pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const AdjArgs A = adj_col(A0, col);
+  const AdjFull F = full_col(F0, A, col);
+  const double* __restrict__ gx = bcol(gxb, col, A.nx);
+  double* __restrict__ glv = glvb + col * (int64_t)A.nx;
   GRID_LOOP(t, nfix) {
     double hs = 0.0, as = 0.0;
     for (int q = fhsp[t]; q < fhsp[t + 1]; ++q) {
@@ -524,6 +604,18 @@ PostSolve& MPCSolver::post_state() {
 AdjArgs PostSolve::args(MPCSolver& S) {
   return AdjArgs{S.n_,    S.m_,    S.nx_,   S.obj_scale_,         S.H_->sgn,  adj.sol.p,  S.x_.p,    S.xl_.p, S.xu_.p,
                  S.zl_.p, S.zu_.p, S.y_.p,  S.device_con_scale(), S.lbpos_.p, S.ubpos_.p, S.fixed_.p};
+}
+
+SensView PostSolve::sens_view(MPCSolver& S, bool batch, bool shifted, bool tangent) {
+  if (!batch) {  // adj.scal's second entry is never read: a single call is its own first chunk of one column
+    if (shifted) need_shift(S.n_ + S.m_, S.nx_);
+    return SensView{1,           S.d_.p,    S.p_.p,     adj.sol.p, adj.rowres.p, adj.scal.p + 1, adj.shift.p,
+                    adj.apx.p,   tan.base.p, tan.dx.p,  &tan.dir,  &adj.out,     &tan.out,       &adj.ct};
+  }
+  SensBatch& b = bat;
+  b.need((int64_t)S.n_ + S.m_, S.nx_, S.n_, shifted, tangent);
+  return SensView{SENS_W,  b.d.p,    b.p.p,  b.sol.p, b.rowres.p, b.scal.p, b.shift.p,
+                  b.apx.p, b.base.p, b.dx.p, &b.dir,  &b.grad,    &b.out,   &b.ct};
 }
 
 void PostSolve::adjoint_lists(MPCSolver& S, bool needA, bool needH, bool needFix) {
@@ -613,113 +705,17 @@ void MPCSolver::sens_factor(const std::string& who) {
   ++a.n_fact;
 }
 
-// With the right-hand side in d (and in p, which keeps it): adj.sol = K^-1 p, refined; the residual ratio
-// into resid[0]
-void MPCSolver::sens_solve(double* resid) {
-  Adjoint& a = post_->adj;
-  const AdjArgs A = post_->args(*this);
-  const DV D = view();
-  hipStream_t s = stream_;
-  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
-  const int64_t N = (int64_t)n_ + m_;
-  kkt_solve();
-  k_adj_acc<<<nb, NT, 0, s>>>(a.sol.p, d_.p, N, 1);
-  // iterative refinement towards the system without the regularisation (the factor is the regularised
-  // matrix's: each step gains about -log10(delta |K^-1|) digits); a fixed count, so nothing is read back
-  for (int it = 0; it < adj_refine_steps(); ++it) {
-    SPMV_LAUNCH(k_adj_resid, nbs, s, D, A, a.sol.p, d_.p, a.rowres.p);
-    kkt_solve();
-    k_adj_acc<<<nb, NT, 0, s>>>(a.sol.p, d_.p, N, 0);
-  }
-  SPMV_LAUNCH(k_adj_resid, nbs, s, D, A, a.sol.p, (double*)nullptr, a.rowres.p);
-  k_adj_resmax<<<1, NT, 0, s>>>(a.rowres.p, p_.p, N, resid);
-}
-
 void MPCSolver::adjoint(const double* gx, const madipm_qp_gradients& g, bool device, hipStream_t caller) {
   adjoint(madipm_qp_cotangents{gx, nullptr, nullptr, nullptr, nullptr}, g, device, caller, nullptr);
 }
 
-// name == nullptr: madipm_solver_adjoint / _adjoint_device (gx alone, which must be given).  full: a
-// cotangent other than gx is given, and the shifted system of §13d is solved; without one the kernels and
-// their order are those of the gx-only call whichever entry point was taken.
+// name == nullptr: madipm_solver_adjoint / _adjoint_device (gx alone, which must be given).  One column on the
+// single call's scratch (adjoint_cols, §13i).
 void MPCSolver::adjoint(const madipm_qp_cotangents& ct, const madipm_qp_gradients& g, bool device,
                         hipStream_t caller, const char* name) {
   const std::string who =
       name ? std::string(name) + ": " : (device ? "madipm_solver_adjoint_device: " : "madipm_solver_adjoint: ");
-  const double* const gx = ct.x;
-  const bool full = ct.y || ct.zl || ct.zu || ct.cons;
-  QPHost& P = *H_;
-  // ---- refusals, before anything is allocated or enqueued
-  sens_refuse(who);
-  if (name)
-    MADIPM_REQUIRE(gx || full, who + "all five cotangents are NULL");
-  else
-    MADIPM_REQUIRE(gx, who + "gx is NULL");
-  double* const user[7] = {g.c, g.Hvals, g.Avals, g.lcon, g.ucon, g.lvar, g.uvar};
-  MADIPM_REQUIRE(g.c || g.Hvals || g.Avals || g.lcon || g.ucon || g.lvar || g.uvar,
-                 who + "all seven outputs are NULL");
-  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
-  const bool needA = g.Avals && na > 0, needH = g.Hvals && nh > 0, needFix = g.lvar && P.anyfix;
-  MADIPM_REQUIRE(plan_ || !(needA || needH || needFix),
-                 who + "Avals, Hvals (and lvar on a problem with fixed variables) need "
-                       "madipm_solver_prepare_update first (it keeps the index arrays and the raw values)");
-  hipStream_t s = stream_;
-  // ---- allocations, each by the first call that needs it
-  PostSolve& ps = post_state();
-  Adjoint& a = ps.adj;
-  const AdjArgs A = ps.args(*this);
-  const double* const cot[5] = {gx, ct.y, ct.zl, ct.zu, ct.cons};
-  const int64_t clen[5] = {nx_, m_, nx_, nx_, m_};
-  const double* dct[5];  // gx, gy, gzl, gzu, gcons on the device
-  a.ct.bind(cot, clen, device, dct);
-  if (full) ps.need_shift(n_ + m_, nx_);
-  if (g.lcon || g.ucon) ps.rowslack(P, s);
-  ps.adjoint_lists(*this, needA, needH, needFix);
-  const int64_t len[7] = {nx_, nh, na, m_, m_, nx_, nx_};
-  double* out[7];
-  a.out.bind(user, len, device, out);
-  // ---- the factor of the K2 matrix at the final iterate: once per solve
-  const DV D = view();
-  sens_factor(who);
-  // ---- right-hand side, solve, residual
-  if (device)
-    ps.sync.begin(caller, s);  // the cotangents are read after the work already enqueued on the caller's stream
-  else
-    a.ct.upload(cot, clen, s);
-  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
-  const AdjFull F{dct[2], dct[3], dct[4], a.apx.p};
-  if (full) {  // the shifted system K a~' = g' (§13d); p keeps g' for the residual
-    k_adj_shift<<<nb, NT, 0, s>>>(A, F, a.shift.p, take_fact_end());
-    SPMV_LAUNCH(k_adj_rhs_full, nbs, s, D, A, dct[0], dct[1], (const double*)a.shift.p);
-  } else {
-    k_adj_rhs<<<nb, NT, 0, s>>>(D, dct[0], take_fact_end());
-  }
-  sens_solve(a.scal.p);
-  if (full && nx_) k_adj_unshift<<<blocks(nx_), NT, 0, s>>>(nx_, a.shift.p, a.sol.p, a.apx.p);
-  // ---- gradients
-  const bool vec = (out[0] || out[3] || out[4] || out[5] || out[6]) && std::max(nx_, m_);
-  const bool fix = needFix && a.nfix > 0;
-  auto gradients = [&](auto is_full) {  // the <true> instantiations read F (§13d)
-    constexpr bool FULL = decltype(is_full)::value;
-    if (vec)
-      k_adj_vec<FULL><<<blocks(std::max(nx_, m_)), NT, 0, s>>>(A, F, a.rowslack.p, out[0], out[5], out[6], out[3],
-                                                                out[4]);
-    if (fix)
-      k_adj_fix<FULL><<<blocks(a.nfix), NT, 0, s>>>(A, F, a.nfix, a.fix.p, a.fhsp.p, a.fh.p, a.fasp.p, a.fa.p,
-                                                     plan_->Hraw.p, plan_->Araw.p, dct[0], out[5]);
-    if (needA) k_adj_avals<FULL><<<blocks(na), NT, 0, s>>>(A, F, na, a.Ar.p, a.Ac.p, out[2]);
-  };
-  if (full)
-    gradients(std::true_type{});
-  else
-    gradients(std::false_type{});
-  if (needH) k_adj_hvals<<<blocks(nh), NT, 0, s>>>(A, nh, a.Hr.p, a.Hc.p, out[1]);
-  MADIPM_HIP(hipGetLastError());
-  if (device)
-    ps.sync.end(s, caller);  // work enqueued on the caller's stream from now on sees the outputs
-  else
-    a.out.download(user, len, s);
-  ++a.n_adjoints;
+  adjoint_cols(who, 1, false, false, !name, ct, g, device, caller);
 }
 
 // the residual ratio the last call left on the device (0 before the first call)
@@ -759,15 +755,23 @@ __device__ __forceinline__ double tan_dl(const AdjArgs& A, const TanDir& T, int 
 __device__ __forceinline__ double tan_du(const AdjArgs& A, const TanDir& T, int i) {
   return (T.uvar && A.ubpos[i] >= 0) ? T.uvar[i] : 0.0;
 }
+// the directions of column j (the kernels below: column blockIdx.y, as the adjoint's)
+__device__ __forceinline__ TanDir tan_col(const TanDir& T, const AdjArgs& A, const BLen& L, int j) {
+  return TanDir{bcol(T.c, j, A.nx),   bcol(T.Hv, j, L.nh),  bcol(T.Av, j, L.na),  bcol(T.lcon, j, A.m),
+                bcol(T.ucon, j, A.m), bcol(T.lvar, j, A.nx), bcol(T.uvar, j, A.nx)};
+}
 
 // v = [p; p~_s; 0]: p_i = (Sigma_l dlvar + Sigma_u duvar)_i / (Sigma_l + Sigma_u)_i on a free variable with a
 // bound, else 0 (the scalings cancel in p); the slack k of row r: p~_s,k = con_scale_r (Sigma_l,k dlcon_r +
 // Sigma_u,k ducon_r) / (Sigma_l,k + Sigma_u,k).  One thread per variable and per row; a row's thread writes
 // its slack's entry.
-__global__ __launch_bounds__(NT) void k_tan_shift(AdjArgs A, TanDir T, const int32_t* __restrict__ rowslack,
-                                                  double* __restrict__ v, LDLStatus* t1) {
+__global__ __launch_bounds__(NT) void k_tan_shift(AdjArgs A, TanDir T0, BLen L, const int32_t* __restrict__ rowslack,
+                                                  double* __restrict__ vb, LDLStatus* t1) {
 #pragma clang fp contract(off)
-  if (t1 && blockIdx.x == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  if (t1 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ldl_status_end(t1);
+  const int col = blockIdx.y;
+  const TanDir T = tan_col(T0, A, L, col);
+  double* __restrict__ v = vb + col * ((int64_t)A.n + A.m);
   GRID_LOOP(i, A.n + A.m) {
     if (i < A.nx) {
       double o = 0.0;
@@ -794,12 +798,15 @@ __global__ __launch_bounds__(NT) void k_tan_shift(AdjArgs A, TanDir T, const int
 // multiplier, os y_r = con_scale_r y~_r; 0 on a fixed variable and a slack.  Row r (public space):
 // base_r = (dA x)_r + (A dxfix)_r.  dxfix = dlvar on the fixed variables.  Without lists (gsp == null) the
 // sums are empty: no Hvals / Avals direction and no fixed variable with an lvar direction.
-__global__ __launch_bounds__(NT) void k_tan_data(AdjArgs A, TanDir T, const int32_t* __restrict__ gsp,
+__global__ __launch_bounds__(NT) void k_tan_data(AdjArgs A, TanDir T0, BLen L, const int32_t* __restrict__ gsp,
                                                  const int2* __restrict__ ge, const int32_t* __restrict__ csp,
                                                  const int2* __restrict__ ce, const int32_t* __restrict__ asp,
                                                  const int2* __restrict__ ae, const double* __restrict__ Hraw,
-                                                 const double* __restrict__ Araw, double* __restrict__ base) {
+                                                 const double* __restrict__ Araw, double* __restrict__ baseb) {
 #pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const TanDir T = tan_col(T0, A, L, col);
+  double* __restrict__ base = baseb + col * ((int64_t)A.n + A.m);
   GRID_LOOP(i, A.n + A.m) {
     double o = 0.0;
     if (i < A.nx) {
@@ -833,15 +840,22 @@ __global__ __launch_bounds__(NT) void k_tan_data(AdjArgs A, TanDir T, const int3
   }
 }
 
-// The shifted right-hand side into d (and p, which keeps it for the residual), k_adj_rhs_full's access
+// The shifted right-hand side into bd (and bp, which keeps it for the residual), k_adj_rhs_full's access
 // pattern applied to v: base_i - (H~ p)_i on a free variable (v's row part is 0: J~^T adds nothing), 0 on a
 // fixed one and on a slack, con_scale_r (db_r - base_r) - (J~ p - p~_s)_r on row r, db = dlcon on an equality
 // row.  Every entry is of the directions' magnitude.
 template <int G>
-__global__ __launch_bounds__(NT) void k_tan_rhs(DV D, AdjArgs A, TanDir T, const int32_t* __restrict__ rowslack,
-                                                const double* __restrict__ v, const double* __restrict__ base) {
+__global__ __launch_bounds__(NT) void k_tan_rhs(DV D, AdjArgs A, TanDir T0, BLen L,
+                                                const int32_t* __restrict__ rowslack, const double* __restrict__ vb,
+                                                const double* __restrict__ baseb, double* __restrict__ bd,
+                                                double* __restrict__ bp) {
 #pragma clang fp contract(off)
   const int n = D.n, m = D.m;
+  const int col = blockIdx.y;
+  const int64_t off = col * ((int64_t)n + m);
+  const TanDir T = tan_col(T0, A, L, col);
+  const double* __restrict__ v = vb + off;
+  const double* __restrict__ base = baseb + off;
   const bool lead = (threadIdx.x & (G - 1)) == 0;
   GROUP_LOOP(i, n + m, G) {
     double g = 0.0;
@@ -854,8 +868,8 @@ __global__ __launch_bounds__(NT) void k_tan_rhs(DV D, AdjArgs A, TanDir T, const
       g = A.cscale[r] * (db - base[i]) - jq;
     }
     if (lead) {
-      D.d[i] = g;
-      D.p[i] = g;
+      bd[off + i] = g;
+      bp[off + i] = g;
     }
   }
 }
@@ -865,11 +879,20 @@ __global__ __launch_bounds__(NT) void k_tan_rhs(DV D, AdjArgs A, TanDir T, const
 // k_tan_cons); dy = con_scale dy~ / obj_scale; dzl = -Sigma_l dx' + h (dlvar - duvar), dzu = Sigma_u dx' +
 // h (dlvar - duvar) with the public Sigma = Sigma~ / obj_scale and h = Sigma_l Sigma_u / (Sigma_l + Sigma_u);
 // 0 without that bound and on a fixed variable.
-__global__ __launch_bounds__(NT) void k_tan_out(AdjArgs A, TanDir T, const double* __restrict__ v,
-                                                double* __restrict__ dxs, double* __restrict__ ox,
-                                                double* __restrict__ oy, double* __restrict__ ozl,
-                                                double* __restrict__ ozu) {
+__global__ __launch_bounds__(NT) void k_tan_out(AdjArgs A0, TanDir T0, BLen L, const double* __restrict__ vb,
+                                                double* __restrict__ dxsb, double* __restrict__ oxb,
+                                                double* __restrict__ oyb, double* __restrict__ ozlb,
+                                                double* __restrict__ ozub) {
 #pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const AdjArgs A = adj_col(A0, col);
+  const TanDir T = tan_col(T0, A, L, col);
+  const double* __restrict__ v = vb + col * ((int64_t)A.n + A.m);
+  double* __restrict__ dxs = dxsb + col * (int64_t)A.n;
+  double* __restrict__ ox = bcol(oxb, col, A.nx);
+  double* __restrict__ oy = bcol(oyb, col, A.m);
+  double* __restrict__ ozl = bcol(ozlb, col, A.nx);
+  double* __restrict__ ozu = bcol(ozub, col, A.nx);
   const int ns = A.n - A.nx;
   const int top = A.nx > A.m ? A.nx : A.m;
   GRID_LOOP(i, (top > ns ? top : ns)) {
@@ -898,9 +921,13 @@ __global__ __launch_bounds__(NT) void k_tan_out(AdjArgs A, TanDir T, const doubl
 // dcons_r = (A dx)_r + (dA x)_r: J~'s structural columns times dx / con_scale_r (J~ has no fixed column, and
 // dxs is 0 on the slacks), + base_r, which holds the fixed columns' part and dA x
 template <int G>
-__global__ __launch_bounds__(NT) void k_tan_cons(DV D, AdjArgs A, const double* __restrict__ dxs,
-                                                 const double* __restrict__ base, double* __restrict__ ocons) {
+__global__ __launch_bounds__(NT) void k_tan_cons(DV D, AdjArgs A, const double* __restrict__ dxsb,
+                                                 const double* __restrict__ baseb, double* __restrict__ oconsb) {
 #pragma clang fp contract(off)
+  const int col = blockIdx.y;
+  const double* __restrict__ dxs = dxsb + col * (int64_t)D.n;
+  const double* __restrict__ base = baseb + col * ((int64_t)D.n + D.m);
+  double* __restrict__ ocons = oconsb + col * (int64_t)D.m;
   const bool lead = (threadIdx.x & (G - 1)) == 0;
   GROUP_LOOP(r, D.m, G) {
     const double s = gdot<G>(D.J, r, dxs);
@@ -913,62 +940,7 @@ __global__ __launch_bounds__(NT) void k_tan_cons(DV D, AdjArgs A, const double* 
 void MPCSolver::tangent(const madipm_qp_directions& dr, const madipm_qp_point_tangents& o, bool device,
                         hipStream_t caller) {
   const std::string who = device ? "madipm_solver_tangent_device: " : "madipm_solver_tangent: ";
-  QPHost& P = *H_;
-  // ---- refusals, before anything is allocated or enqueued
-  sens_refuse(who);
-  const double* const dir[7] = {dr.c, dr.Hvals, dr.Avals, dr.lcon, dr.ucon, dr.lvar, dr.uvar};
-  double* const user[5] = {o.x, o.y, o.zl, o.zu, o.cons};
-  MADIPM_REQUIRE(dr.c || dr.Hvals || dr.Avals || dr.lcon || dr.ucon || dr.lvar || dr.uvar,
-                 who + "all seven directions are NULL");
-  MADIPM_REQUIRE(o.x || o.y || o.zl || o.zu || o.cons, who + "all five outputs are NULL");
-  const int64_t na = P.nnzA, nh = (int64_t)P.Hv.size();
-  const bool needLists = (dr.Avals && na > 0) || (dr.Hvals && nh > 0) || (dr.lvar && P.anyfix);
-  MADIPM_REQUIRE(plan_ || !needLists,
-                 who + "Avals, Hvals (and lvar on a problem with fixed variables) need "
-                       "madipm_solver_prepare_update first (it keeps the index arrays and the raw values)");
-  hipStream_t s = stream_;
-  // ---- allocations, each by the first call that needs it
-  PostSolve& ps = post_state();
-  Adjoint& a = ps.adj;
-  Tangent& t = ps.tan;
-  const AdjArgs A = ps.args(*this);
-  ps.need_shift(n_ + m_, nx_);  // as the five-cotangent adjoint allocates them
-  ps.rowslack(P, s);
-  ps.tangent_scratch(*this, needLists);
-  const int64_t dlen[7] = {nx_, nh, na, m_, m_, nx_, nx_};
-  const int64_t olen[5] = {nx_, m_, nx_, nx_, m_};
-  const double* ddir[7];
-  double* out[5];
-  t.dir.bind(dir, dlen, device, ddir);
-  t.out.bind(user, olen, device, out);
-  // ---- the factor of the K2 matrix at the final iterate: the adjoint's, once per solve
-  const DV D = view();
-  sens_factor(who);
-  if (device)
-    ps.sync.begin(caller, s);  // the directions are read after the work already enqueued on the caller's stream
-  else
-    t.dir.upload(dir, dlen, s);
-  // ---- right-hand side, solve, residual
-  const int nb = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
-  const TanDir T{ddir[0], ddir[1], ddir[2], ddir[3], ddir[4], ddir[5], ddir[6]};
-  const bool ls = needLists;  // lists built by an earlier call are not walked when this one has no use for them
-  k_tan_shift<<<nb, NT, 0, s>>>(A, T, a.rowslack.p, a.shift.p, take_fact_end());
-  k_tan_data<<<nb, NT, 0, s>>>(A, T, ls ? t.gsp.p : nullptr, t.ge.p, t.csp.p, t.ce.p, ls ? t.asp.p : nullptr, t.ae.p,
-                               plan_ ? plan_->Hraw.p : nullptr, plan_ ? plan_->Araw.p : nullptr, t.base.p);
-  SPMV_LAUNCH(k_tan_rhs, nbs, s, D, A, T, (const int32_t*)a.rowslack.p, (const double*)a.shift.p,
-              (const double*)t.base.p);
-  sens_solve(t.scal.p);
-  // ---- outputs
-  k_tan_out<<<blocks(std::max(std::max(nx_, m_), std::max(n_ - nx_, 1))), NT, 0, s>>>(
-      A, T, a.shift.p, t.dx.p, out[0], out[1], out[2], out[3]);
-  if (out[4] && m_)
-    SPMV_LAUNCH(k_tan_cons, spmv_blocks(m_), s, D, A, (const double*)t.dx.p, (const double*)t.base.p, out[4]);
-  MADIPM_HIP(hipGetLastError());
-  if (device)
-    ps.sync.end(s, caller);  // work enqueued on the caller's stream from now on sees the outputs
-  else
-    t.out.download(user, olen, s);
-  ++t.n_tangents;
+  tangent_cols(who, 1, false, false, dr, o, device, caller);  // one column on the single call's scratch (§13i)
 }
 
 void MPCSolver::tangent_info(int64_t* n_tangents, double* last_residual) {
@@ -2017,8 +1989,9 @@ void MPCSolver::tangent_polished(const madipm_qp_directions& dr, const madipm_qp
   const int nb = blocks(n_ + m_);
   const TanDir T{ddir[0], ddir[1], ddir[2], ddir[3], ddir[4], ddir[5], ddir[6]};
   const bool ls = needLists;
-  k_tan_data<<<nb, NT, 0, s>>>(A, T, ls ? t.gsp.p : nullptr, t.ge.p, t.csp.p, t.ce.p, ls ? t.asp.p : nullptr, t.ae.p,
-                               plan_ ? plan_->Hraw.p : nullptr, plan_ ? plan_->Araw.p : nullptr, t.base.p);
+  k_tan_data<<<nb, NT, 0, s>>>(A, T, BLen{nh, na}, ls ? t.gsp.p : nullptr, t.ge.p, t.csp.p, t.ce.p,
+                               ls ? t.asp.p : nullptr, t.ae.p, plan_ ? plan_->Hraw.p : nullptr,
+                               plan_ ? plan_->Araw.p : nullptr, t.base.p);
   k_pst_rhs<<<nb, NT, 0, s>>>(A, T, (const int8_t*)p.codes.p, (const int32_t*)p.ineq.p,
                               (const int32_t*)ps.adj.rowslack.p, (const double*)t.base.p, q.u.p, q.rhs.p,
                               take_fact_end());
@@ -2110,268 +2083,16 @@ void MPCSolver::polished_sens_info(int64_t* n_tangents, int64_t* n_adjoints, int
 
 }  // namespace madipm
 
-// ======================================================================= batched sensitivities
-// madipm_solver_tangent_batch / _adjoint_batch / _device: k columns of one point per call.  At the end point
-// the columns run in chunks of kc <= SENS_W through the kernels below: the single calls' kernels with the column
-// in blockIdx.y (every expression, and so every bit, is the single kernel's), and the residual k_adj_resid_b,
-// whose lane groups load a row's entries and column indices once and gather from each column's vector.  The
-// solves are ldl_->solve_async on one column after the other.  The single calls launch none of these.
+// ======================================================================= one column or k: the host path
+// madipm_solver_tangent / _adjoint are one column on a SensView of the single calls' scratch,
+// madipm_solver_tangent_batch / _adjoint_batch / _device k columns of one point in chunks of kc <= SENS_W on the
+// view of SensBatch: one implementation of each (tangent_cols, adjoint_cols) and one refined solve (sens_solve),
+// launching §13c-§13e's kernels with the chunk's columns in gridDim.y.  Only the residual has two kernels: a
+// chunk of one column runs k_adj_resid, a chunk of more k_adj_resid_b below, whose lane groups load a row's
+// entries and column indices once and gather from each column's vector.  The solves are ldl_->solve_async on one
+// column after the other.
 namespace madipm {
 namespace {
-
-struct BLen {  // entries of Hvals / Avals: the column strides the kernels cannot read from AdjArgs
-  int64_t nh, na;
-};
-// column j of a block of vectors of length len (null stays null)
-__device__ __forceinline__ const double* bcol(const double* p, int j, int64_t len) { return p ? p + j * len : nullptr; }
-__device__ __forceinline__ double* bcol(double* p, int j, int64_t len) { return p ? p + j * len : nullptr; }
-__device__ __forceinline__ AdjArgs adj_col(AdjArgs A, int j) {  // a~ of column j
-  A.d = A.d + j * ((int64_t)A.n + A.m);
-  return A;
-}
-__device__ __forceinline__ TanDir tan_col(const TanDir& T, const AdjArgs& A, const BLen& L, int j) {
-  return TanDir{bcol(T.c, j, A.nx),   bcol(T.Hv, j, L.nh),  bcol(T.Av, j, L.na),  bcol(T.lcon, j, A.m),
-                bcol(T.ucon, j, A.m), bcol(T.lvar, j, A.nx), bcol(T.uvar, j, A.nx)};
-}
-__device__ __forceinline__ AdjFull full_col(const AdjFull& F, const AdjArgs& A, int j) {
-  return AdjFull{bcol(F.gzl, j, A.nx), bcol(F.gzu, j, A.nx), bcol(F.gcons, j, A.m), bcol(F.apx, j, A.nx)};
-}
-
-// ---- the tangent's kernels, column blockIdx.y (bodies: k_tan_shift, k_tan_data, k_tan_rhs, k_tan_out, k_tan_cons)
-__global__ __launch_bounds__(NT) void k_tan_shift_b(AdjArgs A, TanDir T0, BLen L, const int32_t* __restrict__ rowslack,
-                                                    double* __restrict__ vb, LDLStatus* t1) {
-#pragma clang fp contract(off)
-  if (t1 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ldl_status_end(t1);
-  const int col = blockIdx.y;
-  const TanDir T = tan_col(T0, A, L, col);
-  double* __restrict__ v = vb + col * ((int64_t)A.n + A.m);
-  GRID_LOOP(i, A.n + A.m) {
-    if (i < A.nx) {
-      double o = 0.0;
-      if (!A.fixed[i]) {
-        const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
-        if (sm > 0.0) o = (sl * tan_dl(A, T, (int)i) + su * tan_du(A, T, (int)i)) / sm;
-      }
-      v[i] = o;
-    } else if (i >= A.n) {
-      const int r = (int)(i - A.n), k = rowslack[r];
-      v[i] = 0.0;
-      if (k >= 0) {
-        const double sl = adj_sig_l(A, k), su = adj_sig_u(A, k), sm = sl + su;
-        const double dl = (T.lcon && A.lbpos[k] >= 0) ? T.lcon[r] : 0.0;
-        const double du = (T.ucon && A.ubpos[k] >= 0) ? T.ucon[r] : 0.0;
-        v[k] = sm > 0.0 ? A.cscale[r] * ((sl * dl + su * du) / sm) : 0.0;
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(NT) void k_tan_data_b(AdjArgs A, TanDir T0, BLen L, const int32_t* __restrict__ gsp,
-                                                   const int2* __restrict__ ge, const int32_t* __restrict__ csp,
-                                                   const int2* __restrict__ ce, const int32_t* __restrict__ asp,
-                                                   const int2* __restrict__ ae, const double* __restrict__ Hraw,
-                                                   const double* __restrict__ Araw, double* __restrict__ baseb) {
-#pragma clang fp contract(off)
-  const int col = blockIdx.y;
-  const TanDir T = tan_col(T0, A, L, col);
-  double* __restrict__ base = baseb + col * ((int64_t)A.n + A.m);
-  GRID_LOOP(i, A.n + A.m) {
-    double o = 0.0;
-    if (i < A.nx) {
-      if (!A.fixed[i]) {
-        double hs = 0.0, as = 0.0;
-        if (gsp) {
-          for (int q = gsp[i]; q < gsp[i + 1]; ++q) {
-            const int2 e = ge[q];
-            if (T.Hv) hs = hs + T.Hv[e.x] * A.x[e.y];
-            if (T.lvar && A.fixed[e.y]) hs = hs + Hraw[e.x] * T.lvar[e.y];
-          }
-          if (T.Av)
-            for (int q = csp[i]; q < csp[i + 1]; ++q) {
-              const int2 e = ce[q];
-              as = as + T.Av[e.x] * (A.cscale[e.y] * A.y[e.y]);
-            }
-        }
-        const double dc = T.c ? T.c[i] : 0.0;
-        o = -((A.os * A.sgn) * (dc + hs) + as);
-      }
-    } else if (i >= A.n) {
-      const int r = (int)(i - A.n);
-      if (asp)
-        for (int q = asp[r]; q < asp[r + 1]; ++q) {
-          const int2 e = ae[q];
-          if (T.Av) o = o + T.Av[e.x] * A.x[e.y];
-          if (T.lvar && A.fixed[e.y]) o = o + Araw[e.x] * T.lvar[e.y];
-        }
-    }
-    base[i] = o;
-  }
-}
-
-// bd: the solves' vectors, bp: the right-hand sides kept for the residual (DV's d and p of the single call)
-template <int G>
-__global__ __launch_bounds__(NT) void k_tan_rhs_b(DV D, AdjArgs A, TanDir T0, BLen L,
-                                                  const int32_t* __restrict__ rowslack, const double* __restrict__ vb,
-                                                  const double* __restrict__ baseb, double* __restrict__ bd,
-                                                  double* __restrict__ bp) {
-#pragma clang fp contract(off)
-  const int n = D.n, m = D.m;
-  const int col = blockIdx.y;
-  const int64_t off = col * ((int64_t)n + m);
-  const TanDir T = tan_col(T0, A, L, col);
-  const double* __restrict__ v = vb + off;
-  const double* __restrict__ base = baseb + off;
-  const bool lead = (threadIdx.x & (G - 1)) == 0;
-  GROUP_LOOP(i, n + m, G) {
-    double g = 0.0;
-    if (i < n) {
-      if (i < D.nx && !D.fixed[i]) g = base[i] - gdot<G>(D.H, i, v);
-    } else {
-      const int r = (int)(i - n);
-      const double jq = gdot<G>(D.J, r, v);
-      const double db = (T.lcon && rowslack[r] < 0) ? T.lcon[r] : 0.0;
-      g = A.cscale[r] * (db - base[i]) - jq;
-    }
-    if (lead) {
-      bd[off + i] = g;
-      bp[off + i] = g;
-    }
-  }
-}
-
-// A0.d: the solutions' columns; ox .. ozu: the output blocks' first column of the chunk (null: not wanted)
-__global__ __launch_bounds__(NT) void k_tan_out_b(AdjArgs A0, TanDir T0, BLen L, const double* __restrict__ vb,
-                                                  double* __restrict__ dxsb, double* __restrict__ oxb,
-                                                  double* __restrict__ oyb, double* __restrict__ ozlb,
-                                                  double* __restrict__ ozub) {
-#pragma clang fp contract(off)
-  const int col = blockIdx.y;
-  const AdjArgs A = adj_col(A0, col);
-  const TanDir T = tan_col(T0, A, L, col);
-  const double* __restrict__ v = vb + col * ((int64_t)A.n + A.m);
-  double* __restrict__ dxs = dxsb + col * (int64_t)A.n;
-  double* __restrict__ ox = bcol(oxb, col, A.nx);
-  double* __restrict__ oy = bcol(oyb, col, A.m);
-  double* __restrict__ ozl = bcol(ozlb, col, A.nx);
-  double* __restrict__ ozu = bcol(ozub, col, A.nx);
-  const int ns = A.n - A.nx;
-  const int top = A.nx > A.m ? A.nx : A.m;
-  GRID_LOOP(i, (top > ns ? top : ns)) {
-    if (i < A.nx) {
-      double dx, dzl = 0.0, dzu = 0.0;
-      if (A.fixed[i]) {
-        dx = T.lvar ? T.lvar[i] : 0.0;
-      } else {
-        const double dxp = A.d[i];
-        dx = dxp + v[i];
-        const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
-        const double hd = sm > 0.0 ? ((sl * su / sm) / A.os) * (tan_dl(A, T, (int)i) - tan_du(A, T, (int)i)) : 0.0;
-        if (A.lbpos[i] >= 0) dzl = hd - (sl / A.os) * dxp;
-        if (A.ubpos[i] >= 0) dzu = (su / A.os) * dxp + hd;
-      }
-      dxs[i] = dx;
-      if (ox) ox[i] = dx;
-      if (ozl) ozl[i] = dzl;
-      if (ozu) ozu[i] = dzu;
-    }
-    if (i < ns) dxs[A.nx + i] = 0.0;
-    if (i < A.m && oy) oy[i] = A.d[A.n + i] * A.cscale[i] / A.os;
-  }
-}
-
-template <int G>
-__global__ __launch_bounds__(NT) void k_tan_cons_b(DV D, AdjArgs A, const double* __restrict__ dxsb,
-                                                   const double* __restrict__ baseb, double* __restrict__ oconsb) {
-#pragma clang fp contract(off)
-  const int col = blockIdx.y;
-  const double* __restrict__ dxs = dxsb + col * (int64_t)D.n;
-  const double* __restrict__ base = baseb + col * ((int64_t)D.n + D.m);
-  double* __restrict__ ocons = oconsb + col * (int64_t)D.m;
-  const bool lead = (threadIdx.x & (G - 1)) == 0;
-  GROUP_LOOP(r, D.m, G) {
-    const double s = gdot<G>(D.J, r, dxs);
-    if (lead) ocons[r] = s / A.cscale[r] + base[D.n + r];
-  }
-}
-
-// ---- the adjoint's kernels, column blockIdx.y (bodies: k_adj_shift, k_adj_rhs_full, k_adj_rhs, k_adj_unshift,
-// k_adj_vec, k_adj_avals, k_adj_hvals, k_adj_fix)
-__global__ __launch_bounds__(NT) void k_adj_shift_b(AdjArgs A, AdjFull F0, double* __restrict__ vb, LDLStatus* t1) {
-#pragma clang fp contract(off)
-  if (t1 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ldl_status_end(t1);
-  const int col = blockIdx.y;
-  const AdjFull F = full_col(F0, A, col);
-  double* __restrict__ v = vb + col * ((int64_t)A.n + A.m);
-  GRID_LOOP(i, A.n + A.m) {
-    double o = 0.0;
-    if (i < A.nx) {
-      if (!A.fixed[i]) {
-        const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
-        if (sm > 0.0) o = ((sl * adj_gzl(A, F, (int)i) - su * adj_gzu(A, F, (int)i)) / sm) / A.os;
-      }
-    } else if (i >= A.n && F.gcons) {
-      o = F.gcons[i - A.n] / A.cscale[i - A.n];
-    }
-    v[i] = o;
-  }
-}
-
-template <int G>
-__global__ __launch_bounds__(NT) void k_adj_rhs_full_b(DV D, AdjArgs A, const double* __restrict__ gxb,
-                                                       const double* __restrict__ gyb, const double* __restrict__ vb,
-                                                       double* __restrict__ bd, double* __restrict__ bp) {
-#pragma clang fp contract(off)
-  const int n = D.n, m = D.m;
-  const int col = blockIdx.y;
-  const int64_t off = col * ((int64_t)n + m);
-  const double* __restrict__ gx = bcol(gxb, col, D.nx);
-  const double* __restrict__ gy = bcol(gyb, col, m);
-  const double* __restrict__ v = vb + off;
-  const bool lead = (threadIdx.x & (G - 1)) == 0;
-  GROUP_LOOP(i, n + m, G) {
-    double g = 0.0;
-    if (i < n) {
-      if (i < D.nx && !D.fixed[i]) {
-        double hd, jd;
-        gdot2<G>(D.H, i, v, D.JT, i, v + n, hd, jd);
-        g = (gx ? gx[i] : 0.0) + (hd + jd);
-      }
-    } else {
-      const double jq = gdot<G>(D.J, i - n, v);
-      g = (gy ? A.cscale[i - n] * gy[i - n] / A.os : 0.0) + jq;
-    }
-    if (lead) {
-      bd[off + i] = g;
-      bp[off + i] = g;
-    }
-  }
-}
-
-__global__ __launch_bounds__(NT) void k_adj_rhs_b(DV D, const double* __restrict__ gxb, double* __restrict__ bd,
-                                                  double* __restrict__ bp, LDLStatus* t1) {
-  if (t1 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ldl_status_end(t1);
-  const int col = blockIdx.y;
-  const int64_t off = col * ((int64_t)D.n + D.m);
-  const double* __restrict__ gx = gxb + col * (int64_t)D.nx;
-  GRID_LOOP(i, D.n + D.m) {
-    const double v = (i < D.nx && !D.fixed[i]) ? gx[i] : 0.0;
-    bd[off + i] = v;
-    bp[off + i] = v;
-  }
-}
-
-__global__ __launch_bounds__(NT) void k_adj_unshift_b(int nx, int64_t N, const double* __restrict__ vb,
-                                                      double* __restrict__ solb, double* __restrict__ apxb) {
-  const int col = blockIdx.y;
-  const double* __restrict__ v = vb + col * N;
-  double* __restrict__ sol = solb + col * N;
-  double* __restrict__ apx = apxb + col * (int64_t)nx;
-  GRID_LOOP(i, nx) {
-    const double ap = sol[i];
-    apx[i] = ap;
-    sol[i] = ap - v[i];
-  }
-}
 
 // The refinement residual of the chunk's kc columns (k_adj_resid for each): a lane group per K2 row loads its
 // entries of H~ and J~^T (or J~) and their column indices once per trip, two entries a trip as gdot / gdot2 issue
@@ -2512,157 +2233,12 @@ __global__ __launch_bounds__(NT) void k_adj_resid_b(DV D, AdjArgs A, int kc, con
   }
 }
 
-// k_adj_resmax of column blockIdx.x: out[column] = max_i rowres[i] / max(1, max_i |g_i|)
-__global__ __launch_bounds__(NT) void k_adj_resmax_b(const double* __restrict__ rowresb, const double* __restrict__ gb,
-                                                     int64_t N, double* __restrict__ out) {
-  __shared__ double sw[NT], sg[NT];
-  const int t = threadIdx.x;
-  const double* __restrict__ rowres = rowresb + blockIdx.x * N;
-  const double* __restrict__ g = gb + blockIdx.x * N;
-  double w = 0.0, gm = 0.0;
-  for (int64_t i = t; i < N; i += NT) {
-    w = nmax(w, rowres[i]);
-    gm = nmax(gm, fabs(g[i]));
-  }
-  sw[t] = w;
-  sg[t] = gm;
-  __syncthreads();
-  for (int o = NT / 2; o > 0; o >>= 1) {
-    if (t < o) {
-      sw[t] = nmax(sw[t], sw[t + o]);
-      sg[t] = nmax(sg[t], sg[t + o]);
-    }
-    __syncthreads();
-  }
-  if (t == 0) out[blockIdx.x] = sw[0] / (sg[0] > 1.0 ? sg[0] : 1.0);
-}
-
 // out[0] = the largest of the chunk's ratios and, after the call's first chunk, of out[0] (a NaN is kept)
 __global__ void k_sens_fold(const double* __restrict__ col, int kc, int first, double* __restrict__ out) {
   if (blockIdx.x || threadIdx.x) return;
   double w = first ? col[0] : out[0];
   for (int j = first ? 1 : 0; j < kc; ++j) w = nmax(w, col[j]);
   out[0] = w;
-}
-
-template <bool FULL>
-__global__ __launch_bounds__(NT) void k_adj_vec_b(AdjArgs A0, AdjFull F0, const int32_t* __restrict__ rowslack,
-                                                  double* __restrict__ gcb, double* __restrict__ glvb,
-                                                  double* __restrict__ guvb, double* __restrict__ glcb,
-                                                  double* __restrict__ gucb) {
-#pragma clang fp contract(off)
-  const int col = blockIdx.y;
-  const AdjArgs A = adj_col(A0, col);
-  const AdjFull F = full_col(F0, A, col);
-  double* __restrict__ gc = bcol(gcb, col, A.nx);
-  double* __restrict__ glv = bcol(glvb, col, A.nx);
-  double* __restrict__ guv = bcol(guvb, col, A.nx);
-  double* __restrict__ glc = bcol(glcb, col, A.m);
-  double* __restrict__ guc = bcol(gucb, col, A.m);
-  GRID_LOOP(i, (A.nx > A.m ? A.nx : A.m)) {
-    if (i < A.nx) {
-      const bool fx = A.fixed[i];
-      const double at = fx ? 0.0 : A.d[i];
-      if (gc) gc[i] = -(A.sgn * (A.os * at));
-      if (!fx) {
-        if constexpr (FULL) {
-          const double sl = adj_sig_l(A, (int)i), su = adj_sig_u(A, (int)i), sm = sl + su;
-          const double ap = F.apx[i];
-          const double hg = sm > 0.0 ? (sl * su / sm) / A.os * (adj_gzl(A, F, (int)i) + adj_gzu(A, F, (int)i)) : 0.0;
-          if (glv) glv[i] = sl * ap + hg;
-          if (guv) guv[i] = su * ap - hg;
-        } else {
-          if (glv) glv[i] = adj_sig_l(A, (int)i) * at;
-          if (guv) guv[i] = adj_sig_u(A, (int)i) * at;
-        }
-      } else if (guv) {
-        guv[i] = 0.0;
-      }
-    }
-    if (i < A.m && (glc || guc)) {
-      const int k = rowslack[i];
-      const double cs = A.cscale[i];
-      if (k < 0) {
-        if (glc) glc[i] = cs * A.d[A.n + i];
-        if (guc) guc[i] = 0.0;
-      } else {
-        const double as = A.d[k];
-        if (glc) glc[i] = cs * (adj_sig_l(A, k) * as);
-        if (guc) guc[i] = cs * (adj_sig_u(A, k) * as);
-      }
-    }
-  }
-}
-
-template <bool FULL>
-__global__ __launch_bounds__(NT) void k_adj_avals_b(AdjArgs A0, AdjFull F0, int64_t nnz,
-                                                    const int32_t* __restrict__ Ar, const int32_t* __restrict__ Ac,
-                                                    double* __restrict__ outb) {
-#pragma clang fp contract(off)
-  const int col = blockIdx.y;
-  const AdjArgs A = adj_col(A0, col);
-  const AdjFull F = full_col(F0, A, col);
-  double* __restrict__ out = outb + col * nnz;
-  GRID_LOOP(k, nnz) {
-    const int r = Ar[k], c = Ac[k];
-    const double yr = A.y[r] * A.cscale[r] / A.os;
-    const double v = -(adj_ax(A, c) * yr + adj_ay(A, r) * A.x[c]);
-    if constexpr (FULL)
-      out[k] = F.gcons ? v + F.gcons[r] * A.x[c] : v;
-    else
-      out[k] = v;
-  }
-}
-
-__global__ __launch_bounds__(NT) void k_adj_hvals_b(AdjArgs A0, int64_t nnz, const int32_t* __restrict__ Hr,
-                                                    const int32_t* __restrict__ Hc, double* __restrict__ outb) {
-#pragma clang fp contract(off)
-  const int col = blockIdx.y;
-  const AdjArgs A = adj_col(A0, col);
-  double* __restrict__ out = outb + col * nnz;
-  GRID_LOOP(k, nnz) {
-    const int r = Hr[k], c = Hc[k];
-    const double ar = adj_ax(A, r);
-    const double v = r == c ? ar * A.x[r] : ar * A.x[c] + adj_ax(A, c) * A.x[r];
-    out[k] = -(A.sgn * v);
-  }
-}
-
-template <bool FULL>
-__global__ __launch_bounds__(NT) void k_adj_fix_b(AdjArgs A0, AdjFull F0, int nfix, const int32_t* __restrict__ fix,
-                                                  const int32_t* __restrict__ fhsp, const int2* __restrict__ fh,
-                                                  const int32_t* __restrict__ fasp, const int2* __restrict__ fa,
-                                                  const double* __restrict__ Hraw, const double* __restrict__ Araw,
-                                                  const double* __restrict__ gxb, double* __restrict__ glvb) {
-#pragma clang fp contract(off)
-  const int col = blockIdx.y;
-  const AdjArgs A = adj_col(A0, col);
-  const AdjFull F = full_col(F0, A, col);
-  const double* __restrict__ gx = bcol(gxb, col, A.nx);
-  double* __restrict__ glv = glvb + col * (int64_t)A.nx;
-  GRID_LOOP(t, nfix) {
-    double hs = 0.0, as = 0.0;
-    for (int q = fhsp[t]; q < fhsp[t + 1]; ++q) {
-      const int2 e = fh[q];
-      hs = hs + Hraw[e.x] * (A.os * A.d[e.y]);
-    }
-    for (int q = fasp[t]; q < fasp[t + 1]; ++q) {
-      const int2 e = fa[q];
-      as = as + Araw[e.x] * adj_ay(A, e.y);
-    }
-    const int f = fix[t];
-    if constexpr (FULL) {
-      double gs = 0.0;
-      if (F.gcons)
-        for (int q = fasp[t]; q < fasp[t + 1]; ++q) {
-          const int2 e = fa[q];
-          gs = gs + Araw[e.x] * F.gcons[e.y];
-        }
-      glv[f] = ((gx ? gx[f] : 0.0) + gs) - A.sgn * hs - as;
-    } else {
-      glv[f] = gx[f] - A.sgn * hs - as;
-    }
-  }
 }
 
 // column c0 of a block of the caller's (null stays null)
@@ -2687,38 +2263,48 @@ T* at_col(T* p, int64_t c0, int64_t len) {
 
 int MPCSolver::sens_batch_cols() { return SENS_W; }
 
-// With the chunk's right-hand sides in bat.d (and in bat.p, which keeps them): bat.sol = K^-1 bat.p column by
-// column, refined as sens_solve refines; the largest residual ratio into resid[0]
-void MPCSolver::sens_solve_batch(int kc, double* resid, bool first_chunk) {
-  SensBatch& b = post_->bat;
+// With a chunk's kc right-hand sides in V.d (and in V.p, which keeps them): V.sol = K^-1 V.p column by column,
+// refined; the largest residual ratio of the call so far into resid[0]
+void MPCSolver::sens_solve(const SensView& V, int kc, double* resid, bool first_chunk) {
   AdjArgs A = post_->args(*this);
-  A.d = b.sol.p;
+  A.d = V.sol;
   const DV D = view();
   hipStream_t s = stream_;
   const int64_t N = (int64_t)n_ + m_;
   const int nb = blocks(kc * N), nbs = spmv_blocks(n_ + m_);
-  auto solves = [&] {
-    for (int j = 0; j < kc; ++j) ldl_->solve_async(b.d.p + j * N, s);
+  auto solves = [&] {  // kkt_solve() of the K2 formulation (sens_refuse admits no other), on each column
+    for (int j = 0; j < kc; ++j) ldl_->solve_async(V.d + j * N, s);
+  };
+  auto residual = [&](double* r) {
+    if (kc == 1)
+      SPMV_LAUNCH(k_adj_resid, nbs, s, D, A, (const double*)V.p, (const double*)V.sol, r, V.rowres);
+    else
+      SPMV_LAUNCH(k_adj_resid_b, nbs, s, D, A, kc, (const double*)V.p, (const double*)V.sol, r, V.rowres);
   };
   solves();
-  k_adj_acc<<<nb, NT, 0, s>>>(b.sol.p, b.d.p, kc * N, 1);  // the columns are contiguous: one flat pass
+  k_adj_acc<<<nb, NT, 0, s>>>(V.sol, V.d, kc * N, 1);  // the columns are contiguous: one flat pass
+  // iterative refinement towards the system without the regularisation (the factor is the regularised
+  // matrix's: each step gains about -log10(delta |K^-1|) digits); a fixed count, so nothing is read back
   for (int it = 0; it < adj_refine_steps(); ++it) {
-    SPMV_LAUNCH(k_adj_resid_b, nbs, s, D, A, kc, (const double*)b.p.p, (const double*)b.sol.p, b.d.p, b.rowres.p);
+    residual(V.d);
     solves();
-    k_adj_acc<<<nb, NT, 0, s>>>(b.sol.p, b.d.p, kc * N, 0);
+    k_adj_acc<<<nb, NT, 0, s>>>(V.sol, V.d, kc * N, 0);
   }
-  SPMV_LAUNCH(k_adj_resid_b, nbs, s, D, A, kc, (const double*)b.p.p, (const double*)b.sol.p, (double*)nullptr,
-              b.rowres.p);
-  k_adj_resmax_b<<<kc, NT, 0, s>>>(b.rowres.p, b.p.p, N, b.scal.p);
-  k_sens_fold<<<1, 1, 0, s>>>(b.scal.p, kc, first_chunk ? 1 : 0, resid);
+  residual(nullptr);
+  // a first chunk of one column (every single call) is the call's ratio itself: no fold
+  const bool direct = first_chunk && kc == 1;
+  k_adj_resmax<<<kc, NT, 0, s>>>(V.rowres, V.p, N, direct ? resid : V.scal);
+  if (!direct) k_sens_fold<<<1, 1, 0, s>>>(V.scal, kc, first_chunk ? 1 : 0, resid);
 }
 
-void MPCSolver::tangent_batch(int32_t k, const madipm_qp_directions& dr, const madipm_qp_point_tangents& o,
-                              bool polished, bool device, hipStream_t caller) {
-  const std::string who = device ? "madipm_solver_tangent_batch_device: " : "madipm_solver_tangent_batch: ";
+// The tangents of k columns of directions (§13e), in chunks of the view's width.  batch: on SensBatch, else
+// k = 1 on the single call's scratch; polished: one tangent_polished per column, with offset pointers (its bits
+// by construction).  Returns the chunks run.
+int64_t MPCSolver::tangent_cols(const std::string& who, int64_t k, bool batch, bool polished,
+                                const madipm_qp_directions& dr, const madipm_qp_point_tangents& o, bool device,
+                                hipStream_t caller) {
   QPHost& P = *H_;
   // ---- refusals, before anything is allocated or enqueued
-  MADIPM_REQUIRE(k >= 1, who + "k = " + std::to_string(k) + ", a batch holds at least one column");
   if (polished)
     polished_refuse(who);
   else
@@ -2735,7 +2321,7 @@ void MPCSolver::tangent_batch(int32_t k, const madipm_qp_directions& dr, const m
                        "madipm_solver_prepare_update first (it keeps the index arrays and the raw values)");
   const int64_t dlen[7] = {nx_, nh, na, m_, m_, nx_, nx_};
   const int64_t olen[5] = {nx_, m_, nx_, nx_, m_};
-  if (polished) {  // the single polished call per column, with offset pointers: its bits by construction
+  if (polished) {
     for (int64_t j = 0; j < k; ++j) {
       const madipm_qp_directions dj{at_col(dir[0], j, dlen[0]), at_col(dir[1], j, dlen[1]), at_col(dir[2], j, dlen[2]),
                                     at_col(dir[3], j, dlen[3]), at_col(dir[4], j, dlen[4]), at_col(dir[5], j, dlen[5]),
@@ -2745,93 +2331,90 @@ void MPCSolver::tangent_batch(int32_t k, const madipm_qp_directions& dr, const m
                                         at_col(user[4], j, olen[4])};
       tangent_polished(dj, oj, device, caller);
     }
-    SensBatch& b = post_->bat;
-    ++b.n_batches;
-    b.n_columns += k;
-    return;
+    return 0;
   }
   hipStream_t s = stream_;
   // ---- allocations, each by the first call that needs it
   PostSolve& ps = post_state();
   Adjoint& a = ps.adj;
   Tangent& t = ps.tan;
-  SensBatch& b = ps.bat;
-  const int64_t N = (int64_t)n_ + m_;
-  constexpr int W = SENS_W;
   ps.rowslack(P, s);
   ps.tangent_scratch(*this, needLists);
-  b.need(N, nx_, n_, true, true);
+  const SensView V = ps.sens_view(*this, batch, true, true);  // shifted, as the five-cotangent adjoint
   int64_t dcap[7], ocap[5];  // a chunk's staging
-  for (int q = 0; q < 7; ++q) dcap[q] = W * dlen[q];
-  for (int q = 0; q < 5; ++q) ocap[q] = W * olen[q];
+  for (int q = 0; q < 7; ++q) dcap[q] = V.W * dlen[q];
+  for (int q = 0; q < 5; ++q) ocap[q] = V.W * olen[q];
   const double* ddir[7];
   double* out[5];
-  b.dir.bind(dir, dcap, device, ddir);
-  b.out.bind(user, ocap, device, out);
+  V.dir->bind(dir, dcap, device, ddir);
+  V.out->bind(user, ocap, device, out);
   AdjArgs A = ps.args(*this);
-  A.d = b.sol.p;
+  A.d = V.sol;
   const BLen L{nh, na};
-  // ---- the factor of the K2 matrix at the final iterate: the single calls', once per solve
+  // ---- the factor of the K2 matrix at the final iterate: the adjoint's, once per solve
   const DV D = view();
   sens_factor(who);
   if (device) ps.sync.begin(caller, s);  // the directions are read after the work already enqueued on the caller's stream
-  const bool ls = needLists;
+  const bool ls = needLists;  // lists built by an earlier call are not walked when this one has no use for them
   const int nbv = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
-  for (int64_t c0 = 0; c0 < k; c0 += W) {
-    const int kc = (int)std::min<int64_t>(W, k - c0);
+  int64_t chunks = 0;
+  for (int64_t c0 = 0; c0 < k; c0 += V.W, ++chunks) {
+    const int kc = (int)std::min<int64_t>(V.W, k - c0);
     const int64_t co = device ? c0 : 0;  // the host route stages the chunk's columns from 0
     if (!device) {
       const double* uc[7];
       int64_t ul[7];
       for (int q = 0; q < 7; ++q) uc[q] = at_col(dir[q], c0, dlen[q]), ul[q] = kc * dlen[q];
-      b.dir.upload(uc, ul, s);
+      V.dir->upload(uc, ul, s);
     }
     // ---- right-hand sides, solves, residuals
     const TanDir T{at_col(ddir[0], co, dlen[0]), at_col(ddir[1], co, dlen[1]), at_col(ddir[2], co, dlen[2]),
                    at_col(ddir[3], co, dlen[3]), at_col(ddir[4], co, dlen[4]), at_col(ddir[5], co, dlen[5]),
                    at_col(ddir[6], co, dlen[6])};
-    k_tan_shift_b<<<dim3(nbv, kc), NT, 0, s>>>(A, T, L, a.rowslack.p, b.shift.p, take_fact_end());
-    k_tan_data_b<<<dim3(nbv, kc), NT, 0, s>>>(A, T, L, ls ? t.gsp.p : nullptr, t.ge.p, t.csp.p, t.ce.p,
-                                             ls ? t.asp.p : nullptr, t.ae.p, plan_ ? plan_->Hraw.p : nullptr,
-                                             plan_ ? plan_->Araw.p : nullptr, b.base.p);
-    SPMV_LAUNCH_B(k_tan_rhs_b, nbs, kc, s, D, A, T, L, (const int32_t*)a.rowslack.p, (const double*)b.shift.p,
-                  (const double*)b.base.p, b.d.p, b.p.p);
-    sens_solve_batch(kc, t.scal.p, c0 == 0);
+    k_tan_shift<<<dim3(nbv, kc), NT, 0, s>>>(A, T, L, a.rowslack.p, V.shift, take_fact_end());
+    k_tan_data<<<dim3(nbv, kc), NT, 0, s>>>(A, T, L, ls ? t.gsp.p : nullptr, t.ge.p, t.csp.p, t.ce.p,
+                                           ls ? t.asp.p : nullptr, t.ae.p, plan_ ? plan_->Hraw.p : nullptr,
+                                           plan_ ? plan_->Araw.p : nullptr, V.base);
+    SPMV_LAUNCH_B(k_tan_rhs, nbs, kc, s, D, A, T, L, (const int32_t*)a.rowslack.p, (const double*)V.shift,
+                  (const double*)V.base, V.d, V.p);
+    sens_solve(V, kc, t.scal.p, c0 == 0);
     // ---- outputs
-    k_tan_out_b<<<dim3(blocks(std::max(std::max(nx_, m_), std::max(n_ - nx_, 1))), kc), NT, 0, s>>>(
-        A, T, L, b.shift.p, b.dx.p, at_col(out[0], co, olen[0]), at_col(out[1], co, olen[1]),
+    k_tan_out<<<dim3(blocks(std::max(std::max(nx_, m_), std::max(n_ - nx_, 1))), kc), NT, 0, s>>>(
+        A, T, L, V.shift, V.dx, at_col(out[0], co, olen[0]), at_col(out[1], co, olen[1]),
         at_col(out[2], co, olen[2]), at_col(out[3], co, olen[3]));
     if (out[4] && m_)
-      SPMV_LAUNCH_B(k_tan_cons_b, spmv_blocks(m_), kc, s, D, A, (const double*)b.dx.p, (const double*)b.base.p,
+      SPMV_LAUNCH_B(k_tan_cons, spmv_blocks(m_), kc, s, D, A, (const double*)V.dx, (const double*)V.base,
                     at_col(out[4], co, olen[4]));
     MADIPM_HIP(hipGetLastError());
     if (!device) {
       double* uc[5];
       int64_t ul[5];
       for (int q = 0; q < 5; ++q) uc[q] = at_col(user[q], c0, olen[q]), ul[q] = kc * olen[q];
-      b.out.download(uc, ul, s);  // synchronises: the next chunk reuses the staging
+      V.out->download(uc, ul, s);  // synchronises: the next chunk reuses the staging
     }
-    ++b.n_chunks;
   }
   if (device) ps.sync.end(s, caller);  // work enqueued on the caller's stream from now on sees the outputs
   t.n_tangents += k;
-  ++b.n_batches;
-  b.n_columns += k;
+  return chunks;
 }
 
-void MPCSolver::adjoint_batch(int32_t k, const madipm_qp_cotangents& ct, const madipm_qp_gradients& g, bool polished,
-                              bool device, hipStream_t caller) {
-  const std::string who = device ? "madipm_solver_adjoint_batch_device: " : "madipm_solver_adjoint_batch: ";
+// The adjoints of k columns of cotangents (§13c, §13d), as tangent_cols.  need_gx: the entry point takes gx alone,
+// which must be given.  full: a cotangent block other than gx is given, and every column solves the shifted system
+// of §13d; without one the kernels and their order are those of the gx-only call whichever entry point was taken.
+int64_t MPCSolver::adjoint_cols(const std::string& who, int64_t k, bool batch, bool polished, bool need_gx,
+                                const madipm_qp_cotangents& ct, const madipm_qp_gradients& g, bool device,
+                                hipStream_t caller) {
   QPHost& P = *H_;
   // ---- refusals, before anything is allocated or enqueued
-  MADIPM_REQUIRE(k >= 1, who + "k = " + std::to_string(k) + ", a batch holds at least one column");
   if (polished)
     polished_refuse(who);
   else
     sens_refuse(who);
-  // full: a cotangent block other than gx is given, and every column solves the shifted system of §13d
   const bool full = ct.y || ct.zl || ct.zu || ct.cons;
-  MADIPM_REQUIRE(ct.x || full, who + "all five cotangents are NULL");
+  if (need_gx)
+    MADIPM_REQUIRE(ct.x, who + "gx is NULL");
+  else
+    MADIPM_REQUIRE(ct.x || full, who + "all five cotangents are NULL");
   double* const user[7] = {g.c, g.Hvals, g.Avals, g.lcon, g.ucon, g.lvar, g.uvar};
   MADIPM_REQUIRE(g.c || g.Hvals || g.Avals || g.lcon || g.ucon || g.lvar || g.uvar,
                  who + "all seven outputs are NULL");
@@ -2843,7 +2426,7 @@ void MPCSolver::adjoint_batch(int32_t k, const madipm_qp_cotangents& ct, const m
   const double* const cot[5] = {ct.x, ct.y, ct.zl, ct.zu, ct.cons};
   const int64_t clen[5] = {nx_, m_, nx_, nx_, m_};
   const int64_t len[7] = {nx_, nh, na, m_, m_, nx_, nx_};
-  if (polished) {  // the single polished call per column, with offset pointers: its bits by construction
+  if (polished) {
     for (int64_t j = 0; j < k; ++j) {
       const madipm_qp_cotangents cj{at_col(cot[0], j, clen[0]), at_col(cot[1], j, clen[1]), at_col(cot[2], j, clen[2]),
                                     at_col(cot[3], j, clen[3]), at_col(cot[4], j, clen[4])};
@@ -2852,89 +2435,99 @@ void MPCSolver::adjoint_batch(int32_t k, const madipm_qp_cotangents& ct, const m
                                    at_col(user[6], j, len[6])};
       adjoint_polished(cj, gj, device, caller);
     }
-    SensBatch& b = post_->bat;
-    ++b.n_batches;
-    b.n_columns += k;
-    return;
+    return 0;
   }
   hipStream_t s = stream_;
   // ---- allocations, each by the first call that needs it
   PostSolve& ps = post_state();
   Adjoint& a = ps.adj;
-  SensBatch& b = ps.bat;
-  const int64_t N = (int64_t)n_ + m_;
-  constexpr int W = SENS_W;
-  b.need(N, nx_, n_, full, false);
+  const SensView V = ps.sens_view(*this, batch, full, false);
   if (g.lcon || g.ucon) ps.rowslack(P, s);
   ps.adjoint_lists(*this, needA, needH, needFix);
   int64_t ccap[5], gcap[7];  // a chunk's staging
-  for (int q = 0; q < 5; ++q) ccap[q] = W * clen[q];
-  for (int q = 0; q < 7; ++q) gcap[q] = W * len[q];
+  for (int q = 0; q < 5; ++q) ccap[q] = V.W * clen[q];
+  for (int q = 0; q < 7; ++q) gcap[q] = V.W * len[q];
   const double* dct[5];  // gx, gy, gzl, gzu, gcons on the device
   double* out[7];
-  b.ct.bind(cot, ccap, device, dct);
-  b.grad.bind(user, gcap, device, out);
+  V.ct->bind(cot, ccap, device, dct);
+  V.grad->bind(user, gcap, device, out);
   AdjArgs A = ps.args(*this);
-  A.d = b.sol.p;
-  // ---- the factor of the K2 matrix at the final iterate: the single calls', once per solve
+  A.d = V.sol;
+  const int64_t N = (int64_t)n_ + m_;
+  // ---- the factor of the K2 matrix at the final iterate: once per solve
   const DV D = view();
   sens_factor(who);
   if (device) ps.sync.begin(caller, s);  // the cotangents are read after the work already enqueued on the caller's stream
   const int nbv = blocks(n_ + m_), nbs = spmv_blocks(n_ + m_);
   const bool vec = (out[0] || out[3] || out[4] || out[5] || out[6]) && std::max(nx_, m_);
   const bool fix = needFix && a.nfix > 0;
-  for (int64_t c0 = 0; c0 < k; c0 += W) {
-    const int kc = (int)std::min<int64_t>(W, k - c0);
+  int64_t chunks = 0;
+  for (int64_t c0 = 0; c0 < k; c0 += V.W, ++chunks) {
+    const int kc = (int)std::min<int64_t>(V.W, k - c0);
     const int64_t co = device ? c0 : 0;  // the host route stages the chunk's columns from 0
     if (!device) {
       const double* uc[5];
       int64_t ul[5];
       for (int q = 0; q < 5; ++q) uc[q] = at_col(cot[q], c0, clen[q]), ul[q] = kc * clen[q];
-      b.ct.upload(uc, ul, s);
+      V.ct->upload(uc, ul, s);
     }
     const double* const gx = at_col(dct[0], co, clen[0]);
     const double* const gy = at_col(dct[1], co, clen[1]);
-    const AdjFull F{at_col(dct[2], co, clen[2]), at_col(dct[3], co, clen[3]), at_col(dct[4], co, clen[4]), b.apx.p};
+    const AdjFull F{at_col(dct[2], co, clen[2]), at_col(dct[3], co, clen[3]), at_col(dct[4], co, clen[4]), V.apx};
     double* oc[7];
     for (int q = 0; q < 7; ++q) oc[q] = at_col(out[q], co, len[q]);
     // ---- right-hand sides, solves, residuals
-    if (full) {
-      k_adj_shift_b<<<dim3(nbv, kc), NT, 0, s>>>(A, F, b.shift.p, take_fact_end());
-      SPMV_LAUNCH_B(k_adj_rhs_full_b, nbs, kc, s, D, A, gx, gy, (const double*)b.shift.p, b.d.p, b.p.p);
+    if (full) {  // the shifted system K a~' = g' (§13d); V.p keeps g' for the residual
+      k_adj_shift<<<dim3(nbv, kc), NT, 0, s>>>(A, F, V.shift, take_fact_end());
+      SPMV_LAUNCH_B(k_adj_rhs_full, nbs, kc, s, D, A, gx, gy, (const double*)V.shift, V.d, V.p);
     } else {
-      k_adj_rhs_b<<<dim3(nbv, kc), NT, 0, s>>>(D, gx, b.d.p, b.p.p, take_fact_end());
+      k_adj_rhs<<<dim3(nbv, kc), NT, 0, s>>>(D, gx, V.d, V.p, take_fact_end());
     }
-    sens_solve_batch(kc, a.scal.p, c0 == 0);
-    if (full && nx_) k_adj_unshift_b<<<dim3(blocks(nx_), kc), NT, 0, s>>>(nx_, N, b.shift.p, b.sol.p, b.apx.p);
+    sens_solve(V, kc, a.scal.p, c0 == 0);
+    if (full && nx_) k_adj_unshift<<<dim3(blocks(nx_), kc), NT, 0, s>>>(nx_, N, V.shift, V.sol, V.apx);
     // ---- gradients
     auto gradients = [&](auto is_full) {  // the <true> instantiations read F (§13d)
       constexpr bool FULL = decltype(is_full)::value;
       if (vec)
-        k_adj_vec_b<FULL><<<dim3(blocks(std::max(nx_, m_)), kc), NT, 0, s>>>(A, F, a.rowslack.p, oc[0], oc[5], oc[6],
-                                                                            oc[3], oc[4]);
+        k_adj_vec<FULL><<<dim3(blocks(std::max(nx_, m_)), kc), NT, 0, s>>>(A, F, a.rowslack.p, oc[0], oc[5], oc[6],
+                                                                          oc[3], oc[4]);
       if (fix)
-        k_adj_fix_b<FULL><<<dim3(blocks(a.nfix), kc), NT, 0, s>>>(A, F, a.nfix, a.fix.p, a.fhsp.p, a.fh.p, a.fasp.p,
-                                                                 a.fa.p, plan_->Hraw.p, plan_->Araw.p, gx, oc[5]);
-      if (needA) k_adj_avals_b<FULL><<<dim3(blocks(na), kc), NT, 0, s>>>(A, F, na, a.Ar.p, a.Ac.p, oc[2]);
+        k_adj_fix<FULL><<<dim3(blocks(a.nfix), kc), NT, 0, s>>>(A, F, a.nfix, a.fix.p, a.fhsp.p, a.fh.p, a.fasp.p,
+                                                               a.fa.p, plan_->Hraw.p, plan_->Araw.p, gx, oc[5]);
+      if (needA) k_adj_avals<FULL><<<dim3(blocks(na), kc), NT, 0, s>>>(A, F, na, a.Ar.p, a.Ac.p, oc[2]);
     };
     if (full)
       gradients(std::true_type{});
     else
       gradients(std::false_type{});
-    if (needH) k_adj_hvals_b<<<dim3(blocks(nh), kc), NT, 0, s>>>(A, nh, a.Hr.p, a.Hc.p, oc[1]);
+    if (needH) k_adj_hvals<<<dim3(blocks(nh), kc), NT, 0, s>>>(A, nh, a.Hr.p, a.Hc.p, oc[1]);
     MADIPM_HIP(hipGetLastError());
     if (!device) {
       double* uc[7];
       int64_t ul[7];
       for (int q = 0; q < 7; ++q) uc[q] = at_col(user[q], c0, len[q]), ul[q] = kc * len[q];
-      b.grad.download(uc, ul, s);  // synchronises: the next chunk reuses the staging
+      V.grad->download(uc, ul, s);  // synchronises: the next chunk reuses the staging
     }
-    ++b.n_chunks;
   }
   if (device) ps.sync.end(s, caller);  // work enqueued on the caller's stream from now on sees the outputs
   a.n_adjoints += k;
-  ++b.n_batches;
-  b.n_columns += k;
+  return chunks;
+}
+
+void MPCSolver::tangent_batch(int32_t k, const madipm_qp_directions& dr, const madipm_qp_point_tangents& o,
+                              bool polished, bool device, hipStream_t caller) {
+  const std::string who = device ? "madipm_solver_tangent_batch_device: " : "madipm_solver_tangent_batch: ";
+  MADIPM_REQUIRE(k >= 1, who + "k = " + std::to_string(k) + ", a batch holds at least one column");
+  const int64_t chunks = tangent_cols(who, k, true, polished, dr, o, device, caller);
+  post_->bat.count(k, chunks);
+}
+
+void MPCSolver::adjoint_batch(int32_t k, const madipm_qp_cotangents& ct, const madipm_qp_gradients& g, bool polished,
+                              bool device, hipStream_t caller) {
+  const std::string who = device ? "madipm_solver_adjoint_batch_device: " : "madipm_solver_adjoint_batch: ";
+  MADIPM_REQUIRE(k >= 1, who + "k = " + std::to_string(k) + ", a batch holds at least one column");
+  const int64_t chunks = adjoint_cols(who, k, true, polished, false, ct, g, device, caller);
+  post_->bat.count(k, chunks);
 }
 
 void MPCSolver::sens_batch_info(int64_t* n_batches, int64_t* n_columns, int64_t* n_chunks) const {
