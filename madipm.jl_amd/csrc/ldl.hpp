@@ -252,14 +252,22 @@ class LDLSolver : public LinSolver {
   void kernel_stats(KernelStat out[KK_COUNT]) override;
 
  private:
+  // ---- front tables: the symbolic plan, the kernels' view of it (T_) and the tables T_ points to;
+  // the factor itself (L panels and update blocks in arena_, pivots in D_)
   SymbolicPlan S_;
   LdlKnobs knobs_;  // the MADIPM_* environment, read once by the constructor
   FrontTab T_{};
-  Comm* comm_ = nullptr;
-  std::vector<Launch> fact1_, fact2_;      // phase 1 (this shard's subtrees; everything unsharded), phase 2 (top)
-  std::vector<SolveLevel> slev1_, slev2_;  // per level, leaves first
-  int64_t xg_off_ = 0;                     // (top front, 256-row chunk) pairs of the external forward gather
-  int nxg_ = 0;
+  DBuf<int32_t> first_, nrows_, rows_, u_ld_, child_ptr_, child_list_, rel_, perm_, sched_;
+  DBuf<int32_t> bigslot_;
+  DBuf<int64_t> fs_off_, sv_ptr_, sv_src_;
+  DBuf<int64_t> row_ptr_, l_off_, u_off_, uvec_off_, asm_ptr_, asm_src_, asm_dst64_, rel_ptr_;
+  DBuf<uint16_t> sv_nt_;
+  DBuf<int64_t> upos_;
+  DBuf<uint8_t> fs_img_;
+  DBuf<double> arena_, D_;
+
+  // ---- factorisation (ldl.hip)
+  std::vector<Launch> fact1_, fact2_;  // phase 1 (this shard's subtrees; everything unsharded), phase 2 (top)
   // launches [b, e) of L on s; stamp: SMALL* launches stamp the factorisation's end into it
   void run_fact(const std::vector<Launch>& L, const double* Kx, hipStream_t s, size_t b = 0, size_t e = SIZE_MAX,
                 LDLStatus* stamp = nullptr);
@@ -277,9 +285,13 @@ class LDLSolver : public LinSolver {
   DBuf<uint8_t> tside_;
   hipStream_t side_ = nullptr;
   hipEvent_t ev_join_ = nullptr;
-  void fwd_levels(const std::vector<SolveLevel>& V, int phase, double* b, hipStream_t s);
-  void bwd_levels(const std::vector<SolveLevel>& V, int phase, double* b, hipStream_t s);
-  DBuf<int64_t> xoff_, sx_ptr_, sx_src_;
+  // assembly
+  DBuf<int32_t> g_ptr_;
+  DBuf<BigChildRec> brec_;
+  DBuf<int64_t> g_src_, g_chunk_, chunk_ids_;
+  DBuf<int32_t> g_src32_;
+  DBuf<SymbolicPlan::AsmTile> atiles_;
+  DBuf<double> minv_, fscratch_, gpart_;
   // batched leaf columns (SymbolicPlan::lb): W, pivots, member tables, per-level launch lists
   DBuf<double> lbW_, lbd_, lbpart_;
   DBuf<int32_t> lbmem_, lbgid_, lbwrow_, lbgpos_, lbxrow_;
@@ -287,8 +299,51 @@ class LDLSolver : public LinSolver {
   DBuf<SymbolicPlan::LBGroup> lbg_;
   std::vector<std::vector<int>> lb_at_level_;
   void lb_syrk(int g, hipStream_t s);
+  // factorisation tree (k_fact_tree): fronts in topological order, their tree children, flags
+  // (per-factorisation epoch), ticket counters (reset by the launch's last workgroup)
+  int nftree_ = 0, fepoch_ = 0;
+  DBuf<int32_t> ft_order_, ft_dptr_, ft_dep_, fflags_, fcnt_;
+  DBuf<int64_t> fdbg_, ab_first_, ab_loff_, fold_poff_, fold_row0_;
+  DBuf<int32_t> ab_src0_, ab_src1_, ab_k_, ab_f0_, ab_wrc_, fold_bptr_, fold_bat_, fold_plen_, fold_rmax_, fold_lmax_;
+  DBuf<FoldStart> fstart_;
+  DBuf<int32_t> fold_help_;
+  DBuf<FoldHelp> fhelp_;
+  DBuf<double> fimg_;
+  DBuf<uint16_t> fimg_dst_;
+  int nfhelp_ = 0;  // fold helper tickets (k_fact_tree: before the fronts')
+  DBuf<uint8_t> absorb_, fold_pk_;
+  DBuf<int32_t> mc_ptr_;
+  DBuf<uint32_t> fold_prod_, fold_chead_;
+  // big fronts as one task graph per launch (k_big_dag)
+  DBuf<int32_t> dag_tasks_;  // DagTask (4 int32) per task of every DAG launch, in launch order
+  DBuf<int32_t> dag_dptr_;   // per task: its first dependency in dag_dlist_ (launch-local tickets), + end
+  DBuf<int32_t> dag_dlist_;
+  DBuf<int32_t> dag_flags_;  // per task: the epoch of the factorisation that completed it
+  DBuf<int32_t> dag_cnt_;    // ticket + done counters (reset by the last workgroup out)
+  DBuf<double> dag_m_;       // M_K blocks per (big front, panel)
+  DBuf<int64_t> dag_mslot_;  // per front: its first panel's slot in dag_m_
+  int cepoch_ = 0;
+  int dag_grid_ = 256;
+  DBuf<int64_t> dag_dbg_;          // MADIPM_DAG_DEBUG: 4 stamps per task
+  std::vector<int32_t> dag_kind_;  // (its host copy of the task words)
+  void dag_debug_dump(hipStream_t s, const Launch& L);
+  DBuf<double> upsum_;    // k_big_upd128 split K on launches of few tiles: its partial products
+  DBuf<int32_t> uptick_;  // its per-tile tickets (reset by each tile's last part)
+  // status
+  DBuf<LDLStatus> status_;
+  LDLStatus* h_status_ = nullptr;
+  LDLStatus* st_ = nullptr;    // status in use: status_ or the caller's (external_status)
+  LDLStatus* h_st_ = nullptr;  // its host copy
+  bool ext_status_ = false;
+  bool inertia_stale_ = false;  // lazy_inertia: npos / nneg / nzero not counted for the current factor
+
+  // ---- solves (ldl_solve.hip)
+  std::vector<SolveLevel> slev1_, slev2_;  // per level, leaves first
+  void fwd_levels(const std::vector<SolveLevel>& V, int phase, double* b, hipStream_t s);
+  void bwd_levels(const std::vector<SolveLevel>& V, int phase, double* b, hipStream_t s);
   void lb_fwd(const double* b, hipStream_t s);
   void lb_bwd(int g, double* b, hipStream_t s);
+  DBuf<double> xi_, uvec_, vwork_;
   // tree solves (k_fwd_tree / k_bwd_tree): the phase-1 fronts solved by ONE dependency-driven launch
   // per direction (topological ticket order, forward dependencies = tree children, backward = tree
   // parent), between the level-0 launches and the remaining levels
@@ -304,41 +359,19 @@ class LDLSolver : public LinSolver {
   double leaf_bytes_ = 0, leaf_flops_ = 0, leaf_alg_ = 0;  // the flat leaf launches (per direction)
   DBuf<SolveLeaf> tleaf_;
   DBuf<int2> tlrow_;
-  DBuf<int64_t> tdbg_, upos_;
+  DBuf<int64_t> tdbg_;
   DBuf<double> gbuf_;
-  void tree_debug_dump(hipStream_t s, const char* what, const int64_t* dbuf, int nt, const char* p1, const char* p2,
-                       const char* p3, const char* p4, const char* p5, int stride);
-  // factorisation tree (k_fact_tree): fronts in topological order, their tree children, flags
-  // (per-factorisation epoch), ticket counters (reset by the launch's last workgroup)
-  int nftree_ = 0, fepoch_ = 0;
-  DBuf<int32_t> ft_order_, ft_dptr_, ft_dep_, fflags_, fcnt_;
+  // big-front task queues (k_fwd_big / k_bwd_big)
   DBuf<uint64_t> xll_;
-  DBuf<uint16_t> sv_nt_;
-  DBuf<int64_t> fdbg_, ab_first_, ab_loff_, fold_poff_, fold_row0_;
-  DBuf<int32_t> dag_tasks_;  // DagTask (4 int32) per task of every DAG launch, in launch order
-  DBuf<int32_t> dag_dptr_;   // per task: its first dependency in dag_dlist_ (launch-local tickets), + end
-  DBuf<int32_t> dag_dlist_;
-  DBuf<int32_t> dag_flags_;  // per task: the epoch of the factorisation that completed it
-  DBuf<int32_t> dag_cnt_;    // ticket + done counters (reset by the last workgroup out)
-  DBuf<double> dag_m_;       // M_K blocks per (big front, panel)
-  DBuf<int64_t> dag_mslot_;  // per front: its first panel's slot in dag_m_
-  int cepoch_ = 0;
-  int dag_grid_ = 256;
-  DBuf<int64_t> dag_dbg_;          // MADIPM_DAG_DEBUG: 4 stamps per task
-  std::vector<int32_t> dag_kind_;  // (its host copy of the task words)
-  void dag_debug_dump(hipStream_t s, const Launch& L);
-  DBuf<double> upsum_;    // k_big_upd128 split K on launches of few tiles: its partial products
-  DBuf<int32_t> uptick_;  // its per-tile tickets (reset by each tile's last part)
-  DBuf<int32_t> ab_src0_, ab_src1_, ab_k_, ab_f0_, ab_wrc_, fold_bptr_, fold_bat_, fold_plen_, fold_rmax_, fold_lmax_;
-  DBuf<FoldStart> fstart_;
-  DBuf<int32_t> fold_help_;
-  DBuf<FoldHelp> fhelp_;
-  DBuf<double> fimg_;
-  DBuf<uint16_t> fimg_dst_;
-  int nfhelp_ = 0;  // fold helper tickets (k_fact_tree: before the fronts')
-  DBuf<uint8_t> absorb_, fold_pk_, fs_img_;
-  DBuf<int32_t> mc_ptr_;
-  DBuf<uint32_t> fold_prod_, fold_chead_;
+  DBuf<int32_t> tasks_, flags_, flag_off_, counters_, bp_off_;
+  DBuf<double> bpart_;
+  int epoch_ = 0;
+
+  // ---- sharding and timing
+  Comm* comm_ = nullptr;
+  int64_t xg_off_ = 0;  // (top front, 256-row chunk) pairs of the external forward gather
+  int nxg_ = 0;
+  DBuf<int64_t> xoff_, sx_ptr_, sx_src_;
   DBuf<double> xch_;
   DBuf<double> xpack_;     // sharded: packed top-front lower triangles (+ status slots), all-reduced
   DBuf<int64_t> topcol_;   // per top-front column: arena offset, packed offset, length
@@ -350,25 +383,9 @@ class LDLSolver : public LinSolver {
   DBuf<int32_t> gidx_;
   DBuf<double> gsol_;
   int64_t gper_ = 0;
-  DBuf<int32_t> tasks_, flags_, flag_off_, counters_, bp_off_;
-  DBuf<double> bpart_;
-  int epoch_ = 0;
-  // device data
-  DBuf<int32_t> first_, nrows_, rows_, u_ld_, child_ptr_, child_list_, rel_, perm_, sched_;
-  DBuf<int32_t> bigslot_, g_ptr_;
-  DBuf<BigChildRec> brec_;
-  DBuf<int64_t> fs_off_, sv_ptr_, sv_src_, g_src_, g_chunk_, chunk_ids_;
-  DBuf<int32_t> g_src32_;
-  DBuf<SymbolicPlan::AsmTile> atiles_;
-  DBuf<double> minv_, fscratch_, gpart_;
-  DBuf<int64_t> row_ptr_, l_off_, u_off_, uvec_off_, asm_ptr_, asm_src_, asm_dst64_, rel_ptr_;
-  DBuf<double> arena_, D_, xi_, uvec_, vwork_;
-  DBuf<LDLStatus> status_;
-  LDLStatus* h_status_ = nullptr;
-  LDLStatus* st_ = nullptr;    // status in use: status_ or the caller's (external_status)
-  LDLStatus* h_st_ = nullptr;  // its host copy
-  bool ext_status_ = false;
-  bool inertia_stale_ = false;  // lazy_inertia: npos / nneg / nzero not counted for the current factor
+  // MADIPM_TREE_DEBUG: the stamps of a tree launch (k_fact_tree, k_fwd_tree), summarised on stderr
+  void tree_debug_dump(hipStream_t s, const char* what, const int64_t* dbuf, int nt, const char* p1, const char* p2,
+                       const char* p3, const char* p4, const char* p5, int stride);
   // live timing
   unsigned tmask_ = 0;
   std::vector<hipEvent_t> evs_;

@@ -14,7 +14,7 @@
 
 namespace madipm {
 
-// Constants the kernels (ldl.hip) and the planner share; defined here and nowhere else.
+// Constants the kernels (ldl.hip, ldl_solve.hip) and the planner share; defined here and nowhere else.
 namespace ldlconst {
 constexpr int NT = 256;  // threads of most kernels
 // assembly, LDS source path: sources per window (five per thread of the 1024-thread assembly kernels),

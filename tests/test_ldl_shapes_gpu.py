@@ -1,5 +1,5 @@
-"""Front shapes across the kernel boundaries of csrc/ldl.hip, against the oracle's LDL^T in the same
-pivot order.
+"""Front shapes across the kernel boundaries of csrc/ldl.hip and csrc/ldl_solve.hip, against
+the oracle's LDL^T in the same pivot order.
 
 helpers.front_tree_k2 prescribes the fronts (pinned on the host in test_front_tree_cpu.py), so a case
 places fronts exactly on a boundary: r = 32/33, 64/65, 128/129, 192/193, 256/257 rows, w <= 2 (micro
