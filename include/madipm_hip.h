@@ -805,6 +805,34 @@ int madipm_solver_adjoint_batch_device(madipm_solver_t s, int32_t k, const madip
  * ran (ceil(k / W) each; a polished batch adds none); no device access.  Any pointer may be NULL. */
 int madipm_solver_sens_batch_info(madipm_solver_t s, int64_t* n_batches, int64_t* n_columns, int64_t* n_chunks);
 
+/* ------------------------------------------------------------------ multi-right-hand-side solve  [ABI 0.2.14, additive]
+ * nrhs right-hand sides through ONE pass over the factor per chunk of `width` columns: every L
+ * panel is read once and every launch paid once per chunk instead of once per column.  In place, column j at
+ * d_x + j * n; nrhs >= 1.  The native route runs on an unsharded factorisation without batched-leaf groups;
+ * elsewhere the call is the loop of madipm_ldl_solve.  A column's bits depend neither on nrhs nor on the
+ * column's position; they are NOT those of madipm_ldl_solve (another summation order), which keeps its loop
+ * and its bits, also after calls of this entry. */
+/* (a struct tag only, no typedef: the entry that fills it carries the same name, so write
+ * `struct madipm_ldl_multi_info`) */
+struct madipm_ldl_multi_info {
+  int32_t width;        /* columns of one chunk (8) */
+  int32_t native;       /* 1: the multi-column route, 0: the loop of single solves */
+  int64_t n_calls;      /* multi-solve calls so far */
+  int64_t n_chunks;     /* ceil(nrhs / width) of every call */
+  int64_t n_columns;
+  int64_t n_big_fronts; /* fronts the native route solves column by column inside a chunk (past 192 rows, or a
+                           panel beyond the small kernels' LDS): they gain nothing from the route */
+};
+int madipm_ldl_solve_multi(madipm_ldl_t ls, double* d_x, int32_t nrhs, madipm_stream_t stream);
+int madipm_ldl_multi_info(madipm_ldl_t ls, struct madipm_ldl_multi_info* info);
+/* on != 0: madipm_solver_tangent_batch / _adjoint_batch (and their _device forms) at the interior-point end
+ * point solve every chunk of columns, a chunk of one column included, with the multi-right-hand-side solve: a
+ * row's bits then do not depend on k, and are within the formulas' tolerance of (not bitwise equal to) the
+ * single calls'.  Default 0: every bit as before.  The single calls and the polished calls never change. */
+int madipm_solver_set_multi_solve(madipm_solver_t s, int32_t on);
+/* The multi-solve counters of the solver's linear solver (those of madipm_ldl_multi_info). */
+int madipm_solver_multi_solve_info(madipm_solver_t s, struct madipm_ldl_multi_info* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -429,6 +429,33 @@ int madipm_ldl_solve(madipm_ldl_t ls, double* d_x, int32_t nrhs, madipm_stream_t
   MADIPM_API_END
 }
 
+static void fill_multi_info(const MultiStat& m, struct madipm_ldl_multi_info* info) {
+  info->width = m.width;
+  info->native = m.native;
+  info->n_calls = m.n_calls;
+  info->n_chunks = m.n_chunks;
+  info->n_columns = m.n_columns;
+  info->n_big_fronts = m.n_big_fronts;
+}
+
+int madipm_ldl_solve_multi(madipm_ldl_t ls, double* d_x, int32_t nrhs, madipm_stream_t stream) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(ls && (d_x || ls->s->n() == 0), "null argument");
+  MADIPM_REQUIRE(nrhs >= 1, "madipm_ldl_solve_multi: nrhs must be at least 1");
+  require_idle(ls);
+  ls->lin->solve_multi_async(d_x, nrhs, (hipStream_t)stream);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_ldl_multi_info(madipm_ldl_t ls, struct madipm_ldl_multi_info* info) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(ls && info, "null argument");
+  fill_multi_info(ls->lin->multi_stat(), info);
+  return 0;
+  MADIPM_API_END
+}
+
 int madipm_ldl_inertia(madipm_ldl_t ls, int32_t* pos, int32_t* zero, int32_t* neg) {
   MADIPM_API_BEGIN
   MADIPM_REQUIRE(ls, "null handle");
@@ -1007,6 +1034,22 @@ int madipm_solver_sens_batch_info(madipm_solver_t s, int64_t* n_batches, int64_t
   MADIPM_API_BEGIN
   MADIPM_REQUIRE(s, "null handle");
   s->s->sens_batch_info(n_batches, n_columns, n_chunks);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_set_multi_solve(madipm_solver_t s, int32_t on) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s, "null handle");
+  s->s->set_multi_solve(on != 0);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_multi_solve_info(madipm_solver_t s, struct madipm_ldl_multi_info* info) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s && info, "null argument");
+  fill_multi_info(s->s->multi_solve_stat(), info);
   return 0;
   MADIPM_API_END
 }

@@ -150,6 +150,14 @@ Comm* make_rccl_comm(int nranks, int rank, const void* unique_id /* 128 bytes */
 void rccl_unique_id(void* out /* 128 bytes */);
 Comm* make_host_comm(int nranks, int rank, int (*fn)(double*, int64_t, void*), void* ctx);
 
+// What a solver's multi-right-hand-side solves did so far (madipm_ldl_multi_info).
+struct MultiStat {
+  int32_t width = ldlconst::MULTI_W;  // columns of one chunk
+  int32_t native = 0;                 // 1: the level-scheduled multi-column route, 0: the loop of single solves
+  int64_t n_calls = 0, n_chunks = 0, n_columns = 0;
+  int64_t n_big_fronts = 0;  // fronts the native route solves column by column (task-queue kernels)
+};
+
 // Linear-solver interface the MPC driver uses (MadNLP.AbstractLinearSolver methods).
 class LinSolver {
  public:
@@ -166,6 +174,16 @@ class LinSolver {
     return false;
   }
   virtual void solve_async(double* b, hipStream_t s) = 0;
+  // k right-hand sides in place, column j at b + j n().  The default is the loop of single solves (column by
+  // column the bits of solve_async); LDLSolver has a multi-column route
+  virtual void solve_multi_async(double* b, int k, hipStream_t s) {
+    if (k <= 0) return;
+    ++mstat_.n_calls;
+    mstat_.n_columns += k;
+    mstat_.n_chunks += (k + mstat_.width - 1) / mstat_.width;
+    for (int j = 0; j < k; ++j) solve_async(b + (int64_t)j * n(), s);
+  }
+  const MultiStat& multi_stat() const { return mstat_; }
   virtual const SymbolicPlan& plan() const = 0;
   virtual void set_timing(unsigned mask) = 0;
   virtual void kernel_stats(KernelStat out[]) = 0;
@@ -192,6 +210,9 @@ class LinSolver {
   // kernel enqueued right after factorize_async is not final: read it after the next solve.
   virtual bool tail_async() const { return false; }
   virtual void join(hipStream_t s) { (void)s; }
+
+ protected:
+  MultiStat mstat_;
 };
 
 class LDLSolver : public LinSolver {
@@ -210,6 +231,7 @@ class LDLSolver : public LinSolver {
   bool external_status(LDLStatus* dev, LDLStatus* host) override;
   // In-place solve K x = b for a device vector of length n (caller's ordering).
   void solve_async(double* b, hipStream_t s) override;
+  void solve_multi_async(double* b, int k, hipStream_t s) override;
 
   // Phases of a sharded factorisation / solve, for callers that run their own collective
   // (ShardGroup below, or a host binding with its own RCCL communicator):
@@ -344,6 +366,10 @@ class LDLSolver : public LinSolver {
   void lb_fwd(const double* b, hipStream_t s);
   void lb_bwd(int g, double* b, hipStream_t s);
   DBuf<double> xi_, uvec_, vwork_;
+  // multi-right-hand-side solve: every phase-1 front by level (LaunchPlan::mlev), and MULTI_W columns of the
+  // internal and the update vector, allocated by the first solve_multi_async
+  std::vector<SolveLevel> mlev_;
+  DBuf<double> xim_, uvm_;
   // tree solves (k_fwd_tree / k_bwd_tree): the phase-1 fronts solved by ONE dependency-driven launch
   // per direction (topological ticket order, forward dependencies = tree children, backward = tree
   // parent), between the level-0 launches and the remaining levels

@@ -74,6 +74,12 @@ bool solve_small(const SymbolicPlan& S, int s) {
   const int r = S.nrows[s], w = S.first[s + 1] - S.first[s];
   return r <= SMALL_SOLVE_MAX && 8 * (r | 1) * w <= 150 * 1024;
 }
+// multi-right-hand-side small class (LaunchPlan::mlev): the panel and MULTI_W staged columns of
+// SMALL_SOLVE_MAX doubles share the workgroup's LDS
+bool solve_small_multi(const SymbolicPlan& S, int s) {
+  const int r = S.nrows[s], w = S.first[s + 1] - S.first[s];
+  return solve_small(S, s) && 8 * (r | 1) * w + 8 * MULTI_W * SMALL_SOLVE_MAX <= kWorkgroupLds;
+}
 bool in_phase(const SymbolicPlan& S, int s, int phase) {
   if (lb_member(S, s)) return false;  // batched leaves: W build + the parent's SYRK + GEMV solves
   return phase == 1 ? (!S.top(s) && S.mine(s)) : S.top(s);
@@ -884,18 +890,26 @@ void plan_fact(const SymbolicPlan& S, const LdlKnobs& K, LaunchPlan& P) {
 }
 
 // ------------------------------------------------------------------ solve levels
-// per level, small fronts (wave per front) and big fronts (task queues)
-void build_solve(const SymbolicPlan& S, LaunchPlan& P, int phase, std::vector<SolveLevel>& out) {
+// per level, small fronts (wave per front) and big fronts (task queues).  multi (LaunchPlan::mlev): every
+// front of the phase, the tree tasks' and the flat leaves' included; a front that is big in both lists keeps
+// the bp_off the first list gave it
+void build_solve(const SymbolicPlan& S, LaunchPlan& P, int phase, std::vector<SolveLevel>& out, bool multi = false) {
   std::vector<int32_t>&sched = P.sched, &tasks = P.tasks;
+  std::vector<char> has_bp;
+  if (multi) {
+    has_bp.assign(std::max(S.nsuper, 1), 0);
+    for (const SolveLevel& L : P.slev1)
+      for (int k = 0; k < L.nbig; ++k) has_bp[sched[L.big_off + k]] = 1;
+  }
   for (int lev = 0; lev < S.nlevels; ++lev) {
     std::vector<int32_t> tiny, small, big, micro;
     for (int q = S.level_ptr[lev]; q < S.level_ptr[lev + 1]; ++q) {
       const int s = S.level_list[q];
-      if (!in_phase(S, s, phase) || (phase == 1 && (P.in_tree[s] || P.sleaf[s]))) continue;
+      if (!in_phase(S, s, phase) || (phase == 1 && !multi && (P.in_tree[s] || P.sleaf[s]))) continue;
       const int r = S.nrows[s], w = S.first[s + 1] - S.first[s];
       if (r <= 32 && w <= 2)
         micro.push_back(s);
-      else if (solve_small(S, s))
+      else if (solve_small(S, s) && (!multi || r <= 32 || solve_small_multi(S, s)))
         (r > 32 ? small : tiny).push_back(s);
       else
         big.push_back(s);
@@ -929,8 +943,10 @@ void build_solve(const SymbolicPlan& S, LaunchPlan& P, int phase, std::vector<So
       const int w = S.first[s + 1] - S.first[s], r = S.nrows[s];
       if (r == w) continue;
       const int np = (int)cdiv(w, 64), nch = (int)cdiv(r - w, BWD_CHUNK);
-      P.bp_off[s] = (int32_t)P.nbpart;
-      P.nbpart += (int64_t)np * nch;
+      if (!multi || !has_bp[s]) {
+        P.bp_off[s] = (int32_t)P.nbpart;
+        P.nbpart += (int64_t)np * nch;
+      }
       for (int p = 0; p < np; ++p)
         for (int c = 0; c < nch; ++c) sched.insert(sched.end(), {s, p | (c << 16)});
     }
@@ -1143,6 +1159,16 @@ void plan_solve(const SymbolicPlan& S, LaunchPlan& P) {
       if (S.top(s))
         for (int c = 0; c < cdiv(S.nrows[s], NT); ++c) P.sched.insert(P.sched.end(), {s, c});
     P.nxg = (int)(((int64_t)P.sched.size() - P.xg_off) / 2);
+  } else {
+    // the multi-right-hand-side levels, after everything the single solve reads (no offset of it moves).  A
+    // front that passes solve_small but not the multi small class's LDS test is big there and has no flags yet
+    for (int s = 0; s < ns; ++s)
+      if (S.nrows[s] > 32 && solve_small(S, s) && !solve_small_multi(S, s)) {
+        P.flag_off[s] = (int32_t)P.nflags;
+        P.nflags += cdiv(S.first[s + 1] - S.first[s], 64);
+      }
+    align2(P.sched);
+    build_solve(S, P, 1, P.mlev, true);
   }
 }
 

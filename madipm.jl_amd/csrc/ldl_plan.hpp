@@ -27,6 +27,9 @@ constexpr int LB_KCHUNK = 2048;  // members per SYRK launch (m x 2048 doubles of
 constexpr int GAT_ROWS = NT / 8;
 constexpr int BWD_CHUNK = 256;
 constexpr int SMALL_SOLVE_MAX = 192;
+constexpr int MULTI_W = 8;  // right-hand sides one pass of the multi-column level kernels carries
+constexpr int kWorkgroupLds = 160 * 1024;  // LDS one gfx950 workgroup may hold (static + dynamic)
+constexpr int kSolveSmallMultiLds = kWorkgroupLds - 8 * MULTI_W * SMALL_SOLVE_MAX;  // k_fwd_small_m / k_bwd_small_m's panel
 constexpr int MED_SOLVE_MAX = SymbolicPlan::kFactTreeMedMax;
 constexpr int TREE_ROOT_LDS = 150 * 1024;  // the big etree roots' own forward launch (LaunchPlan::nroot_task)
 constexpr int TREE_SOLVE_LDS = 76 * 1024;
@@ -194,6 +197,9 @@ struct LaunchPlan {
   int64_t upd_np = 0, upd_nt = 0;  // k_big_upd128's split-K scratch: parts, tiles of the largest split launch
   // solves: per level, leaves first
   std::vector<SolveLevel> slev1, slev2;
+  // multi-right-hand-side solve (unsharded plans): the levels of phase 1 with EVERY front in them, the
+  // tree tasks' and the flat leaves' too; its lists follow the single solve's in sched / tasks
+  std::vector<SolveLevel> mlev;
   std::vector<int32_t> tasks, flag_off, bp_off;
   int64_t nflags = 0, nbpart = 0;
   int64_t xg_off = 0;  // (top front, 256-row chunk) pairs of the external forward gather
@@ -230,5 +236,6 @@ double lb_alg(const SymbolicPlan& S, size_t g);  // solve bytes of a batched-lea
 bool lb_member(const SymbolicPlan& S, int s);
 bool in_phase(const SymbolicPlan& S, int s, int phase);
 bool solve_small(const SymbolicPlan& S, int s);
+bool solve_small_multi(const SymbolicPlan& S, int s);  // small in LaunchPlan::mlev
 
 }  // namespace madipm

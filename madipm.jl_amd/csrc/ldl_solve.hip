@@ -505,6 +505,388 @@ __global__ __launch_bounds__(NT) void k_bwd_tiny(FrontTab T, const int32_t* __re
   }
 }
 
+// ------------------------------------------------------------------ multi-right-hand-side level kernels
+// The level kernels above over kc <= MW columns (LDLSolver::solve_multi_async): column j of
+// the right-hand side / solution at b + j n, of the internal vector at xi + j N, of the update vector at
+// uvec + j ustride.  Every L entry, row index, gather index and pivot is loaded once per front and used for
+// all kc columns.  A front's update entries always go to its own update vector (never through T.upos into
+// T.gbuf) and the children's are read through sv_src, which indexes the update vector for every row of every
+// front.  A column's operations and their order are those of the single-column kernel: kc is a uniform loop
+// bound or guard only, so a column's bits depend neither on kc nor on its slot.  The plans that take this
+// route are unsharded (T.xoff = -1 everywhere): the initial value is the caller's entry.
+constexpr int MW = MULTI_W;
+
+__global__ __launch_bounds__(NT) void k_fwd_micro_m(FrontTab T, const int32_t* __restrict__ fronts, int nf, int kc,
+                                                    const double* __restrict__ arena, const double* __restrict__ b,
+                                                    int64_t n, double* __restrict__ xi, int64_t N,
+                                                    double* __restrict__ uvec, int64_t ustride) {
+  const int g = threadIdx.x / MG, l = threadIdx.x & (MG - 1);
+  const int q = blockIdx.x * (NT / MG) + g;
+  const bool live = q < nf;
+  const int s = fronts[live ? q : nf - 1];
+  const int f0 = T.first[s], w = T.first[s + 1] - f0, r = T.nrows[s];
+  const double* __restrict__ L = arena + T.l_off[s];
+  const int64_t uo = T.uvec_off[s];
+  double v[2][MW], c0[2], c1[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int i = l + 16 * h;
+    double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+    for (int j = 0; j < MW; ++j) v[h][j] = 0.0;
+    if (i < r) {
+      if (i < w) {
+        const int64_t pi = T.perm[f0 + i];
+#pragma unroll
+        for (int j = 0; j < MW; ++j)
+          if (j < kc) v[h][j] = b[j * n + pi];
+      }
+      const int64_t e = T.row_ptr[s] + i;
+      const int64_t p1 = T.sv_ptr[e + 1];
+      for (int64_t p = T.sv_ptr[e]; p < p1; ++p) {
+        const int64_t src = T.sv_src[p];
+#pragma unroll
+        for (int j = 0; j < MW; ++j)
+          if (j < kc) v[h][j] += uvec[j * ustride + src];
+      }
+      a0 = L[i];
+      if (w == 2) a1 = L[i + r];
+    }
+    c0[h] = a0;
+    c1[h] = a1;
+  }
+  const double l10 = __shfl(c0[0], 1, MG);
+#pragma unroll
+  for (int j = 0; j < MW; ++j) {
+    if (j >= kc) break;  // uniform
+    const double x0 = __shfl(v[0][j], 0, MG);
+    const double x1 = (w == 2) ? __shfl(v[0][j], 1, MG) - l10 * x0 : 0.0;
+    if (!live) continue;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int i = l + 16 * h;
+      if (i < w) {
+        xi[j * N + f0 + i] = (i == 0) ? x0 : x1;
+      } else if (i < r) {
+        uvec[j * ustride + uo + (i - w)] = (v[h][j] - c0[h] * x0) - c1[h] * x1;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_bwd_micro_m(FrontTab T, const int32_t* __restrict__ fronts, int nf, int kc,
+                                                    const double* __restrict__ arena, const double* __restrict__ D,
+                                                    double* __restrict__ xi, int64_t N, double* __restrict__ out,
+                                                    int64_t n) {
+  const int g = threadIdx.x / MG, l = threadIdx.x & (MG - 1);
+  const int q = blockIdx.x * (NT / MG) + g;
+  const bool live = q < nf;
+  const int s = fronts[live ? q : nf - 1];
+  const int f0 = T.first[s], w = T.first[s + 1] - f0, r = T.nrows[s];
+  const double* __restrict__ L = arena + T.l_off[s];
+  const int32_t* __restrict__ rows = T.rows + T.row_ptr[s];
+  double a0[MW], a1[MW], l10 = 0.0;
+#pragma unroll
+  for (int j = 0; j < MW; ++j) a0[j] = a1[j] = 0.0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int i = l + 16 * h;
+    if (i >= w && i < r) {
+      const int64_t row = rows[i];  // final: ancestors
+      const double c0 = L[i], c1 = (w == 2) ? L[i + r] : 0.0;
+#pragma unroll
+      for (int j = 0; j < MW; ++j)
+        if (j < kc) {
+          const double x = xi[j * N + row];
+          a0[j] = fma(c0, x, a0[j]);
+          if (w == 2) a1[j] = fma(c1, x, a1[j]);
+        }
+    }
+    if (i == 1 && w == 2) l10 = L[1];
+  }
+  l10 = __shfl(l10, 1, MG);
+  const bool head = live && l == 0;
+  const double d0 = D[f0], d1 = (w == 2) ? D[f0 + 1] : 1.0;
+  const int64_t p0 = T.perm[f0], p1 = (w == 2) ? T.perm[f0 + 1] : 0;
+  const bool wo = T.wout[s];
+#pragma unroll
+  for (int j = 0; j < MW; ++j) {
+    if (j >= kc) break;  // uniform
+    double s0 = a0[j], s1 = a1[j];
+#pragma unroll
+    for (int o = MG / 2; o > 0; o >>= 1) {
+      s0 += __shfl_xor(s0, o, MG);
+      s1 += __shfl_xor(s1, o, MG);
+    }
+    if (!head) continue;
+    double* __restrict__ xj = xi + j * N;
+    const double v1 = (w == 2) ? xj[f0 + 1] / d1 - s1 : 0.0;
+    const double v0 = xj[f0] / d0 - s0 - l10 * v1;
+    xj[f0] = v0;
+    if (wo) out[j * n + p0] = v0;
+    if (w == 2) {
+      xj[f0 + 1] = v1;
+      if (wo) out[j * n + p1] = v1;
+    }
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_fwd_tiny_m(FrontTab T, const int32_t* __restrict__ fronts, int nf, int kc,
+                                                   const double* __restrict__ arena, const double* __restrict__ b,
+                                                   int64_t n, double* __restrict__ xi, int64_t N,
+                                                   double* __restrict__ uvec, int64_t ustride) {
+  const int lane = threadIdx.x & 63, lr = lane & 31;
+  const int q = (blockIdx.x * SW + (threadIdx.x >> 6)) * 2 + (lane >> 5);
+  const bool live = q < nf;
+  const int s = fronts[live ? q : nf - 1];
+  const int f0 = T.first[s], w = T.first[s + 1] - f0, r = T.nrows[s];
+  const double* __restrict__ L = arena + T.l_off[s];
+  double v[MW];
+#pragma unroll
+  for (int j = 0; j < MW; ++j) v[j] = 0.0;
+  if (lr < r) {
+    if (lr < w) {
+      const int64_t pi = T.perm[f0 + lr];
+#pragma unroll
+      for (int j = 0; j < MW; ++j)
+        if (j < kc) v[j] = b[j * n + pi];
+    }
+    const int64_t e = T.row_ptr[s] + lr;
+    const int64_t p1 = T.sv_ptr[e + 1];
+    for (int64_t p = T.sv_ptr[e]; p < p1; ++p) {
+      const int64_t src = T.sv_src[p];
+#pragma unroll
+      for (int j = 0; j < MW; ++j)
+        if (j < kc) v[j] += uvec[j * ustride + src];
+    }
+  }
+  const int wmax = max(__builtin_amdgcn_readlane(w, 0), __builtin_amdgcn_readlane(w, 32));
+  const int cl = min(lr, r - 1);
+  for (int t4 = 0; t4 < wmax; t4 += 4) {
+    double c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = L[cl + (int64_t)min(t4 + k, w - 1) * r];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int t = t4 + k;
+      const double ck = (t < w && lr > t) ? -c[k] : 0.0;
+#pragma unroll
+      for (int j = 0; j < MW; ++j)
+        if (j < kc) {  // uniform
+          const double xt = __shfl(v[j], t & 31, 32);
+          v[j] = fma(ck, xt, v[j]);
+        }
+    }
+  }
+  if (live && lr < r) {
+    const int64_t uo = T.uvec_off[s];
+#pragma unroll
+    for (int j = 0; j < MW; ++j)
+      if (j < kc) {
+        if (lr < w)
+          xi[j * N + f0 + lr] = v[j];
+        else
+          uvec[j * ustride + uo + (lr - w)] = v[j];
+      }
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_bwd_tiny_m(FrontTab T, const int32_t* __restrict__ fronts, int nf, int kc,
+                                                   const double* __restrict__ arena, const double* __restrict__ D,
+                                                   double* __restrict__ xi, int64_t N, double* __restrict__ out,
+                                                   int64_t n) {
+  const int lane = threadIdx.x & 63, lr = lane & 31;
+  const int q = (blockIdx.x * SW + (threadIdx.x >> 6)) * 2 + (lane >> 5);
+  const bool live = q < nf;
+  const int s = fronts[live ? q : nf - 1];
+  const int f0 = T.first[s], w = T.first[s + 1] - f0, r = T.nrows[s];
+  const double* __restrict__ L = arena + T.l_off[s];
+  const int32_t* __restrict__ rows = T.rows + T.row_ptr[s];
+  const int nb = r - w;
+  double xb[MW], acc[MW], v[MW];  // xb: x of below row w + lr (final)
+  const int64_t brow = (lr < nb) ? rows[w + lr] : 0;
+#pragma unroll
+  for (int j = 0; j < MW; ++j) {
+    xb[j] = (lr < nb && j < kc) ? xi[j * N + brow] : 0.0;
+    acc[j] = 0.0;
+  }
+  const int cj = min(lr, w - 1);
+  const int nbmax = max(__builtin_amdgcn_readlane(nb, 0), __builtin_amdgcn_readlane(nb, 32));
+  for (int k4 = 0; k4 < nbmax; k4 += 4) {
+    double c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = L[min(w + k4 + k, r - 1) + (int64_t)cj * r];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const double ck = (k4 + k < nb) ? c[k] : 0.0;
+#pragma unroll
+      for (int j = 0; j < MW; ++j)
+        if (j < kc) {  // uniform
+          const double x = __shfl(xb[j], (k4 + k) & 31, 32);
+          acc[j] = fma(ck, x, acc[j]);
+        }
+    }
+  }
+  const double dj = D[f0 + cj];
+#pragma unroll
+  for (int j = 0; j < MW; ++j) v[j] = (lr < w && j < kc) ? xi[j * N + f0 + lr] / dj - acc[j] : 0.0;
+  const int wmax = max(__builtin_amdgcn_readlane(w, 0), __builtin_amdgcn_readlane(w, 32));
+  for (int t4 = wmax - 1; t4 > 0; t4 -= 4) {
+    double c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = L[min(max(t4 - k, 0), w - 1) + (int64_t)cj * r];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int t = t4 - k;
+      const double ck = (t > 0 && t < w && lr < t) ? -c[k] : 0.0;
+#pragma unroll
+      for (int j = 0; j < MW; ++j)
+        if (j < kc) {  // uniform
+          const double xt = __shfl(v[j], max(t, 0) & 31, 32);
+          v[j] = fma(ck, xt, v[j]);
+        }
+    }
+  }
+  if (live && lr < w) {
+    const int64_t pi = T.perm[f0 + lr];
+    const bool wo = T.wout[s];
+#pragma unroll
+    for (int j = 0; j < MW; ++j)
+      if (j < kc) {
+        xi[j * N + f0 + lr] = v[j];
+        if (wo) out[j * n + pi] = v[j];
+      }
+  }
+}
+
+// Small fronts: the panel staged once by the whole workgroup, the kc initial vectors through LDS, then wave q
+// substitutes columns q and q + 4 one after the other, each exactly as wave 0 of k_fwd_small / k_bwd_small
+// does (one column per wave in two rounds: the registers of the single-column kernel, and four columns already
+// keep all four waves busy).
+__global__ __launch_bounds__(NT) void k_fwd_small_m(FrontTab T, const int32_t* __restrict__ fronts, int nf, int kc,
+                                                    const double* __restrict__ arena, const double* __restrict__ b,
+                                                    int64_t n, double* __restrict__ xi, int64_t N,
+                                                    double* __restrict__ uvec, int64_t ustride) {
+  extern __shared__ __attribute__((aligned(16))) double Ls[];
+  __shared__ double v0s[MW][SMALL_SOLVE_MAX];
+  const int s = fronts[blockIdx.x];
+  const int f0 = T.first[s], w = T.first[s + 1] - f0, r = T.nrows[s];
+  const int rl = r | 1;
+  stage_panel(arena + T.l_off[s], Ls, r, w, rl);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < r; i += NT) {
+    const int64_t e = T.row_ptr[s] + i;
+    const int64_t p1 = T.sv_ptr[e + 1];
+    int64_t p = T.sv_ptr[e];
+    const int64_t pi = T.perm[f0 + min(i, w - 1)];
+    double vi[MW];
+#pragma unroll
+    for (int j = 0; j < MW; ++j) vi[j] = 0.0;
+    for (; p + 3 < p1; p += 4) {
+      const int64_t q0 = T.sv_src[p], q1 = T.sv_src[p + 1], q2 = T.sv_src[p + 2], q3 = T.sv_src[p + 3];
+#pragma unroll
+      for (int j = 0; j < MW; ++j)
+        if (j < kc) {
+          const double* __restrict__ u = uvec + j * ustride;
+          vi[j] += (u[q0] + u[q1]) + (u[q2] + u[q3]);
+        }
+    }
+    for (; p < p1; ++p) {
+      const int64_t q0 = T.sv_src[p];
+#pragma unroll
+      for (int j = 0; j < MW; ++j)
+        if (j < kc) vi[j] += uvec[j * ustride + q0];
+    }
+#pragma unroll
+    for (int j = 0; j < MW; ++j)
+      if (j < kc) v0s[j][i] = vi[j] + ((i < w) ? b[j * n + pi] : 0.0);
+  }
+  __syncthreads();
+  const int64_t uo = T.uvec_off[s];
+  for (int j = wave; j < kc; j += NT / 64) {
+    double v[3];
+#pragma unroll
+    for (int h = 0; h < 3; ++h) {
+      const int i = lane + 64 * h;
+      v[h] = (i < r) ? v0s[j][i] : 0.0;
+    }
+    fwd_subst16(v, Ls, rl, r, w, lane);  // v[i] -= L(i, t) v[t] for i > t, t < w
+#pragma unroll
+    for (int h = 0; h < 3; ++h) {
+      const int i = lane + 64 * h;
+      if (i < w)
+        xi[j * N + f0 + i] = v[h];
+      else if (i < r)
+        uvec[j * ustride + uo + (i - w)] = v[h];
+    }
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_bwd_small_m(FrontTab T, const int32_t* __restrict__ fronts, int nf, int kc,
+                                                    const double* __restrict__ arena, const double* __restrict__ D,
+                                                    double* __restrict__ xi, int64_t N, double* __restrict__ out,
+                                                    int64_t n) {
+  extern __shared__ __attribute__((aligned(16))) double Ls[];
+  // per column: [0, w) the own entries x_j / d_j, [w, r) x of the rows below the pivot block (ancestors: final)
+  __shared__ double xbs[MW][SMALL_SOLVE_MAX];
+  const int s = fronts[blockIdx.x];
+  const int f0 = T.first[s], w = T.first[s + 1] - f0, r = T.nrows[s];
+  const int rl = r | 1;
+  stage_panel(arena + T.l_off[s], Ls, r, w, rl);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int32_t* __restrict__ rows = T.rows + T.row_ptr[s];
+  const int nb = r - w;
+  for (int i = threadIdx.x; i < r; i += NT) {
+    if (i < w) {
+      const double d = D[f0 + i];
+#pragma unroll
+      for (int j = 0; j < MW; ++j)
+        if (j < kc) xbs[j][i] = xi[j * N + f0 + i] / d;
+    } else {
+      const int64_t row = rows[i];
+#pragma unroll
+      for (int j = 0; j < MW; ++j)
+        if (j < kc) xbs[j][i] = xi[j * N + row];
+    }
+  }
+  __syncthreads();
+  int cj[3];
+#pragma unroll
+  for (int h = 0; h < 3; ++h) cj[h] = min(lane + 64 * h, w - 1);
+  int64_t pj[3];
+#pragma unroll
+  for (int h = 0; h < 3; ++h) pj[h] = T.perm[f0 + cj[h]];
+  const bool wo = T.wout[s];
+  for (int j = wave; j < kc; j += NT / 64) {
+    const double* xb = xbs[j] + w;
+    // v[j] = x_j / d_j - sum_{i >= w} L(i, j) x_i
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int k8 = 0; k8 < nb; k8 += 8) {
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk) {
+        const int k = k8 + kk;
+        if (k < nb) {
+          const double x = xb[k];
+#pragma unroll
+          for (int h = 0; h < 3; ++h) acc[h] = fma(Ls[(w + k) + cj[h] * rl], x, acc[h]);
+        }
+      }
+    }
+    double v[3];
+#pragma unroll
+    for (int h = 0; h < 3; ++h) v[h] = (lane + 64 * h < w) ? xbs[j][cj[h]] - acc[h] : 0.0;
+    bwd_subst16(v, Ls, rl, w, lane);  // for t = w-1 .. 1: v[j] -= L(t, j) v[t] for j < t
+#pragma unroll
+    for (int h = 0; h < 3; ++h) {
+      const int c = lane + 64 * h;
+      if (c < w) {
+        xi[j * N + f0 + c] = v[h];
+        if (wo) out[j * n + pj[h]] = v[h];
+      }
+    }
+  }
+}
+
 // initial forward vector of a big front (own b entries + children's update vectors), in HBM;
 // task = (front, chunk of GAT_ROWS rows), GAT_G lanes per row stride the row's gather list (children
 // in list order per lane, lanes combined by a fixed butterfly: deterministic)
@@ -1707,6 +2089,8 @@ __global__ __launch_bounds__(NT) void k_gather_scatter(const int32_t* gidx, int6
 void ldl_solve_kernel_attributes() {
   set_max_dyn_lds((const void*)k_fwd_small, kSolveSmallLds);
   set_max_dyn_lds((const void*)k_bwd_small, kSolveSmallLds);
+  set_max_dyn_lds((const void*)k_fwd_small_m, kSolveSmallMultiLds);
+  set_max_dyn_lds((const void*)k_bwd_small_m, kSolveSmallMultiLds);
   set_max_dyn_lds((const void*)k_fwd_tree, TREE_SOLVE_LDS);
   set_max_dyn_lds((const void*)k_bwd_tree, TREE_SOLVE_LDS);
   set_max_dyn_lds((const void*)k_root_solve, TREE_ROOT_LDS);
@@ -1891,6 +2275,87 @@ void LDLSolver::solve_async(double* b, hipStream_t s) {
   solve_phase2(b, s);
   comm_->allgather_inplace(solve_gbuf(), gper_, s);
   solve_phase3(b, s);
+}
+
+// ------------------------------------------------------------------ multi-right-hand-side solve
+// k columns in place, column j at b + j n.  Native route (unsharded, no batched-leaf groups): chunks of kc <= MW
+// columns, each forward over mlev_ level by level and backward in reverse, one multi-column launch per non-empty
+// class of a level, ordered by the stream: no kernel of it waits on another workgroup of a different launch.  A
+// level's big fronts go through the single-column task-queue kernels, column after column inside the level, each
+// pass with its own epoch and zeroed counters.  Otherwise: the loop of solve_async.
+void LDLSolver::solve_multi_async(double* b, int k, hipStream_t s) {
+  if (k <= 0) return;
+  ++mstat_.n_calls;
+  mstat_.n_columns += k;
+  mstat_.n_chunks += cdiv(k, MW);
+  if (!mstat_.native) {
+    for (int j = 0; j < k; ++j) solve_async(b + (int64_t)j * S_.N, s);
+    return;
+  }
+  join(s);  // the factorisation's root tail may still be on the side stream
+  const int64_t N = S_.N, us = std::max<int64_t>(S_.uvec_size, 1);
+  if (!xim_.p) {  // the first multi call: MW columns of the internal and the update vector
+    xim_.alloc(MW * N);
+    uvm_.alloc(MW * us);
+  }
+  const SolveTask* tasks = reinterpret_cast<const SolveTask*>(tasks_.p);
+  const int NL = (int)mlev_.size();
+  for (int c0 = 0; c0 < k; c0 += MW) {
+    const int kc = std::min(MW, k - c0);
+    double* bc = b + (int64_t)c0 * N;
+    const int e0 = epoch_;  // column j's passes: the epochs of single solve e0 + 1 + j
+    epoch_ += kc;
+    for (int lev = 0; lev < NL; ++lev) {
+      const SolveLevel& L = mlev_[lev];
+      if (L.nmicro)
+        TIMED(KK_FWD_TINY, L.micro_bytes, L.micro_alg, L.micro_flops,
+              (k_fwd_micro_m<<<(unsigned)cdiv(L.nmicro, NT / MG), NT, 0, s>>>(T_, sched_.p + L.micro_off, L.nmicro, kc, arena_,
+                                                                             bc, N, xim_, N, uvm_, us)));
+      if (L.ntiny)
+        TIMED(KK_FWD_TINY, L.tiny_bytes, L.tiny_alg, L.tiny_flops,
+              (k_fwd_tiny_m<<<(unsigned)cdiv(L.ntiny, 2 * SW), NT, 0, s>>>(T_, sched_.p + L.tiny_off, L.ntiny, kc, arena_, bc,
+                                                                          N, xim_, N, uvm_, us)));
+      if (L.nsmall)
+        TIMED(KK_FWD_SMALL, L.small_bytes, L.small_alg, L.small_flops,
+              (k_fwd_small_m<<<(unsigned)L.nsmall, NT, L.small_lds, s>>>(T_, sched_.p + L.small_off, L.nsmall, kc, arena_, bc,
+                                                                        N, xim_, N, uvm_, us)));
+      for (int j = 0; L.nbig && j < kc; ++j) {
+        MADIPM_HIP(hipMemsetAsync(counters_.p + 2 * lev, 0, 2 * sizeof(int32_t), s));
+        TIMED(KK_FWD_GATHER, L.gat_bytes, 0.0, 0.0,
+              (k_fwd_gather<<<L.ngat, NT, 0, s>>>(T_, sched_.p + L.gat_off, bc + j * N, uvm_.p + j * us, vwork_)));
+        TIMED(KK_FWD_BIG, L.big_bytes, L.big_alg + L.below_alg, L.big_flops,
+              (k_fwd_big<<<std::min(L.nftask, knobs_.big_solve_wg), NT, 0, s>>>(
+                  T_, tasks + L.ftask_off, L.nftask, counters_.p + 2 * lev, flags_, flag_off_, 2 * (e0 + 1 + j) - 1, arena_,
+                  vwork_, xim_.p + j * N, uvm_.p + j * us, &st_->err)));
+      }
+    }
+    for (int lev = NL - 1; lev >= 0; --lev) {
+      const SolveLevel& L = mlev_[lev];
+      for (int j = 0; L.nbig && j < kc; ++j) {
+        MADIPM_HIP(hipMemsetAsync(counters_.p + 2 * lev, 0, 2 * sizeof(int32_t), s));
+        if (L.nbelow)
+          TIMED(KK_BWD_BELOW, L.below_bytes, L.below_alg, 0.25 * L.below_bytes,
+                (k_bwd_below<<<L.nbelow, NT, 0, s>>>(T_, sched_.p + L.below_off, bp_off_, arena_, xim_.p + j * N, bpart_)));
+        TIMED(KK_BWD_BIG, L.big_bytes - L.below_bytes, L.big_alg, L.big_flops - 0.25 * L.below_bytes,
+              (k_bwd_big<<<std::min(L.nbtask, knobs_.big_solve_wg), NT, 0, s>>>(
+                  T_, tasks + L.btask_off, L.nbtask, counters_.p + 2 * lev + 1, flags_, flag_off_, 2 * (e0 + 1 + j), arena_, D_,
+                  xim_.p + j * N, bc + j * N, bp_off_, bpart_, &st_->err)));
+      }
+      if (L.nsmall)
+        TIMED(KK_BWD_SMALL, L.small_bytes, L.small_alg, L.small_flops,
+              (k_bwd_small_m<<<(unsigned)L.nsmall, NT, L.small_lds, s>>>(T_, sched_.p + L.small_off, L.nsmall, kc, arena_, D_,
+                                                                        xim_, N, bc, N)));
+      if (L.ntiny)
+        TIMED(KK_BWD_TINY, L.tiny_bytes, L.tiny_alg, L.tiny_flops,
+              (k_bwd_tiny_m<<<(unsigned)cdiv(L.ntiny, 2 * SW), NT, 0, s>>>(T_, sched_.p + L.tiny_off, L.ntiny, kc, arena_, D_,
+                                                                          xim_, N, bc, N)));
+      if (L.nmicro)
+        TIMED(KK_BWD_TINY, L.micro_bytes, L.micro_alg, L.micro_flops,
+              (k_bwd_micro_m<<<(unsigned)cdiv(L.nmicro, NT / MG), NT, 0, s>>>(T_, sched_.p + L.micro_off, L.nmicro, kc, arena_,
+                                                                             D_, xim_, N, bc, N)));
+    }
+  }
+  MADIPM_HIP(hipGetLastError());
 }
 
 }  // namespace madipm

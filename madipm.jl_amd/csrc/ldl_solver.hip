@@ -209,6 +209,9 @@ LDLSolver::LDLSolver(int n, const int64_t* colptr, const int32_t* rowval, const 
   // ---- solve levels, tree-solve tables, big-front solve tasks
   slev1_ = std::move(P.slev1);
   slev2_ = std::move(P.slev2);
+  mlev_ = std::move(P.mlev);
+  mstat_.native = S.nshards == 1 && S.lb.empty() && !mlev_.empty();
+  for (const SolveLevel& L : mlev_) mstat_.n_big_fronts += mstat_.native ? L.nbig : 0;
   xg_off_ = P.xg_off;
   nxg_ = P.nxg;
   ntree_ = P.ntree;

@@ -137,6 +137,10 @@ class MPCSolver {
   void adjoint_batch(int32_t k, const madipm_qp_cotangents& g, const madipm_qp_gradients& out, bool polished,
                      bool device, hipStream_t caller);
   void sens_batch_info(int64_t* n_batches, int64_t* n_columns, int64_t* n_chunks) const;
+  // on: the batched end-point sensitivities solve every chunk with LinSolver::solve_multi_async:
+  // a row's bits then do not depend on k, and differ from the single calls' within the formulas' tolerance
+  void set_multi_solve(bool on) { multi_solve_ = on; }
+  const MultiStat& multi_solve_stat() const { return ldl_->multi_stat(); }
   int64_t n_analyses() const { return n_analyses_; }
   int64_t n_updates() const { return n_updates_; }
   double last_update_s() const { return last_update_s_; }
@@ -212,6 +216,7 @@ class MPCSolver {
   hipStream_t stream_ = nullptr;
   std::unique_ptr<QPHost> H_;
   std::unique_ptr<LinSolver> ldl_;
+  bool multi_solve_ = false;  // set_multi_solve
   Comm* comm_ = nullptr;
   // sizes
   int nx_ = 0, ns_ = 0, n_ = 0, m_ = 0, nlb_ = 0, nub_ = 0;

@@ -2272,7 +2272,11 @@ void MPCSolver::sens_solve(const SensView& V, int kc, double* resid, bool first_
   hipStream_t s = stream_;
   const int64_t N = (int64_t)n_ + m_;
   const int nb = blocks(kc * N), nbs = spmv_blocks(n_ + m_);
-  auto solves = [&] {  // kkt_solve() of the K2 formulation (sens_refuse admits no other), on each column
+  // kkt_solve() of the K2 formulation (sens_refuse admits no other), on each column; a batch with
+  // set_multi_solve on: the chunk's columns in one multi-right-hand-side solve, a chunk of one column too
+  const bool multi = multi_solve_ && V.W > 1;
+  auto solves = [&] {
+    if (multi) return ldl_->solve_multi_async(V.d, kc, s);
     for (int j = 0; j < kc; ++j) ldl_->solve_async(V.d + j * N, s);
   };
   auto residual = [&](double* r) {

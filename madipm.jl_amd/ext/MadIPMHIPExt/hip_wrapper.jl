@@ -708,3 +708,46 @@ function solver_sens_batch_info(h::Ptr{Cvoid})
                 h, nb, nc, nk), "madipm_solver_sens_batch_info")
     return (n_batches = nb[], n_columns = nc[], n_chunks = nk[])
 end
+
+# ---- multi-right-hand-side LDL^T solve (ABI 0.2.14, DESIGN §13j).  Like every entry of this file these four
+# are not executed in this repository (no Julia toolchain in the image): unexercised; the Python mirror
+# (HIPLDLSolver.solve_multi / multi_info, MPCSolver.set_multi_solve / multi_solve_info) is the tested one.
+# struct madipm_ldl_multi_info
+struct MadipmLDLMultiInfo
+    width::Int32
+    native::Int32
+    n_calls::Int64
+    n_chunks::Int64
+    n_columns::Int64
+    n_big_fronts::Int64
+end
+MadipmLDLMultiInfo() = MadipmLDLMultiInfo(0, 0, 0, 0, 0, 0)
+
+# nrhs columns of length n in place at the DEVICE pointer d_x (column j at d_x + j n): one pass over the factor
+# per chunk of `width` columns; a column's bits depend neither on nrhs nor on its position
+function ldl_solve_multi(h::Ptr{Cvoid}, d_x::Ptr{Float64}, nrhs::Integer; stream::Ptr{Cvoid}=C_NULL)
+    check(ccall((:madipm_ldl_solve_multi, libmadipm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Cvoid}),
+                h, d_x, nrhs, stream), "madipm_ldl_solve_multi")
+    return
+end
+
+function ldl_multi_info(h::Ptr{Cvoid})
+    info = Ref(MadipmLDLMultiInfo())
+    check(ccall((:madipm_ldl_multi_info, libmadipm), Cint, (Ptr{Cvoid}, Ref{MadipmLDLMultiInfo}), h, info),
+          "madipm_ldl_multi_info")
+    return info[]
+end
+
+# on: the batched interior-point sensitivities solve every chunk with the multi-right-hand-side solve
+function solver_set_multi_solve(h::Ptr{Cvoid}, on::Bool=true)
+    check(ccall((:madipm_solver_set_multi_solve, libmadipm), Cint, (Ptr{Cvoid}, Int32), h, on ? 1 : 0),
+          "madipm_solver_set_multi_solve")
+    return
+end
+
+function solver_multi_solve_info(h::Ptr{Cvoid})
+    info = Ref(MadipmLDLMultiInfo())
+    check(ccall((:madipm_solver_multi_solve_info, libmadipm), Cint, (Ptr{Cvoid}, Ref{MadipmLDLMultiInfo}), h, info),
+          "madipm_solver_multi_solve_info")
+    return info[]
+end

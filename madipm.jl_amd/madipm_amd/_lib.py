@@ -47,6 +47,14 @@ class LDLInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LDLMultiInfo(C.Structure):   # madipm_ldl_multi_info
+    _fields_ = [("width", C.c_int32), ("native", C.c_int32), ("n_calls", C.c_int64), ("n_chunks", C.c_int64),
+                ("n_columns", C.c_int64), ("n_big_fronts", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 NKERNELS = 24  # MADIPM_NKERNELS
 
 
@@ -87,6 +95,8 @@ _sig("madipm_ldl_factorize", C.c_int, [vp, vp, vp])
 _sig("madipm_ldl_factorize_async", C.c_int, [vp, vp, vp])
 _sig("madipm_ldl_is_factorized", C.c_int, [vp])
 _sig("madipm_ldl_solve", C.c_int, [vp, vp, C.c_int32, vp])
+_sig("madipm_ldl_solve_multi", C.c_int, [vp, vp, C.c_int32, vp])
+_sig("madipm_ldl_multi_info", C.c_int, [vp, C.POINTER(LDLMultiInfo)])
 _sig("madipm_ldl_inertia", C.c_int, [vp, i32p, i32p, i32p])
 _sig("madipm_ldl_get_d", C.c_int, [vp, f64p])
 _sig("madipm_ldl_perm", C.c_int, [vp, i32p])
@@ -219,6 +229,8 @@ _sig("madipm_solver_adjoint_batch", C.c_int, [vp, C.c_int32, C.POINTER(QPCot), C
 _sig("madipm_solver_adjoint_batch_device", C.c_int, [vp, C.c_int32, C.POINTER(QPCot), C.POINTER(QPGrad), C.c_int32,
                                                      vp])
 _sig("madipm_solver_sens_batch_info", C.c_int, [vp, i64p, i64p, i64p])
+_sig("madipm_solver_set_multi_solve", C.c_int, [vp, C.c_int32])
+_sig("madipm_solver_multi_solve_info", C.c_int, [vp, C.POINTER(LDLMultiInfo)])
 
 
 class MadIPMError(RuntimeError):

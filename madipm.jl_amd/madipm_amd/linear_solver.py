@@ -72,6 +72,26 @@ class HIPLDLSolver:
                 "madipm_ldl_solve")
         return x
 
+    def solve_multi(self, X, stream=None):
+        """k right-hand sides in one pass over the factor per chunk of multi_info()["width"] columns (DESIGN
+        §13j): in place on a contiguous float64 GPU tensor of shape (k, n), row j one right-hand side.  Row j's
+        bits depend neither on k nor on j's position; they are not solve()'s (another summation order).  On a
+        sharded factorisation or one with batched-leaf groups it is the loop of solve().  TypeError for anything
+        but a float64 GPU tensor, ValueError for a non-contiguous tensor, another shape or k = 0, all before
+        any library call."""
+        k, n = check_multi_rhs(X, self.n)
+        L.check(L.lib.madipm_ldl_solve_multi(self.h, C.c_void_p(X.data_ptr()), k, C.c_void_p(_stream(stream))),
+                "madipm_ldl_solve_multi")
+        return X
+
+    def multi_info(self) -> dict:
+        """width: the columns of one chunk; native: 1 when solve_multi runs the multi-column route (0: the loop
+        of single solves); n_calls, n_chunks (ceil(k / width) per call), n_columns so far; n_big_fronts: the
+        fronts a chunk still solves column by column."""
+        inf = L.LDLMultiInfo()
+        L.check(L.lib.madipm_ldl_multi_info(self.h, C.byref(inf)), "madipm_ldl_multi_info")
+        return inf.as_dict()
+
     def is_inertia(self) -> bool:
         return True
 
@@ -133,6 +153,26 @@ class HIPLDLSolver:
         if h:
             L.lib.madipm_ldl_destroy(h)
             self.h = None
+
+
+def check_multi_rhs(X, n: int, who: str = "solve_multi") -> tuple:
+    """The argument check of HIPLDLSolver.solve_multi, before any library call, in the style of
+    solver.check_device_array: X must be a torch tensor on the GPU, float64, contiguous, of shape (k, n) with
+    k >= 1.  Returns (k, n)."""
+    import torch
+    if not isinstance(X, torch.Tensor):
+        raise TypeError(f"{who}: X must be a torch tensor on the GPU, not {type(X).__name__}")
+    if X.dtype != torch.float64:
+        raise TypeError(f"{who}: X has dtype {X.dtype}, expected torch.float64")
+    if not X.is_contiguous():
+        raise ValueError(f"{who}: X is not contiguous")
+    if X.device.type != "cuda":
+        raise TypeError(f"{who}: X is on {X.device}, expected a GPU tensor")
+    if X.dim() != 2 or X.shape[1] != int(n):
+        raise ValueError(f"{who}: X has shape {tuple(X.shape)}, expected (k, {int(n)})")
+    if X.shape[0] < 1:
+        raise ValueError(f"{who}: X holds no right-hand side (k = 0)")
+    return int(X.shape[0]), int(n)
 
 
 def local_allreduce(ptrs, n, stream=None):

@@ -1190,6 +1190,21 @@ class MPCSolver:
                 "sens_batch_info")
         return {"n_batches": int(nb.value), "n_columns": int(nc.value), "n_chunks": int(nk.value)}
 
+    def set_multi_solve(self, on: bool = True):
+        """on: tangent_batch / adjoint_batch (and jacobian, QPLayer.jacobian) at the interior point solve every
+        chunk of columns with the multi-right-hand-side LDL^T solve, a chunk of one column too.
+        A row's bits then do not depend on k; they agree with the single calls' within the formulas' tolerance,
+        not bit for bit.  Default off: every bit as before.  tangent() / adjoint() and polished=True calls are
+        unchanged either way."""
+        L.check(L.lib.madipm_solver_set_multi_solve(self.h, int(bool(on))), "set_multi_solve")
+
+    def multi_solve_info(self) -> dict:
+        """HIPLDLSolver.multi_info() of the solver's linear solver: native is 0 where the switch falls back to
+        the loop of single solves (sharded, batched-leaf groups)."""
+        inf = L.LDLMultiInfo()
+        L.check(L.lib.madipm_solver_multi_solve_info(self.h, C.byref(inf)), "multi_solve_info")
+        return inf.as_dict()
+
     def tangent_batch(self, want=None, *, polished=False, c=None, Hvals=None, Avals=None, lcon=None, ucon=None,
                       lvar=None, uvar=None) -> dict:
         """k tangent() calls on one point in one library call: every direction block has shape (k, len) (row j

@@ -5,7 +5,8 @@
 // triangular CSC pattern, then ordering relax small_front_max nshards shard.  The MADIPM_* environment
 // applies as in the solver.  Exit status 1 with a message on the first violated invariant; otherwise
 // one line per LaunchPlan array: "<class> <name> <count> <FNV-1a 64>" (classes: front, tree, solve,
-// launch; the model sums as raw bits).
+// launch; the model sums as raw bits), then "info" lines: the fronts of the multi-right-hand-side levels (mlev) by
+// level and class, and their class totals.
 #include <algorithm>
 #include <climits>
 #include <cstdint>
@@ -15,6 +16,7 @@
 #include <exception>
 #include <fstream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../madipm.jl_amd/csrc/ldl_plan.hpp"
@@ -171,6 +173,109 @@ void check_plan(const SymbolicPlan& S, const LaunchPlan& P) {
       CHECK(P.chunk_ids[k] >= S.chunk_lev[g] && P.chunk_ids[k] < S.chunk_lev[g + 1], at("chunk id outside its group, group", g));
 }
 
+// ---- multi-right-hand-side levels: every front of the plan exactly once over all levels and classes, its
+// children at strictly lower levels, and a level's gather / below / task lists cover exactly its big fronts
+void check_mlev(const SymbolicPlan& S, const LaunchPlan& P) {
+  const int ns = S.nsuper;
+  const int64_t nsched = (int64_t)P.sched.size(), ntask = (int64_t)P.tasks.size() / 2;
+  if (S.nshards > 1) {
+    CHECK(P.mlev.empty(), "mlev on a sharded plan");
+    return;
+  }
+  CHECK((int)P.mlev.size() == S.nlevels, "mlev levels");
+  std::vector<int> at_level(std::max(ns, 1), -1);
+  for (int lev = 0; lev < (int)P.mlev.size(); ++lev) {
+    const SolveLevel& L = P.mlev[lev];
+    const int64_t off[4] = {L.micro_off, L.tiny_off, L.small_off, L.big_off};
+    const int cnt[4] = {L.nmicro, L.ntiny, L.nsmall, L.nbig};
+    std::vector<int32_t> big;
+    for (int c = 0; c < 4; ++c) {
+      CHECK(off[c] >= 0 && off[c] + cnt[c] <= nsched, at("mlev list outside sched, level", lev));
+      for (int k = 0; k < cnt[c]; ++k) {
+        const int s = P.sched[off[c] + k];
+        CHECK(s >= 0 && s < ns, at("mlev front id, level", lev));
+        CHECK(at_level[s] < 0, at("front twice in mlev, front", s));
+        at_level[s] = lev;
+        const int r = S.nrows[s], w = S.first[s + 1] - S.first[s];
+        const int cls = (r <= 32 && w <= 2) ? 0 : !solve_small(S, s) ? 3 : r <= 32 ? 1 : solve_small_multi(S, s) ? 2 : 3;
+        CHECK(cls == c, at("mlev class of front", s));
+        if (c == 2) CHECK(8 * (r | 1) * w <= L.small_lds && L.small_lds + 8 * MULTI_W * SMALL_SOLVE_MAX <= kWorkgroupLds,
+                          at("mlev small front beyond the level's LDS, front", s));
+        if (c == 3) big.push_back(s);
+      }
+    }
+    // gather pairs: (front, chunk) for every chunk of GAT_ROWS rows of every big front, and of no other
+    CHECK(L.gat_off % 2 == 0 && L.gat_off + 2 * (int64_t)L.ngat <= nsched, at("mlev gather pairs, level", lev));
+    CHECK(L.below_off % 2 == 0 && L.below_off + 2 * (int64_t)L.nbelow <= nsched, at("mlev below pairs, level", lev));
+    CHECK(L.ftask_off + L.nftask <= ntask && L.btask_off + L.nbtask <= ntask, at("mlev tasks, level", lev));
+    auto pairs = [](std::vector<std::pair<int, int>>& v) { std::sort(v.begin(), v.end()); };
+    std::vector<std::pair<int, int>> wg, gg, wb, gb, wf, gf, wt, gt;
+    for (int s : big) {
+      const int r = S.nrows[s], w = S.first[s + 1] - S.first[s];
+      for (int c = 0; c < cdiv(r, GAT_ROWS); ++c) wg.push_back({s, c});
+      const int np = (int)cdiv(w, 64), nch = (int)cdiv(r - w, BWD_CHUNK);
+      for (int p = 0; p < np; ++p)
+        for (int c = 0; c < nch; ++c) wb.push_back({s, p | (c << 16)});
+      for (int i = 0; i < cdiv(r, 64); ++i) wf.push_back({s, i});
+      for (int p = 0; p < np; ++p) wt.push_back({s, p});
+      CHECK(P.flag_off[s] >= 0 && P.flag_off[s] + np <= P.nflags, at("mlev big front's flags, front", s));
+      CHECK(r == w || (P.bp_off[s] >= 0 && P.bp_off[s] + (int64_t)np * nch <= P.nbpart), at("mlev big front's bp_off, front", s));
+    }
+    for (int k = 0; k < L.ngat; ++k) gg.push_back({P.sched[L.gat_off + 2 * k], P.sched[L.gat_off + 2 * k + 1]});
+    for (int k = 0; k < L.nbelow; ++k) gb.push_back({P.sched[L.below_off + 2 * k], P.sched[L.below_off + 2 * k + 1]});
+    for (int k = 0; k < L.nftask; ++k) gf.push_back({P.tasks[2 * (L.ftask_off + k)], P.tasks[2 * (L.ftask_off + k) + 1]});
+    for (int k = 0; k < L.nbtask; ++k) gt.push_back({P.tasks[2 * (L.btask_off + k)], P.tasks[2 * (L.btask_off + k) + 1]});
+    // queue order: a front's forward blocks ascend and its backward panels descend (a task only waits for
+    // tasks dequeued before it)
+    for (size_t a = 0; a < gf.size(); ++a)
+      for (size_t b = a + 1; b < gf.size(); ++b)
+        if (gf[a].first == gf[b].first) {
+          CHECK(gf[a].second < gf[b].second, at("mlev forward tasks of a front out of order, level", lev));
+          break;
+        }
+    for (size_t a = 0; a < gt.size(); ++a)
+      for (size_t b = a + 1; b < gt.size(); ++b)
+        if (gt[a].first == gt[b].first) {
+          CHECK(gt[a].second > gt[b].second, at("mlev backward tasks of a front out of order, level", lev));
+          break;
+        }
+    pairs(wg), pairs(gg), pairs(wb), pairs(gb), pairs(wf), pairs(gf), pairs(wt), pairs(gt);
+    CHECK(wg == gg, at("mlev gather list does not cover exactly the big fronts, level", lev));
+    CHECK(wb == gb, at("mlev below list does not cover exactly the big fronts, level", lev));
+    CHECK(wf == gf, at("mlev forward tasks do not cover exactly the big fronts, level", lev));
+    CHECK(wt == gt, at("mlev backward tasks do not cover exactly the big fronts, level", lev));
+  }
+  for (int s = 0; s < ns; ++s) {
+    const bool want = in_phase(S, s, 1);
+    CHECK((at_level[s] >= 0) == want, at("front missing from (or wrongly in) mlev, front", s));
+    if (!want) continue;
+    for (int q = S.child_ptr[s]; q < S.child_ptr[s + 1]; ++q) {
+      const int c = S.child_list[q];
+      CHECK(!in_phase(S, c, 1) || at_level[c] < at_level[s], at("mlev child not at a lower level, front", s));
+    }
+  }
+}
+
+// the fronts of mlev, level by level and class by class ("info" lines: not digests)
+void print_mlev(const SymbolicPlan& S, const LaunchPlan& P) {
+  static const char* const cname[4] = {"micro", "tiny", "small", "big"};
+  int64_t tot[4] = {0, 0, 0, 0};
+  for (int lev = 0; lev < (int)P.mlev.size(); ++lev) {
+    const SolveLevel& L = P.mlev[lev];
+    const int64_t off[4] = {L.micro_off, L.tiny_off, L.small_off, L.big_off};
+    const int cnt[4] = {L.nmicro, L.ntiny, L.nsmall, L.nbig};
+    for (int c = 0; c < 4; ++c) {
+      if (!cnt[c]) continue;
+      tot[c] += cnt[c];
+      printf("info mlev_fronts %d %s", lev, cname[c]);
+      for (int k = 0; k < cnt[c]; ++k) printf(" %d", P.sched[off[c] + k]);
+      printf("\n");
+    }
+  }
+  printf("info mlev_classes levels %zu fronts %d micro %lld tiny %lld small %lld big %lld\n", P.mlev.size(), S.nsuper,
+         (long long)tot[0], (long long)tot[1], (long long)tot[2], (long long)tot[3]);
+}
+
 void print_digests(const LaunchPlan& P) {
   dump("front", "u_ld", P.u_ld), dump("front", "fs_img", P.fs_img), dump("front", "g_src32", P.g_src32);
   dump("front", "brec", P.brec), dump("front", "atiles", P.atiles), dump("front", "g_ptr", P.g_ptr);
@@ -200,6 +305,7 @@ void print_digests(const LaunchPlan& P) {
   dump("solve", "scalars", Fnv() << P.nflags << P.nbpart);
   dump("launch", "fact1", hash_launches(P.fact1), P.fact1.size()), dump("launch", "fact2", hash_launches(P.fact2), P.fact2.size());
   dump("launch", "slev1", hash_levels(P.slev1), P.slev1.size()), dump("launch", "slev2", hash_levels(P.slev2), P.slev2.size());
+  dump("launch", "mlev", hash_levels(P.mlev), P.mlev.size());
   dump("launch", "sched", P.sched), dump("launch", "dag_tasks", P.dag_tasks), dump("launch", "dag_dptr", P.dag_dptr);
   dump("launch", "dag_dlist", P.dag_dlist), dump("launch", "mslot", P.mslot), dump("launch", "tside", P.tside);
   dump("launch", "scalars", Fnv() << P.nmslot << P.upd_np << P.upd_nt << P.xg_off << P.nxg << (int)P.tail_ok << (int)P.asm_side
@@ -231,7 +337,9 @@ int main(int argc, char** argv) {
     LaunchPlan P;
     build_launch_plan(S, read_ldl_knobs(), P);
     check_plan(S, P);
+    check_mlev(S, P);
     print_digests(P);
+    print_mlev(S, P);
   } catch (const std::exception& e) {
     fail(e.what());
   }

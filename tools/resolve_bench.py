@@ -72,7 +72,10 @@ tangent_device that factorises the point, one tangent_batch_device and one adjoi
 columns (all seven direction blocks / all five cotangents given, all outputs), each against K single tangent_device /
 adjoint_device calls of the same columns on the same point, stream synchronised, medians of 10:
 sens_batch_tangent_s / sens_loop_tangent_s, sens_batch_adjoint_s / sens_loop_adjoint_s, and sens_batch_same_bits (every
-row of the batches is the single call's).  The instance name random_qp:N is instances.random_qp with N variables, N / 4 rows and about 8 entries per row."""
+row of the batches is the single call's).  --multi-solve (with --sens-batch) times the two batched calls once more with
+MPCSolver.set_multi_solve on: sens_multi_tangent_s / sens_multi_adjoint_s beside the batched and looped
+columns, sens_multi_rel_diff (the rows' largest difference to the switch off, relative to max(1, max |block|)), the
+spread (max - min) of the ten looped samples and multi_solve_info().  The instance name random_qp:N is instances.random_qp with N variables, N / 4 rows and about 8 entries per row."""
 import dataclasses
 import json
 import os
@@ -116,7 +119,7 @@ def build_problem(name):
 
 
 def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polish=False, polished_sens=False,
-        active_set=False, sens_batch=None):
+        active_set=False, sens_batch=None, multi_solve=False):
     qp, desc = build_problem(name)
     opts = bench.solver_opts()
     MPCSolver(qp, **opts)                      # the first construction of a process pays one-off set-up
@@ -451,6 +454,8 @@ def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polis
         draw = lambda sz: {k: torch.as_tensor(drng.standard_normal((K, n)), device="cuda") for k, n in sz.items()}  # noqa: E731
         sync = lambda: torch.cuda.current_stream().synchronize()  # noqa: E731
         bt, lt, ba, la, same, bstat = [], [], [], [], True, set()
+        mt, ma, mrel = [], [], 0.0   # --multi-solve: the batched calls again with set_multi_solve on
+        rel = lambda a, b: float((a - b).abs().max() / max(1.0, float(b.abs().max()))) if b.numel() else 0.0  # noqa: E731
         for rep in range(WARMUP + REPS):
             s.update_device(**{k: torch.as_tensor(v, device="cuda") for k, v in perturb(qp, rng).items()})
             st_ = s.solve(fetch_solution=False).status
@@ -478,6 +483,21 @@ def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polis
             t_la = time.perf_counter() - t
             same = same and all(torch.equal(tb[k][j], ts[j][k]) for j in range(K) for k in tb) \
                 and all(torch.equal(gb[k][j], gs[j][k]) for j in range(K) for k in gb)
+            if multi_solve:
+                s.set_multi_solve(True)
+                t = time.perf_counter()
+                tm = s.tangent_batch_device(**d)
+                sync()
+                t_mt = time.perf_counter() - t
+                t = time.perf_counter()
+                gm = s.adjoint_batch_device(**cot)
+                sync()
+                t_ma = time.perf_counter() - t
+                s.set_multi_solve(False)
+                mrel = max([mrel] + [rel(tm[k], tb[k]) for k in tb] + [rel(gm[k], gb[k]) for k in gb])
+                if rep >= WARMUP:
+                    mt.append(t_mt)
+                    ma.append(t_ma)
             if rep >= WARMUP:
                 bt.append(t_bt)
                 lt.append(t_lt)
@@ -487,6 +507,11 @@ def run(name, warm=None, adjoint=False, adjoint_full=False, tangent=False, polis
         wres.update({"sens_batch_k": K, "sens_batch_cols": s.sens_batch_cols(), "sens_batch_tangent_s": med(bt),
                      "sens_loop_tangent_s": med(lt), "sens_batch_adjoint_s": med(ba), "sens_loop_adjoint_s": med(la),
                      "sens_batch_same_bits": bool(same), "sens_batch_status": sorted(bstat), **s.sens_batch_info()})
+        spread = lambda v: (max(v) - min(v)) if v else float("nan")  # noqa: E731
+        wres.update({"sens_loop_tangent_spread_s": spread(lt), "sens_loop_adjoint_spread_s": spread(la)})
+        if multi_solve:
+            wres.update({"sens_multi_tangent_s": med(mt), "sens_multi_adjoint_s": med(ma), "sens_multi_rel_diff": mrel,
+                         "sens_multi_info": s.multi_solve_info()})
         c = s.counters()
     update_s, solve_s = statistics.median(upd), statistics.median(sol)
     return {**wres, "instance": name, "description": desc, "nvar": qp.nvar, "ncon": qp.ncon, "nnzj": qp.nnzj, "nnzh": qp.nnzh,
@@ -540,13 +565,16 @@ def main():
         k = args.index("--sens-batch")
         sens_batch = int(args[k + 1])
         del args[k:k + 2]
+    multi_solve = "--multi-solve" in args
+    if multi_solve:
+        args.remove("--multi-solve")
     if "--rel" in args:
         global REL
         k = args.index("--rel")
         REL = float(args[k + 1])
         del args[k:k + 2]
     for name in args or ["ex10", "supportcase10"]:
-        r = run(name, warm, adjoint, adjoint_full, tangent, polish, polished_sens, active_set, sens_batch)
+        r = run(name, warm, adjoint, adjoint_full, tangent, polish, polished_sens, active_set, sens_batch, multi_solve)
         print(f"{name}: construct_s {r['construct_s']:.4f}  prepare_update_s {r['prepare_update_s']:.4f}  "
               f"update_s {r['update_s']:.5f}  solve_s {r['solve_s']:.4f}  ->  update + solve "
               f"{r['update_plus_solve_s']:.4f} s against construct + solve {r['construct_plus_solve_s']:.4f} s "
@@ -602,6 +630,15 @@ def main():
                   f"adjoint_batch_device {r['sens_batch_adjoint_s'] * 1e3:.3f} ms against {K} adjoint_device calls "
                   f"{r['sens_loop_adjoint_s'] * 1e3:.3f} ms (x{r['sens_loop_adjoint_s'] / r['sens_batch_adjoint_s']:.2f}); "
                   f"same bits {r['sens_batch_same_bits']}, status {r['sens_batch_status']}", flush=True)
+            if multi_solve:
+                mi = r["sens_multi_info"]
+                print(f"{name}: multi-solve on ({'native' if mi['native'] else 'the loop'}, {mi['n_big_fronts']} fronts per "
+                      f"column): tangent_batch_device {r['sens_multi_tangent_s'] * 1e3:.3f} ms "
+                      f"(x{r['sens_loop_tangent_s'] / r['sens_multi_tangent_s']:.2f} of the loop, whose samples spread "
+                      f"{r['sens_loop_tangent_spread_s'] * 1e3:.3f} ms); adjoint_batch_device "
+                      f"{r['sens_multi_adjoint_s'] * 1e3:.3f} ms (x{r['sens_loop_adjoint_s'] / r['sens_multi_adjoint_s']:.2f}, "
+                      f"spread {r['sens_loop_adjoint_spread_s'] * 1e3:.3f} ms); rows within "
+                      f"{r['sens_multi_rel_diff']:.1e} of the switch off", flush=True)
         out.append(r)
     print(json.dumps({"resolve_bench": out, "warmup": WARMUP, "reps": REPS, "rel_noise": REL}))
 
