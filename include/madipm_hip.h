@@ -820,8 +820,8 @@ struct madipm_ldl_multi_info {
   int64_t n_calls;      /* multi-solve calls so far */
   int64_t n_chunks;     /* ceil(nrhs / width) of every call */
   int64_t n_columns;
-  int64_t n_big_fronts; /* fronts the native route solves column by column inside a chunk (past 192 rows, or a
-                           panel beyond the small kernels' LDS): they gain nothing from the route */
+  int64_t n_big_fronts; /* fronts of the native route's big class (past 192 rows, or a panel beyond the small
+                           kernels' LDS): solved by the task-queue kernels, see madipm_ldl_multi_big_info */
 };
 int madipm_ldl_solve_multi(madipm_ldl_t ls, double* d_x, int32_t nrhs, madipm_stream_t stream);
 int madipm_ldl_multi_info(madipm_ldl_t ls, struct madipm_ldl_multi_info* info);
@@ -832,6 +832,25 @@ int madipm_ldl_multi_info(madipm_ldl_t ls, struct madipm_ldl_multi_info* info);
 int madipm_solver_set_multi_solve(madipm_solver_t s, int32_t on);
 /* The multi-solve counters of the solver's linear solver (those of madipm_ldl_multi_info). */
 int madipm_solver_multi_solve_info(madipm_solver_t s, struct madipm_ldl_multi_info* info);
+
+/* ------------------------------------------------------------------ multi-column big fronts  [ABI 0.2.15, additive]
+ * The native route's big fronts carry a chunk's columns through ONE pass per level and direction:
+ * their L entries are read once per chunk and the launches paid once, as for the other classes.  A column's
+ * arithmetic is that of the single-column big-front kernels, so the rows of madipm_ldl_solve_multi are bit for bit
+ * the same with the switch on or off; off (or MADIPM_MULTI_BIG=0 at creation) keeps the column-after-column
+ * passes as the reference.  Sharded solvers and plans with batched-leaf groups keep the loop of single solves
+ * (native = 0) and only record the switch.  (Three symbols and one struct; `struct madipm_ldl_multi_info` and
+ * everything above are unchanged; madipm_version() still returns 203.) */
+struct madipm_ldl_multi_big_info {
+  int32_t multi_big;     /* 1: big fronts carry a chunk's columns in one pass; 0: column after column */
+  int32_t n_big_levels;  /* levels of mlev that hold a big front */
+  int64_t n_big_passes;  /* (level, direction) big passes launched so far: 2 * n_big_levels per chunk
+                            with multi_big, times the chunk's columns without */
+  int64_t big_bytes;     /* device bytes of the multi hand-off, vwork and bpart buffers (0 before the first use) */
+};
+int madipm_ldl_set_multi_big(madipm_ldl_t ls, int32_t on);
+int madipm_ldl_multi_big_info(madipm_ldl_t ls, struct madipm_ldl_multi_big_info* info);
+int madipm_solver_multi_big_info(madipm_solver_t s, struct madipm_ldl_multi_big_info* info);
 
 #ifdef __cplusplus
 }

@@ -456,6 +456,29 @@ int madipm_ldl_multi_info(madipm_ldl_t ls, struct madipm_ldl_multi_info* info) {
   MADIPM_API_END
 }
 
+static void fill_multi_big_info(const MultiBigStat& m, struct madipm_ldl_multi_big_info* info) {
+  info->multi_big = m.multi_big;
+  info->n_big_levels = m.n_big_levels;
+  info->n_big_passes = m.n_big_passes;
+  info->big_bytes = m.big_bytes;
+}
+
+int madipm_ldl_set_multi_big(madipm_ldl_t ls, int32_t on) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(ls, "null handle");
+  ls->lin->set_multi_big(on != 0);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_ldl_multi_big_info(madipm_ldl_t ls, struct madipm_ldl_multi_big_info* info) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(ls && info, "null argument");
+  fill_multi_big_info(ls->lin->multi_big_stat(), info);
+  return 0;
+  MADIPM_API_END
+}
+
 int madipm_ldl_inertia(madipm_ldl_t ls, int32_t* pos, int32_t* zero, int32_t* neg) {
   MADIPM_API_BEGIN
   MADIPM_REQUIRE(ls, "null handle");
@@ -1050,6 +1073,14 @@ int madipm_solver_multi_solve_info(madipm_solver_t s, struct madipm_ldl_multi_in
   MADIPM_API_BEGIN
   MADIPM_REQUIRE(s && info, "null argument");
   fill_multi_info(s->s->multi_solve_stat(), info);
+  return 0;
+  MADIPM_API_END
+}
+
+int madipm_solver_multi_big_info(madipm_solver_t s, struct madipm_ldl_multi_big_info* info) {
+  MADIPM_API_BEGIN
+  MADIPM_REQUIRE(s && info, "null argument");
+  fill_multi_big_info(s->s->multi_big_stat(), info);
   return 0;
   MADIPM_API_END
 }

@@ -155,7 +155,14 @@ struct MultiStat {
   int32_t width = ldlconst::MULTI_W;  // columns of one chunk
   int32_t native = 0;                 // 1: the level-scheduled multi-column route, 0: the loop of single solves
   int64_t n_calls = 0, n_chunks = 0, n_columns = 0;
-  int64_t n_big_fronts = 0;  // fronts the native route solves column by column (task-queue kernels)
+  int64_t n_big_fronts = 0;  // fronts of the native route's big class (task-queue kernels)
+};
+// How the native route solves its big fronts (madipm_ldl_multi_big_info).
+struct MultiBigStat {
+  int32_t multi_big = 1;     // 1: a chunk's columns in one pass per level and direction, 0: column after column
+  int32_t n_big_levels = 0;  // levels of the native route that hold a big front
+  int64_t n_big_passes = 0;  // (level, direction) big passes launched so far
+  int64_t big_bytes = 0;     // device bytes of the multi hand-off, vwork and bpart buffers (0 before the first use)
 };
 
 // Linear-solver interface the MPC driver uses (MadNLP.AbstractLinearSolver methods).
@@ -184,6 +191,9 @@ class LinSolver {
     for (int j = 0; j < k; ++j) solve_async(b + (int64_t)j * n(), s);
   }
   const MultiStat& multi_stat() const { return mstat_; }
+  const MultiBigStat& multi_big_stat() const { return mbig_; }
+  // the switch of the big fronts' multi-column pass; solvers without the native route only record it
+  virtual void set_multi_big(bool on) { mbig_.multi_big = on ? 1 : 0; }
   virtual const SymbolicPlan& plan() const = 0;
   virtual void set_timing(unsigned mask) = 0;
   virtual void kernel_stats(KernelStat out[]) = 0;
@@ -213,6 +223,7 @@ class LinSolver {
 
  protected:
   MultiStat mstat_;
+  MultiBigStat mbig_;
 };
 
 class LDLSolver : public LinSolver {
@@ -232,6 +243,7 @@ class LDLSolver : public LinSolver {
   // In-place solve K x = b for a device vector of length n (caller's ordering).
   void solve_async(double* b, hipStream_t s) override;
   void solve_multi_async(double* b, int k, hipStream_t s) override;
+  void set_multi_big(bool on) override;
 
   // Phases of a sharded factorisation / solve, for callers that run their own collective
   // (ShardGroup below, or a host binding with its own RCCL communicator):
@@ -370,6 +382,10 @@ class LDLSolver : public LinSolver {
   // internal and the update vector, allocated by the first solve_multi_async
   std::vector<SolveLevel> mlev_;
   DBuf<double> xim_, uvm_;
+  // its big fronts' multi-column pass (§13k): MULTI_W columns of the hand-off words (epoch-tagged like xll_, its
+  // own buffer), of vwork_ and of bpart_, allocated by the first such pass
+  DBuf<uint64_t> xllm_;
+  DBuf<double> vwm_, bpm_;
   // tree solves (k_fwd_tree / k_bwd_tree): the phase-1 fronts solved by ONE dependency-driven launch
   // per direction (topological ticket order, forward dependencies = tree children, backward = tree
   // parent), between the level-0 launches and the remaining levels

@@ -30,6 +30,7 @@ LdlKnobs read_ldl_knobs() {
   K.upd_split = !off("MADIPM_UPD_SPLIT");
   K.big_dag = !off("MADIPM_BIG_DAG");
   if (const char* e = env("MADIPM_BIG_SOLVE_WG")) K.big_solve_wg = std::max(64, std::atoi(e));
+  K.multi_big = !off("MADIPM_MULTI_BIG");
   K.fact_pipe = off("MADIPM_FACT_PIPE") ? 0 : 1;
   K.pipe_fault = one("MADIPM_DEBUG_PIPE_FAULT") ? 1 : 0;
   if (const char* e = env("MADIPM_DEBUG_ASM_SRC_CAP")) K.asm_src_cap = std::atoi(e);

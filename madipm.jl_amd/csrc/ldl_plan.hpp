@@ -139,6 +139,7 @@ struct LdlKnobs {
   bool upd_split = true;    // UPD_SPLIT=0: one workgroup per k_big_upd128 tile (A/B)
   bool big_dag = true;      // BIG_DAG=0: one launch per panel step and kind (A/B)
   int big_solve_wg = 512;   // BIG_SOLVE_WG: persistent workgroups of the big-front solve kernels (>= 64)
+  bool multi_big = true;    // MULTI_BIG=0: the multi-RHS solve takes its big fronts column after column (A/B)
   int fact_pipe = 1;        // FACT_PIPE=0: the barrier schedule, bitwise the same factor
   int pipe_fault = 0;       // DEBUG_PIPE_FAULT=1, tests: drop one hand-off (sticky error)
   int asm_src_cap = ldlconst::kAsmLdsSrc * ldlconst::kAsmLdsWinMax;  // DEBUG_ASM_SRC_CAP=<n>, tests: a smaller bound

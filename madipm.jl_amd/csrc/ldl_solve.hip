@@ -1201,6 +1201,314 @@ __global__ __launch_bounds__(NT) void k_bwd_big(FrontTab T, const SolveTask* __r
   }
 }
 
+// ------------------------------------------------------------------ big fronts, multi-right-hand-side
+// The four big-front kernels above over the kc <= MW columns of a chunk: same task lists, same ticket order, same
+// grid.  Every L entry, row index and gather index is loaded once per task and used for all kc columns; column
+// j's operations and their order are those of the single-column kernel (kc is a uniform bound only), so a
+// column has the bits the single-column kernels give it.  Column j of the gathered vector is at vwork + j
+// vstride, of the below-row partials at bpart + j bstride; the hand-off words of (front, panel, column j) are
+// the 128 words at xllm + ((flag_off[front] + panel) MW + j) 128, a buffer of the multi route alone (T.xll and
+// its epochs belong to the single-column kernels).  Wave q polls / substitutes / writes columns q and q + 4.
+__global__ __launch_bounds__(NT) void k_fwd_gather_m(FrontTab T, const int32_t* __restrict__ list, int kc,
+                                                     const double* __restrict__ b, int64_t n,
+                                                     const double* __restrict__ uvec, int64_t ustride,
+                                                     double* __restrict__ vwork, int64_t vstride) {
+  int s, chunk;
+  task_of(list, s, chunk);
+  const int f0 = T.first[s], w = T.first[s + 1] - f0, r = T.nrows[s];
+  const int i = chunk * GAT_ROWS + threadIdx.x / GAT_G, gl = threadIdx.x & (GAT_G - 1);
+  if (i >= r) return;  // whole groups leave together
+  const int64_t e = T.row_ptr[s] + i;
+  const int64_t p1 = T.sv_ptr[e + 1];
+  const int64_t pi = T.perm[f0 + min(i, max(w - 1, 0))];
+  double vi[MW];
+#pragma unroll
+  for (int j = 0; j < MW; ++j) vi[j] = 0.0;
+  for (int64_t p = T.sv_ptr[e] + gl; p < p1; p += GAT_G) {
+    const int64_t src = T.sv_src[p];
+#pragma unroll
+    for (int j = 0; j < MW; ++j)
+      if (j < kc) vi[j] += uvec[j * ustride + src];
+  }
+#pragma unroll
+  for (int j = 0; j < MW; ++j) {
+    if (j >= kc) break;  // uniform
+    double v = vi[j];
+#pragma unroll
+    for (int o = GAT_G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, GAT_G);
+    if (gl == 0) vwork[j * vstride + e] = v + ((i < w) ? b[j * n + pi] : 0.0);
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_fwd_big_m(FrontTab T, const SolveTask* __restrict__ tasks, int ntasks, int kc,
+                                                  int32_t* counter, uint64_t* xllm, const int32_t* __restrict__ flag_off,
+                                                  int epoch, const double* __restrict__ arena,
+                                                  const double* __restrict__ vwork, int64_t vstride,
+                                                  double* __restrict__ xi, int64_t N, double* __restrict__ uvec,
+                                                  int64_t ustride, int32_t* err) {
+  __shared__ int s_task;
+  __shared__ double xs[MW][64];
+  __shared__ double part[MW][4][64];
+  __shared__ double Ld[64 * 65];
+  const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
+  for (;;) {
+    if (tid == 0) s_task = atomicAdd(counter, 1);
+    __syncthreads();
+    const int t = s_task;
+    __syncthreads();
+    if (t >= ntasks) return;
+    const int s = tasks[t].front, i = tasks[t].blk;
+    const int f0 = T.first[s], w = T.first[s + 1] - f0, r = T.nrows[s];
+    const double* __restrict__ L = arena + T.l_off[s];
+    const int row0 = i * 64, nrow = min(64, r - row0);
+    const int npan = (w + 63) >> 6;
+    const int np = min(i, npan);
+    const int row = row0 + lane;
+    const bool pivot_blk = row0 < w;
+    const int kw = pivot_blk ? min(64, w - row0) : 0;
+    const int rowc = row0 + min(lane, nrow - 1);  // (unconditional loads from clamped addresses, masked after)
+    if (kw > 0) {
+      double v[16];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) v[e] = L[rowc + (int64_t)(row0 + min(g + 4 * e, kw - 1)) * r];
+#pragma unroll
+      for (int e = 0; e < 16; ++e)
+        if (g + 4 * e < kw) Ld[(g + 4 * e) * 65 + lane] = (lane < nrow) ? v[e] : 0.0;
+    }
+    double acc[MW];
+#pragma unroll
+    for (int j = 0; j < MW; ++j) acc[j] = 0.0;
+    uint64_t* const xw = xllm + (int64_t)flag_off[s] * MW * 128 + 2 * lane;
+    double lv[16], ln[16];
+    auto load_panel = [&](double (&dst)[16], int p) {
+      const int cb = p * 64 + g * 16;
+#pragma unroll
+      for (int cc = 0; cc < 16; ++cc) dst[cc] = L[rowc + (int64_t)min(cb + cc, w - 1) * r];
+    };
+    if (np > 0) load_panel(lv, 0);
+    for (int p = 0; p < np; ++p) {
+      if (p + 1 < np) load_panel(ln, p + 1);  // wave-uniform
+      const int cb = p * 64 + g * 16;
+#pragma unroll
+      for (int cc = 0; cc < 16; ++cc) lv[cc] = (lane < nrow && cb + cc < w) ? lv[cc] : 0.0;
+      for (int j = g; j < kc; j += 4) {  // wave-uniform
+        const double xv = ll_get(xw + ((int64_t)p * MW + j) * 128, epoch, err);
+        xs[j][lane] = (p * 64 + lane < w) ? xv : 0.0;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < MW; ++j) {
+        if (j >= kc) break;  // uniform
+#pragma unroll
+        for (int cc = 0; cc < 16; ++cc) acc[j] += lv[cc] * xs[j][g * 16 + cc];
+      }
+#pragma unroll
+      for (int cc = 0; cc < 16; ++cc) lv[cc] = ln[cc];
+      __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < MW; ++j)
+      if (j < kc) part[j][g][lane] = acc[j];
+    __syncthreads();
+    const int64_t uo = T.uvec_off[s], e0 = T.row_ptr[s] + row0 + min(lane, nrow - 1);
+    for (int j = g; j < kc; j += 4) {  // wave-uniform
+      const double vj = vwork[j * vstride + e0];
+      double a = (lane < nrow) ? vj - ((part[j][0][lane] + part[j][1][lane]) + (part[j][2][lane] + part[j][3][lane])) : 0.0;
+      a = tri_fwd64(a, Ld, kw, lane);
+      if (pivot_blk) ll_put(xw + ((int64_t)i * MW + j) * 128, a, epoch);  // every lane: 0 past nrow
+      if (lane < nrow) {
+        if (row < w)
+          xi[j * N + f0 + row] = a;
+        else
+          uvec[j * ustride + uo + row - w] = a;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_bwd_below_m(FrontTab T, const int32_t* __restrict__ list, int kc,
+                                                    const int32_t* __restrict__ bp_off,
+                                                    const double* __restrict__ arena, const double* __restrict__ xi,
+                                                    int64_t N, double* __restrict__ bpart, int64_t bstride) {
+  __shared__ double tile[64 * 65];
+  __shared__ double xr[MW][64];
+  __shared__ double part[MW][4][64];
+  int s, pc;
+  task_of(list, s, pc);
+  const int p = pc & 0xffff, chunk = pc >> 16;
+  const int f0 = T.first[s], w = T.first[s + 1] - f0, r = T.nrows[s];
+  const double* __restrict__ L = arena + T.l_off[s];
+  const int32_t* __restrict__ rows = T.rows + T.row_ptr[s];
+  const int c0 = p * 64, kw = min(64, w - c0);
+  const int nch = (r - w + BWD_CHUNK - 1) / BWD_CHUNK;
+  const int R0 = w + chunk * BWD_CHUNK, R1 = min(r, R0 + BWD_CHUNK);
+  const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
+  const bool c1on = g + 4 < kc;  // wave g carries the x of columns g and g + 4 (kc >= 1: wave 0 always has one)
+  const int64_t o0 = (int64_t)min(g, kc - 1) * N, o1 = (int64_t)min(g + 4, kc - 1) * N;
+  double acc[MW];
+#pragma unroll
+  for (int j = 0; j < MW; ++j) acc[j] = 0.0;
+  double v[16], vn[16], xv[2] = {0.0, 0.0}, xvn[2] = {0.0, 0.0};
+  auto load_blk = [&](double (&dst)[16], double (&x)[2], int rb) {
+    const int nr = min(64, R1 - rb);
+    const int rc = rb + min(lane, nr - 1);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dst[e] = L[rc + (int64_t)(c0 + min(g + 4 * e, kw - 1)) * r];
+    const int64_t xrow = rows[rc];
+    x[0] = xi[o0 + xrow];
+    x[1] = xi[o1 + xrow];
+  };
+  if (R0 < R1) load_blk(v, xv, R0);
+  for (int rb = R0; rb < R1; rb += 64) {
+    const int nr = min(64, R1 - rb);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) tile[lane * 65 + g + 4 * e] = (lane < nr && g + 4 * e < kw) ? v[e] : 0.0;
+    if (g < kc) xr[g][lane] = (lane < nr) ? xv[0] : 0.0;
+    if (c1on) xr[g + 4][lane] = (lane < nr) ? xv[1] : 0.0;
+    __syncthreads();
+    if (rb + 64 < R1) load_blk(vn, xvn, rb + 64);  // block-uniform
+    double tv[16];
+#pragma unroll
+    for (int rr = 0; rr < 16; ++rr) tv[rr] = tile[(g * 16 + rr) * 65 + lane];
+#pragma unroll
+    for (int j = 0; j < MW; ++j) {
+      if (j >= kc) break;  // uniform
+#pragma unroll
+      for (int rr = 0; rr < 16; ++rr) acc[j] += tv[rr] * xr[j][g * 16 + rr];
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) v[e] = vn[e];
+    xv[0] = xvn[0];
+    xv[1] = xvn[1];
+    __syncthreads();
+  }
+#pragma unroll
+  for (int j = 0; j < MW; ++j)
+    if (j < kc) part[j][g][lane] = acc[j];
+  __syncthreads();
+  for (int j = g; j < kc; j += 4)  // wave-uniform
+    bpart[j * bstride + ((int64_t)bp_off[s] + (int64_t)p * nch + chunk) * 64 + lane] =
+        (part[j][0][lane] + part[j][1][lane]) + (part[j][2][lane] + part[j][3][lane]);
+  (void)f0;
+}
+
+// LDS of k_bwd_big_m (dynamic: past the 64 KiB of a static carve): the tile, the diagonal block, kc x 64 x values;
+// the per-column partials reuse the tile once its last products are done
+constexpr int BIGM_TILE = 64 * 65;
+constexpr int kBwdBigMultiLds = 8 * (2 * BIGM_TILE + MW * 64);
+static_assert(MW * 4 * 64 <= BIGM_TILE, "the partials fit the tile");
+static_assert(kBwdBigMultiLds <= kWorkgroupLds, "k_bwd_big_m's LDS");
+__global__ __launch_bounds__(NT) void k_bwd_big_m(FrontTab T, const SolveTask* __restrict__ tasks, int ntasks, int kc,
+                                                  int32_t* counter, uint64_t* xllm, const int32_t* __restrict__ flag_off,
+                                                  int epoch, const double* __restrict__ arena,
+                                                  const double* __restrict__ D, double* __restrict__ xi, int64_t N,
+                                                  double* __restrict__ out, int64_t n,
+                                                  const int32_t* __restrict__ bp_off, const double* __restrict__ bpart,
+                                                  int64_t bstride, int32_t* err) {
+  extern __shared__ __attribute__((aligned(16))) double bigm_lds[];
+  __shared__ int s_task;
+  double* const tile = bigm_lds;
+  double* const Ld = tile + BIGM_TILE;
+  double(*const xr)[64] = reinterpret_cast<double(*)[64]>(Ld + BIGM_TILE);
+  double(*const part)[4][64] = reinterpret_cast<double(*)[4][64]>(tile);
+  const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
+  for (;;) {
+    if (tid == 0) s_task = atomicAdd(counter, 1);
+    __syncthreads();
+    const int t = s_task;
+    __syncthreads();
+    if (t >= ntasks) return;
+    const int s = tasks[t].front, p = tasks[t].blk;
+    const int f0 = T.first[s], w = T.first[s + 1] - f0, r = T.nrows[s];
+    const double* __restrict__ L = arena + T.l_off[s];
+    const int c0 = p * 64, kw = min(64, w - c0);
+    const int npan = (w + 63) >> 6;
+    {
+      double v[16];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) v[e] = L[(c0 + min(lane, kw - 1)) + (int64_t)(c0 + min(g + 4 * e, kw - 1)) * r];
+#pragma unroll
+      for (int e = 0; e < 16; ++e)
+        if (g + 4 * e < kw) Ld[lane * 65 + g + 4 * e] = (lane < kw) ? v[e] : 0.0;
+    }
+    double acc[MW];
+#pragma unroll
+    for (int j = 0; j < MW; ++j) acc[j] = 0.0;
+    uint64_t* const xw = xllm + (int64_t)flag_off[s] * MW * 128 + 2 * lane;
+    const int nq = npan - 1 - p;
+    double v[16], vn[16];
+    auto load_tile = [&](double (&dst)[16], int q) {
+      const int rb = q * 64, nr = min(64, w - rb);
+      const int rc = rb + min(lane, nr - 1);
+#pragma unroll
+      for (int e = 0; e < 16; ++e) dst[e] = L[rc + (int64_t)(c0 + min(g + 4 * e, kw - 1)) * r];
+    };
+    if (nq > 0) load_tile(v, npan - 1);
+    for (int k = 0; k < nq; ++k) {
+      const int q = npan - 1 - k;
+      const int rb = q * 64, nr = min(64, w - rb);
+#pragma unroll
+      for (int e = 0; e < 16; ++e)
+        if (g + 4 * e < kw) tile[lane * 65 + g + 4 * e] = (lane < nr) ? v[e] : 0.0;
+      for (int j = g; j < kc; j += 4) {  // wave-uniform
+        const double xv = ll_get(xw + ((int64_t)q * MW + j) * 128, epoch, err);
+        xr[j][lane] = (lane < nr) ? xv : 0.0;
+      }
+      __syncthreads();
+      if (k + 1 < nq) load_tile(vn, q - 1);  // block-uniform
+      double tv[16];
+#pragma unroll
+      for (int rr = 0; rr < 16; ++rr) tv[rr] = tile[(g * 16 + rr) * 65 + lane];
+#pragma unroll
+      for (int j = 0; j < MW; ++j) {
+        if (j >= kc) break;  // uniform
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) acc[j] += tv[rr] * xr[j][g * 16 + rr];
+      }
+#pragma unroll
+      for (int e = 0; e < 16; ++e) v[e] = vn[e];
+      __syncthreads();
+    }
+    // wave q finishes columns q and q + 4: their below-row partials (k_bwd_below_m's chunks in chunk order) are
+    // loaded before the barrier and added to wave 0's partial, as k_bwd_big adds them to wave 0's acc
+    double below[2] = {0.0, 0.0};
+    if (r > w) {
+      const int nch = (r - w + BWD_CHUNK - 1) / BWD_CHUNK;
+      const double* __restrict__ bp = bpart + ((int64_t)bp_off[s] + (int64_t)p * nch) * 64 + lane;
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        if (g + 4 * h < kc)
+          for (int c = 0; c < nch; ++c) below[h] += bp[(g + 4 * h) * bstride + c * 64];
+    }
+#pragma unroll
+    for (int j = 0; j < MW; ++j)
+      if (j < kc) part[j][g][lane] = acc[j];
+    __syncthreads();
+    const int c = f0 + c0 + min(lane, kw - 1);
+    const double dc = D[c];
+    const int64_t pc = T.perm[c];
+    const bool wo = T.wout[s];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int j = g + 4 * h;
+      if (j >= kc) break;  // wave-uniform
+      double a = 0.0;
+      if (lane < kw) {
+        const double p0 = (r > w) ? part[j][0][lane] + below[h] : part[j][0][lane];
+        a = xi[j * N + c] / dc - ((p0 + part[j][1][lane]) + (part[j][2][lane] + part[j][3][lane]));
+      }
+      a = tri_bwd64(a, Ld, kw, lane);
+      ll_put(xw + ((int64_t)p * MW + j) * 128, a, epoch);  // every lane (masked by the readers)
+      if (lane < kw) {
+        xi[j * N + c] = a;
+        if (wo) out[j * n + pc] = a;
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // ------------------------------------------------------------------ tree solves (dependency-driven)
 // ONE launch per direction covers every "tree" front (LDLSolver ctor: phase-1 fronts whose L panel
 // fits LDS and whose children are leaves of <= 32 rows — done by the level-0 launches — or tree
@@ -2091,6 +2399,7 @@ void ldl_solve_kernel_attributes() {
   set_max_dyn_lds((const void*)k_bwd_small, kSolveSmallLds);
   set_max_dyn_lds((const void*)k_fwd_small_m, kSolveSmallMultiLds);
   set_max_dyn_lds((const void*)k_bwd_small_m, kSolveSmallMultiLds);
+  set_max_dyn_lds((const void*)k_bwd_big_m, kBwdBigMultiLds);
   set_max_dyn_lds((const void*)k_fwd_tree, TREE_SOLVE_LDS);
   set_max_dyn_lds((const void*)k_bwd_tree, TREE_SOLVE_LDS);
   set_max_dyn_lds((const void*)k_root_solve, TREE_ROOT_LDS);
@@ -2281,8 +2590,13 @@ void LDLSolver::solve_async(double* b, hipStream_t s) {
 // k columns in place, column j at b + j n.  Native route (unsharded, no batched-leaf groups): chunks of kc <= MW
 // columns, each forward over mlev_ level by level and backward in reverse, one multi-column launch per non-empty
 // class of a level, ordered by the stream: no kernel of it waits on another workgroup of a different launch.  A
-// level's big fronts go through the single-column task-queue kernels, column after column inside the level, each
-// pass with its own epoch and zeroed counters.  Otherwise: the loop of solve_async.
+// level's big fronts go through the multi-column task-queue kernels (§13k: one zeroing of the level's two
+// counters and one pass per direction for the chunk, hand-off words tagged with the chunk's epoch in a buffer
+// of their own), or with set_multi_big(false) / MADIPM_MULTI_BIG=0 through the single-column ones, column after
+// column inside the level, each pass with its own epoch and zeroed counters: bit for bit the same columns.
+// Otherwise: the loop of solve_async.
+void LDLSolver::set_multi_big(bool on) { mbig_.multi_big = on ? 1 : 0; }
+
 void LDLSolver::solve_multi_async(double* b, int k, hipStream_t s) {
   if (k <= 0) return;
   ++mstat_.n_calls;
@@ -2298,6 +2612,15 @@ void LDLSolver::solve_multi_async(double* b, int k, hipStream_t s) {
     xim_.alloc(MW * N);
     uvm_.alloc(MW * us);
   }
+  const bool mbig = mbig_.multi_big && mbig_.n_big_levels > 0;
+  if (mbig && !xllm_.p) {  // the first multi-column big pass: MW columns of the hand-off words, vwork and bpart
+    xllm_.alloc(MW * xll_.n);
+    xllm_.zero(s);  // no epoch is 0
+    vwm_.alloc(MW * vwork_.n);
+    bpm_.alloc(MW * bpart_.n);
+    mbig_.big_bytes = (int64_t)(xllm_.n * sizeof(uint64_t) + (vwm_.n + bpm_.n) * sizeof(double));
+  }
+  const int64_t vs = (int64_t)vwork_.n, bs = (int64_t)bpart_.n;
   const SolveTask* tasks = reinterpret_cast<const SolveTask*>(tasks_.p);
   const int NL = (int)mlev_.size();
   for (int c0 = 0; c0 < k; c0 += MW) {
@@ -2319,7 +2642,18 @@ void LDLSolver::solve_multi_async(double* b, int k, hipStream_t s) {
         TIMED(KK_FWD_SMALL, L.small_bytes, L.small_alg, L.small_flops,
               (k_fwd_small_m<<<(unsigned)L.nsmall, NT, L.small_lds, s>>>(T_, sched_.p + L.small_off, L.nsmall, kc, arena_, bc,
                                                                         N, xim_, N, uvm_, us)));
-      for (int j = 0; L.nbig && j < kc; ++j) {
+      if (L.nbig && mbig) {
+        ++mbig_.n_big_passes;
+        MADIPM_HIP(hipMemsetAsync(counters_.p + 2 * lev, 0, 2 * sizeof(int32_t), s));
+        TIMED(KK_FWD_GATHER, L.gat_bytes, 0.0, 0.0,
+              (k_fwd_gather_m<<<L.ngat, NT, 0, s>>>(T_, sched_.p + L.gat_off, kc, bc, N, uvm_, us, vwm_, vs)));
+        TIMED(KK_FWD_BIG, L.big_bytes, L.big_alg + L.below_alg, L.big_flops,
+              (k_fwd_big_m<<<std::min(L.nftask, knobs_.big_solve_wg), NT, 0, s>>>(
+                  T_, tasks + L.ftask_off, L.nftask, kc, counters_.p + 2 * lev, xllm_, flag_off_, 2 * (e0 + 1) - 1, arena_,
+                  vwm_, vs, xim_, N, uvm_, us, &st_->err)));
+      }
+      for (int j = 0; L.nbig && !mbig && j < kc; ++j) {
+        ++mbig_.n_big_passes;
         MADIPM_HIP(hipMemsetAsync(counters_.p + 2 * lev, 0, 2 * sizeof(int32_t), s));
         TIMED(KK_FWD_GATHER, L.gat_bytes, 0.0, 0.0,
               (k_fwd_gather<<<L.ngat, NT, 0, s>>>(T_, sched_.p + L.gat_off, bc + j * N, uvm_.p + j * us, vwork_)));
@@ -2331,7 +2665,19 @@ void LDLSolver::solve_multi_async(double* b, int k, hipStream_t s) {
     }
     for (int lev = NL - 1; lev >= 0; --lev) {
       const SolveLevel& L = mlev_[lev];
-      for (int j = 0; L.nbig && j < kc; ++j) {
+      if (L.nbig && mbig) {
+        ++mbig_.n_big_passes;
+        MADIPM_HIP(hipMemsetAsync(counters_.p + 2 * lev, 0, 2 * sizeof(int32_t), s));
+        if (L.nbelow)
+          TIMED(KK_BWD_BELOW, L.below_bytes, L.below_alg, 0.25 * L.below_bytes,
+                (k_bwd_below_m<<<L.nbelow, NT, 0, s>>>(T_, sched_.p + L.below_off, kc, bp_off_, arena_, xim_, N, bpm_, bs)));
+        TIMED(KK_BWD_BIG, L.big_bytes - L.below_bytes, L.big_alg, L.big_flops - 0.25 * L.below_bytes,
+              (k_bwd_big_m<<<std::min(L.nbtask, knobs_.big_solve_wg), NT, kBwdBigMultiLds, s>>>(
+                  T_, tasks + L.btask_off, L.nbtask, kc, counters_.p + 2 * lev + 1, xllm_, flag_off_, 2 * (e0 + 1), arena_, D_,
+                  xim_, N, bc, N, bp_off_, bpm_, bs, &st_->err)));
+      }
+      for (int j = 0; L.nbig && !mbig && j < kc; ++j) {
+        ++mbig_.n_big_passes;
         MADIPM_HIP(hipMemsetAsync(counters_.p + 2 * lev, 0, 2 * sizeof(int32_t), s));
         if (L.nbelow)
           TIMED(KK_BWD_BELOW, L.below_bytes, L.below_alg, 0.25 * L.below_bytes,

@@ -212,6 +212,8 @@ LDLSolver::LDLSolver(int n, const int64_t* colptr, const int32_t* rowval, const 
   mlev_ = std::move(P.mlev);
   mstat_.native = S.nshards == 1 && S.lb.empty() && !mlev_.empty();
   for (const SolveLevel& L : mlev_) mstat_.n_big_fronts += mstat_.native ? L.nbig : 0;
+  for (const SolveLevel& L : mlev_) mbig_.n_big_levels += mstat_.native && L.nbig > 0;
+  mbig_.multi_big = knobs_.multi_big ? 1 : 0;
   xg_off_ = P.xg_off;
   nxg_ = P.nxg;
   ntree_ = P.ntree;

@@ -141,6 +141,7 @@ class MPCSolver {
   // a row's bits then do not depend on k, and differ from the single calls' within the formulas' tolerance
   void set_multi_solve(bool on) { multi_solve_ = on; }
   const MultiStat& multi_solve_stat() const { return ldl_->multi_stat(); }
+  const MultiBigStat& multi_big_stat() const { return ldl_->multi_big_stat(); }
   int64_t n_analyses() const { return n_analyses_; }
   int64_t n_updates() const { return n_updates_; }
   double last_update_s() const { return last_update_s_; }

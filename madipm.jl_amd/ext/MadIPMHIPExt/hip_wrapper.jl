@@ -751,3 +751,37 @@ function solver_multi_solve_info(h::Ptr{Cvoid})
           "madipm_solver_multi_solve_info")
     return info[]
 end
+
+# ---- multi-column big fronts of the multi-right-hand-side solve (ABI 0.2.15, DESIGN §13k); unexercised here
+# like the four entries above, whose Python mirror (HIPLDLSolver.set_multi_big / multi_info,
+# MPCSolver.multi_solve_info) is the tested one.
+# struct madipm_ldl_multi_big_info
+struct MadipmLDLMultiBigInfo
+    multi_big::Int32
+    n_big_levels::Int32
+    n_big_passes::Int64
+    big_bytes::Int64
+end
+MadipmLDLMultiBigInfo() = MadipmLDLMultiBigInfo(0, 0, 0, 0)
+
+# on (the default): the big fronts carry a chunk's columns in one pass per level and direction; off: column after
+# column with the single-column kernels.  The rows of ldl_solve_multi are bit for bit the same either way.
+function ldl_set_multi_big(h::Ptr{Cvoid}, on::Bool=true)
+    check(ccall((:madipm_ldl_set_multi_big, libmadipm), Cint, (Ptr{Cvoid}, Int32), h, on ? 1 : 0),
+          "madipm_ldl_set_multi_big")
+    return
+end
+
+function ldl_multi_big_info(h::Ptr{Cvoid})
+    info = Ref(MadipmLDLMultiBigInfo())
+    check(ccall((:madipm_ldl_multi_big_info, libmadipm), Cint, (Ptr{Cvoid}, Ref{MadipmLDLMultiBigInfo}), h, info),
+          "madipm_ldl_multi_big_info")
+    return info[]
+end
+
+function solver_multi_big_info(h::Ptr{Cvoid})
+    info = Ref(MadipmLDLMultiBigInfo())
+    check(ccall((:madipm_solver_multi_big_info, libmadipm), Cint, (Ptr{Cvoid}, Ref{MadipmLDLMultiBigInfo}), h, info),
+          "madipm_solver_multi_big_info")
+    return info[]
+end

@@ -55,6 +55,14 @@ class LDLMultiInfo(C.Structure):   # madipm_ldl_multi_info
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class LDLMultiBigInfo(C.Structure):   # madipm_ldl_multi_big_info
+    _fields_ = [("multi_big", C.c_int32), ("n_big_levels", C.c_int32), ("n_big_passes", C.c_int64),
+                ("big_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 NKERNELS = 24  # MADIPM_NKERNELS
 
 
@@ -97,6 +105,8 @@ _sig("madipm_ldl_is_factorized", C.c_int, [vp])
 _sig("madipm_ldl_solve", C.c_int, [vp, vp, C.c_int32, vp])
 _sig("madipm_ldl_solve_multi", C.c_int, [vp, vp, C.c_int32, vp])
 _sig("madipm_ldl_multi_info", C.c_int, [vp, C.POINTER(LDLMultiInfo)])
+_sig("madipm_ldl_set_multi_big", C.c_int, [vp, C.c_int32])
+_sig("madipm_ldl_multi_big_info", C.c_int, [vp, C.POINTER(LDLMultiBigInfo)])
 _sig("madipm_ldl_inertia", C.c_int, [vp, i32p, i32p, i32p])
 _sig("madipm_ldl_get_d", C.c_int, [vp, f64p])
 _sig("madipm_ldl_perm", C.c_int, [vp, i32p])
@@ -231,6 +241,7 @@ _sig("madipm_solver_adjoint_batch_device", C.c_int, [vp, C.c_int32, C.POINTER(QP
 _sig("madipm_solver_sens_batch_info", C.c_int, [vp, i64p, i64p, i64p])
 _sig("madipm_solver_set_multi_solve", C.c_int, [vp, C.c_int32])
 _sig("madipm_solver_multi_solve_info", C.c_int, [vp, C.POINTER(LDLMultiInfo)])
+_sig("madipm_solver_multi_big_info", C.c_int, [vp, C.POINTER(LDLMultiBigInfo)])
 
 
 class MadIPMError(RuntimeError):

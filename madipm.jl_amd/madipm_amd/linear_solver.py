@@ -87,10 +87,21 @@ class HIPLDLSolver:
     def multi_info(self) -> dict:
         """width: the columns of one chunk; native: 1 when solve_multi runs the multi-column route (0: the loop
         of single solves); n_calls, n_chunks (ceil(k / width) per call), n_columns so far; n_big_fronts: the
-        fronts a chunk still solves column by column."""
-        inf = L.LDLMultiInfo()
+        fronts of the route's big class (past 192 rows, or a panel beyond the small kernels' LDS).  How those are
+        solved: multi_big (1: a chunk's columns in one pass per level and direction, 0: column
+        after column), n_big_levels (levels that hold a big front), n_big_passes (big passes launched so far:
+        2 n_big_levels per chunk with multi_big, times the chunk's columns without), big_bytes (device bytes of
+        the multi-column big-front buffers, 0 before the first such pass)."""
+        inf, big = L.LDLMultiInfo(), L.LDLMultiBigInfo()
         L.check(L.lib.madipm_ldl_multi_info(self.h, C.byref(inf)), "madipm_ldl_multi_info")
-        return inf.as_dict()
+        L.check(L.lib.madipm_ldl_multi_big_info(self.h, C.byref(big)), "madipm_ldl_multi_big_info")
+        return {**inf.as_dict(), **big.as_dict()}
+
+    def set_multi_big(self, on: bool = True):
+        """on (the default, unless MADIPM_MULTI_BIG=0 was set at construction): solve_multi carries a chunk's
+        columns through the big fronts in one pass per level and direction; off: column after column with the
+        single-column kernels.  The rows of solve_multi are bit for bit the same either way."""
+        L.check(L.lib.madipm_ldl_set_multi_big(self.h, int(bool(on))), "madipm_ldl_set_multi_big")
 
     def is_inertia(self) -> bool:
         return True

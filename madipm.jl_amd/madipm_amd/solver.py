@@ -1200,10 +1200,13 @@ class MPCSolver:
 
     def multi_solve_info(self) -> dict:
         """HIPLDLSolver.multi_info() of the solver's linear solver: native is 0 where the switch falls back to
-        the loop of single solves (sharded, batched-leaf groups)."""
-        inf = L.LDLMultiInfo()
+        the loop of single solves (sharded, batched-leaf groups); multi_big, n_big_levels, n_big_passes and
+        big_bytes say how the route solves its big fronts (MADIPM_MULTI_BIG=0 at construction takes
+        them column after column, with the same bits)."""
+        inf, big = L.LDLMultiInfo(), L.LDLMultiBigInfo()
         L.check(L.lib.madipm_solver_multi_solve_info(self.h, C.byref(inf)), "multi_solve_info")
-        return inf.as_dict()
+        L.check(L.lib.madipm_solver_multi_big_info(self.h, C.byref(big)), "multi_big_info")
+        return {**inf.as_dict(), **big.as_dict()}
 
     def tangent_batch(self, want=None, *, polished=False, c=None, Hvals=None, Avals=None, lcon=None, ucon=None,
                       lvar=None, uvar=None) -> dict:

@@ -75,7 +75,8 @@ sens_batch_tangent_s / sens_loop_tangent_s, sens_batch_adjoint_s / sens_loop_adj
 row of the batches is the single call's).  --multi-solve (with --sens-batch) times the two batched calls once more with
 MPCSolver.set_multi_solve on: sens_multi_tangent_s / sens_multi_adjoint_s beside the batched and looped
 columns, sens_multi_rel_diff (the rows' largest difference to the switch off, relative to max(1, max |block|)), the
-spread (max - min) of the ten looped samples and multi_solve_info().  The instance name random_qp:N is instances.random_qp with N variables, N / 4 rows and about 8 entries per row."""
+spread (max - min) of the ten looped samples and multi_solve_info(), which says how the big fronts were solved (DESIGN
+§13k: a chunk's columns in one pass; with MADIPM_MULTI_BIG=0 in the environment column after column).  The instance name random_qp:N is instances.random_qp with N variables, N / 4 rows and about 8 entries per row."""
 import dataclasses
 import json
 import os
@@ -632,8 +633,11 @@ def main():
                   f"same bits {r['sens_batch_same_bits']}, status {r['sens_batch_status']}", flush=True)
             if multi_solve:
                 mi = r["sens_multi_info"]
-                print(f"{name}: multi-solve on ({'native' if mi['native'] else 'the loop'}, {mi['n_big_fronts']} fronts per "
-                      f"column): tangent_batch_device {r['sens_multi_tangent_s'] * 1e3:.3f} ms "
+                big = (f"{mi['n_big_fronts']} big fronts at {mi['n_big_levels']} levels, "
+                       + ("a chunk's columns in one pass" if mi["multi_big"] else "column after column")
+                       + f", {mi['n_big_passes']} big passes, {mi['big_bytes']} B of multi-column big-front buffers")
+                print(f"{name}: multi-solve on ({'native' if mi['native'] else 'the loop'}, {big}): "
+                      f"tangent_batch_device {r['sens_multi_tangent_s'] * 1e3:.3f} ms "
                       f"(x{r['sens_loop_tangent_s'] / r['sens_multi_tangent_s']:.2f} of the loop, whose samples spread "
                       f"{r['sens_loop_tangent_spread_s'] * 1e3:.3f} ms); adjoint_batch_device "
                       f"{r['sens_multi_adjoint_s'] * 1e3:.3f} ms (x{r['sens_loop_adjoint_s'] / r['sens_multi_adjoint_s']:.2f}, "
